@@ -22,6 +22,9 @@ The JSON line also carries
                  container (profiles/r02_reference_cpu.json)
   parity_sample: 8 rows of the timed output against the oracle (tests/parity.py), outside the timed region
   e2e          : host-buffer and DataFrame -> DataFrame rates of the same plan (PCIe-inclusive; never `value`)
+
+--dump-outputs DIR writes the feature matrix of the last timed step as .npy files (dump_outputs), so that two builds run
+with the same arguments -- and therefore the same seeded inputs -- can be compared output for output.
 """
 import argparse
 import json
@@ -35,6 +38,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: everything it writes, .npy headers included
+DUMP_SEED = 20261015         # --dump-outputs: the row sample of a matrix larger than DUMP_MAX_BYTES
 
 
 def _cpu_baseline_worker(args):
@@ -219,6 +224,37 @@ def e2e_block(plan, fplan, params_cls, n, L, calls=4):
     return res
 
 
+def nan_by_definition(name):
+    """query_similarity_count without a query: the reference returns NaN for every series (fc.py:2475-2519)."""
+    return name.startswith("query_similarity_count__query_None__")
+
+
+def dump_outputs(directory, full, names):
+    """--dump-outputs DIR: the feature matrix the last timed step wrote, as DIR/features.npy (float64).  Its columns are
+    the plan's (`names`) except those that are NaN by definition (nan_by_definition), chosen by name so that every build
+    dumps the same columns; DIR/cols.npy holds their positions in the plan, DIR/rows.npy the row of the matrix each line
+    of features.npy is (both float64).  A matrix over DUMP_MAX_BYTES is sampled: the same seeded, sorted choice of rows
+    for the same shape, so two builds run with the same arguments can be compared output for output.  -> a summary for
+    the JSON line."""
+    import torch
+    n_rows = full.shape[0]
+    cols = np.array([j for j, nm in enumerate(names) if not nan_by_definition(nm)], dtype=np.int64)
+    keep = (DUMP_MAX_BYTES - 3 * 4096 - 8 * len(cols)) // (8 * (len(cols) + 1))
+    if n_rows <= keep:
+        rows = np.arange(n_rows, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=keep, replace=False))
+    picked = full.index_select(0, torch.from_numpy(rows).to(full.device))
+    features = picked.index_select(1, torch.from_numpy(cols).to(full.device)).cpu().numpy()
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "features.npy"), features.astype(np.float64, copy=False))
+    np.save(os.path.join(directory, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(directory, "cols.npy"), cols.astype(np.float64))
+    return {"dir": directory, "rows": int(len(rows)), "of_rows": int(n_rows), "cols": int(len(cols)),
+            "of_cols": len(names), "left_out": [nm for nm in names if nan_by_definition(nm)],
+            "nonfinite_cells": int(np.count_nonzero(~np.isfinite(features)))}
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
@@ -288,7 +324,13 @@ def main():
     ap.add_argument("--chunks", type=int, default=0,
                     help="N > 1: row chunks per step; the all-gather of chunk c runs on RCCL's stream while chunk c + 1 is "
                          "being extracted (0 = 8 when N > 1, else 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the feature matrix of the last one to DIR/features.npy (a seeded row "
+                         "sample when it exceeds 64 MB; DIR/rows.npy and DIR/cols.npy name the rows and the plan's "
+                         "columns; columns that are NaN by definition are left out)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.plan_only:
         if args.strong and args.ragged:
@@ -431,6 +473,8 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         assert bool((hi == lo).all().item()), "exchange: ranks disagree on the gathered matrix"
+    # before anything below writes into `full` again (the compute-only and profiled passes)
+    dumped = dump_outputs(args.dump_outputs, full, fplan.names) if args.dump_outputs and rank == 0 else None
 
     # ---- N > 1: what the exchange costs on top of the extraction (outside the timed region) ----
     multi = None
@@ -530,6 +574,8 @@ def main():
         }
         if plan_options:
             line["config"]["plan_options"] = plan_options
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if multi is None and dist is not None:   # a world of one through the distributed code path
             multi = {"world": dist.get_world_size(), "ranks_seen_by_rccl": ranks_seen, "row_chunks": n_chunks}
         if multi is not None:

@@ -96,6 +96,85 @@ def test_configs4_as_a_strong_scaling_job_is_a_valid_command(capsys, monkeypatch
     assert doc["exchange"] == "all_gather" and doc["shard_rows"] == [125000] * 8
 
 
+def test_dump_outputs_writes_the_matrix_or_a_fixed_sample_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: the whole matrix when it fits, else the same seeded row sample for the same shape, under the byte
+    budget; float64 throughout; the columns that are NaN by definition left out by name."""
+    import numpy as np
+    import torch
+
+    import bench
+    names = ["c%d" % j for j in range(7)]
+    names[3] = "query_similarity_count__query_None__threshold_0.0"
+    full = torch.arange(50 * 7, dtype=torch.float64).reshape(50, 7)
+    full[:, 3] = float("nan")
+    keep = [0, 1, 2, 4, 5, 6]
+    doc = bench.dump_outputs(str(tmp_path / "all"), full, names)
+    assert doc == {"dir": str(tmp_path / "all"), "rows": 50, "of_rows": 50, "cols": 6, "of_cols": 7,
+                   "left_out": [names[3]], "nonfinite_cells": 0}
+    got = np.load(tmp_path / "all" / "features.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, full.numpy()[:, keep]) and np.isfinite(got).all()
+    assert np.array_equal(np.load(tmp_path / "all" / "rows.npy"), np.arange(50.0))
+    assert np.array_equal(np.load(tmp_path / "all" / "cols.npy"), np.array(keep, dtype=np.float64))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 * 4096 + 8 * 6 + 8 * 7 * 20)   # 20 rows of 6 columns + their row number
+    for d in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / d), full, names)["rows"] == 20
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+    assert np.all(np.diff(rows) > 0) and rows.max() < 50
+    got = np.load(tmp_path / "a" / "features.npy")
+    assert np.array_equal(got, full.numpy()[rows.astype(np.int64)][:, keep])
+    files = ("features.npy", "rows.npy", "cols.npy")
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_MAX_BYTES
+
+
+def test_steps_below_one_are_refused(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_its_timed_step_computed(gpu, tmp_path):
+    """The dump of a run holds the matrix of its timed steps: every row of the seeded input, and a few of them against the
+    oracle."""
+    import numpy as np
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from oracle.extract import oracle_matrix
+    from parity import compare
+    from tsfresh_amd import ComprehensiveFCParameters
+    from tsfresh_amd.feature_extraction.plan import compile_fc_parameters
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    n, L = 3000, 256
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--n-series", str(n), "--length", str(L), "--no-cpu-baseline", "--no-e2e",
+                          "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    doc = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert doc["steps"] == 2 and doc["ms_per_step"] > 0
+    left_out = ["query_similarity_count__query_None__threshold_0.0"]
+    assert doc["dumped_outputs"] == {"dir": str(tmp_path), "rows": n, "of_rows": n, "cols": 782, "of_cols": 783,
+                                     "left_out": left_out, "nonfinite_cells": 0}
+    got = np.load(tmp_path / "features.npy")
+    assert got.shape == (n, 782) and got.dtype == np.float64 and np.isfinite(got).all()
+    assert np.array_equal(np.load(tmp_path / "rows.npy"), np.arange(float(n)))
+    x = np.random.default_rng(42).standard_normal((n, L), dtype=np.float32)   # bench.py's input at rank 0
+    pick = [0, 1, n // 2, n - 1]
+    values = x[pick].astype(np.float64).reshape(-1)
+    offsets = np.arange(len(pick) + 1, dtype=np.int64) * L
+    params = ComprehensiveFCParameters()
+    names, want = oracle_matrix(values, offsets, params)
+    plan_cols = compile_fc_parameters(params).names
+    cols = ["value__" + plan_cols[int(j)] for j in np.load(tmp_path / "cols.npy")]
+    assert [c for c in plan_cols if "value__" + c not in cols] == left_out
+    names, want = [c for c in names if c in cols], want[:, [names.index(c) for c in names if c in cols]]
+    bad = compare(names, got[pick][:, [cols.index(c) for c in names]], want, [x[i].astype(np.float64) for i in pick])
+    assert not bad, bad[:5]
+
+
 @pytest.mark.gpu
 def test_strong_ragged_bench_runs_on_one_gpu(gpu):
     """The same command at --gpus 1 on the device (a shard = the whole job): the layout code path, ragged lengths, one rank."""
