@@ -21,32 +21,53 @@ TSFA_DEV int adf_maxlag_for(int n) {
     return maxlag;
 }
 
-// Cholesky factorization G = L L^T (lower triangle, in place, leading dimension ld).  Serial.
-TSFA_DEV bool chol_factor(double *G, int p, int ld) {
+// The normal matrices and their Cholesky factors are PACKED LOWER TRIANGLES: entry (i, j), i >= j, at ar_tri(i, j).  Only
+// the lower triangle is ever read, and the square (with a second square for the lag products) is what held the family
+// to 8 resident series per CU at 1024 samples.  A matrix of dimension p < P takes ar_tri_doubles(P).
+TSFA_DEV int ar_tri(int i, int j) { return ((i * (i + 1)) >> 1) + j; }
+TSFA_DEV int ar_tri_doubles(int P) { return (P * (P - 1)) / 2; }
+
+// LDS exchange inside the family.  A one-wavefront workgroup (every launch group up to 2048 samples) needs no s_barrier:
+// its LDS instructions complete in issue order, so waiting for its own (lgkmcnt) orders a lane's read after another
+// lane's write, and the "memory" clobber keeps the compiler from moving LDS accesses across the wait.  The family never
+// reads back what it stores to global memory, so no vmcnt wait is needed either.
+TSFA_DEV void ar_sync(const Blk &b) {
+#if TSFA_GPU && !defined(TSFA_LONG)
+    if (b.nt <= 64) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        return;
+    }
+#endif
+    (void)b;
+    blk_sync();
+}
+
+// Cholesky factorization G = L L^T (packed lower triangle, in place).  Serial.
+TSFA_DEV bool chol_factor(double *G, int p) {
     for (int j = 0; j < p; ++j) {
-        double d = G[j + j * ld];
-        for (int k = 0; k < j; ++k) d -= G[j + k * ld] * G[j + k * ld];
+        double d = G[ar_tri(j, j)];
+        for (int k = 0; k < j; ++k) d -= G[ar_tri(j, k)] * G[ar_tri(j, k)];
         if (!(d > 0.0)) return false;
         d = sqrt(d);
-        G[j + j * ld] = d;
+        G[ar_tri(j, j)] = d;
         for (int i = j + 1; i < p; ++i) {
-            double s = G[i + j * ld];
-            for (int k = 0; k < j; ++k) s -= G[i + k * ld] * G[j + k * ld];
-            G[i + j * ld] = s / d;
+            double s = G[ar_tri(i, j)];
+            for (int k = 0; k < j; ++k) s -= G[ar_tri(i, k)] * G[ar_tri(j, k)];
+            G[ar_tri(i, j)] = s / d;
         }
     }
     return true;
 }
-TSFA_DEV void chol_solve(const double *L, int p, int ld, const double *rhs, double *x) {
+TSFA_DEV void chol_solve(const double *L, int p, const double *rhs, double *x) {
     for (int i = 0; i < p; ++i) {
         double s = rhs[i];
-        for (int k = 0; k < i; ++k) s -= L[i + k * ld] * x[k];
-        x[i] = s * (1.0 / L[i + i * ld]);   // reciprocal pivots, as in blk_chol_solve: one division per pivot, not per use
+        for (int k = 0; k < i; ++k) s -= L[ar_tri(i, k)] * x[k];
+        x[i] = s * (1.0 / L[ar_tri(i, i)]);   // reciprocal pivots, as in blk_chol_solve: one division per pivot, not per use
     }
     for (int i = p - 1; i >= 0; --i) {
         double s = x[i];
-        for (int k = i + 1; k < p; ++k) s -= L[k + i * ld] * x[k];
-        x[i] = s * (1.0 / L[i + i * ld]);
+        for (int k = i + 1; k < p; ++k) s -= L[ar_tri(k, i)] * x[k];
+        x[i] = s * (1.0 / L[ar_tri(i, i)]);
     }
 }
 
@@ -54,26 +75,26 @@ TSFA_DEV void chol_solve(const double *L, int p, int ld, const double *rhs, doub
 // triangular solves are column-oriented (x_k is broadcast with readlane, every lane below / above subtracts its
 // L entry times x_k), so a solve costs 2p dependent steps instead of p^2 dependent LDS reads on one thread; all
 // wavefronts compute the same result, thread 0 stores it.  The caller provides the barriers around it.
-TSFA_DEV void blk_chol_solve(const Blk &b, const double *L, int p, int ld, const double *rhs, double *x) {
+TSFA_DEV void blk_chol_solve(const Blk &b, const double *L, int p, const double *rhs, double *x) {
 #if TSFA_GPU
     const int lane = b.tid & 63;
     const bool live = lane < p;
     double s = live ? rhs[lane] : 0.0;
     // a float64 division is ~30 instructions and the family is issue bound: one reciprocal per pivot (lane), then products
-    const double dg = live ? 1.0 / L[lane + lane * ld] : 1.0;
+    const double dg = live ? 1.0 / L[ar_tri(lane, lane)] : 1.0;
     for (int k = 0; k < p; ++k) {  // forward: L w = rhs
         const double wk = readlane_f64(s, k) * readlane_f64(dg, k);
         if (lane == k) s = wk;
-        else if (live && lane > k) s -= L[lane + k * ld] * wk;
+        else if (live && lane > k) s -= L[ar_tri(lane, k)] * wk;
     }
     for (int k = p - 1; k >= 0; --k) {  // backward: L^T x = w
         const double xk = readlane_f64(s, k) * readlane_f64(dg, k);
         if (lane == k) s = xk;
-        else if (live && lane < k) s -= L[k + lane * ld] * xk;
+        else if (live && lane < k) s -= L[ar_tri(k, lane)] * xk;
     }
     if (b.tid < p) x[b.tid] = s;
 #else
-    if (b.tid == 0) chol_solve(L, p, ld, rhs, x);
+    if (b.tid == 0) chol_solve(L, p, rhs, x);
 #endif
 }
 
@@ -87,66 +108,67 @@ TSFA_DEV void blk_chol_solve(const Blk &b, const double *L, int p, int ld, const
 // listed for the double-double second pass (fam_ar_dd.h); an absolute `d > 0` test lets round-off pass for a pivot.
 #define TSFA_AR_PIVOT_TOL 1e-6   // (1e-9 until round 3: a noiseless float32 sine + offset keeps 16 pivots at 1.5e-9 of their columns,
                                  //  the float64 factor then loses the ADF statistic's 4th digit -- found by the fuzz, adjudicated in 60 digits)
-TSFA_DEV bool blk_chol_factor(const Blk &b, double *G, int p, int ld, double *diag0, double *dmin = nullptr) {
-    for (int a = b.tid; a < p; a += b.nt) diag0[a] = G[a + a * ld];
+TSFA_DEV bool blk_chol_factor(const Blk &b, double *G, int p, double *diag0, double *dmin = nullptr) {
+    for (int a = b.tid; a < p; a += b.nt) diag0[a] = G[ar_tri(a, a)];
     double dm = TSFA_INF;
     for (int j = 0; j < p; ++j) {
-        blk_sync();
-        const double d = G[j + j * ld];
+        ar_sync(b);
+        const double d = G[ar_tri(j, j)];
         if (!(d > TSFA_AR_PIVOT_TOL * diag0[j])) return false;
         dm = fmin(dm, d);
         if (dmin) *dmin = dm;   // uniform: the smallest pivot so far
         const double sd = sqrt(d);
-        blk_sync();
+        ar_sync(b);
         const double rsd = 1.0 / sd;
-        for (int i = j + b.tid; i < p; i += b.nt) G[i + j * ld] = (i == j) ? sd : G[i + j * ld] * rsd;
-        blk_sync();
+        for (int i = j + b.tid; i < p; i += b.nt) G[ar_tri(i, j)] = (i == j) ? sd : G[ar_tri(i, j)] * rsd;
+        ar_sync(b);
         // trailing update, (row, column) = (tid % 32, tid / 32) strides: shifts instead of an integer division and a
         // modulo per element (the family is VALU-issue bound, and those two cost ~80 instructions)
         const int rsh = (b.nt >= 32) ? 5 : 0;  // nt is 1 (emulation) or a multiple of 64
         for (int i = j + 1 + (b.tid & ((1 << rsh) - 1)); i < p; i += (1 << rsh)) {
-            const double lij = G[i + j * ld];
+            const double lij = G[ar_tri(i, j)];
             for (int k = j + 1 + (b.tid >> rsh); k <= i; k += (b.nt >> rsh))
-                G[i + k * ld] = G[i + k * ld] - lij * G[k + j * ld];
+                G[ar_tri(i, k)] = G[ar_tri(i, k)] - lij * G[ar_tri(k, j)];
         }
     }
-    blk_sync();
+    ar_sync(b);
     return true;
 }
 // w = L^-1 rhs by column-oriented forward substitution (same subtraction order as the serial row loop).
 // `w` is overwritten in place: pass a copy of rhs.  GPU (p <= 64): lane i of every wavefront holds w_i, w_j travels by
 // readlane -- p dependent steps without a barrier (every wavefront computes the same values, thread i < p stores).
-TSFA_DEV void blk_chol_forward(const Blk &b, const double *L, int p, int ld, double *w) {
+TSFA_DEV void blk_chol_forward(const Blk &b, const double *L, int p, double *w) {
 #if TSFA_GPU
     if (p <= 64) {
         const int lane = b.tid & 63;
         const bool live = lane < p;
         double s = live ? w[lane] : 0.0;
-        const double dg = live ? 1.0 / L[lane + lane * ld] : 1.0;
+        const double dg = live ? 1.0 / L[ar_tri(lane, lane)] : 1.0;
         for (int k = 0; k < p; ++k) {
             const double wk = readlane_f64(s, k) * readlane_f64(dg, k);
             if (lane == k) s = wk;
-            else if (live && lane > k) s = s - L[lane + k * ld] * wk;
+            else if (live && lane > k) s = s - L[ar_tri(lane, k)] * wk;
         }
-        blk_sync();
+        ar_sync(b);
         if (b.tid < p) w[b.tid] = s;
-        blk_sync();
+        ar_sync(b);
         return;
     }
 #endif
     for (int i = 0; i < p; ++i) {
-        blk_sync();
-        const double wi = w[i] * (1.0 / L[i + i * ld]);
-        blk_sync();
+        ar_sync(b);
+        const double wi = w[i] * (1.0 / L[ar_tri(i, i)]);
+        ar_sync(b);
         if (b.tid == 0) w[i] = wi;
-        for (int k = i + 1 + b.tid; k < p; k += b.nt) w[k] = w[k] - L[k + i * ld] * wi;
+        for (int k = i + 1 + b.tid; k < p; k += b.nt) w[k] = w[k] - L[ar_tri(k, i)] * wi;
     }
-    blk_sync();
+    ar_sync(b);
 }
 
 // (Measured and dropped, round 3: the same factorization by ONE wavefront with the matrix in registers -- lane = row,
 //  columns by readlane, no barrier.  Fewer instructions, but the other wavefront of the workgroup idles through p
-//  dependent sqrt / reciprocal chains: k_ar 5.90 -> 6.56 ms per 100 000 series.)
+//  dependent sqrt / reciprocal chains: k_ar 5.90 -> 6.56 ms per 100 000 series.  Groups up to 2048 samples now launch
+//  one wavefront per series instead, so nobody idles: the other series of the CU fill the SIMDs.)
 
 // ---------------------------------------------------------------------------------------------
 // Lagged sums on register tiles.  Every sum of the family has the form  S[j] = sum_t A(t) B(t - j)  over a row range,
@@ -219,6 +241,8 @@ TSFA_DEV void tile_axpy8(const double (&cf)[8], const double (&lo)[8], const dou
 //   sums (or null): sums[0] = sum_t A(t), sums[1] = sum_t A(t)^2  (every thread receives them)
 //   part (or null): LDS scratch of part_doubles doubles.  With it the wavefronts leave their partial sums of ALL sweeps
 //                   there and meet once (two barriers per call instead of two per sweep; lane = lag adds them up).
+//                   One wavefront has nobody to meet: its sums stay in registers (the same bits: one wavefront's part
+//                   is its reduce-scatter, which blk_sum_multi reads back by readlane).
 // store() is called by one thread per lag; the caller provides the barrier before anybody else reads what it wrote.
 // One tile per thread (n <= 8 nt, the short-series launch): A and the upper block stay in registers across the sweeps.
 #define TSFA_AR_PART_STRIDE 72   // 64 lags + the two row sums, per wavefront
@@ -232,7 +256,7 @@ TSFA_DEV void blk_tile_lagdots(const Blk &b, int nrows, int nlags, LA loadA, LB 
 #else
     const int nwv = 1, wv = 0;
 #endif
-    const bool deferred = (part != nullptr) && (nwv * TSFA_AR_PART_STRIDE <= part_doubles) && (nlags <= 64);
+    const bool deferred = (part != nullptr) && (nwv > 1) && (nwv * TSFA_AR_PART_STRIDE <= part_doubles) && (nlags <= 64);
     if (deferred) blk_sync();   // the previous user of `part`
     double A[8], lo[8], hi[8];
     for (int j0 = 0; j0 < nlags; j0 += 8) {
@@ -300,24 +324,55 @@ TSFA_DEV void blk_tile_lagdots(const Blk &b, int nrows, int nlags, LA loadA, LB 
     }
 }
 
-// Lag-product matrix of sequence s over rows t in [t0, t1):  T[i + j*ld] = sum_t s(t-i) s(t-j), 0 <= j <= i <= Lg,
-// and column sums C[j] = sum_t s(t-j), from the first column T[0 .. Lg] and C[0] (blk_tile_lagdots; thread 0 wrote
-// them).  Requires t0 >= Lg.  S(u) returns s[u].
+// Lag-product matrix of sequence s over rows t in [t0, t1):  T(i, j) = sum_t s(t-i) s(t-j), 1 <= j <= i <= Lg, generated
+// from the first column Tc[i] = T(i, 0) (blk_tile_lagdots) straight into the packed matrix G at (i + off, j + off) -- no
+// copy of T is kept: a second design over the same rows generates its entries again, with the same bits.  With C, also
+// the column sums C[j] = sum_t s(t-j), j <= Lg, from c0 = C[0].  Requires t0 >= Lg and Lg < 64.  S(u) returns s[u].
+// GPU: lane j holds s(t0-1-j) and s(t1-1-j); C runs down the lanes by readlane in the serial order, and lane dg walks
+// diagonal i - j = dg with the other factor of each product from lane i (every lane of the first wavefront runs every
+// step, so the shuffles never read an inactive lane).  The caller provides the barrier before G or C is read.
 template <class S>
-TSFA_DEV void blk_lag_products_rest(const Blk &b, S s, int Lg, int t0, int t1, double *T, int ld, double *C) {
-    if (b.tid == 0) {
+TSFA_DEV void ar_lag_products_into(const Blk &b, S s, int Lg, int t0, int t1, const double *Tc, double *G, int off,
+                                   double *C = nullptr, double c0 = 0.0) {
+#if TSFA_GPU
+    if (b.tid < 64) {
+        const int lane = b.tid;
+        const double sa = (lane < Lg) ? s(t0 - 1 - lane) : 0.0;
+        const double sb = (lane < Lg) ? s(t1 - 1 - lane) : 0.0;
+        if (C != nullptr) {
+            double c = c0, mine = c0;
+            for (int j = 0; j < Lg; ++j) {
+                c = c + readlane_f64(sa, j) - readlane_f64(sb, j);
+                if (lane == j + 1) mine = c;
+            }
+            if (lane <= Lg) C[lane] = mine;
+        }
+        const int dg = lane;
+        double v = (dg < Lg) ? Tc[dg] : 0.0;
+        for (int j = 0; j < Lg; ++j) {
+            const int i = dg + j;
+            const int src = (i < 64) ? i : 0;
+            const double ai = __shfl(sa, src), bi = __shfl(sb, src);
+            if (i + 1 <= Lg) {
+                v = v + ai * readlane_f64(sa, j) - bi * readlane_f64(sb, j);
+                G[ar_tri(i + 1 + off, j + 1 + off)] = v;
+            }
+        }
+    }
+#else
+    if (b.tid == 0 && C != nullptr) {
+        C[0] = c0;
         for (int j = 0; j < Lg; ++j) C[j + 1] = C[j] + s(t0 - 1 - j) - s(t1 - 1 - j);
     }
-    blk_sync();
     for (int dg = b.tid; dg <= Lg; dg += b.nt) {  // one lane per diagonal i - j = dg
-        double v = T[dg];
+        double v = Tc[dg];
         for (int j = 0; dg + j + 1 <= Lg; ++j) {
             const int i = dg + j;
             v = v + s(t0 - 1 - i) * s(t0 - 1 - j) - s(t1 - 1 - i) * s(t1 - 1 - j);
-            T[(i + 1) + (j + 1) * ld] = v;
+            G[ar_tri(i + 1 + off, j + 1 + off)] = v;
         }
     }
-    blk_sync();
+#endif
 }
 
 // statsmodels.tsa.adfvalues.mackinnonp(teststat, regression="c", N=1)
@@ -330,9 +385,9 @@ TSFA_DEV double mackinnon_p_c1(double t) {
     return tsfa_norm_cdf(z);
 }
 
-// LDS scratch of the family, carved from `aw`:  P = max regressors + 1 (leading dimension of the matrices)
-//   T (P*P) | G (P*P) | 7 vectors of P | acv 64 | res 16 | pac 48 | arres 40 | pacw 128
-TSFA_DEV int ar_scratch_doubles(int P) { return 2 * P * P + 7 * P + 64 + 16 + 48 + 40 + 128; }
+// LDS scratch of the family, carved from `aw`:  P = max regressors + 1
+//   G (packed triangle, ar_tri_doubles(P)) | 8 vectors of P | acv 64 | res 8 | pac 48 | arres 32   (ArLds::scratch_doubles)
+TSFA_DEV int ar_scratch_doubles(int P) { return ar_tri_doubles(P) + 8 * P + 64 + 8 + 48 + 32; }
 
 // Evaluate the AR specs of one series.
 //   xv   : sample accessor
@@ -398,7 +453,7 @@ struct ArCentred {
 template <class ST, class X>
 TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int nspecs, double *out_row, void *xc_raw,
                             double *aw, int P, int hint_acf, int hint_pacf, int hint_adf, int n_loop = -1,
-                            const double *stats = nullptr) {
+                            const double *stats = nullptr, double *part = nullptr, int part_doubles = 0) {
     const int nloop = (n_loop >= 0) ? n_loop : nspecs;  // columns [nloop, nspecs): lane = column epilogue
     const double dn = (double)n;
     TSFA_TICKER(tk, 0);
@@ -406,7 +461,7 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
     // autocovariances are pure round-off of x - x.mean(), so the order decides what comes out
     // (stats: the record k_basic left for this series, TSFA_STATS_*: the same sum in the same order)
     const double mean = stats ? stats[TSFA_STATS_MEAN] : np_sum(b, n, [=](int i) { return xv(i); }) / dn;
-    blk_sync();
+    ar_sync(b);
     ST *xs_lds = (ST *)xc_raw + TSFA_AR_PADL;   // zero samples on either side: the blocks of the register tiles
     for (int i = b.tid; i < n + TSFA_AR_PADL + TSFA_AR_PADR; i += b.nt) {
         const int j = i - TSFA_AR_PADL;
@@ -414,14 +469,14 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
     }
     const ArCentred<ST> xc{xs_lds, mean};
     const ArBlocks<ST> blk{xs_lds, mean};
-    blk_sync();
+    ar_sync(b);
     double v0 = 0.0;
     for (int i = b.tid; i < n; i += b.nt) v0 += xc[i] * xc[i];
     const double var = blk_sum(b, v0) / dn;
 
-    double *T = aw;               // lag products
-    double *G = T + P * P;        // normal matrix / Cholesky factor
-    double *g = G + P * P;        // rhs
+    double *G = aw;               // normal matrix / Cholesky factor (packed lower triangle)
+    double *Tc = G + ar_tri_doubles(P);   // first column of the lag products (ar_lag_products_into generates the rest)
+    double *g = Tc + P;           // rhs
     double *beta = g + P;
     double *tmp1 = beta + P;
     double *tmp2 = tmp1 + P;
@@ -429,12 +484,14 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
     double *V = C + P;            // level products (ADF)
     double *diag0 = V + P;        // diagonal of the matrix being factored (relative pivot test)
     double *acv = diag0 + P;      // 64
-    double *res = acv + 64;       // 16
-    double *pac = res + 16;       // 48
-    double *arres = pac + 48;     // 40: cached AR solution
-    double *pacw = arres + 40;    // 128: Levinson-Durbin columns
+    double *res = acv + 64;       // 8
+    double *pac = res + 8;        // 48
+    double *arres = pac + 48;     // 32: cached AR solution (orders <= TSFA_AR_TABLE_K)
     const ArCentred<ST> xcc = xc;
     int degenerate = 0;
+    // scratch of the lagged sums' deferred meeting (several wavefronts only): its own region, else G while G is free
+    double *const pt = part ? part : G;
+    const int ptn = part ? part_doubles : ar_tri_doubles(P);
 
     TSFA_TICK(tk, b, 120);
     // largest agg_autocorrelation maxlag / partial_autocorrelation lag of the plan (-1: none) and whether ADF is
@@ -460,9 +517,9 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
 #pragma unroll
                              for (int q = 0; q < 8; ++q) B[q] = (i0 >= 0) ? B[q] : 0.0;
                          },
-                         [=](int k, double v) { acv[k] = v / (double)(n - k); }, nullptr, G, P * P);
+                         [=](int k, double v) { acv[k] = v / (double)(n - k); }, nullptr, pt, ptn);
     }
-    blk_sync();
+    ar_sync(b);
 
     TSFA_TICK(tk, b, 121);
     // ---- PACF by Levinson-Durbin (stattools.levinson_durbin, isacov=True) ----
@@ -474,7 +531,7 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
             // the same values, bit-identical to the serial recursion below.  (Serial on one lane: 21 k cycles per series.)
             const int lane = b.tid & 63;
             for (int k = b.tid; k <= max_pacf_lag; k += b.nt) pac[k] = TSFA_NAN;
-            blk_sync();
+            ar_sync(b);
             if (n > 1 && pacf_maxlag > 0) {
                 const int ord = pacf_maxlag;
                 const double a0 = acv[0], a1 = acv[1];
@@ -503,7 +560,7 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
             if (n > 1 && pacf_maxlag > 0) {
                 const int ord = pacf_maxlag;
                 // only the previous column of phi is ever read: keep two rolling columns
-                double *prev = pacw, *cur = pacw + 42, *sig = pacw + 84;
+                double prev[42], cur[42], sig[42];
                 prev[1] = acv[1] / acv[0];
                 pac[1] = prev[1];
                 sig[1] = acv[0] - prev[1] * acv[1];
@@ -521,7 +578,7 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
             }
         }
 #endif
-        blk_sync();
+        ar_sync(b);
     }
 
     TSFA_TICK(tk, b, 122);
@@ -543,37 +600,34 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
             double sd[2], sl[2];
             blk_tile_lagdots(b, n, maxlag + 1,
                              [=](int tb, double (&A)[8]) { blk.d8(tb, A); tile_mask_rows(A, tb, t0, t1); }, d_blocks,
-                             [=](int j, double v) { T[j] = v; }, sd, G, P * P);
+                             [=](int j, double v) { Tc[j] = v; }, sd, pt, ptn);
             blk_tile_lagdots(b, n, maxlag + 1,
                              [=](int tb, double (&A)[8]) { blk.y8(tb, A); tile_mask_rows(A, tb, t0, t1); }, d_blocks,
-                             [=](int j, double v) { V[j] = v; }, sl, G, P * P);
-            if (b.tid == 0) C[0] = sd[0];
-            blk_lag_products_rest(b, dif, maxlag, t0, t1, T, P, C);
+                             [=](int j, double v) { V[j] = v; }, sl, pt, ptn);
+            ar_sync(b);   // Tc before the diagonals start from it
+            // assemble the normal matrix in the autolag column order [const, level, d-lag1 .. d-lag maxlag]: the lag block
+            // (a, c >= 2) is T(a - 1, c - 1), generated in place; columns 0 and 1 below
+            ar_lag_products_into(b, dif, maxlag, t0, t1, Tc, G, 1, C, sd[0]);
+            ar_sync(b);
             const double sx = sl[0], sxx = sl[1];
-            // assemble the normal matrix in the autolag column order [const, level, d-lag1 .. d-lag maxlag]
             const int p1 = maxlag + 2;
-            for (int e = b.tid; e < 64 * p1; e += b.nt) {  // (a, c) = (e % 64, e / 64): p1 <= 63 for n <= 65535
-                const int a = e & 63, c = e >> 6;
-                if (a >= p1 || c > a) continue;
+            for (int e = b.tid; e < 2 * p1; e += b.nt) {
+                const int c = (e >= p1) ? 1 : 0, a = e - c * p1;
+                if (c > a) continue;
                 double v;
                 if (a == 0) v = nobs;
                 else if (a == 1) v = (c == 0) ? sx : sxx;
-                else {
-                    const int la = a - 1;
-                    if (c == 0) v = C[la];
-                    else if (c == 1) v = V[la];
-                    else v = T[la + (c - 1) * P];
-                }
-                G[a + c * P] = v;
+                else v = (c == 0) ? C[a - 1] : V[a - 1];
+                G[ar_tri(a, c)] = v;
             }
-            for (int a = b.tid; a < p1; a += b.nt) g[a] = (a == 0) ? C[0] : (a == 1 ? V[0] : T[a - 1]);
-            blk_sync();
-            const double yy = T[0];
+            for (int a = b.tid; a < p1; a += b.nt) g[a] = (a == 0) ? C[0] : (a == 1 ? V[0] : Tc[a - 1]);
+            ar_sync(b);
+            const double yy = Tc[0];
             TSFA_TICK(tk, b, 123);
             {
                 // all nested fits from one factorization: w = L^-1 g, SSR_p = yy - sum_{i<p} w_i^2
                 double dmin1 = 0.0;
-                const bool okf = blk_chol_factor(b, G, p1, P, diag0, &dmin1);
+                const bool okf = blk_chol_factor(b, G, p1, diag0, &dmin1);
                 if (!okf) degenerate |= 2;
                 else {
                     // raw level column: sum (xc + mean)^2 over the rows; the lag columns are differences (no offset)
@@ -583,12 +637,12 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                 }
                 if (okf) {
                     for (int a = b.tid; a < p1; a += b.nt) tmp1[a] = g[a];
-                    blk_chol_forward(b, G, p1, P, tmp1);
+                    blk_chol_forward(b, G, p1, tmp1);
                     if (b.tid == 0) {  // running sum of squares in the serial order
                         double acc = 0.0;
                         for (int i = 0; i < p1; ++i) { acc += tmp1[i] * tmp1[i]; tmp2[i] = acc; }
                     }
-                    blk_sync();
+                    ar_sync(b);
                     for (int i = b.tid; i < p1; i += b.nt) {  // AIC (BIC) of the fit with i + 1 columns
                         const int pcols = i + 1;
                         const double ssr = yy - tmp2[i];
@@ -600,7 +654,7 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                         if (adf_mode == TSFA_AUTOLAG_TSTAT) ic = fabs(wi / sqrt(ssr / (nobs - (double)pcols)));
                         tmp1[i] = ic;
                     }
-                    blk_sync();
+                    ar_sync(b);
                 }
                 if (b.tid == 0) {
                     int best = -1;
@@ -621,9 +675,9 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                     res[0] = (double)best;
                 }
             }
-            blk_sync();
+            ar_sync(b);
             const int bestcols = (int)res[0];
-            blk_sync();
+            ar_sync(b);
             TSFA_TICK(tk, b, 124);
             if (bestcols >= 2) {
                 const int usedlag = bestcols - 2;
@@ -633,6 +687,9 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                 // final design [level, d-lag1..usedlag, const] over rows [usedlag, n-1): the autolag matrix restricted
                 // to those columns plus the rows t in [usedlag, maxlag) that the first regression had trimmed
                 auto reg2 = [=](int a, int t) { return a == 0 ? xcc[t] : (a == p2 - 1 ? 1.0 : dif(t - a)); };
+                // the lag block (both lags >= 1) of the maxlag-row sums: T(a, c) at (a, c) of the final ordering
+                ar_lag_products_into(b, dif, usedlag, t0, t1, Tc, G, 0);
+                ar_sync(b);
                 for (int e = b.tid; e < p2 * p2 + p2; e += b.nt) {
                     const bool is_rhs = e >= p2 * p2;
                     const int a = is_rhs ? e - p2 * p2 : e % p2;
@@ -643,7 +700,7 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                     auto lagidx = [=](int q) { return q == 0 ? -2 : (q == p2 - 1 ? -1 : q); };  // -2 level, -1 const
                     const int A = lagidx(a), Cc = is_rhs ? 0 : lagidx(c);
                     if (is_rhs) {
-                        v = (A == -2) ? V[0] : (A == -1 ? C[0] : T[A]);
+                        v = (A == -2) ? V[0] : (A == -1 ? C[0] : Tc[A]);
                     } else {
                         const int hi = a, lo = c;  // a >= c in final ordering; map each unordered pair
                         (void)hi; (void)lo;
@@ -654,16 +711,16 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                         else if (Cc == -1) v = C[A];
                         else if (A == -2) v = V[Cc];
                         else if (Cc == -2) v = V[A];
-                        else v = (A >= Cc) ? T[A + Cc * P] : T[Cc + A * P];
+                        else v = G[ar_tri(a, c)];   // a >= c here, so A >= Cc
                     }
                     for (int t = u0; t < t0; ++t) v += reg2(a, t) * (is_rhs ? dif(t) : reg2(c, t));
-                    if (is_rhs) g[a] = v; else G[a + c * P] = v;
+                    if (is_rhs) g[a] = v; else G[ar_tri(a, c)] = v;
                 }
-                blk_sync();
-                const bool ok2 = blk_chol_factor(b, G, p2, P, diag0);
+                ar_sync(b);
+                const bool ok2 = blk_chol_factor(b, G, p2, diag0);
                 if (!ok2) degenerate |= 2;
-                if (ok2) blk_chol_solve(b, G, p2, P, g, beta);
-                blk_sync();
+                if (ok2) blk_chol_solve(b, G, p2, g, beta);
+                ar_sync(b);
                 if (ok2) {
                     // one step of iterative refinement on the true residuals, then SSR
                     // (the residual of a row is recomputed where it is used: a few multiply-adds instead of an
@@ -690,13 +747,13 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                                 if (a0 + j < p2) tmp1[a0 + j] = s8[j];
                         }
                     }
-                    blk_sync();
-                    blk_chol_solve(b, G, p2, P, tmp1, tmp2);
-                    blk_sync();
+                    ar_sync(b);
+                    blk_chol_solve(b, G, p2, tmp1, tmp2);
+                    ar_sync(b);
                     if (ar_refinement_suspect(b, beta, tmp2, diag0, p2)) degenerate |= 2;
-                    blk_sync();
+                    ar_sync(b);
                     for (int a = b.tid; a < p2; a += b.nt) beta[a] += tmp2[a];
-                    blk_sync();
+                    ar_sync(b);
                     double ssr = 0.0;
                     for (int t = u0 + b.tid; t < t1; t += b.nt) {
                         double r = dif(t);
@@ -705,9 +762,9 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                     }
                     ssr = blk_sum(b, ssr);
                     for (int i = b.tid; i < p2; i += b.nt) tmp1[i] = (i == 0) ? 1.0 : 0.0;  // (X'X)^-1 [level, level]
-                    blk_sync();
-                    blk_chol_solve(b, G, p2, P, tmp1, tmp2);
-                    blk_sync();
+                    ar_sync(b);
+                    blk_chol_solve(b, G, p2, tmp1, tmp2);
+                    ar_sync(b);
                     if (b.tid == 0) {
                         const double sigma2 = ssr / (nobs2 - (double)p2);
                         const double tstat = beta[0] / sqrt(sigma2 * tmp2[0]);
@@ -715,12 +772,12 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                         res[3] = mackinnon_p_c1(tstat);
                         res[4] = (double)usedlag;
                     }
-                    blk_sync();
+                    ar_sync(b);
                     adf_stat = res[2];
                     adf_p = res[3];
                     adf_lag = res[4];
                     if (adf_stat != adf_stat) adf_p = TSFA_NAN;
-                    blk_sync();
+                    ar_sync(b);
                 }
             }
         }
@@ -832,19 +889,17 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                 double sy[2];
                 blk_tile_lagdots(b, n, k + 1,
                                  [=](int tb, double (&A)[8]) { blk.y8(tb, A); tile_mask_rows(A, tb, k, n); }, y_blocks,
-                                 [=](int j, double v) { T[j] = v; }, sy, G, P * P);
-                if (b.tid == 0) C[0] = sy[0];
-                blk_lag_products_rest(b, sx, k, k, n, T, P, C);
+                                 [=](int j, double v) { Tc[j] = v; }, sy, pt, ptn);
+                ar_sync(b);
+                // the lag block (a, c >= 1) is T(a, c), generated in place; column 0 is [rows, C[1 ..]]
+                ar_lag_products_into(b, sx, k, k, n, Tc, G, 0, C, sy[0]);
+                ar_sync(b);
                 const int p = k + 1;
-                for (int e = b.tid; e < p * p; e += b.nt) {
-                    const int a = e % p, c = e / p;
-                    if (c > a) continue;
-                    G[a + c * P] = (a == 0) ? (double)(n - k) : (c == 0 ? C[a] : T[a + c * P]);
-                }
-                for (int a = b.tid; a < p; a += b.nt) g[a] = (a == 0) ? C[0] : T[a];
-                blk_sync();
+                for (int a = b.tid; a < p; a += b.nt) G[ar_tri(a, 0)] = (a == 0) ? (double)(n - k) : C[a];
+                for (int a = b.tid; a < p; a += b.nt) g[a] = (a == 0) ? C[0] : Tc[a];
+                ar_sync(b);
                 double dmin_ar = 0.0;
-                ar_ok = blk_chol_factor(b, G, p, P, diag0, &dmin_ar);
+                ar_ok = blk_chol_factor(b, G, p, diag0, &dmin_ar);
                 if (!ar_ok) degenerate |= 1;
                 else {
                     const double mu = xcc.mean, rows = (double)(n - k);
@@ -864,24 +919,24 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                     double tr0 = 0.0, s0 = 0.0;
                     for (int a = 0; a < p; ++a) { tr0 += diag0[a]; s0 += 1.0 / diag0[a]; }   // uniform
                     for (int a = b.tid; a < p; a += b.nt) tmp1[a] = 1.0 / sqrt(diag0[a] * s0);
-                    blk_sync();
+                    ar_sync(b);
                     double lmin = tr0;
                     for (int it = 0; it < 2; ++it) {
-                        blk_chol_solve(b, G, p, P, tmp1, tmp2);
-                        blk_sync();
+                        blk_chol_solve(b, G, p, tmp1, tmp2);
+                        ar_sync(b);
                         double nrm2 = 0.0;
                         for (int a = 0; a < p; ++a) nrm2 += tmp2[a] * tmp2[a];   // uniform: every thread reads the same LDS values
                         const double nrm = sqrt(nrm2);
                         if (!(nrm > 0.0) || isinf(nrm) || nrm != nrm) { lmin = 0.0; break; }
                         lmin = 1.0 / nrm;
-                        blk_sync();
+                        ar_sync(b);
                         for (int a = b.tid; a < p; a += b.nt) tmp1[a] = tmp2[a] / nrm;
-                        blk_sync();
+                        ar_sync(b);
                     }
                     if (!(lmin >= 1e-12 * tr0)) degenerate |= 1;
                 }
-                if (ar_ok) blk_chol_solve(b, G, p, P, g, beta);
-                blk_sync();
+                if (ar_ok) blk_chol_solve(b, G, p, g, beta);
+                ar_sync(b);
                 if (ar_ok) {
                     // X^T r of the refinement step: r(t) = y(t) - beta_0 - sum_c beta_c y(t - c) on the tile, then the same
                     // lagged sums with A = r  (lag 0 is the constant's entry: sum_t r(t))
@@ -907,13 +962,13 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                                          }
                                          tile_mask_rows(A, tb, k, n);
                                      },
-                                     y_blocks, [=](int a, double v) { if (a > 0) tmp1[a] = v; }, sr, T, P * P);
+                                     y_blocks, [=](int a, double v) { if (a > 0) tmp1[a] = v; }, sr, part, part_doubles);
                     if (b.tid == 0) tmp1[0] = sr[0];
-                    blk_sync();
-                    blk_chol_solve(b, G, p, P, tmp1, tmp2);
-                    blk_sync();
+                    ar_sync(b);
+                    blk_chol_solve(b, G, p, tmp1, tmp2);
+                    ar_sync(b);
                     if (ar_refinement_suspect(b, beta, tmp2, diag0, p)) degenerate |= 1;
-                    blk_sync();
+                    ar_sync(b);
                     if (b.tid == 0) {
                         double sphi = 0.0;
                         for (int a = 0; a < p; ++a) {
@@ -923,7 +978,7 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
                         arres[0] = beta[0] + mean * (1.0 - sphi);  // undo the centring of the constant
                         for (int a = 1; a < p; ++a) arres[a] = beta[a];
                     }
-                    blk_sync();
+                    ar_sync(b);
                 }
                 ar_cached_k = k;
             }
@@ -936,7 +991,7 @@ TSFA_DEV int fam_ar_series(const Blk &b, X xv, int n, const TsfaSpec *specs, int
     }
     if (nloop < nspecs) {
         // lane = column: reads of pac[], the ADF outputs and the cached AR fit (all resident in LDS / uniform)
-        blk_sync();
+        ar_sync(b);
         for (int s = nloop + b.tid; s < nspecs; s += b.nt) {
             const TsfaSpec sp = specs[s];
             double v = TSFA_NAN;

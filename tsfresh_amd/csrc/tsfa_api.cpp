@@ -643,7 +643,10 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                 // Wavefronts per series, measured on MI355X at n = 1024 (profiles/r01_*): the LDS footprint of a series
                 // caps the workgroups per CU, so the latency-bound families gain from more wavefronts per workgroup,
                 // while k_basic's many short reductions lose to the extra barriers.  At least 4 samples per thread.
-                static const int pref[TSFA_N_FAMILIES] = {64, 128, 128, 128, 256, 256, 128, 64};
+                // AR: one wavefront per series.  Its time is serial linear algebra that a second wavefront only repeated,
+                // and its layout (10 144 B at 1024 samples) puts 16 one-wavefront series on a CU; the workgroup size is
+                // then the same for every length up to 2048, so a series gives the same bits in whatever group it lands.
+                static const int pref[TSFA_N_FAMILIES] = {64, 128, 128, 64, 256, 256, 128, 64};
                 const int cap = std::max(64, ((maxn / 4 + 63) / 64) * 64);
                 a.nt = std::min(pref[f], cap);
             }

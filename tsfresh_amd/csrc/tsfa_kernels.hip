@@ -314,13 +314,13 @@ __global__ void __launch_bounds__(1024) k_ar(const T *__restrict__ values, const
     const int64_t off = starts[sidx];
     const int n = (int)(ends[sidx] - off);
     ArLds L;
-    L.carve(tsfa_base, maxn, P, (int)sizeof(T));
+    L.carve(tsfa_base, maxn, P, (int)sizeof(T), (int)blockDim.x);
     TSFA_TICKS_BEGIN();
     Blk b{(int)threadIdx.x, (int)blockDim.x, L.red, L.np};
     const T *g = values + off;
     const int flags = fam_ar_series<T>(b, [=](int i) { return (double)g[i]; }, n, specs, nspecs, out + sidx * ld,
                                        (void *)L.xc, L.aw, P, hint_acf, hint_pacf, hint_adf, n_loop,
-                                       stats_in ? stats_in + sidx * TSFA_STATS_N : nullptr);
+                                       stats_in ? stats_in + sidx * TSFA_STATS_N : nullptr, L.part, L.part_doubles);
     // rank-deficient / ill-conditioned regressions: list the series for k_ar_degenerate
     if (flags && threadIdx.x == 0) deg_list[atomicAdd(deg_count, 1)] = ((long long)sidx << 2) | flags;
     TSFA_TICKS_END();
@@ -1090,7 +1090,7 @@ static int launch_all_t(const TsfaLaunch &a, const T *values) {
         }
     } else if (a.fam == TSFA_FAM_AR) {
         ArLds L;
-        const size_t lds = L.carve(nullptr, a.maxn, a.ar_P, (int)sizeof(T));
+        const size_t lds = L.carve(nullptr, a.maxn, a.ar_P, (int)sizeof(T), nt);
         TSFA_KLAUNCH(k_ar<T>, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, a.ar_P,
                      a.hint_a, a.hint_b, a.hint_c, a.hint_d, a.deg_list, a.deg_count, a.stats_in);
     } else if (a.fam == TSFA_FAM_ENTROPY) {
@@ -1312,7 +1312,7 @@ size_t tsfa_family_lds_bytes(int fam, int maxn, int nt, int aux) {
     case TSFA_FAM_TREND: { BasicLds L; return L.carve(nullptr, maxn, nt, 8, 2, aux); }
     case TSFA_FAM_SORT: { SortLds L; return L.carve(nullptr, maxn, nt); }
     case TSFA_FAM_SPECTRAL: { SpectralLds L; return L.carve(nullptr, maxn, aux); }
-    case TSFA_FAM_AR: { ArLds L; return L.carve(nullptr, maxn, aux); }
+    case TSFA_FAM_AR: { ArLds L; return L.carve(nullptr, maxn, aux, 8, nt); }
     case TSFA_FAM_CWT: {   // beyond a CU's LDS the long-series build runs, with 32-bit column indices
         CwtPeaksLayout L;
         const size_t lds16 = L.carve(nullptr, maxn, aux, 8, 2);

@@ -158,11 +158,14 @@ struct SpectralLds {
 };
 
 struct ArLds {
-    double *red; NpScratch *np; double *xc; double *aw;
-    // P: leading dimension of the normal matrices = (max regressors) + 1, chosen by the host for the batch
-    TSFA_HD static int scratch_doubles(int P) { return 2 * P * P + 7 * P + 64 + 16 + 48 + 40 + 128; }
+    double *red; NpScratch *np; double *xc; double *aw; double *part; int part_doubles;
+    // P: (max regressors) + 1, chosen by the host for the batch.  The matrix is a packed lower triangle of dimension P - 1,
+    // then eight P-vectors, acv 64 | res 8 | pac 48 | arres 32 (fam_ar.h: ar_scratch_doubles).  At 1024 float32 samples
+    // (P = 25) the workgroup takes 10 144 B: 16 resident series per CU.
+    TSFA_HD static int scratch_doubles(int P) { return (P * (P - 1)) / 2 + 8 * P + 64 + 8 + 48 + 32; }
     // xs_bytes: element size of the resident series (4: float32 input kept as float32, 8: float64)
-    TSFA_HD size_t carve(unsigned char *base, int maxn, int P, int xs_bytes = 8) {
+    // nt > 64: the wavefronts' partial sums of the lagged sums (blk_tile_lagdots), 72 doubles per wavefront
+    TSFA_HD size_t carve(unsigned char *base, int maxn, int P, int xs_bytes = 8, int nt = 64) {
         LdsCarve c{base, 0};
         red = c.take<double>(TSFA_RED_DOUBLES);
         xc = (double *)(void *)c.take<unsigned char>((size_t)(maxn + 64 + 16) * xs_bytes);  // TSFA_AR_PADL + n + TSFA_AR_PADR (fam_ar.h)
@@ -171,6 +174,8 @@ struct ArLds {
         unsigned char *u = c.take<unsigned char>(ab > sizeof(NpScratch) ? ab : sizeof(NpScratch));
         aw = (double *)u;
         np = (NpScratch *)u;
+        part_doubles = (nt > 64) ? 72 * ((nt + 63) / 64) : 0;
+        part = part_doubles ? c.take<double>((size_t)part_doubles) : nullptr;
         return c.off;
     }
 };
