@@ -14,7 +14,14 @@ timed region.  Per-GPU work is fixed -> "scaling": "weak".
 Workload at N = 1: BASELINE.json configs[2] -- 100k synthetic float32 series x len 1024,
 ComprehensiveFCParameters (783 columns) -- the configuration the metric/target is quoted on.
 
-The JSON line also carries
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes --dump-outputs and prints
+the JSON line (metric, value, unit, ms_per_step, config, ...).  With --full the run goes on, outside the timed region, to
+everything else the benchmark measures and checks, and the JSON line also carries
+  kernel_ms    : per-kernel HIP-event timings of two profiled passes of the plan
+  outputs_finite, nonfinite_columns: every column of the output finite except those that are NaN by definition
+  multi_gpu    : N > 1: per-block checksums of the gathered matrix agree on all ranks, and the same pipeline timed with
+                 the exchange off (compute_only_ms_per_step, exchange_ms_exposed); without --full the block only says
+                 what the job was (world, ranks_seen_by_rccl, row_chunks, self_launched)
   roofline     : dominant kernel's algorithmic HBM bytes per launch / its HIP-event duration vs 8 TB/s
   cpu_baseline : the numpy oracle (a port of the reference's calculators) timed on a bounded sample of the same
                  workload on the host cores (warm pool, >= 32 series per worker; one run, --cpu-baseline-full: median of 3) -- a reported baseline,
@@ -310,12 +317,18 @@ def main():
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: --n-series is the TOTAL of the job, split evenly over the N ranks (configs[3]: "
                          "`--strong --n-series 1000000 --length 256 --gpus N`); the default is weak (series per GPU fixed)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline (outside the timed "
+                         "region): per-kernel timings and roofline, finiteness of the output, the N > 1 exchange checksums "
+                         "and compute-only pass, the parity sample, the e2e boundary timings and the CPU baseline.  Off: "
+                         "set up, warm up, time the steps, write --dump-outputs, print the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-full", action="store_true",
-                    help="three runs of the CPU protocol (median) and the reference's default n_jobs = cpu_count() // 2 as a "
-                         "second leg (~4 min of wall clock) instead of one run (~1 min): profiles/r04_z_bench.json was taken so")
-    ap.add_argument("--cpu-workers", type=int, default=0, help="worker processes of the CPU baseline (default: every physical core)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffer / DataFrame boundary timings")
+                    help="--full: three runs of the CPU protocol (median) and the reference's default n_jobs = cpu_count() // 2 "
+                         "as a second leg (~4 min of wall clock) instead of one run (~1 min): profiles/r04_z_bench.json was taken so")
+    ap.add_argument("--cpu-workers", type=int, default=0,
+                    help="--full: worker processes of the CPU baseline (default: every physical core)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the host-buffer / DataFrame boundary timings")
     ap.add_argument("--plan-option", action="append", default=[], metavar="NAME=VALUE",
                     help="tsfa_plan_set_option on every plan of the run (A/B of an alternative route to the same numbers, e.g. "
                          "seq_rows=0); recorded in config.plan_options.  The default line sets none")
@@ -465,7 +478,7 @@ def main():
         elapsed = float(t.item())
     ms_per_step = 1000.0 * elapsed / max(args.steps, 1)
     value = row0[-1] * args.steps / elapsed
-    if dist is not None and world > 1:
+    if args.full and dist is not None and world > 1:
         # every rank holds every rank's rows: a checksum of each rank's block (NaNs zeroed), all-reduced with MAX and
         # MIN, must agree on all ranks -- i.e. everybody received the same bytes for every block
         sums = torch.stack([torch.nan_to_num(full[row0[r]:row0[r + 1]]).sum() for r in range(world)])
@@ -473,12 +486,12 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         assert bool((hi == lo).all().item()), "exchange: ranks disagree on the gathered matrix"
-    # before anything below writes into `full` again (the compute-only and profiled passes)
+    # before anything below writes into `full` again (the compute-only and profiled passes of --full)
     dumped = dump_outputs(args.dump_outputs, full, fplan.names) if args.dump_outputs and rank == 0 else None
 
-    # ---- N > 1: what the exchange costs on top of the extraction (outside the timed region) ----
+    # ---- --full, N > 1: what the exchange costs on top of the extraction (outside the timed region) ----
     multi = None
-    if dist is not None and world > 1:
+    if args.full and dist is not None and world > 1:
         try:   # diagnostics only: a failure here (the same on every rank) must not cost the bench line
             local = ShardPipeline(fplan.native_specs(_native.calc_id), n_cols, local_rank, dist=None, n_chunks=n_chunks,
                                   length_hint=None if args.ragged else (L, L))
@@ -506,18 +519,19 @@ def main():
         except Exception as e:  # noqa: BLE001
             multi = {"world": dist.get_world_size(), "ranks_seen_by_rccl": ranks_seen, "error": repr(e)}
 
-    # ---- per-kernel HIP-event timings (events recorded on the launch stream), 2 profiled passes ----
-    plan.set_profiling(True)
+    # ---- --full: per-kernel HIP-event timings (events recorded on the launch stream), 2 profiled passes ----
     kt = {}
-    reps = 2
-    for _ in range(reps):
-        plan.extract_device(values.data_ptr(), _native.TSFA_F32, offsets.data_ptr(), n, out.data_ptr(), n_cols, stream)
-        for name, ms in plan.last_timings():
-            kt[name] = kt.get(name, 0.0) + ms / reps
-    plan.set_profiling(False)
-    # every column of the TIMED output: finite everywhere, except the columns that are NaN by definition
-    nonfinite_cols = [fplan.names[j] for j in torch.nonzero(~torch.isfinite(out).all(dim=0)).flatten().tolist()]
-    finite = all(nm.startswith("query_similarity_count") for nm in nonfinite_cols)
+    if args.full:
+        plan.set_profiling(True)
+        reps = 2
+        for _ in range(reps):
+            plan.extract_device(values.data_ptr(), _native.TSFA_F32, offsets.data_ptr(), n, out.data_ptr(), n_cols, stream)
+            for name, ms in plan.last_timings():
+                kt[name] = kt.get(name, 0.0) + ms / reps
+        plan.set_profiling(False)
+        # every column of the TIMED output: finite everywhere, except the columns that are NaN by definition
+        nonfinite_cols = [fplan.names[j] for j in torch.nonzero(~torch.isfinite(out).all(dim=0)).flatten().tolist()]
+        finite = all(nm.startswith("query_similarity_count") for nm in nonfinite_cols)
 
     if rank == 0:
         dom = max(kt, key=kt.get) if kt else None
@@ -570,8 +584,9 @@ def main():
                                        ", id-sharded + RCCL all-gather of the feature matrix" if world > 1 else ""),
                        "n_series_per_gpu": n, "length": L, "n_cols": n_cols, "parallelism": "ids%d" % world,
                        "row_chunks_per_step": n_chunks},
-            "kernel_ms": kt, "outputs_finite": finite, "roofline": roof,
         }
+        if args.full:
+            line.update({"kernel_ms": kt, "outputs_finite": finite, "roofline": roof})
         if plan_options:
             line["config"]["plan_options"] = plan_options
         if dumped is not None:
@@ -581,10 +596,11 @@ def main():
         if multi is not None:
             multi["self_launched"] = bool(os.environ.get("TSFA_BENCH_LAUNCHED"))
             line["multi_gpu"] = multi
-        line["nonfinite_columns"] = nonfinite_cols
+        if args.full:
+            line["nonfinite_columns"] = nonfinite_cols
         params_name = args.params.capitalize() + "FCParameters"
         pool = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             import multiprocessing as mp
             for v in ("OMP_NUM_THREADS", "MKL_NUM_THREADS", "OPENBLAS_NUM_THREADS"):
                 os.environ[v] = "1"  # the reference's own advice (docs/text/tsfresh_on_a_cluster.rst:216-231)
@@ -595,7 +611,7 @@ def main():
             workers = args.cpu_workers if args.cpu_workers > 0 else min(physical_cores()[0], 64)
             pool = mp.get_context("spawn").Pool(workers)
             pool.map(_cpu_warm, range(4 * workers))
-        if world == 1 and not args.ragged:
+        if args.full and world == 1 and not args.ragged:
             # ~8 rows of the timed output against the oracle, outside the timed region
             pick = sorted(set([0, 1, 2, n // 3, n // 2, n - 3, n - 2, n - 1]))
             if L > 4096:   # the oracle's entropies hold n x n float64 matrices (the reference's own arithmetic)
@@ -604,7 +620,7 @@ def main():
             rows_in = values.view(n, L)[pick].cpu().numpy()
             rows_out = out[pick].cpu().numpy()
             line["parity_sample"] = parity_sample(pool, rows_in, rows_out, fplan.names, params_name) if pick else "skipped (series too long for the oracle)"
-        if world == 1 and not args.ragged and not args.no_e2e:
+        if args.full and world == 1 and not args.ragged and not args.no_e2e:
             line["e2e"] = e2e_block(plan, fplan, cls, min(n, 20_000), L)
             if n > 20_000 and n * L <= 110_000_000:
                 # the headline shape itself: configs[2] as a long frame is 102 M rows

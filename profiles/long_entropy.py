@@ -11,8 +11,8 @@ CASES = [(4096, 512), (4097, 256), (5000, 256), (8192, 128), (16384, 64), (32768
 
 
 def one(length, n):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-e2e",
-           "--n-series", str(n), "--length", str(length)]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+           "--no-e2e", "--n-series", str(n), "--length", str(length)]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
     except subprocess.TimeoutExpired:

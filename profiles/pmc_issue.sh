@@ -46,7 +46,7 @@ doc = {"workload": line["config"], "units": "means per launch (= per step) of ea
        "wave-instructions, *ACTIVE* / *BUSY* counters quad-cycles summed over the SIMDs; GRBM_GUI_ACTIVE cycles summed over the 8 XCDs",
        "kernels": {}, "step": None}
 with open("gpurun_out/pmc_issue/summary.md", "w") as out:
-    out.write("means per launch of each kernel = per step (rocprofv3 --pmc, bench.py default workload: 4 launches per pass, one pass per counter set)\n\n")
+    out.write("means per launch of each kernel = per step (rocprofv3 --pmc, bench.py default workload: the warm-up and the timed step, one pass per counter set)\n\n")
     out.write("| kernel | launches | " + " | ".join(cols) + " | VALU busy | ms at full VALU issue | MFMA busy |\n")
     out.write("|---|---|" + "---|" * (len(cols) + 3) + "\n")
     tot_insts = tot_active = tot_gui = tot_full = 0.0

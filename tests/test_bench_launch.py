@@ -176,13 +176,34 @@ def test_bench_dumps_what_its_timed_step_computed(gpu, tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_carries_only_the_headline(gpu):
+    """Without --full a run prints the headline line and nothing that needs passes, pools or checks of its own: no
+    per-kernel timings, roofline, parity sample, boundary timings or CPU baseline."""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--n-series", "2000", "--length", "256"], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    doc = json.loads(lines[0])
+    assert doc["metric"] == "series/sec (comprehensive, len=256)" and doc["unit"] == "series/sec"
+    assert doc["higher_is_better"] is True and doc["dtype"] == "f64"
+    assert doc["steps"] == 2 and doc["warmup"] == 1 and doc["ms_per_step"] > 0
+    assert abs(doc["value"] - 2000 * 1000.0 / doc["ms_per_step"]) <= 1e-6 * doc["value"]
+    extras = {"kernel_ms", "outputs_finite", "roofline", "nonfinite_columns", "multi_gpu", "parity_sample", "e2e",
+              "e2e_headline", "cpu_baseline"}
+    assert not extras & set(doc), sorted(extras & set(doc))
+
+
+@pytest.mark.gpu
 def test_strong_ragged_bench_runs_on_one_gpu(gpu):
     """The same command at --gpus 1 on the device (a shard = the whole job): the layout code path, ragged lengths, one rank."""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--strong", "--ragged", "300:700",
-                          "--n-series", "3000", "--params", "efficient", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                          "--no-e2e"], env=env, capture_output=True, text=True, timeout=600)
+                          "--n-series", "3000", "--params", "efficient", "--steps", "2", "--warmup", "1", "--full",
+                          "--no-cpu-baseline", "--no-e2e"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     doc = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert doc["scaling"] == "strong" and doc["value"] > 0 and doc["outputs_finite"]
@@ -195,8 +216,8 @@ def test_bench_self_launch_path_on_one_gpu(gpu):
     env = dict(os.environ, TSFA_BENCH_SELF_LAUNCH="1", TSFA_BENCH_FORCE_DIST="1")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--n-series", "2000", "--no-cpu-baseline", "--no-e2e"], env=env, capture_output=True, text=True,
-                         timeout=600)
+                          "--n-series", "2000", "--full", "--no-cpu-baseline", "--no-e2e"], env=env, capture_output=True,
+                         text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
