@@ -38,7 +38,12 @@ typedef enum tsfa_status {
 } tsfa_status;
 
 /* element type of the ragged value buffer */
-typedef enum tsfa_dtype { TSFA_F32 = 0, TSFA_F64 = 1, TSFA_I64 = 2, TSFA_I32 = 3 /* ids / sort keys only */ } tsfa_dtype;
+/* (tsfa_extract* take TSFA_F32 / TSFA_F64 samples; the integer types and TSFA_BOOL name id / sort-key columns and the value
+ * columns tsfa_pack_device converts to float64) */
+typedef enum tsfa_dtype {
+    TSFA_F32 = 0, TSFA_F64 = 1, TSFA_I64 = 2, TSFA_I32 = 3,
+    TSFA_I8 = 4, TSFA_I16 = 5, TSFA_U8 = 6, TSFA_U16 = 7, TSFA_U32 = 8, TSFA_U64 = 9, TSFA_BOOL = 10 /* one byte, 0 | 1 */
+} tsfa_dtype;
 
 /* where the caller's buffers live */
 typedef enum tsfa_memspace { TSFA_HOST = 0, TSFA_DEVICE = 1 } tsfa_memspace;
@@ -192,6 +197,47 @@ int tsfa_plan_set_length_hint(tsfa_plan *plan, int64_t min_len, int64_t max_len)
 int tsfa_pack_scan(const void *ids, int32_t id_type, const void *sort, int32_t sort_type, const void *values,
                    int32_t value_type, int64_t n_rows, int32_t *flags, int64_t *n_groups);
 int tsfa_pack_offsets(int64_t *offsets, int64_t n_groups, int64_t n_rows);
+
+/* Device packer: the same grouping for a frame in ANY row order (rows in time order with the ids interleaved -- the usual
+ * sensor log --, tsfresh's long format, a shuffled frame), on the GPU.  Replaces the pandas groupby of LongTsFrameAdapter
+ * (data.py:233-291) and WideTsFrameAdapter (:181-230) and the host's factorize + lexsort + gather.  The three columns go to
+ * HBM as they are (space: TSFA_HOST pointers are staged, TSFA_DEVICE pointers are used in place), the rows are sorted stably
+ * by (id, sort) with an LSD radix sort of order-preserving keys (passes whose digit is constant over all rows are skipped;
+ * a frame that is already in order is not sorted at all), group boundaries are found, and the values are gathered into the
+ * ragged buffer tsfa_extract* takes with TSFA_DEVICE pointers.  The handle owns that buffer, the int64 offsets
+ * (n_groups + 1), the unique ids (ascending, the id column's own element type) and, with TSFA_PACK_KEEP_SORT, the sort
+ * column in packed order; tsfa_pack_device_destroy frees all of them.
+ *   ids         any integer type of tsfa_dtype except TSFA_BOOL
+ *   sort        NULL (stable sort by id alone) or any integer type, TSFA_F32, TSFA_F64 (no NaN; -0.0 equals +0.0)
+ *   values      TSFA_F32 stays float32, TSFA_F64 stays float64, TSFA_BOOL and every integer type become float64 exactly as
+ *               numpy's astype(float64) (64-bit integers beyond 2^53 round to nearest even)
+ *   options     TSFA_PACK_KEEP_SORT or 0
+ * Scratch while the call runs: 40 bytes per row (two buffers of 16-byte composite key + 4-byte row index) + 1 KiB per 4096
+ * rows + the staged columns; an allocation that fails is TSFA_ERR_HIP with the byte count in the message.  More than
+ * 2^32 - 1 rows: TSFA_ERR_TOO_LONG.  No HIP device: TSFA_ERR_NO_DEVICE (there is no CPU route in the library).
+ * Synchronous; the handle may be destroyed from any thread.
+ *   tsfa_pack_device_flags: TSFA_PACK_VALUE_NAN (a float value is NaN: the caller raises the reference's ValueError,
+ *                           data.py:148-167) | TSFA_PACK_IN_ORDER (the rows were already in order: nothing was sorted)
+ *   tsfa_pack_device_n_passes: radix passes that ran (0 .. 16)
+ *   tsfa_pack_device_values: device pointer and element type (TSFA_F32 | TSFA_F64) of the ragged buffer (n_rows elements)
+ *   tsfa_pack_device_offsets: device pointer of the int64 offsets
+ *   tsfa_pack_device_copy_ids / _offsets / _sort: copies to host arrays of n_groups ids / n_groups + 1 int64 / n_rows sort
+ *                           keys (TSFA_ERR_INVALID without TSFA_PACK_KEEP_SORT) */
+#define TSFA_PACK_IN_ORDER 4
+#define TSFA_PACK_KEEP_SORT 1
+typedef struct tsfa_pack tsfa_pack; /* opaque; owned by the library */
+int tsfa_pack_device(const void *ids, int32_t id_type, const void *sort, int32_t sort_type, const void *values,
+                     int32_t value_type, int64_t n_rows, int32_t space, int32_t options, int32_t device, tsfa_pack **out_pack);
+int64_t tsfa_pack_device_n_rows(const tsfa_pack *pack);
+int64_t tsfa_pack_device_n_groups(const tsfa_pack *pack);
+int32_t tsfa_pack_device_flags(const tsfa_pack *pack);
+int32_t tsfa_pack_device_n_passes(const tsfa_pack *pack);
+int tsfa_pack_device_values(const tsfa_pack *pack, const void **values, int32_t *dtype);
+const int64_t *tsfa_pack_device_offsets(const tsfa_pack *pack);
+int tsfa_pack_device_copy_ids(const tsfa_pack *pack, void *ids_host);
+int tsfa_pack_device_copy_offsets(const tsfa_pack *pack, int64_t *offsets_host);
+int tsfa_pack_device_copy_sort(const tsfa_pack *pack, void *sort_host);
+void tsfa_pack_device_destroy(tsfa_pack *pack);
 
 /* Page-locked host memory for the TSFA_HOST form.  tsfa_extract* accepts ANY host pointer; from pageable memory the HIP
  * runtime stages every transfer through its own bounce buffers, from memory obtained here the copy engines read and

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Registers / scratch / occupancy of every kernel as the compiler reports them (no GPU needed):
-    python profiles/kernel_resources.py [substring filter]"""
+    python profiles/kernel_resources.py [substring filter [source file of csrc/, default tsfa_kernels.hip]]
+    python profiles/kernel_resources.py k_pack tsfa_pack_device.hip"""
 import os
 import re
 import subprocess
@@ -9,7 +10,7 @@ import sys
 csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tsfresh_amd", "csrc")
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
        "-Wno-unused-function", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-mllvm", "-disable-machine-licm",
-       "-Rpass-analysis=kernel-resource-usage", "-c", "tsfa_kernels.hip", "-o", "/tmp/tsfa_k.o"]
+       "-Rpass-analysis=kernel-resource-usage", "-c", sys.argv[2] if len(sys.argv) > 2 else "tsfa_kernels.hip", "-o", "/tmp/tsfa_k.o"]
 txt = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in txt.splitlines():

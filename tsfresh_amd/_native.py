@@ -20,7 +20,9 @@ TSFA_ERR_NO_DEVICE = -3
 TSFA_ERR_HIP = -4
 TSFA_ERR_TOO_LONG = -5
 TSFA_F32, TSFA_F64, TSFA_I64, TSFA_I32 = 0, 1, 2, 3
-TSFA_PACK_UNSORTED, TSFA_PACK_VALUE_NAN = 1, 2
+TSFA_I8, TSFA_I16, TSFA_U8, TSFA_U16, TSFA_U32, TSFA_U64, TSFA_BOOL = 4, 5, 6, 7, 8, 9, 10
+TSFA_PACK_UNSORTED, TSFA_PACK_VALUE_NAN, TSFA_PACK_IN_ORDER = 1, 2, 4
+TSFA_PACK_KEEP_SORT = 1
 TSFA_HOST, TSFA_DEVICE = 0, 1
 
 # every symbol include/tsfresh_amd.h declares
@@ -36,6 +38,17 @@ EXPORTS = (
     "tsfa_host_free",
     "tsfa_pack_scan",
     "tsfa_pack_offsets",
+    "tsfa_pack_device",
+    "tsfa_pack_device_n_rows",
+    "tsfa_pack_device_n_groups",
+    "tsfa_pack_device_flags",
+    "tsfa_pack_device_n_passes",
+    "tsfa_pack_device_values",
+    "tsfa_pack_device_offsets",
+    "tsfa_pack_device_copy_ids",
+    "tsfa_pack_device_copy_offsets",
+    "tsfa_pack_device_copy_sort",
+    "tsfa_pack_device_destroy",
     "tsfa_impute",
     "tsfa_relevance_classes",
     "tsfa_relevance_classes_ks",
@@ -117,6 +130,21 @@ def load():
     lib.tsfa_pack_scan.restype = ctypes.c_int
     lib.tsfa_pack_offsets.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
     lib.tsfa_pack_offsets.restype = ctypes.c_int
+    lib.tsfa_pack_device.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                     ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.POINTER(ctypes.c_void_p)]
+    lib.tsfa_pack_device.restype = ctypes.c_int
+    for name, res in (("n_rows", ctypes.c_int64), ("n_groups", ctypes.c_int64), ("flags", ctypes.c_int32),
+                      ("n_passes", ctypes.c_int32), ("offsets", ctypes.c_void_p)):
+        fn = getattr(lib, "tsfa_pack_device_" + name)
+        fn.argtypes, fn.restype = [ctypes.c_void_p], res
+    lib.tsfa_pack_device_values.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32)]
+    lib.tsfa_pack_device_values.restype = ctypes.c_int
+    for name in ("copy_ids", "copy_offsets", "copy_sort"):
+        fn = getattr(lib, "tsfa_pack_device_" + name)
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
+    lib.tsfa_pack_device_destroy.argtypes = [ctypes.c_void_p]
+    lib.tsfa_pack_device_destroy.restype = None
     lib.tsfa_host_alloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
     lib.tsfa_host_alloc.restype = ctypes.c_int
     lib.tsfa_host_free.argtypes = [ctypes.c_void_p]
@@ -241,6 +269,108 @@ def pack_scan(ids, sort_values, values):
     offsets = np.empty(groups.value + 1, dtype=np.int64)
     _check(lib, lib.tsfa_pack_offsets(offsets.ctypes.data_as(ctypes.c_void_p), groups.value, n))
     return flags.value, offsets
+
+
+# element types tsfa_pack_device takes (ids: the integer ones; sort keys: those and the two float types; values: all)
+_DEVICE_PACK_TYPES = {np.dtype(np.float32): TSFA_F32, np.dtype(np.float64): TSFA_F64, np.dtype(np.int64): TSFA_I64,
+                      np.dtype(np.int32): TSFA_I32, np.dtype(np.int8): TSFA_I8, np.dtype(np.int16): TSFA_I16,
+                      np.dtype(np.uint8): TSFA_U8, np.dtype(np.uint16): TSFA_U16, np.dtype(np.uint32): TSFA_U32,
+                      np.dtype(np.uint64): TSFA_U64, np.dtype(np.bool_): TSFA_BOOL}
+
+
+def pack_column(a):
+    """A column as tsfa_pack_device reads it: -> (C-contiguous 1-D ndarray, tsfa_dtype code), or None for an element type /
+    shape the device packer does not take.  datetime64 / timedelta64 are viewed as their int64 ticks (they compare alike);
+    a strided column (one column of a DataFrame block) is copied once."""
+    if not isinstance(a, np.ndarray) or a.ndim != 1:
+        return None
+    if a.dtype.kind in "mM" and a.dtype.itemsize == 8:
+        a = a.view(np.int64)
+    if not a.dtype.isnative:
+        return None
+    code = _DEVICE_PACK_TYPES.get(a.dtype)
+    if code is None:
+        return None
+    return np.ascontiguousarray(a), code
+
+
+class DevicePack:
+    """Owns a `tsfa_pack*`: one kind of a frame in ANY row order, grouped by id and ordered by the sort column on the device
+    (tsfa_pack_device).  The ragged sample buffer and the offsets stay in HBM and go to `Plan.extract_pack` / the
+    `pack=` form of `extract_into` as device pointers; only the unique ids (`.ids`) come back at once, `.offsets`, `.sort`
+    and `.values_host()` when asked for.  ids / sort / values: what `pack_column` returned (sort may be None)."""
+
+    def __init__(self, ids, sort, values, device=0, keep_sort=False):
+        lib = load()
+        _bind_device_api(lib)
+        (ids_a, ids_t), (val_a, val_t) = ids, values
+        sort_a, sort_t = sort if sort is not None else (None, 0)
+        if len(val_a) != len(ids_a) or (sort_a is not None and len(sort_a) != len(ids_a)):
+            raise ValueError("the id, sort and value columns must have one entry per row")
+        handle = ctypes.c_void_p()
+        _check(lib, lib.tsfa_pack_device(
+            ids_a.ctypes.data_as(ctypes.c_void_p), ids_t,
+            None if sort_a is None else sort_a.ctypes.data_as(ctypes.c_void_p), sort_t,
+            val_a.ctypes.data_as(ctypes.c_void_p), val_t, len(ids_a), TSFA_HOST,
+            TSFA_PACK_KEEP_SORT if (keep_sort and sort_a is not None) else 0, int(device), ctypes.byref(handle)))
+        self._lib, self._h, self.device = lib, handle, int(device)
+        self.n_rows = int(lib.tsfa_pack_device_n_rows(handle))
+        self.n_series = int(lib.tsfa_pack_device_n_groups(handle))
+        self.flags = int(lib.tsfa_pack_device_flags(handle))
+        self.n_passes = int(lib.tsfa_pack_device_n_passes(handle))
+        vptr, vtype = ctypes.c_void_p(), ctypes.c_int32()
+        _check(lib, lib.tsfa_pack_device_values(handle, ctypes.byref(vptr), ctypes.byref(vtype)))
+        self.values_ptr, self.values_type = vptr.value, int(vtype.value)
+        self.values_dtype = np.dtype(np.float32 if self.values_type == TSFA_F32 else np.float64)
+        self.offsets_ptr = lib.tsfa_pack_device_offsets(handle)
+        self._sort_dtype = None if sort_a is None or not keep_sort else sort_a.dtype
+        self._offsets = self._sort = None
+        self.ids = np.empty(self.n_series, dtype=ids_a.dtype)
+        _check(lib, lib.tsfa_pack_device_copy_ids(handle, self.ids.ctypes.data_as(ctypes.c_void_p)))
+
+    @property
+    def value_nan(self):
+        return bool(self.flags & TSFA_PACK_VALUE_NAN)
+
+    @property
+    def was_in_order(self):
+        return bool(self.flags & TSFA_PACK_IN_ORDER)
+
+    @property
+    def offsets(self):
+        if self._offsets is None:
+            out = np.empty(self.n_series + 1, dtype=np.int64)
+            _check(self._lib, self._lib.tsfa_pack_device_copy_offsets(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+            self._offsets = out
+        return self._offsets
+
+    @property
+    def sort(self):
+        """The sort column in packed order (None unless the pack was made with keep_sort=True)."""
+        if self._sort is None and self._sort_dtype is not None:
+            out = np.empty(self.n_rows, dtype=self._sort_dtype)
+            _check(self._lib, self._lib.tsfa_pack_device_copy_sort(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+            self._sort = out
+        return self._sort
+
+    def values_host(self):
+        """A host copy of the ragged sample buffer (tsfa_device_copy)."""
+        out = np.empty(self.n_rows, dtype=self.values_dtype)
+        _check(self._lib, self._lib.tsfa_device_copy(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(self.values_ptr),
+                                                     out.nbytes, 0, self.device))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.tsfa_pack_device_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            if not sys.is_finalizing():
+                self.close()
+        except Exception:
+            pass
 
 
 def _result_matrix(n_rows, n_cols):
@@ -377,9 +507,34 @@ class Plan:
             ends.ctypes.data_as(ctypes.c_void_p), n, out.ctypes.data_as(ctypes.c_void_p), self.n_cols, TSFA_HOST, None))
         return out
 
-    def extract_into(self, values, offsets, matrix, col0=0, times=None):
+    def extract_pack(self, pack, out=None):
+        """The series of a DevicePack -> float64 [n_series, n_cols] on the host: the samples never visit the host
+        (tsfa_extract with the pack's device pointers into a device matrix that comes back in one copy)."""
+        if out is None:
+            out = _result_matrix(pack.n_series, self.n_cols)
+        if pack.n_series == 0 or self.n_cols == 0:
+            return out
+        dm = DeviceMatrix(pack.n_series, self.n_cols, self.device)
+        try:
+            self.extract_into(None, None, dm, pack=pack)
+            dm.to_host(out=out)
+        finally:
+            dm.free()
+        return out
+
+    def extract_into(self, values, offsets, matrix, col0=0, times=None, pack=None):
         """Host arrays in, columns [col0, col0 + n_cols) of the DeviceMatrix `matrix` out: the samples are copied to the
-        device once and the feature rows stay there (tsfa_extract / tsfa_extract_timed with TSFA_DEVICE pointers)."""
+        device once and the feature rows stay there (tsfa_extract / tsfa_extract_timed with TSFA_DEVICE pointers).
+        pack: a DevicePack on the matrix' device instead of `values` / `offsets` -- nothing is uploaded."""
+        if pack is not None:
+            if pack.device != matrix.device or matrix.shape[0] != pack.n_series or col0 < 0 or col0 + self.n_cols > matrix.shape[1]:
+                raise ValueError("the device matrix does not hold [n_series, col0 + n_cols] cells on the pack's device")
+            if pack.n_series == 0 or self.n_cols == 0:
+                return
+            _check(self._lib, self._lib.tsfa_extract_timed(
+                self._h, ctypes.c_void_p(pack.values_ptr), pack.values_type, None, ctypes.c_void_p(pack.offsets_ptr),
+                pack.n_series, ctypes.c_void_p(matrix.ptr + 8 * col0), matrix.ld, TSFA_DEVICE, None))
+            return
         values = np.ascontiguousarray(values)
         if values.dtype == np.float32:
             dt = TSFA_F32
@@ -452,10 +607,13 @@ class DeviceMatrix:
             except Exception:
                 pass
 
-    def to_host(self, cols=None):
+    def to_host(self, cols=None, out=None):
         n, m = self.shape
         if cols is None:
-            out = np.empty((n, m), dtype=np.float64)
+            if out is None:
+                out = np.empty((n, m), dtype=np.float64)
+            elif out.dtype != np.float64 or out.shape != (n, m) or not out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous float64 matrix of the device matrix' shape")
             _check(self._lib, self._lib.tsfa_device_copy(out.ctypes.data_as(ctypes.c_void_p), self._ptr, out.nbytes, 0,
                                                          self.device))
             return out
@@ -466,13 +624,33 @@ class DeviceMatrix:
         return out
 
 
-def extract_parts_into(parts, values, offsets, matrix, col0=0, times=None):
+def extract_parts_into(parts, values, offsets, matrix, col0=0, times=None, pack=None):
     """Several native plans over ONE upload of the samples: parts = [(Plan, column indices in the caller's order)].  Every
     part's block is extracted into a transient device matrix and scattered (tsfa_scatter_columns) into columns
     col0 + cols of `matrix` (a DeviceMatrix): the composite plans of feature_extraction/extraction.py (several ADF lag
-    selections, more than 128 CWT columns) without an upload per part, and with the matrix staying in HBM."""
+    selections, more than 128 CWT columns) without an upload per part, and with the matrix staying in HBM.
+    pack: a DevicePack on the matrix' device instead of `values` / `offsets` -- no upload at all."""
     lib = load()
     _bind_device_api(lib)
+    if pack is not None:
+        if pack.device != matrix.device or pack.n_series != matrix.shape[0]:
+            raise ValueError("the device matrix does not hold the pack's series on the pack's device")
+        if pack.n_series == 0:
+            return
+        tmp = DeviceMatrix(pack.n_series, max(plan.n_cols for plan, _ in parts), matrix.device)
+        try:
+            for plan, cols in parts:
+                if plan.n_cols == 0:
+                    continue
+                _check(lib, lib.tsfa_extract_timed(plan._h, ctypes.c_void_p(pack.values_ptr), pack.values_type, None,
+                                                   ctypes.c_void_p(pack.offsets_ptr), pack.n_series, ctypes.c_void_p(tmp.ptr),
+                                                   plan.n_cols, TSFA_DEVICE, None))
+                idx = np.ascontiguousarray(np.asarray(cols, dtype=np.int64) + int(col0), dtype=np.int32)
+                _check(lib, lib.tsfa_scatter_columns(ctypes.c_void_p(matrix.ptr), matrix.ld, idx.ctypes.data_as(ctypes.c_void_p),
+                                                     ctypes.c_void_p(tmp.ptr), pack.n_series, plan.n_cols, matrix.device))
+        finally:
+            tmp.free()
+        return
     values = np.ascontiguousarray(values)
     if values.dtype == np.float32:
         dt = TSFA_F32

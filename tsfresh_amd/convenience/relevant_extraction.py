@@ -34,14 +34,16 @@ def extract_relevant_features(timeseries_container, y, X=None, default_fc_parame
                               test_for_binary_target_binary_feature="fisher", test_for_binary_target_real_feature="mann",
                               test_for_real_target_binary_feature="mann", test_for_real_target_real_feature="kendall",
                               fdr_level=0.05, hypotheses_independent=False, n_jobs=None, distributor=None, chunksize=None,
-                              ml_task="auto", device=None, device_resident=False):
+                              ml_task="auto", device=None, device_resident=False, pack="auto"):
     """Arguments, checks and result of the reference (relevant_extraction.py:150-221).
 
     device_resident=True keeps the feature matrix in HBM for the whole chain: the kinds' feature blocks
     are extracted into one device matrix (tsfa_extract with device pointers), imputed in place (tsfa_impute), ranked
     against y (tsfa_relevance_*), and only the selected columns are fetched (tsfa_gather_columns) -- one PCIe crossing of
     the samples in and of the relevant columns out, instead of the whole matrix out, in, out and in again.  The result
-    equals the default path's; every kind must hold the same ids (the reference joins the kinds on the id)."""
+    equals the default path's; every kind must hold the same ids (the reference joins the kinds on the id).
+
+    pack: "auto" | "host" | "device" as in `extract_features`: where a frame that is not in packed order is grouped and sorted."""
     assert isinstance(y, pd.Series), "y needs to be a pandas.Series, received type: {}.".format(type(y))
     assert len(set(y)) > 1, "Feature selection is only possible if more than 1 label/class is provided"
     if X is not None:
@@ -59,7 +61,8 @@ def extract_relevant_features(timeseries_container, y, X=None, default_fc_parame
         X_sel = _relevant_features_on_device(
             timeseries_container, y, default_fc_parameters, kind_to_fc_parameters, column_id, column_sort, column_kind,
             column_value, show_warnings, test_for_binary_target_real_feature, fdr_level, hypotheses_independent, ml_task,
-            device if device is not None else (distributor.device if distributor is not None else None))
+            device if device is not None else (distributor.device if distributor is not None else None),
+            pack if distributor is None else "host")
         if X is None:
             return X_sel
         return pd.merge(X, X_sel, left_index=True, right_index=True, how="left")
@@ -67,7 +70,8 @@ def extract_relevant_features(timeseries_container, y, X=None, default_fc_parame
                              kind_to_fc_parameters=kind_to_fc_parameters, show_warnings=show_warnings,
                              disable_progressbar=disable_progressbar, profile=profile, n_jobs=n_jobs, chunksize=chunksize,
                              column_id=column_id, column_sort=column_sort, column_kind=column_kind,
-                             column_value=column_value, distributor=distributor, impute_function=impute, device=device)
+                             column_value=column_value, distributor=distributor, impute_function=impute, device=device,
+                             pack=pack if distributor is None or pack != "auto" else "host")
     X_sel = select_features(X_ext, y, test_for_binary_target_binary_feature=test_for_binary_target_binary_feature,
                             test_for_binary_target_real_feature=test_for_binary_target_real_feature,
                             test_for_real_target_binary_feature=test_for_real_target_binary_feature,
@@ -81,7 +85,7 @@ def extract_relevant_features(timeseries_container, y, X=None, default_fc_parame
 
 def _relevant_features_on_device(container, y, default_fc_parameters, kind_to_fc_parameters, column_id, column_sort,
                                  column_kind, column_value, show_warnings, test_for_binary_target_real_feature, fdr_level,
-                                 hypotheses_independent, ml_task, device):
+                                 hypotheses_independent, ml_task, device, pack="host"):
     import warnings
 
     import numpy as np
@@ -100,7 +104,7 @@ def _relevant_features_on_device(container, y, default_fc_parameters, kind_to_fc
     if device is None:
         device = _default_device()
     packed, id_dtype, _ = pack_timeseries(container, column_id=column_id, column_kind=column_kind,
-                                          column_value=column_value, column_sort=column_sort)
+                                          column_value=column_value, column_sort=column_sort, pack=pack, device=device)
     if not packed:
         raise ValueError("the time series container holds no series")
     ids = np.asarray(packed[0].ids)
@@ -124,7 +128,11 @@ def _relevant_features_on_device(container, y, default_fc_parameters, kind_to_fc
         dm = _native.DeviceMatrix(len(ids), len(names), device)
         try:
             for pk, nplan, col0 in jobs:
-                nplan.extract_into(pk.values, pk.offsets, dm, col0=col0, times=pk.times)
+                if pk.device_pack is not None:
+                    nplan.extract_into(None, None, dm, col0=col0, pack=pk.device_pack)
+                    pk.device_pack.close()
+                else:
+                    nplan.extract_into(pk.values, pk.offsets, dm, col0=col0, times=pk.times)
             _trim_cache(_thread_cache())
             _native.impute_matrix(dm)  # impute(): +-inf -> column max / min, NaN -> median of the finite values
             index = pd.Index(ids)

@@ -5,28 +5,78 @@ The reference wraps its three input formats in iterables of single `pd.Series`
 to_tsdata :447) and then walks them one series at a time.  Here the same formats, checks and error messages
 produce, per kind, ONE contiguous value buffer plus an offsets array: the `[n_ids x n_kinds x max_len]` ragged
 layout the kernels consume.  Everything is vectorised (factorize + lexsort); no per-series Python.
+
+A frame whose rows are NOT grouped by ascending id with every group in sort order (a sensor log written in time order, the
+long format, a shuffled frame) can be packed on the device instead (`pack="device"` / `"auto"`, `_native.DevicePack`): the
+columns are uploaded as they are, sorted and gathered there, and the ragged buffer goes to the kernels without returning.
 """
+import warnings
+
 import numpy as np
 import pandas as pd
 
 from tsfresh_amd import _native
 
 _NATIVE_SCAN_MIN_ROWS = 1 << 18  # below this the numpy passes are as fast as spawning the scan threads
+# pack="auto": rows of one kind from which a frame that is not in packed order is packed on the device: the smallest measured
+# power of two at which the device route's median is below the host route's (profiles/pack_device_timing.md: 4.7 ms against
+# 6.5 ms at 2^18 rows, 34 ms against 0.80 s at 2^24)
+_DEVICE_PACK_MIN_ROWS = 1 << 18
+PACK_MODES = ("auto", "host", "device")
+
+
+class _LazyHostValues:
+    """The ragged buffer of a DevicePack, fetched from the device the first time the host looks at it (the data-dependent
+    exceptions of the reference, a user's own calculators): an extraction that needs neither never copies the samples back."""
+
+    def __init__(self, pack):
+        self._pack, self._host = pack, None
+        self.dtype = pack.values_dtype
+
+    def _get(self):
+        if self._host is None:
+            self._host = self._pack.values_host()
+        return self._host
+
+    def __len__(self):
+        return self._pack.n_rows
+
+    def __getitem__(self, item):
+        return self._get()[item]
+
+    def __array__(self, dtype=None, copy=None):
+        a = self._get()
+        return a if dtype is None else a.astype(dtype, copy=False)
 
 
 class PackedKind:
-    """All series of one kind: `values[offsets[i]:offsets[i+1]]` is the series of `ids[i]` (ids sorted)."""
+    """All series of one kind: `values[offsets[i]:offsets[i+1]]` is the series of `ids[i]` (ids sorted).
+    With `device_pack` (a `_native.DevicePack`) the samples and the offsets live on the device: `values` is a lazy host view
+    and `offsets` is fetched on first use."""
 
-    def __init__(self, kind, ids, values, offsets, times=None, sort=None):
+    def __init__(self, kind, ids, values, offsets, times=None, sort=None, device_pack=None):
         self.kind = kind
         self.ids = ids
-        self.values = values
-        self.offsets = offsets
+        self.device_pack = device_pack
+        self.values = values if device_pack is None else _LazyHostValues(device_pack)
+        self._offsets = offsets
         self.times = times  # float64 hours since each series' first timestamp (DatetimeIndex input only)
         self.sort = sort    # the sort column in packed order (None without column_sort); names rolled windows
 
     @property
+    def offsets(self):
+        if self._offsets is None and self.device_pack is not None:
+            self._offsets = self.device_pack.offsets
+        return self._offsets
+
+    @offsets.setter
+    def offsets(self, value):
+        self._offsets = value
+
+    @property
     def n_series(self):
+        if self.device_pack is not None:
+            return self.device_pack.n_series
         return len(self.offsets) - 1
 
 
@@ -130,14 +180,87 @@ def _pack_presorted(kind, ids, values, sort_values, index, nan_name=None):
     return PackedKind(str(kind), uniques, vals, offsets, times, sv)
 
 
-def _pack(kind, ids, values, sort_values, index=None, nan_name=None):
+def _device_pack_columns(ids, values, sort_values, index=None):
+    """What tsfa_pack_device would read for these columns: -> (None, (ids column, unique labels or None, sort column or
+    None, value column)), each column as `_native.pack_column` returns it, or (reason, None) when the frame keeps the host
+    route.  Eligible: integer ids (strings / objects are factorized to codes on the host first: that still leaves the
+    lexsort and the gather to the device); a sort column of an integer type, float32 / float64, datetime64 / timedelta64,
+    or none; a value column of bool, an integer type, float32 or float64.  NOT eligible, and follow-ups rather than part of
+    the device packer: float ids, float16 / longdouble values, sort values that do not compare element-wise (objects),
+    and frames with a DatetimeIndex (the `times` of linear_trend_timewise are pandas arithmetic, `_hours_since_first`).
+    `extract_rolled_features` needs the packed sort column on the host anyway and always packs there."""
+    ids = np.asarray(ids)
+    if index is not None:
+        return "the frame has a DatetimeIndex (linear_trend_timewise's times are computed on the host)", None
+    if len(ids) < 1:
+        return "the frame holds no rows", None
+    labels = None
+    if ids.dtype.kind in "OUS":
+        codes, labels = pd.factorize(ids, sort=True)
+        ids = np.ascontiguousarray(codes, dtype=np.int64)
+        labels = np.asarray(labels)
+    elif ids.dtype.kind not in "iu":
+        return "the id column has dtype {} (integers, strings or objects are packed on the device)".format(ids.dtype), None
+    id_col = _native.pack_column(ids)
+    if id_col is None:
+        return "the id column has dtype {}".format(ids.dtype), None
+    sort_col = None
+    if sort_values is not None:
+        sv = np.asarray(sort_values)
+        if sv.dtype.kind not in "iufmM" or (sv.dtype.kind == "f" and sv.dtype.itemsize not in (4, 8)):
+            return "the sort column has dtype {} (integers, float32 / float64, datetime64 / timedelta64 are packed on " \
+                   "the device)".format(sv.dtype), None
+        sort_col = _native.pack_column(sv)
+        if sort_col is None:
+            return "the sort column has dtype {}".format(sv.dtype), None
+    raw = np.asarray(values)
+    if raw.dtype.kind not in "biuf" or (raw.dtype.kind == "f" and raw.dtype.itemsize not in (4, 8)):
+        return "the value column has dtype {} (bool, integers, float32 / float64 are packed on the device)".format(
+            raw.dtype), None
+    val_col = _native.pack_column(raw)
+    if val_col is None:
+        return "the value column has dtype {}".format(raw.dtype), None
+    return None, (id_col, labels, sort_col, val_col)
+
+
+def _pack_on_device(kind, columns, nan_name, device):
+    id_col, labels, sort_col, val_col = columns
+    dp = _native.DevicePack(id_col, sort_col, val_col, device=device)
+    if dp.value_nan and nan_name is not None:
+        dp.close()
+        raise ValueError("Column must not contain NaN values: {}".format(nan_name))
+    ids = dp.ids if labels is None else labels[dp.ids]
+    return PackedKind(str(kind), ids, None, None, None, None, device_pack=dp)
+
+
+def _pack(kind, ids, values, sort_values, index=None, nan_name=None, pack="host", device=0):
     """Group `values` by `ids` (ascending), each group ordered by `sort_values` (stable).  `index`: the frame's
     DatetimeIndex (row-aligned with `values`) or None.  nan_name: the value column's name if its NaN check
-    (data.py:148-167) has been left to this function."""
+    (data.py:148-167) has been left to this function.
+    pack: "host" -- factorize + lexsort + gather in numpy; "device" -- a frame that is not already in packed order is
+    sorted and gathered on HIP device `device` (ValueError naming the reason when it is not eligible, see
+    `_device_pack_columns`); "auto" -- the device for eligible frames of at least _DEVICE_PACK_MIN_ROWS rows when a device
+    is visible, the host otherwise and (with one warning) when the device allocation fails.  The proof that a frame is
+    already in packed order (`_pack_presorted`) always runs first: that layout costs what it cost before."""
     ids = np.asarray(ids)
     fast = _pack_presorted(kind, ids, values, sort_values, index, nan_name)
     if fast is not None:
         return fast
+    if pack == "device" or (pack == "auto" and len(ids) >= _DEVICE_PACK_MIN_ROWS and _native.device_count() > 0):
+        reason, columns = _device_pack_columns(ids, values, sort_values, index)
+        if reason is not None:
+            if pack == "device":
+                raise ValueError("pack='device': kind {!r} cannot be packed on the device: {}".format(str(kind), reason))
+        elif pack == "device":
+            return _pack_on_device(kind, columns, nan_name, device)
+        else:
+            try:
+                return _pack_on_device(kind, columns, nan_name, device)
+            except _native.NativeError as exc:
+                if exc.code != _native.TSFA_ERR_HIP:
+                    raise
+                warnings.warn("kind {!r}: packing on the device failed ({}); packing on the host instead".format(
+                    str(kind), exc), RuntimeWarning, stacklevel=2)
     _raise_if_nan(_as_values(values), nan_name)
     codes, uniques = pd.factorize(ids, sort=True)
     order = None
@@ -182,7 +305,7 @@ def _arrow_to_frame(table):
     return pd.DataFrame(cols, copy=False)
 
 
-def _pack_arrow_wide(table, column_id, column_kind, column_value, column_sort):
+def _pack_arrow_wide(table, column_id, column_kind, column_value, column_sort, pack="host", device=0):
     """Wide-format pyarrow Table / RecordBatch with primitive, null-free columns: the Arrow buffers go to the packer as
     numpy views (zero copy) -- no pandas frame, no block consolidation.  None -> the caller converts to a DataFrame
     and takes the general route (strings, nulls, chunked columns that need a copy, the long format)."""
@@ -214,14 +337,18 @@ def _pack_arrow_wide(table, column_id, column_kind, column_value, column_sort):
         _raise_if_nan(arrays[name], name)
     ids = arrays[column_id]
     sort_all = arrays[column_sort] if column_sort is not None else None
-    packed = [_pack(c, ids, arrays[c], sort_all, None, nan_name=c) for c in value_columns]
+    packed = [_pack(c, ids, arrays[c], sort_all, None, nan_name=c, pack=pack, device=device) for c in value_columns]
     return packed, ids.dtype, False
 
 
-def pack_timeseries(container, column_id=None, column_kind=None, column_value=None, column_sort=None):
-    """-> (list[PackedKind] in output-column order, dtype of the id column, has_datetime_index)."""
+def pack_timeseries(container, column_id=None, column_kind=None, column_value=None, column_sort=None, pack="host",
+                    device=0):
+    """-> (list[PackedKind] in output-column order, dtype of the id column, has_datetime_index).
+    pack / device: see `_pack` ("host": every kind is packed in numpy, as before the device packer existed)."""
+    if pack not in PACK_MODES:
+        raise ValueError("pack must be one of {}, not {!r}".format(", ".join(repr(m) for m in PACK_MODES), pack))
     if type(container).__module__.startswith("pyarrow") and hasattr(container, "schema"):
-        direct = _pack_arrow_wide(container, column_id, column_kind, column_value, column_sort)
+        direct = _pack_arrow_wide(container, column_id, column_kind, column_value, column_sort, pack, device)
         if direct is not None:
             return direct
         container = _arrow_to_frame(container)
@@ -252,7 +379,7 @@ def pack_timeseries(container, column_id=None, column_kind=None, column_value=No
             for k, kind in enumerate(kuniq):
                 sel = np.nonzero(kcodes == k)[0]
                 packed.append(_pack(kind, ids_all[sel], vals_all[sel], None if sort_all is None else sort_all[sel],
-                                    None if dt_index is None else dt_index[sel]))
+                                    None if dt_index is None else dt_index[sel], pack=pack, device=device))
             return packed, df[column_id].dtype, isinstance(df.index, pd.DatetimeIndex)
         # wide format (data.py:181-230)
         _check_nan(df, column_id)
@@ -265,8 +392,8 @@ def pack_timeseries(container, column_id=None, column_kind=None, column_value=No
         ids_all = df[column_id].to_numpy()
         sort_all = df[column_sort].to_numpy() if column_sort is not None else None
         dt_index = df.index if isinstance(df.index, pd.DatetimeIndex) else None
-        packed = [_pack(col, ids_all, df[col].to_numpy(), sort_all, dt_index, nan_name=col if col in deferred else None)
-                  for col in value_columns]
+        packed = [_pack(col, ids_all, df[col].to_numpy(), sort_all, dt_index, nan_name=col if col in deferred else None,
+                        pack=pack, device=device) for col in value_columns]
         return packed, df[column_id].dtype, isinstance(df.index, pd.DatetimeIndex)
     if isinstance(container, dict):
         # dict of frames, one per kind (data.py:294-338)
@@ -280,7 +407,7 @@ def pack_timeseries(container, column_id=None, column_kind=None, column_value=No
         for kind, frame in container.items():
             sort_vals = frame[column_sort].to_numpy() if column_sort is not None else None
             packed.append(_pack(kind, frame[column_id].to_numpy(), frame[column_value].to_numpy(), sort_vals,
-                                frame.index if isinstance(frame.index, pd.DatetimeIndex) else None))
+                                frame.index if isinstance(frame.index, pd.DatetimeIndex) else None, pack=pack, device=device))
             id_dtype = frame[column_id].dtype
             has_dt = has_dt or isinstance(frame.index, pd.DatetimeIndex)
         return packed, id_dtype, has_dt

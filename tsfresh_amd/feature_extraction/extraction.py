@@ -24,7 +24,7 @@ import numpy as np
 import pandas as pd
 
 from tsfresh_amd import _native
-from tsfresh_amd.feature_extraction.data import pack_timeseries
+from tsfresh_amd.feature_extraction.data import PACK_MODES, pack_timeseries
 from tsfresh_amd.feature_extraction.plan import compile_fc_parameters
 from tsfresh_amd.feature_extraction.reference_errors import check_reference_data_errors
 from tsfresh_amd.feature_extraction.settings import ComprehensiveFCParameters
@@ -68,7 +68,7 @@ def _warn_long_entropy(fc_parameters, pk, show_warnings=False):
         quadratic = False
     if pk.n_series == 0 or not quadratic:
         return
-    longest = int(np.diff(pk.offsets).max())
+    longest = int(np.diff(pk.offsets).max())   # (a device-packed kind fetches its offsets here: n_series + 1 integers)
     if longest > ENTROPY_FAST_MAX_LEN:
         _LONG_ENTROPY_WARNED = True
         warnings.warn("kind {!r}: series of up to {} samples with sample_entropy / approximate_entropy in the settings: these "
@@ -129,10 +129,22 @@ class _CompositePlan:
     def extract_windows_host(self, values, starts, ends, times=None):
         return self._gather(len(starts), lambda pl: pl.extract_windows_host(values, starts, ends, times=times))
 
-    def extract_into(self, values, offsets, matrix, col0=0, times=None):
+    def extract_pack(self, pack):
+        """The series of a `_native.DevicePack`: every part reads the pack's device buffers; nothing is uploaded."""
+        out = _native._result_matrix(pack.n_series, self.n_cols)
+        dm = _native.DeviceMatrix(pack.n_series, self.n_cols, self.parts[0][0].device)
+        try:
+            self.extract_into(None, None, dm, pack=pack)
+            dm.to_host(out=out)
+        finally:
+            dm.free()
+        return out
+
+    def extract_into(self, values, offsets, matrix, col0=0, times=None, pack=None):
         """Columns [col0, col0 + n_cols) of the DeviceMatrix `matrix` (device_resident=True: the feature matrix never leaves
-        HBM): every part extracts into a transient block that tsfa_scatter_columns puts in the caller's column order."""
-        _native.extract_parts_into(self.parts, values, offsets, matrix, col0=col0, times=times)
+        HBM): every part extracts into a transient block that tsfa_scatter_columns puts in the caller's column order.
+        pack: a `_native.DevicePack` instead of host `values` / `offsets`."""
+        _native.extract_parts_into(self.parts, values, offsets, matrix, col0=col0, times=times, pack=pack)
 
 
 def _split_native_specs(specs):
@@ -234,6 +246,7 @@ def extract_features(
     pivot=True,
     device=None,
     devices=None,
+    pack="auto",
 ):
     """Extract features from a pandas container on one MI355X (or, with `devices`, on several).
 
@@ -249,6 +262,13 @@ def extract_features(
         shards, one per device, extracted concurrently from this process (one plan + host thread per device) into one
         page-locked matrix (`tsfresh_amd.distributed.extract_on_devices`).  The reference's counterpart is
         `n_jobs` / a MultiprocessingDistributor over CPU cores (extraction.py:262-275).
+    :param pack: where a frame whose rows are NOT already grouped by ascending id with every group in sort order (rows in
+        time order, the long format, a shuffled frame) is grouped and sorted.  "host": numpy (factorize + lexsort + gather).
+        "device": on the GPU (`tsfa_pack_device`: radix sort + gather, the samples never return to the host); ValueError
+        naming the reason for a frame the device packer does not take (float ids, float16 / longdouble values, object
+        sort values, a DatetimeIndex).  "auto" (default): the device for eligible kinds of at least
+        `data._DEVICE_PACK_MIN_ROWS` rows, the host otherwise.  The result does not depend on the choice.  A frame that IS in
+        packed order never reaches either.  With `devices=[...]` of several devices or a `distributor` the host route is kept.
     :return: `pd.DataFrame` of dtype float64.
     """
     if default_fc_parameters is None and kind_to_fc_parameters is None:
@@ -271,9 +291,6 @@ def extract_features(
         warnings.warn("profile=True (cProfile of the Python calculators) has no meaning for the GPU path; "
                       "use rocprofv3 or Plan.set_profiling instead", stacklevel=2)
 
-    packed, id_dtype, has_dt_index = pack_timeseries(
-        timeseries_container, column_id=column_id, column_kind=column_kind, column_value=column_value,
-        column_sort=column_sort)
     if devices is not None:
         devices = [int(d) for d in devices]
         if not devices:
@@ -282,6 +299,15 @@ def extract_features(
             device = devices[0]
     if device is None:
         device = _default_device()
+    if pack not in PACK_MODES:
+        raise ValueError("pack must be one of {}, not {!r}".format(", ".join(repr(m) for m in PACK_MODES), pack))
+    if (devices is not None and len(devices) > 1) or distributor is not None:
+        if pack == "device":
+            raise ValueError("pack='device': several devices or a distributor keep the host packer")
+        pack = "host"
+    packed, id_dtype, has_dt_index = pack_timeseries(
+        timeseries_container, column_id=column_id, column_kind=column_kind, column_value=column_value,
+        column_sort=column_sort, pack=pack, device=device)
     for pk in packed:   # outside the filter below: this one is about run time, not about a calculator's domain
         _warn_long_entropy(kind_to_fc_parameters[pk.kind] if kind_to_fc_parameters and pk.kind in kind_to_fc_parameters
                            else default_fc_parameters, pk, show_warnings)
@@ -320,7 +346,7 @@ def extract_features(
         multi = devices is not None and len(devices) > 1
         groups = collections.OrderedDict()
         for j, (pk, fplan, nplan) in enumerate(jobs):
-            if nplan is not None and not multi:
+            if nplan is not None and not multi and pk.device_pack is None:
                 groups.setdefault((id(nplan), pk.values.dtype.str, pk.times is not None), []).append(j)
         for members in groups.values():
             total = sum(len(jobs[j][0].values) for j in members)
@@ -352,6 +378,8 @@ def extract_features(
                 # (several native plans: every device uploads its shard ONCE and runs all the parts on it)
                 matrix = extract_on_devices(specs, pk.values, pk.offsets, devices, times=pk.times,
                                             parts=parts if len(parts) > 1 else None)
+            elif pk.device_pack is not None:
+                matrix = nplan.extract_pack(pk.device_pack)   # the samples are in HBM already
             else:
                 matrix = nplan.extract_host(pk.values, pk.offsets, times=pk.times)
             # the reference's exceptions that depend on the samples (an infinite value under binned_entropy / ar_coefficient)
@@ -359,6 +387,8 @@ def extract_features(
             # user-defined calculators (callable keys): per series on the host, spliced in at their dict position
             names, matrix = fplan.finish(matrix, lambda i, pk=pk: pk.values[pk.offsets[i]:pk.offsets[i + 1]], pk.n_series)
             blocks.append((pk, [pk.kind + "__" + name for name in names], matrix))
+            if pk.device_pack is not None:
+                pk.device_pack.close()   # the kind's device buffers go as soon as its features are out
         _trim_cache(_thread_cache())
 
     return _assemble(blocks, id_dtype, pivot, impute_function)
