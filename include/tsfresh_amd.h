@@ -53,6 +53,8 @@ typedef enum tsfa_memspace { TSFA_HOST = 0, TSFA_DEVICE = 1 } tsfa_memspace;
  * parameter combination of the FCParameters dict (tsfresh/feature_extraction/settings.py:165-280).
  * `calc` comes from tsfa_calc_id("<calculator name>"); the meaning of p[] per calculator is listed in
  * tsfresh_amd/csrc/tsfa_specs.h (string-valued parameters such as attr / f_agg are enum codes).
+ * matrix_profile (feature_calculators.py:2385) is served for one explicit integer window: p[0] = windows >= 4,
+ * p[1] = min / max / mean / median / 25 / 75 as 0 .. 5; columns of one window share one profile per series.
  */
 typedef struct tsfa_feature_spec {
     int32_t calc;

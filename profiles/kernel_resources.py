@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Registers / scratch / occupancy of every kernel as the compiler reports them (no GPU needed):
     python profiles/kernel_resources.py [substring filter [source file of csrc/, default tsfa_kernels.hip]]
-    python profiles/kernel_resources.py k_pack tsfa_pack_device.hip"""
+    python profiles/kernel_resources.py k_pack tsfa_pack_device.hip
+    python profiles/kernel_resources.py mprofile                          (k_mprofile: 36 VGPRs, no scratch, dynamic LDS)
+    python profiles/kernel_resources.py mprofile tsfa_kernels_long.hip    (kl_mprofile, the HBM-scratch build: 56 VGPRs, no scratch)"""
 import os
 import re
 import subprocess

@@ -158,7 +158,7 @@ struct tsfa_plan {
     double fill_value = __builtin_nan("");   // TSFA_DEBUG_FILL=<value>: a sentinel instead (profiles/fill_audit.py)
 };
 
-static const char *fam_names[TSFA_N_FAMILIES] = {"k_basic", "k_sort", "k_spectral", "k_ar", "k_entropy", "k_cwtpeaks", "k_seq", "k_trend"};
+static const char *fam_names[TSFA_N_FAMILIES] = {"k_basic", "k_sort", "k_spectral", "k_ar", "k_entropy", "k_cwtpeaks", "k_seq", "k_trend", "k_mprofile"};
 
 template <class T>
 static int upload(const std::vector<T> &h, T **d) {
@@ -221,7 +221,8 @@ void tsfa_plan_destroy(tsfa_plan *plan) {
     plan->stats_buf.release();
     plan->perm_buf.release();
     plan->sel.release();
-    plan->long_scratch.release();
+    plan->long_scratch.release();   // (the HBM slots of every long-series family, k_mprofile's among them)
+    plan->seq_rows.release();
     for (int i = 0; i < TSFA_MAX_CHUNKS; ++i) {
         if (plan->ev_in[i]) (void)hipEventDestroy(plan->ev_in[i]);
         if (plan->ev_k[i]) (void)hipEventDestroy(plan->ev_k[i]);
@@ -365,7 +366,7 @@ int tsfa_plan_create_with_data(const tsfa_feature_spec *specs, int32_t n_specs, 
         if (ok && plan->n_streams > 1) ok = hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming) == hipSuccess;
     }
     if (const char *e = getenv("TSFA_PAIR")) {
-        static const char *nm[TSFA_N_FAMILIES] = {"basic", "sort", "spectral", "ar", "entropy", "cwt", "seq", "trend"};
+        static const char *nm[TSFA_N_FAMILIES] = {"basic", "sort", "spectral", "ar", "entropy", "cwt", "seq", "trend", "mprofile"};
         for (int f = 0; f < TSFA_N_FAMILIES; ++f)
             if (f != TSFA_FAM_BASIC && f != TSFA_FAM_SORT && f != TSFA_FAM_ENTROPY && strstr(e, nm[f])) plan->side_mask |= 1u << f;   // (SORT reads ENTROPY's sample order: both stay on the main lane)
         if (plan->side_mask) {
@@ -557,11 +558,11 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
     // Launch order: longest kernels first.  With side streams (and no per-kernel timing requested) the families are
     // dealt round-robin over the streams after a fork event; the join events bring them back to `st`.
     static const int order_long_first[TSFA_N_FAMILIES] = {TSFA_FAM_ENTROPY, TSFA_FAM_AR, TSFA_FAM_SORT, TSFA_FAM_CWT, TSFA_FAM_BASIC,
-                                                          TSFA_FAM_SEQ, TSFA_FAM_SPECTRAL, TSFA_FAM_TREND};
+                                                          TSFA_FAM_SEQ, TSFA_FAM_SPECTRAL, TSFA_FAM_TREND, TSFA_FAM_MPROFILE};
     // ... unless k_basic shares its per-series statistics (numpy-order mean / variance, extrema: plan->stats_buf,
     // TSFA_STATS_*) with the ENTROPY, AR, SEQ and SORT families, which then skip their own sums: BASIC goes first
     static const int order_basic_first[TSFA_N_FAMILIES] = {TSFA_FAM_BASIC, TSFA_FAM_ENTROPY, TSFA_FAM_AR, TSFA_FAM_SORT, TSFA_FAM_CWT,
-                                                           TSFA_FAM_SEQ, TSFA_FAM_SPECTRAL, TSFA_FAM_TREND};
+                                                           TSFA_FAM_SEQ, TSFA_FAM_SPECTRAL, TSFA_FAM_TREND, TSFA_FAM_MPROFILE};
     const bool overlap = with_overlap && plan->n_streams > 1 && !plan->profiling;
     const bool share_stats = plan->stats_buf.p != nullptr && !overlap && !plan->stream_ok && plan->opt.stats_share;
     const int *order = share_stats ? order_basic_first : order_long_first;
@@ -635,8 +636,8 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                 // the latency hiding there is.  Measured (profiles/nt_sweep.sh, 5 000 series, lengths 4096..8192 /
                 // 2049..4096): number_cwt_peaks gains up to 1024 threads (31.6 -> 12.3 ms), the others peak at 512
                 // beyond 4096 samples and at 256 below (more barriers than work).
-                static const int nt_8k[TSFA_N_FAMILIES] = {512, 512, 512, 512, 256, 1024, 256, 256};
-                static const int nt_4k[TSFA_N_FAMILIES] = {256, 256, 256, 256, 256, 512, 256, 256};
+                static const int nt_8k[TSFA_N_FAMILIES] = {512, 512, 512, 512, 256, 1024, 256, 256, 256};
+                static const int nt_4k[TSFA_N_FAMILIES] = {256, 256, 256, 256, 256, 512, 256, 256, 256};
                 a.nt = (maxn > 4096) ? nt_8k[f] : nt_4k[f];
             }
             if (maxn <= 2048) {
@@ -646,7 +647,7 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                 // AR: one wavefront per series.  Its time is serial linear algebra that a second wavefront only repeated,
                 // and its layout (10 144 B at 1024 samples) puts 16 one-wavefront series on a CU; the workgroup size is
                 // then the same for every length up to 2048, so a series gives the same bits in whatever group it lands.
-                static const int pref[TSFA_N_FAMILIES] = {64, 128, 128, 64, 256, 256, 128, 64};
+                static const int pref[TSFA_N_FAMILIES] = {64, 128, 128, 64, 256, 256, 128, 64, 256};
                 const int cap = std::max(64, ((maxn / 4 + 63) / 64) * 64);
                 a.nt = std::min(pref[f], cap);
             }
@@ -671,6 +672,7 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
             if (f == TSFA_FAM_SPECTRAL && maxn > 2048 && !TSFA_LAB_ONLY(plan->opt.nt[f] >= 64)) a.nt = 512;
             int aux = 0;
             if (f == TSFA_FAM_TREND) aux = a.alt.small_w;   // no n-double work array in LDS (TsfaAltPlan::small_w)
+            if (f == TSFA_FAM_MPROFILE) aux = (dtype == TSFA_F32) ? 4 : 8;   // the series is resident in its input precision
             if (f == TSFA_FAM_SPECTRAL) {
                 // only non-power-of-two lengths <= 256 use the table-driven DFT (longer ones: Goertzel, no table)
                 a.dft_n = (int)std::min<long long>(max_np2, 256);

@@ -235,6 +235,12 @@ static inline void tsfa_prepare_family(int fam, std::vector<TsfaSpec> &specs, Ts
         specs.insert(specs.end(), epi.begin(), epi.end());
         return;
     }
+    if (fam == TSFA_FAM_MPROFILE) {
+        // columns of one window become neighbours (a spec carries its output column): k_mprofile computes a profile when
+        // the window changes -- once per distinct window and series, the windows one after another
+        std::stable_sort(specs.begin(), specs.end(), [](const TsfaSpec &x, const TsfaSpec &y) { return x.p[0] < y.p[0]; });
+        return;
+    }
     if (fam != TSFA_FAM_BASIC && fam != TSFA_FAM_TREND) return;
     // c = number of columns that stay in the column loop; the rest (closed forms, reads of the agg_linear_trend /
     // linear_trend / index_mass_quantile caches that an earlier loop column fills) follow and go to the epilogue
@@ -634,6 +640,10 @@ static inline std::string tsfa_validate_spec(const TsfaSpec &s) {
     case TSFA_C_NUMBER_CWT_PEAKS: if (!(is_int(p[0]) && p[0] >= 1 && p[0] <= 65536)) return "number_cwt_peaks: n must be in [1, 65536]"; break;   // (beyond 16: fam_general.h)
     case TSFA_C_QUERY_SIMILARITY_COUNT:   // (threshold, normalize, offset of the query in the plan's pool, its length; length 0: query=None)
         if (!(is_int(p[2]) && p[2] >= 0 && is_int(p[3]) && p[3] >= 0 && p[3] <= 16777216.0)) return "query_similarity_count: bad query reference";
+        break;
+    case TSFA_C_MATRIX_PROFILE:   // (the window: fam_mprofile.h TSFA_MP_MIN_W; the feature: TSFA_MP_MIN .. TSFA_MP_P75)
+        if (!(is_int(p[0]) && p[0] >= 4 && p[0] <= 2147483647.0)) return "matrix_profile: windows must be one integer >= 4";
+        if (!(is_int(p[1]) && p[1] >= 0 && p[1] <= 5)) return "matrix_profile: feature code must be in [0, 5]";
         break;
     default: break;
     }

@@ -8,6 +8,7 @@
 #include "fam_entropy.h"
 #include "fam_seq.h"
 #include "fam_perm.h"
+#include "fam_mprofile.h"
 #include "fam_sort.h"
 #include "fam_spectral.h"
 #include "fam_general.h"
@@ -276,6 +277,29 @@ __global__ void __launch_bounds__(1024) k_perm(const T *__restrict__ values, con
     TSFA_SERIES_END
 }
 #endif
+
+// every matrix_profile column of the plan (fam_mprofile.h): one workgroup per series, the profiles of the plan's distinct
+// windows one after another
+template <typename T>
+__global__ void __launch_bounds__(256) k_mprofile(const T *__restrict__ values, const int64_t *__restrict__ starts, const int64_t *__restrict__ ends, int64_t n_series, const int *__restrict__ sel,
+                           const TsfaSpec *__restrict__ specs, int nspecs, double *__restrict__ out, int64_t ld, int maxn TSFA_GS_PARAMS) {
+    TSFA_SERIES_BEGIN
+    const int64_t off = starts[sidx];
+    const int n = (int)(ends[sidx] - off);
+    MpLds L;
+    L.carve(tsfa_base, maxn, (int)sizeof(T));
+    TSFA_TICKS_BEGIN();
+    Blk b{(int)threadIdx.x, (int)blockDim.x, L.red, L.np};
+    T *xs = (T *)L.xs;  // resident in the input precision, read as float64
+    {
+        const T *__restrict__ g = values + off;
+        for (int i = b.tid; i < n; i += b.nt) xs[i] = g[i];
+        blk_sync();
+    }
+    fam_mprofile_series(b, XsView<T>{xs}, n, specs, nspecs, out + sidx * ld, L.w);
+    TSFA_TICKS_END();
+    TSFA_SERIES_END
+}
 
 // BL: with the chirp-z transform of long non-power-of-two series (launched when the plan gave the group HBM scratch)
 template <typename T, bool BL>
@@ -1149,6 +1173,10 @@ static int launch_all_t(const TsfaLaunch &a, const T *values) {
             auto kfn = k_seq<T, false>;
             TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.out, a.ld, a.seq, a.stats_in, (unsigned char *)nullptr);
         }
+    } else if (a.fam == TSFA_FAM_MPROFILE) {
+        MpLds L;
+        const size_t lds = L.carve(nullptr, a.maxn, (int)sizeof(T));
+        TSFA_KLAUNCH(k_mprofile<T>, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn);
     } else if (a.fam == TSFA_FAM_CWT) {  // number_cwt_peaks
         CwtPeaksLayout L;
         const size_t lds = L.carve(nullptr, a.maxn, a.cwt_rowv & 1, (int)sizeof(T));
@@ -1318,6 +1346,7 @@ size_t tsfa_family_lds_bytes(int fam, int maxn, int nt, int aux) {
         const size_t lds16 = L.carve(nullptr, maxn, aux, 8, 2);
         return lds16 > TSFA_LDS_LIMIT ? L.carve(nullptr, maxn, aux, 8, 4) : lds16;
     }
+    case TSFA_FAM_MPROFILE: { MpLds L; return L.carve(nullptr, maxn, aux); }   // aux: element size of the resident series
     default: return 0;
     }
 }

@@ -10,4 +10,5 @@
 #define k_entropy kl_entropy
 #define k_seq kl_seq
 #define k_cwtpeaks kl_cwtpeaks
+#define k_mprofile kl_mprofile
 #include "tsfa_kernels.hip"

@@ -95,7 +95,7 @@ struct TsfaCwtLaunch {
 size_t tsfa_family_lds_bytes(int fam, int maxn, int nt, int aux);
 size_t tsfa_entropy_lds_bytes(int maxn, int with_cnt);
 size_t tsfa_seq_lds_bytes(const TsfaSeqGroup &g);
-int tsfa_launch_family(const TsfaLaunch &a);
+int tsfa_launch_family(const TsfaLaunch &a);         // (TSFA_FAM_MPROFILE: k_mprofile reads specs / nspecs / maxn only; its aux is the sample size)
 int tsfa_launch_rows(const TsfaLaunch &a);          // BASIC / TREND: the series of at most TSFA_ROW_MAXN samples, four per wavefront (k_basic_rows / k_trend_rows)
 int tsfa_launch_family_long(const TsfaLaunch &a);   // working set in a.long_scratch instead of LDS (any length <= 65535)
 // k_general (fam_general.h): a.specs / a.nspecs = the plan's GENERAL columns, every series of the batch in one launch

@@ -9,6 +9,7 @@
 #include "tsfa_common.h"
 #include "fam_cwt.h"
 #include "fam_seq.h"
+#include "fam_mprofile.h"
 #include "tsfa_entb_params.h"
 
 #if defined(__HIPCC__)
@@ -283,6 +284,26 @@ struct PermLds {
         ltab = c.take<double>((size_t)log_doubles);
         iw = c.take<int>((size_t)hist_words + 4);
         xs = (void *)c.take<unsigned char>((size_t)(maxn + 8) * elem_bytes);
+        return c.off;
+    }
+};
+
+// k_mprofile (fam_mprofile.h): the series in the input precision and five 8-byte arrays per window -- mean, inverse norm, the
+// two difference arrays of the diagonal recurrence (contiguous: the epilogue sorts the distances in their storage) and the
+// 64-bit keys of the running maxima.  40 bytes per sample + the series: float64 series up to 3 332 samples, float32 up to
+// 3 636, fit a CU's 160 KB; longer ones run from the long-series build's HBM slot.
+struct MpLds {
+    double *red; NpScratch *np; void *xs; MpWork w;
+    TSFA_HD size_t carve(unsigned char *base, int maxn, int xs_bytes = 8) {
+        LdsCarve c{base, 0};
+        red = c.take<double>(TSFA_RED_DOUBLES);
+        np = c.take<NpScratch>(1);
+        xs = c.take<unsigned char>((size_t)maxn * xs_bytes);
+        w.mu = c.take<double>((size_t)maxn);
+        w.inv = c.take<double>((size_t)maxn);
+        w.df = c.take<double>(2 * (size_t)maxn);
+        w.dg = w.df + maxn;
+        w.key = c.take<mp_key_t>((size_t)maxn);
         return c.off;
     }
 };

@@ -30,6 +30,7 @@
 //   augmented_dickey_fuller         : p0 = attr (TSFA_ADF_*), p1 = lag selection (TSFA_AUTOLAG_*, one value per plan)
 //   approximate_entropy             : p0 = m, p1 = r
 //   cwt_coefficients                : p0 = w (the width), p1 = coeff
+//   matrix_profile                  : p0 = windows (one integer >= 4), p1 = feature (TSFA_MP_*, fam_mprofile.h)
 #ifndef TSFA_SPECS_H
 #define TSFA_SPECS_H
 
@@ -44,7 +45,8 @@ enum tsfa_family {
     TSFA_FAM_CWT = 5,     // Ricker/mexh contractions (MFMA) + ridge lines
     TSFA_FAM_SEQ = 6,     // inherently sequential parses
     TSFA_FAM_TREND = 7,   // cumulative sums / chunk aggregates / regressions over the series (float64 work array)
-    TSFA_N_FAMILIES = 8
+    TSFA_FAM_MPROFILE = 8,// O(L^2) diagonal sweep of the z-normalised self-join (fam_mprofile.h)
+    TSFA_N_FAMILIES = 9
 };
 
 #define TSFA_CALC_LIST(X)                                                              \
@@ -122,7 +124,8 @@ enum tsfa_family {
     X(CWT_COEFFICIENTS, "cwt_coefficients", TSFA_FAM_CWT)                               \
     X(NUMBER_CWT_PEAKS, "number_cwt_peaks", TSFA_FAM_CWT)                               \
     X(LEMPEL_ZIV_COMPLEXITY, "lempel_ziv_complexity", TSFA_FAM_SEQ)                     \
-    X(LINEAR_TREND_TIMEWISE, "linear_trend_timewise", TSFA_FAM_TREND)
+    X(LINEAR_TREND_TIMEWISE, "linear_trend_timewise", TSFA_FAM_TREND)                   \
+    X(MATRIX_PROFILE, "matrix_profile", TSFA_FAM_MPROFILE)
 
 enum tsfa_calc {
 #define X(id, name, fam) TSFA_C_##id,

@@ -51,6 +51,10 @@ _TLS = threading.local()
 # the right values, for any length, but these two calculators are then nearly all of its time and the caller should know
 ENTROPY_FAST_MAX_LEN = 17408
 _QUADRATIC = ("sample_entropy", "approximate_entropy")
+# matrix_profile is O((n - w + 1)^2) as well; its working set leaves LDS for HBM scratch beyond ~3 300 samples
+# (tsfa_layout.h: MpLds), so the caller hears about it from this length on
+MPROFILE_FAST_MAX_LEN = 4096
+_LONG_MPROFILE_WARNED = False
 
 
 _LONG_ENTROPY_WARNED = False
@@ -76,6 +80,26 @@ def _warn_long_entropy(fc_parameters, pk, show_warnings=False):
                       "milliseconds per series at 32 768 samples on a full MI355X, four times that per doubling: nearly all of the "
                       "extraction).  EfficientFCParameters() leaves them out, as the reference recommends for long series.".format(pk.kind, longest, ENTROPY_FAST_MAX_LEN),
                       UserWarning, stacklevel=3)
+
+
+def _warn_long_mprofile(fc_parameters, pk, show_warnings=False):
+    """The O(n^2) warning for plans that hold matrix_profile: once per process, like `_warn_long_entropy`."""
+    global _LONG_MPROFILE_WARNED
+    if _LONG_MPROFILE_WARNED and not show_warnings:
+        return
+    try:
+        quadratic = "matrix_profile" in fc_parameters
+    except TypeError:
+        quadratic = False
+    if pk.n_series == 0 or not quadratic:
+        return
+    longest = int(np.diff(pk.offsets).max())
+    if longest > MPROFILE_FAST_MAX_LEN:
+        _LONG_MPROFILE_WARNED = True
+        warnings.warn("kind {!r}: series of up to {} samples with matrix_profile in the settings: the calculator is "
+                      "O((n - windows)^2) per series and beyond {} samples its working set leaves LDS for HBM scratch: it "
+                      "returns the right values for any length, but is then nearly all of the extraction.".format(
+                          pk.kind, longest, MPROFILE_FAST_MAX_LEN), UserWarning, stacklevel=3)
 
 
 def _thread_cache():
@@ -309,8 +333,10 @@ def extract_features(
         timeseries_container, column_id=column_id, column_kind=column_kind, column_value=column_value,
         column_sort=column_sort, pack=pack, device=device)
     for pk in packed:   # outside the filter below: this one is about run time, not about a calculator's domain
-        _warn_long_entropy(kind_to_fc_parameters[pk.kind] if kind_to_fc_parameters and pk.kind in kind_to_fc_parameters
-                           else default_fc_parameters, pk, show_warnings)
+        fc_of_kind = (kind_to_fc_parameters[pk.kind] if kind_to_fc_parameters and pk.kind in kind_to_fc_parameters
+                      else default_fc_parameters)
+        _warn_long_entropy(fc_of_kind, pk, show_warnings)
+        _warn_long_mprofile(fc_of_kind, pk, show_warnings)
 
     with warnings.catch_warnings():
         if not show_warnings:

@@ -84,8 +84,8 @@ def compile_fc_parameters(fc_parameters, has_datetime_index=False):
 
     Column order follows the reference: calculators in dict order, parameter sets in list order
     (extraction.py:339-378).  Raises UnsupportedFeature for a LIBRARY calculator that has no native kernel
-    (matrix_profile, query_similarity_count with a query) instead of silently computing it on the CPU; a user's own
-    callable key is the user's code and runs on the host (FeaturePlan.finish).
+    (matrix_profile without an explicit integer window, registry._matrix_profile_encode) instead of silently computing
+    it on the CPU; a user's own callable key is the user's code and runs on the host (FeaturePlan.finish).
     """
     names, specs, seen = [], [], set()
     host_calls, layout, seg_start = [], [], 0

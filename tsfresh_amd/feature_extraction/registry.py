@@ -191,9 +191,10 @@ _CALCS = [
     Calc("count_above", "simple", encode=lambda p: (p["t"],)),
     Calc("count_below", "simple", encode=lambda p: (p["t"],)),
     _simple0("benford_correlation"),
-    # feature_calculators.py:2385 needs the optional `matrixprofile` package; without it the reference drops the
-    # calculator from its settings (settings.py:282-292).  It is registered only so that the name is known.
-    Calc("matrix_profile", "combiner", native=False),
+    # feature_calculators.py:2385: served for an explicit window (`_matrix_profile_encode`); the reference drops the
+    # calculator from its settings objects when the optional `matrixprofile` package is missing (settings.py:282-292),
+    # and so do ours
+    Calc("matrix_profile", "combiner", key=convert_to_output_format),
     Calc("query_similarity_count", "combiner", key=convert_to_output_format),
 ]
 
@@ -214,3 +215,34 @@ def _query_similarity_encode(p):
 
 
 CALCULATORS["query_similarity_count"]._encode = _query_similarity_encode
+
+
+FEATURE_MP = {"min": 0, "max": 1, "mean": 2, "median": 3, "25": 4, "75": 5}   # fam_mprofile.h TSFA_MP_*
+
+
+def _matrix_profile_encode(p):
+    """(windows, feature code).  fc.py:2385-2470 has two routes.  With `windows` given as one integer,
+    `matrixprofile.compute(x, windows=w)["mp"]` is the exact z-normalised self-join matrix profile (Yeh et al. 2016):
+    fam_mprofile.h.  Every other route is a search heuristic or a randomised approximation of that package, with no
+    published definition to check a kernel against: refused by name.  `threshold` only steers the no-window search and is
+    ignored (it stays part of the column name)."""
+    import numbers
+    if "windows" not in p or p["windows"] is None:
+        raise UnsupportedFeature("matrix_profile without `windows`: the reference then calls matrixprofile's "
+                                 "maximum_subsequence search, which has no published definition; give one integer window")
+    w = p["windows"]
+    if isinstance(w, bool) or not isinstance(w, numbers.Integral):
+        raise UnsupportedFeature("matrix_profile: `windows` must be a single integer, not {!r} (several windows make "
+                                 "the package's pan-matrix profile, which is not served)".format(w))
+    if w < 4:
+        raise UnsupportedFeature("matrix_profile: `windows` must be at least 4, not {}".format(w))
+    if "sample_pct" in p and p["sample_pct"] != 1:
+        raise UnsupportedFeature("matrix_profile: sample_pct = {!r} selects the package's randomised approximation; only "
+                                 "the exact profile (sample_pct = 1) is served".format(p["sample_pct"]))
+    feature = p.get("feature")
+    if feature not in FEATURE_MP:
+        raise ValueError("Unknown feature {} for the matrix profile".format(feature))   # fc.py:2469
+    return (int(w), FEATURE_MP[feature])
+
+
+CALCULATORS["matrix_profile"]._encode = _matrix_profile_encode

@@ -111,7 +111,8 @@ def _comprehensive_parameters():
         "mean_n_absolute_max": [{"number_of_maxima": 7}],
     })
     # matrix_profile needs the optional `matrixprofile` dependency; the reference drops it when that is
-    # missing (settings.py:282-292), which is the only configuration that can be reproduced here.
+    # missing (settings.py:282-292), which is the only configuration that can be reproduced here.  A caller's own
+    # dict may ask for it with an explicit window (registry._matrix_profile_encode); from_columns round-trips that.
     name_to_param.pop("matrix_profile", None)
     return name_to_param
 
