@@ -241,6 +241,48 @@ int tsfa_pack_device_copy_offsets(const tsfa_pack *pack, int64_t *offsets_host);
 int tsfa_pack_device_copy_sort(const tsfa_pack *pack, void *sort_host);
 void tsfa_pack_device_destroy(tsfa_pack *pack);
 
+/* Pack set: a frame of several kinds -- tsfresh's long format (one kind column), or a wide frame with several value columns
+ * -- is sorted ONCE and hands out one ordinary tsfa_pack per kind.  Replaces, for those two formats, the host's per-kind
+ * selection (factorize, nonzero, three gathers per kind) and the K uploads and K sorts of K tsfa_pack_device calls.
+ *   tsfa_pack_set_create   sorts the rows stably by (kind, id, sort), the kind being the most significant key, with the keys,
+ *                          the LSD radix sort and the pass-skipping rule of tsfa_pack_device.
+ *       kinds      NULL (one kind: a wide frame) or any integer type of tsfa_dtype except TSFA_BOOL (callers with string
+ *                  kinds pass factorized codes; dense codes below 256 cost one pass, a constant column none)
+ *       options    TSFA_PACK_KEEP_SORT or 0
+ *     Shortcuts: rows already in (id, sort) order with the kinds interleaved (the usual long frame) run ONLY the kind passes
+ *     (the sort is stable); rows already in (kind, id, sort) order run none and the set reports TSFA_PACK_IN_ORDER.
+ *     A row heads a series when its (kind, id) differs from its predecessor's: the last series of one kind and the first of
+ *     the next may carry the same id.  Kinds may hold different id sets.
+ *     Bytes per row: the kind key is not part of the sort's scratch record, a kind pass reads its digit through the row index
+ *     (kinds[perm[i]]), so the scratch while the call runs is tsfa_pack_device's 40 bytes per row + 1 KiB per 4096 rows + the
+ *     staged id / sort / kind columns.  The set keeps 4 bytes per row (the permutation), the int64 offsets of the whole sorted
+ *     frame (n_groups + 1), with several kinds every kind's offsets rebased to its first row (n_groups + n_kinds int64), the
+ *     unique ids of every (kind, id) group and, with TSFA_PACK_KEEP_SORT, the sort column in packed order.
+ *   tsfa_pack_set_n_kinds  distinct kind values (1 when kinds == NULL)
+ *   tsfa_pack_set_copy_kinds  the distinct kind values, ascending, in the kind column's own element type (n_kinds elements);
+ *                          TSFA_ERR_INVALID for a set without a kind column
+ *   tsfa_pack_set_flags    TSFA_PACK_IN_ORDER;  tsfa_pack_set_n_passes: radix passes that ran (0 .. 24)
+ *   tsfa_pack_set_values   gathers ONE value column (n_rows elements, row-aligned with the key columns; conversions and the
+ *                          TSFA_PACK_VALUE_NAN flag as in tsfa_pack_device) through the stored permutation into one new buffer
+ *                          and writes n_kinds tsfa_pack handles, kind k (ascending) at out_packs[k].  Each handle is a view:
+ *                          its values are the kind's row range of that buffer, its offsets start at 0, its ids are the kind's
+ *                          own, and every tsfa_pack_device_* accessor and tsfa_extract* work on it unchanged.  A wide frame
+ *                          calls it once per value column (one handle per call; the handles share the set's offsets and ids),
+ *                          a long frame once.  Scratch: the staged value column.
+ * Ownership is reference-counted: the set and the packs may be destroyed in any order (each with its own destroy function);
+ * a shared buffer is freed with its last holder, a value buffer with its last view.  More than 2^31 - 1 kinds:
+ * TSFA_ERR_TOO_LONG.  Otherwise the errors of tsfa_pack_device. */
+typedef struct tsfa_pack_set tsfa_pack_set; /* opaque; owned by the library */
+int tsfa_pack_set_create(const void *ids, int32_t id_type, const void *sort, int32_t sort_type, const void *kinds,
+                         int32_t kind_type, int64_t n_rows, int32_t space, int32_t options, int32_t device,
+                         tsfa_pack_set **out_set);
+int32_t tsfa_pack_set_n_kinds(const tsfa_pack_set *set);
+int tsfa_pack_set_copy_kinds(const tsfa_pack_set *set, void *kinds_host);
+int32_t tsfa_pack_set_flags(const tsfa_pack_set *set);
+int32_t tsfa_pack_set_n_passes(const tsfa_pack_set *set);
+int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int32_t value_type, int32_t space, tsfa_pack **out_packs);
+void tsfa_pack_set_destroy(tsfa_pack_set *set);
+
 /* Page-locked host memory for the TSFA_HOST form.  tsfa_extract* accepts ANY host pointer; from pageable memory the HIP
  * runtime stages every transfer through its own bounce buffers, from memory obtained here the copy engines read and
  * write it directly, so the chunked copy-in / compute / copy-out pipeline of tsfa_extract runs at PCIe rate.  The

@@ -49,6 +49,13 @@ EXPORTS = (
     "tsfa_pack_device_copy_offsets",
     "tsfa_pack_device_copy_sort",
     "tsfa_pack_device_destroy",
+    "tsfa_pack_set_create",
+    "tsfa_pack_set_n_kinds",
+    "tsfa_pack_set_copy_kinds",
+    "tsfa_pack_set_flags",
+    "tsfa_pack_set_n_passes",
+    "tsfa_pack_set_values",
+    "tsfa_pack_set_destroy",
     "tsfa_impute",
     "tsfa_relevance_classes",
     "tsfa_relevance_classes_ks",
@@ -313,6 +320,10 @@ class DevicePack:
             None if sort_a is None else sort_a.ctypes.data_as(ctypes.c_void_p), sort_t,
             val_a.ctypes.data_as(ctypes.c_void_p), val_t, len(ids_a), TSFA_HOST,
             TSFA_PACK_KEEP_SORT if (keep_sort and sort_a is not None) else 0, int(device), ctypes.byref(handle)))
+        self._adopt(lib, handle, device, ids_a.dtype, None if sort_a is None or not keep_sort else sort_a.dtype)
+
+    def _adopt(self, lib, handle, device, ids_dtype, sort_dtype):
+        """Take over a `tsfa_pack*` (one made by tsfa_pack_device, or a view handed out by a DevicePackSet)."""
         self._lib, self._h, self.device = lib, handle, int(device)
         self.n_rows = int(lib.tsfa_pack_device_n_rows(handle))
         self.n_series = int(lib.tsfa_pack_device_n_groups(handle))
@@ -323,9 +334,9 @@ class DevicePack:
         self.values_ptr, self.values_type = vptr.value, int(vtype.value)
         self.values_dtype = np.dtype(np.float32 if self.values_type == TSFA_F32 else np.float64)
         self.offsets_ptr = lib.tsfa_pack_device_offsets(handle)
-        self._sort_dtype = None if sort_a is None or not keep_sort else sort_a.dtype
+        self._sort_dtype = sort_dtype
         self._offsets = self._sort = None
-        self.ids = np.empty(self.n_series, dtype=ids_a.dtype)
+        self.ids = np.empty(self.n_series, dtype=ids_dtype)
         _check(lib, lib.tsfa_pack_device_copy_ids(handle, self.ids.ctypes.data_as(ctypes.c_void_p)))
 
     @property
@@ -364,6 +375,102 @@ class DevicePack:
         if getattr(self, "_h", None):
             self._lib.tsfa_pack_device_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            if not sys.is_finalizing():
+                self.close()
+        except Exception:
+            pass
+
+
+def _bind_pack_set_api(lib):
+    """The tsfa_pack_set_* prototypes, bound on first use (a diagnostics library given through TSFA_LIB may predate them)."""
+    if getattr(lib, "_tsfa_pack_set_bound", False):
+        return
+    lib.tsfa_pack_set_create.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                         ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.POINTER(ctypes.c_void_p)]
+    lib.tsfa_pack_set_create.restype = ctypes.c_int
+    for name in ("n_kinds", "flags", "n_passes"):
+        fn = getattr(lib, "tsfa_pack_set_" + name)
+        fn.argtypes, fn.restype = [ctypes.c_void_p], ctypes.c_int32
+    lib.tsfa_pack_set_copy_kinds.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.tsfa_pack_set_copy_kinds.restype = ctypes.c_int
+    lib.tsfa_pack_set_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.POINTER(ctypes.c_void_p)]
+    lib.tsfa_pack_set_values.restype = ctypes.c_int
+    lib.tsfa_pack_set_destroy.argtypes = [ctypes.c_void_p]
+    lib.tsfa_pack_set_destroy.restype = None
+    lib._tsfa_pack_set_bound = True
+
+
+class DevicePackSet:
+    """Owns a `tsfa_pack_set*`: a frame of several kinds in ANY row order, sorted ONCE by (kind, id, sort) on the device
+    (tsfa_pack_set_create).  `values(column)` gathers one value column through the stored permutation and returns one
+    DevicePack per kind, in ascending order of the kind values (`.kinds`): views into one gathered buffer that share the
+    set's offsets and ids.  The views and the set may be closed in any order; a buffer goes with its last holder.
+    ids / sort / kinds: what `pack_column` returned; sort may be None, kinds may be None (one kind: a wide frame, one
+    `values` call per value column)."""
+
+    def __init__(self, ids, sort, kinds, device=0, keep_sort=False):
+        lib = load()
+        _bind_device_api(lib)
+        _bind_pack_set_api(lib)
+        ids_a, ids_t = ids
+        sort_a, sort_t = sort if sort is not None else (None, 0)
+        kind_a, kind_t = kinds if kinds is not None else (None, 0)
+        if any(c is not None and len(c) != len(ids_a) for c in (sort_a, kind_a)):
+            raise ValueError("the id, sort and kind columns must have one entry per row")
+        handle = ctypes.c_void_p()
+        _check(lib, lib.tsfa_pack_set_create(
+            ids_a.ctypes.data_as(ctypes.c_void_p), ids_t,
+            None if sort_a is None else sort_a.ctypes.data_as(ctypes.c_void_p), sort_t,
+            None if kind_a is None else kind_a.ctypes.data_as(ctypes.c_void_p), kind_t, len(ids_a), TSFA_HOST,
+            TSFA_PACK_KEEP_SORT if (keep_sort and sort_a is not None) else 0, int(device), ctypes.byref(handle)))
+        self._lib, self._h, self.device = lib, handle, int(device)
+        self.n_rows = len(ids_a)
+        self.n_kinds = int(lib.tsfa_pack_set_n_kinds(handle))
+        self.flags = int(lib.tsfa_pack_set_flags(handle))
+        self.n_passes = int(lib.tsfa_pack_set_n_passes(handle))
+        self._ids_dtype = ids_a.dtype
+        self._sort_dtype = None if sort_a is None or not keep_sort else sort_a.dtype
+        self.kinds = None
+        if kind_a is not None:
+            self.kinds = np.empty(self.n_kinds, dtype=kind_a.dtype)
+            _check(lib, lib.tsfa_pack_set_copy_kinds(handle, self.kinds.ctypes.data_as(ctypes.c_void_p)))
+
+    @property
+    def was_in_order(self):
+        return bool(self.flags & TSFA_PACK_IN_ORDER)
+
+    def values(self, column):
+        """column: what `pack_column` returned for a value column of n_rows entries -> [DevicePack per kind]."""
+        val_a, val_t = column
+        if len(val_a) != self.n_rows:
+            raise ValueError("the value column must have one entry per row")
+        if not self._h:
+            raise ValueError("the pack set is closed")
+        handles = (ctypes.c_void_p * self.n_kinds)()
+        _check(self._lib, self._lib.tsfa_pack_set_values(self._h, val_a.ctypes.data_as(ctypes.c_void_p), val_t, TSFA_HOST,
+                                                         handles))
+        packs = []
+        for h in handles:
+            pack = DevicePack.__new__(DevicePack)   # a view: no tsfa_pack_device call
+            packs.append(pack)
+            pack._adopt(self._lib, ctypes.c_void_p(h), self.device, self._ids_dtype, self._sort_dtype)
+        return packs
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.tsfa_pack_set_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:

@@ -16,6 +16,12 @@
 //   + tiles x 256 x 4 B digit counts (one tile = PK_TILE = 4096 rows: 0.25 B per row)
 //   + with TSFA_HOST inputs the staged id / sort / value columns.
 //
+// Pack set (tsfa_pack_set_*): the rows are sorted ONCE by (kind, id, sort) and every value column is gathered through the
+// stored permutation.  The kind key does not travel in the scratch record: a kind pass reads its digit through the row
+// index (PkKindDigit), so the scratch stays at 40 B per row (+ the staged kind column with TSFA_HOST).  What the set keeps
+// after tsfa_pack_set_create: 4 B per row (the permutation), 8 B per group (+ 8 B per group and kind of rebased offsets
+// when there are several kinds), the unique ids, and with TSFA_PACK_KEEP_SORT the packed sort column.
+//
 // Determinism: a pass is three launches (per-tile digit histogram, exclusive scan over (digit, tile), stable scatter).  No
 // workgroup ever waits on a word another workgroup writes: no decoupled look-back, no spin of any kind.  Atomics are used
 // only where the arrival order cannot matter (counts, min / max, the NaN flag).
@@ -246,19 +252,46 @@ static inline int pk_plan_passes(const PkStats *st, int64_t n_rows, int has_sort
 }
 
 // ---------------------------------------------------------------------------------------------
+// Where a pass reads its digit.  PkKeyDigit: byte `shift / 8` of a key word that travels with the row (the id and sort
+// passes).  PkKindDigit: the kind key is NOT part of the scratch record; its digit is read through the row index,
+// kinds[idx[i]], with the minimum subtracted on the fly (the pack set's kind passes: 0 extra bytes of scratch per row,
+// one gathered read of a narrow column per row and launch).
+// ---------------------------------------------------------------------------------------------
+struct PkKeyDigit {
+    const pk_u64 *key;
+    int shift;
+};
+struct PkKindDigit {
+    const void *kinds;
+    int type;
+    pk_u64 kmin;
+    const uint32_t *idx;
+    int shift;
+};
+TSFA_DEV int pk_digit(const PkKeyDigit &d, int64_t i) { return (int)((d.key[i] >> d.shift) & 255u); }
+TSFA_DEV int pk_digit(const PkKindDigit &d, int64_t i) {
+    return (int)(((pk_load_key(d.kinds, d.type, (int64_t)d.idx[i]) - d.kmin) >> d.shift) & 255u);
+}
+
+// ---------------------------------------------------------------------------------------------
 // 3a. per-tile digit histogram -> counts[digit * n_tiles + tile]   (`lh`: 256 uint32 of LDS)
 // ---------------------------------------------------------------------------------------------
-TSFA_DEV void pk_hist_body(const PkBlk &b, int64_t tile, int64_t n_tiles, const pk_u64 *key, int shift, int64_t n,
-                           unsigned int *lh, uint32_t *counts) {
+template <class D>
+TSFA_DEV void pk_hist_impl(const PkBlk &b, int64_t tile, int64_t n_tiles, const D &dg, int64_t n, unsigned int *lh,
+                           uint32_t *counts) {
     for (int d = b.tid; d < PK_RADIX; d += b.nt) lh[d] = 0;
     pk_sync();
     const int64_t t0 = tile * PK_TILE;
     for (int k = b.tid; k < PK_TILE; k += b.nt) {
         const int64_t i = t0 + k;
-        if (i < n) pk_add32(&lh[(int)((key[i] >> shift) & 255u)], 1u);
+        if (i < n) pk_add32(&lh[pk_digit(dg, i)], 1u);
     }
     pk_sync();
     for (int d = b.tid; d < PK_RADIX; d += b.nt) counts[(size_t)d * (size_t)n_tiles + (size_t)tile] = lh[d];
+}
+TSFA_DEV void pk_hist_body(const PkBlk &b, int64_t tile, int64_t n_tiles, const pk_u64 *key, int shift, int64_t n,
+                           unsigned int *lh, uint32_t *counts) {
+    pk_hist_impl(b, tile, n_tiles, PkKeyDigit{key, shift}, n, lh, counts);
 }
 
 // exclusive prefix of v over the lower-numbered threads of the workgroup, and the workgroup total (`ws`: 16 uint32 of LDS)
@@ -319,9 +352,10 @@ TSFA_DEV void pk_scan_body(const PkBlk &b, uint32_t *data, size_t m, unsigned in
 //     eight 64-bit ballots narrow the mask of lanes holding the same digit, rank = popcount of that mask below the lane.
 //     (`wbase`: waves x 256 uint32 of LDS = 4 KiB)
 // ---------------------------------------------------------------------------------------------
-TSFA_DEV void pk_scatter_body(const PkBlk &b, int64_t tile, int64_t n_tiles, const pk_u64 *key, int shift, int64_t n,
-                              const uint32_t *scanned, const pk_u64 *hi_in, const pk_u64 *lo_in, const uint32_t *idx_in,
-                              pk_u64 *hi_out, pk_u64 *lo_out, uint32_t *idx_out, unsigned int *wbase) {
+template <class D>
+TSFA_DEV void pk_scatter_impl(const PkBlk &b, int64_t tile, int64_t n_tiles, const D &dg, int64_t n, const uint32_t *scanned,
+                              const pk_u64 *hi_in, const pk_u64 *lo_in, const uint32_t *idx_in, pk_u64 *hi_out,
+                              pk_u64 *lo_out, uint32_t *idx_out, unsigned int *wbase) {
     const int L = pk_lanes(b), W = b.nt / L, lane = b.tid % L, w = b.tid / L;
     const int chunk = PK_TILE / W, rounds = chunk / L;
     const int64_t w0 = tile * PK_TILE + (int64_t)w * chunk;
@@ -330,7 +364,7 @@ TSFA_DEV void pk_scatter_body(const PkBlk &b, int64_t tile, int64_t n_tiles, con
     pk_sync();
     for (int r = 0; r < rounds; ++r) {
         const int64_t i = w0 + (int64_t)r * L + lane;
-        if (i < n) pk_add32(&mine[(int)((key[i] >> shift) & 255u)], 1u);
+        if (i < n) pk_add32(&mine[pk_digit(dg, i)], 1u);
     }
     pk_sync();
     for (int d = b.tid; d < PK_RADIX; d += b.nt) {
@@ -345,7 +379,7 @@ TSFA_DEV void pk_scatter_body(const PkBlk &b, int64_t tile, int64_t n_tiles, con
     for (int r = 0; r < rounds; ++r) {
         const int64_t i = w0 + (int64_t)r * L + lane;
         const bool valid = i < n;
-        const int d = valid ? (int)((key[i] >> shift) & 255u) : 0;
+        const int d = valid ? pk_digit(dg, i) : 0;
 #if TSFA_GPU
         pk_u64 same = __ballot(valid);
 #pragma unroll
@@ -372,10 +406,46 @@ TSFA_DEV void pk_scatter_body(const PkBlk &b, int64_t tile, int64_t n_tiles, con
         pk_sync();  // the next round reads what this round's leaders wrote
     }
 }
+TSFA_DEV void pk_scatter_body(const PkBlk &b, int64_t tile, int64_t n_tiles, const pk_u64 *key, int shift, int64_t n,
+                              const uint32_t *scanned, const pk_u64 *hi_in, const pk_u64 *lo_in, const uint32_t *idx_in,
+                              pk_u64 *hi_out, pk_u64 *lo_out, uint32_t *idx_out, unsigned int *wbase) {
+    pk_scatter_impl(b, tile, n_tiles, PkKeyDigit{key, shift}, n, scanned, hi_in, lo_in, idx_in, hi_out, lo_out, idx_out, wbase);
+}
 
 // ---------------------------------------------------------------------------------------------
-// 4. group boundaries along the sorted order: row i heads a group when its id key differs from row i - 1's
+// 4. group boundaries along the sorted order: row i heads a group when its id key differs from row i - 1's -- or, in a
+//    pack set with a kind column, when its KIND differs: the last series of kind a and the first series of kind b often
+//    carry the same id.  A kind head is a row whose kind differs from its predecessor's (row 0 is both).  The kind of a
+//    sorted row is read through the row index.  kinds == NULL: one kind, the id alone decides.
 // ---------------------------------------------------------------------------------------------
+TSFA_DEV bool pk_kind_head(const void *kinds, int kind_type, const uint32_t *idx, int64_t i) {
+    if (i == 0) return true;
+    return kinds && pk_load_key(kinds, kind_type, (int64_t)idx[i]) != pk_load_key(kinds, kind_type, (int64_t)idx[i - 1]);
+}
+
+// cnt_lds: 2 uint32 of LDS; tile_kheads may be NULL (no kind column)
+TSFA_DEV void pk_set_heads_count_body(const PkBlk &b, int64_t tile, const pk_u64 *hi, const uint32_t *idx, const void *kinds,
+                                      int kind_type, int64_t n, unsigned int *cnt_lds, uint32_t *tile_heads,
+                                      uint32_t *tile_kheads) {
+    if (b.tid == 0) cnt_lds[0] = cnt_lds[1] = 0;
+    pk_sync();
+    const int64_t t0 = tile * PK_TILE;
+    unsigned int c = 0, ck = 0;
+    for (int k = b.tid; k < PK_TILE; k += b.nt) {
+        const int64_t i = t0 + k;
+        if (i >= n) continue;
+        const bool kh = pk_kind_head(kinds, kind_type, idx, i);
+        if (kh) ++ck;
+        if (kh || hi[i] != hi[i - 1]) ++c;
+    }
+    if (c) pk_add32(&cnt_lds[0], c);
+    if (ck) pk_add32(&cnt_lds[1], ck);
+    pk_sync();
+    if (b.tid == 0) {
+        tile_heads[tile] = cnt_lds[0];
+        if (tile_kheads) tile_kheads[tile] = cnt_lds[1];
+    }
+}
 TSFA_DEV void pk_heads_count_body(const PkBlk &b, int64_t tile, const pk_u64 *hi, int64_t n, unsigned int *cnt_lds,
                                   uint32_t *tile_heads) {
     if (b.tid == 0) *cnt_lds = 0;
@@ -392,15 +462,21 @@ TSFA_DEV void pk_heads_count_body(const PkBlk &b, int64_t tile, const pk_u64 *hi
 }
 
 // offsets[g] = first sorted row of group g, uniq[g] = its id in the column's own dtype; offsets[n_groups] = n.
-// tile_heads: the exclusive scan of pk_heads_count_body's counts.  (`ws`: 16 uint32 of LDS)
-TSFA_DEV void pk_groups_body(const PkBlk &b, int64_t tile, const pk_u64 *hi, const uint32_t *idx, int64_t n,
-                             const uint32_t *tile_heads, int64_t n_groups, const void *ids, int id_size, int64_t *offsets,
-                             void *uniq, unsigned int *ws) {
+// tile_heads: the exclusive scan of the head counts.  (`ws`: 16 uint32 of LDS)
+// With a kind column (tile_kheads: the exclusive scan of the kind-head counts) also, for kind number k in ascending order:
+// kind_rows[k] = its first sorted row, kind_groups[k] = its first group, kind_vals[k] = its value in the kind column's own
+// dtype; kind_rows[n_kinds] = n and kind_groups[n_kinds] = n_groups.  Without one (tile_kheads == NULL) the kind_* outputs
+// are not touched.
+TSFA_DEV void pk_set_groups_body(const PkBlk &b, int64_t tile, const pk_u64 *hi, const uint32_t *idx, const void *kinds,
+                                 int kind_type, int64_t n, const uint32_t *tile_heads, const uint32_t *tile_kheads,
+                                 int64_t n_groups, int64_t n_kinds, const void *ids, int id_size, int64_t *offsets, void *uniq,
+                                 int64_t *kind_rows, int64_t *kind_groups, void *kind_vals, unsigned int *ws) {
     const int64_t t0 = tile * PK_TILE;
-    uint32_t run = tile_heads[tile];
+    uint32_t run = tile_heads[tile], krun = tile_kheads ? tile_kheads[tile] : 0u;
     for (int k0 = 0; k0 < PK_TILE; k0 += b.nt) {
         const int64_t i = t0 + k0 + b.tid;
-        const bool head = i < n && (i == 0 || hi[i] != hi[i - 1]);
+        const bool khead = i < n && pk_kind_head(kinds, kind_type, idx, i);
+        const bool head = i < n && (khead || hi[i] != hi[i - 1]);
         uint32_t tot;
         const uint32_t g = run + pk_blk_excl_sum(b, head ? 1u : 0u, ws, &tot);
         if (head && (int64_t)g < n_groups) {
@@ -409,6 +485,119 @@ TSFA_DEV void pk_groups_body(const PkBlk &b, int64_t tile, const pk_u64 *hi, con
         }
         if (i == n - 1) offsets[n_groups] = n;
         run += tot;
+        if (tile_kheads) {
+            uint32_t ktot;
+            const uint32_t kk = krun + pk_blk_excl_sum(b, khead ? 1u : 0u, ws, &ktot);
+            if (khead && (int64_t)kk < n_kinds) {
+                kind_rows[kk] = i;
+                kind_groups[kk] = (int64_t)g;
+                if (kinds) pk_copy_raw(kind_vals, (int64_t)kk, kinds, (int64_t)idx[i], pk_itemsize(kind_type));
+            }
+            if (i == n - 1) {
+                kind_rows[n_kinds] = n;
+                kind_groups[n_kinds] = n_groups;
+            }
+            krun += ktot;
+        }
+    }
+}
+TSFA_DEV void pk_groups_body(const PkBlk &b, int64_t tile, const pk_u64 *hi, const uint32_t *idx, int64_t n,
+                             const uint32_t *tile_heads, int64_t n_groups, const void *ids, int id_size, int64_t *offsets,
+                             void *uniq, unsigned int *ws) {
+    pk_set_groups_body(b, tile, hi, idx, nullptr, 0, n, tile_heads, nullptr, n_groups, 0, ids, id_size, offsets, uniq, nullptr,
+                       nullptr, nullptr, ws);
+}
+
+// ---------------------------------------------------------------------------------------------
+// 4b. the pack set's third key.  One read of the three key columns: min / max of the kind key and the descents of the
+//     composite (kind, id, sort) key (grid-stride; `red`: 3 pk_u64 of LDS); then the 256-bin histogram of every
+//     significant byte of (kind key - minimum) (`lh`: 8 x 256 uint32 of LDS).
+// ---------------------------------------------------------------------------------------------
+struct PkSetStats {
+    pk_u64 kmin, kmax;            // kind key (order-preserving image, before the minimum is subtracted)
+    pk_u64 descents;              // rows whose (kind, id, sort) key is smaller than their predecessor's
+    unsigned int n_kinds;         // total of the kind-head scan
+    unsigned int hist[8][PK_RADIX];
+};
+
+static inline void pk_set_stats_init(PkSetStats *s) {
+    memset(s, 0, sizeof(*s));
+    s->kmin = ~0ull;
+}
+
+TSFA_DEV void pk_kind_minmax_body(const PkBlk &b, int64_t first, int64_t stride, const void *kinds, int kind_type,
+                                  const void *ids, int id_type, const void *sort, int sort_type, int64_t n, pk_u64 *red,
+                                  PkSetStats *st) {
+    if (b.tid == 0) {
+        red[0] = ~0ull; red[1] = 0; red[2] = 0;
+    }
+    pk_sync();
+    pk_u64 mn = ~0ull, mx = 0, desc = 0;
+    for (int64_t i = first + b.tid; i < n; i += stride) {
+        const pk_u64 kk = pk_load_key(kinds, kind_type, i);
+        mn = kk < mn ? kk : mn; mx = kk > mx ? kk : mx;
+        if (i > 0) {
+            const pk_u64 pv = pk_load_key(kinds, kind_type, i - 1);
+            bool less = kk < pv;
+            if (kk == pv) {
+                const pk_u64 k0 = pk_load_key(ids, id_type, i), p0 = pk_load_key(ids, id_type, i - 1);
+                less = k0 < p0;
+                if (k0 == p0 && sort) less = pk_load_key(sort, sort_type, i) < pk_load_key(sort, sort_type, i - 1);
+            }
+            if (less) ++desc;
+        }
+    }
+    pk_min64(&red[0], mn); pk_max64(&red[1], mx);
+    if (desc) pk_add64(&red[2], desc);
+    pk_sync();
+    if (b.tid == 0) {
+        pk_min64(&st->kmin, red[0]); pk_max64(&st->kmax, red[1]);
+        if (red[2]) pk_add64(&st->descents, red[2]);
+    }
+}
+
+TSFA_DEV void pk_kind_hist_body(const PkBlk &b, int64_t first, int64_t stride, const void *kinds, int kind_type, int64_t n,
+                                pk_u64 kmin, int nb, unsigned int *lh, PkSetStats *st) {
+    for (int k = b.tid; k < 8 * PK_RADIX; k += b.nt) lh[k] = 0;
+    pk_sync();
+    for (int64_t i = first + b.tid; i < n; i += stride) {
+        const pk_u64 kk = pk_load_key(kinds, kind_type, i) - kmin;
+        for (int k = 0; k < nb; ++k) pk_add32(&lh[k * PK_RADIX + (int)((kk >> (8 * k)) & 255u)], 1u);
+    }
+    pk_sync();
+    for (int k = b.tid; k < 8 * PK_RADIX; k += b.nt)
+        if (lh[k]) pk_add32(&st->hist[k >> 8][k & 255], lh[k]);
+}
+
+// The kind passes, least significant first, by pk_plan_passes' rule.  They run AFTER the sort and id passes: the kind is
+// the most significant key.  Host code.
+static inline int pk_plan_kind_passes(const PkSetStats *st, int64_t n_rows, int *pass_byte) {
+    int np = 0;
+    const int nb = pk_sig_bytes(st->kmax - st->kmin);
+    for (int k = 0; k < nb; ++k) {
+        bool constant = false;
+        for (int d = 0; d < PK_RADIX; ++d)
+            if ((int64_t)st->hist[k][d] == n_rows) { constant = true; break; }
+        if (!constant) pass_byte[np++] = k;
+    }
+    return np;
+}
+
+// ---------------------------------------------------------------------------------------------
+// 4c. the offsets of every kind of a pack set, rebased to the kind's first row, in ONE buffer of n_groups + n_kinds int64:
+//     kind k owns elements [kind_groups[k] + k, kind_groups[k + 1] + k + 1) = global[kind_groups[k] .. kind_groups[k + 1]]
+//     - kind_rows[k].  Element e finds its kind by bisection over the n_kinds starts.  (grid-stride)
+// ---------------------------------------------------------------------------------------------
+TSFA_DEV void pk_rebase_body(const PkBlk &b, int64_t first, int64_t stride, const int64_t *global, const int64_t *kind_rows,
+                             const int64_t *kind_groups, int64_t n_kinds, int64_t total, int64_t *out) {
+    for (int64_t e = first + b.tid; e < total; e += stride) {
+        int64_t lo = 0, hi = n_kinds - 1;  // the largest k with kind_groups[k] + k <= e
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (kind_groups[mid] + mid <= e) lo = mid;
+            else hi = mid - 1;
+        }
+        out[e] = global[e - lo] - kind_rows[lo];
     }
 }
 

@@ -2,7 +2,9 @@
 // and the host code that strings them together.  See pack_device.h for the scratch formula and the sort's design.
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <string>
+#include <vector>
 
 #include "pack_device.h"
 
@@ -13,11 +15,31 @@ struct tsfa_pack {
     int64_t n_rows = 0, n_groups = 0;
     int32_t flags = 0, n_passes = 0;
     int32_t id_type = 0, sort_type = 0, out_type = TSFA_F64;
-    // owned device buffers: ALL of them are freed by tsfa_pack_device_destroy
+    // device buffers.  A pack made by tsfa_pack_device owns all four: tsfa_pack_device_destroy frees them.  A pack handed
+    // out by tsfa_pack_set_values is a VIEW: the pointers look into buffers it shares with the set and with its sibling
+    // packs, hold[k] keeps buffer k alive, and destroying the pack only drops those references.
     void *values = nullptr;      // ragged buffer, n_rows x out_type
     int64_t *offsets = nullptr;  // n_groups + 1
     void *uniq = nullptr;        // n_groups x id_type
     void *sort = nullptr;        // n_rows x sort_type (TSFA_PACK_KEEP_SORT)
+    std::shared_ptr<void> hold[4];  // values, offsets, uniq, sort
+};
+
+// One frame sorted once by (kind, id, sort): see include/tsfresh_amd.h.  Every device buffer is reference-counted: it goes
+// with its last holder, the set or a pack, whichever is destroyed last.
+struct tsfa_pack_set {
+    int32_t device = 0;
+    int64_t n_rows = 0, n_groups = 0;
+    int32_t n_kinds = 0, flags = 0, n_passes = 0;
+    int32_t id_type = 0, sort_type = 0, kind_type = 0;
+    bool has_kinds = false;
+    std::shared_ptr<void> perm;     // n_rows x uint32: sorted position -> input row
+    std::shared_ptr<void> offsets;  // n_groups + 1 int64 over the whole sorted frame
+    std::shared_ptr<void> rebased;  // n_groups + n_kinds int64 (several kinds only): pk_rebase_body's layout
+    std::shared_ptr<void> uniq;     // n_groups x id_type; kind k owns [kind_groups[k], kind_groups[k + 1])
+    std::shared_ptr<void> sort;     // n_rows x sort_type (TSFA_PACK_KEEP_SORT)
+    std::vector<int64_t> kind_rows, kind_groups;  // n_kinds + 1 each (host copies)
+    std::vector<unsigned char> kind_vals;         // n_kinds x kind_type (host copy), ascending
 };
 
 namespace {
@@ -85,15 +107,74 @@ __global__ void __launch_bounds__(PK_GRID_THREADS) k_pack_gather_raw(const void 
     pk_gather_raw_body(b, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, col, itemsize, idx, n, out);
 }
 
-int pk_fail_hip(const char *what, hipError_t e) {
-    return tsfa_fail(TSFA_ERR_HIP, (std::string("tsfa_pack_device: ") + what + ": " + hipGetErrorString(e)).c_str());
+// ---- the pack set's kernels ----
+__global__ void __launch_bounds__(PK_GRID_THREADS) k_pack_kind_minmax(const void *kinds, int kind_type, const void *ids, int id_type,
+                                                                        const void *sort, int sort_type, int64_t n, PkSetStats *st) {
+    __shared__ pk_u64 red[3];
+    const PkBlk b{(int)threadIdx.x, (int)blockDim.x};
+    pk_kind_minmax_body(b, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, kinds, kind_type, ids, id_type, sort,
+                        sort_type, n, red, st);
 }
+
+__global__ void __launch_bounds__(PK_GRID_THREADS) k_pack_kind_hist(const void *kinds, int kind_type, int64_t n, pk_u64 kmin, int nb,
+                                                                      PkSetStats *st) {
+    __shared__ unsigned int lh[8 * PK_RADIX];
+    const PkBlk b{(int)threadIdx.x, (int)blockDim.x};
+    pk_kind_hist_body(b, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, kinds, kind_type, n, kmin, nb, lh, st);
+}
+
+__global__ void __launch_bounds__(PK_THREADS) k_pack_hist_kind(int64_t n_tiles, PkKindDigit dg, int64_t n, uint32_t *counts) {
+    __shared__ unsigned int lh[PK_RADIX];
+    const PkBlk b{(int)threadIdx.x, PK_THREADS};
+    pk_hist_impl(b, (int64_t)blockIdx.x, n_tiles, dg, n, lh, counts);
+}
+
+__global__ void __launch_bounds__(PK_THREADS) k_pack_scatter_kind(int64_t n_tiles, PkKindDigit dg, int64_t n, const uint32_t *scanned,
+                                                                   const pk_u64 *hi_in, const pk_u64 *lo_in, const uint32_t *idx_in,
+                                                                   pk_u64 *hi_out, pk_u64 *lo_out, uint32_t *idx_out) {
+    __shared__ unsigned int wbase[(PK_THREADS / 64) * PK_RADIX];
+    const PkBlk b{(int)threadIdx.x, PK_THREADS};
+    pk_scatter_impl(b, (int64_t)blockIdx.x, n_tiles, dg, n, scanned, hi_in, lo_in, idx_in, hi_out, lo_out, idx_out, wbase);
+}
+
+__global__ void __launch_bounds__(PK_THREADS) k_pack_set_heads(const pk_u64 *hi, const uint32_t *idx, const void *kinds, int kind_type,
+                                                                int64_t n, uint32_t *tile_heads, uint32_t *tile_kheads) {
+    __shared__ unsigned int cnt[2];
+    const PkBlk b{(int)threadIdx.x, PK_THREADS};
+    pk_set_heads_count_body(b, (int64_t)blockIdx.x, hi, idx, kinds, kind_type, n, cnt, tile_heads, tile_kheads);
+}
+
+__global__ void __launch_bounds__(PK_THREADS) k_pack_set_groups(const pk_u64 *hi, const uint32_t *idx, const void *kinds, int kind_type,
+                                                                 int64_t n, const uint32_t *tile_heads, const uint32_t *tile_kheads,
+                                                                 int64_t n_groups, int64_t n_kinds, const void *ids, int id_size,
+                                                                 int64_t *offsets, void *uniq, int64_t *kind_rows, int64_t *kind_groups,
+                                                                 void *kind_vals) {
+    __shared__ unsigned int ws[16];
+    const PkBlk b{(int)threadIdx.x, PK_THREADS};
+    pk_set_groups_body(b, (int64_t)blockIdx.x, hi, idx, kinds, kind_type, n, tile_heads, tile_kheads, n_groups, n_kinds, ids, id_size,
+                       offsets, uniq, kind_rows, kind_groups, kind_vals, ws);
+}
+
+__global__ void __launch_bounds__(PK_GRID_THREADS) k_pack_rebase(const int64_t *global, const int64_t *kind_rows,
+                                                                   const int64_t *kind_groups, int64_t n_kinds, int64_t total,
+                                                                   int64_t *out) {
+    const PkBlk b{(int)threadIdx.x, (int)blockDim.x};
+    pk_rebase_body(b, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, global, kind_rows, kind_groups, n_kinds, total,
+                   out);
+}
+
+int pk_fail_hip(const char *what, hipError_t e, const char *who = "tsfa_pack_device") {
+    return tsfa_fail(TSFA_ERR_HIP, (std::string(who) + ": " + what + ": " + hipGetErrorString(e)).c_str());
+}
+
+// the function the two macros below name in their messages (redefined in front of tsfa_pack_set_*)
+#define PK_WHO "tsfa_pack_device"
 
 #define PK_HIP(expr)                                        \
     do {                                                    \
         hipError_t e_ = (expr);                             \
         if (e_ != hipSuccess) {                             \
-            rc = pk_fail_hip(#expr, e_);                    \
+            rc = pk_fail_hip(#expr, e_, PK_WHO);                 \
             goto done;                                      \
         }                                                   \
     } while (0)
@@ -105,7 +186,7 @@ int pk_fail_hip(const char *what, hipError_t e) {
         hipError_t e_ = hipMalloc((void **)&(ptr), nb_ ? nb_ : 1);                                                        \
         if (e_ != hipSuccess) {                                                                                           \
             (ptr) = nullptr;                                                                                              \
-            rc = tsfa_fail(TSFA_ERR_HIP, (std::string("tsfa_pack_device: cannot allocate ") + std::to_string(nb_) +       \
+            rc = tsfa_fail(TSFA_ERR_HIP, (std::string(PK_WHO ": cannot allocate ") + std::to_string(nb_) +                 \
                                           " bytes of device memory for " + (what) + ": " + hipGetErrorString(e_)).c_str()); \
             goto done;                                                                                                    \
         }                                                                                                                 \
@@ -283,12 +364,269 @@ extern "C" int tsfa_pack_device_copy_sort(const tsfa_pack *pack, void *sort_host
 
 extern "C" void tsfa_pack_device_destroy(tsfa_pack *pack) {
     if (!pack) return;
-    if (pack->values || pack->offsets || pack->uniq || pack->sort) {
+    void *const bufs[4] = {pack->values, pack->offsets, pack->uniq, pack->sort};
+    for (int k = 0; k < 4; ++k) {
+        if (pack->hold[k] || !bufs[k]) continue;  // a view: the reference goes with `delete`
         (void)hipSetDevice(pack->device);
-        (void)hipFree(pack->values);
-        (void)hipFree(pack->offsets);
-        (void)hipFree(pack->uniq);
-        (void)hipFree(pack->sort);
+        (void)hipFree(bufs[k]);
     }
     delete pack;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Pack set: one sort per frame, one ordinary tsfa_pack per kind and value column
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+std::shared_ptr<void> pk_share(void *p, int32_t device) {
+    return std::shared_ptr<void>(p, [device](void *q) {
+        (void)hipSetDevice(device);
+        (void)hipFree(q);
+    });
+}
+
+}  // namespace
+
+#undef PK_WHO
+#define PK_WHO "tsfa_pack_set_create"
+extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void *sort, int32_t sort_type, const void *kinds,
+                                    int32_t kind_type, int64_t n_rows, int32_t space, int32_t options, int32_t device,
+                                    tsfa_pack_set **out_set) {
+    if (!out_set) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: out_set is NULL");
+    *out_set = nullptr;
+    if (!ids || n_rows < 1 || (space != TSFA_HOST && space != TSFA_DEVICE) || (options & ~TSFA_PACK_KEEP_SORT))
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: bad arguments");
+    if (!pk_is_key_type(id_type, false)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: the id column must be of an integer type");
+    if (sort && !pk_is_key_type(sort_type, true))
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: the sort column must be of an integer type, float32 or float64");
+    if (kinds && !pk_is_key_type(kind_type, false))
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: the kind column must be of an integer type");
+    if ((options & TSFA_PACK_KEEP_SORT) && !sort)
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: TSFA_PACK_KEEP_SORT without a sort column");
+    int rc = pk_check_device(device);
+    if (rc) return rc;
+    if (n_rows > 0xffffffffll)
+        return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_pack_set_create: more than 4 294 967 295 rows (the row indices are 32 bits wide)");
+
+    const int64_t n = n_rows, n_tiles = (n + PK_TILE - 1) / PK_TILE;
+    const int id_size = pk_itemsize(id_type), sort_size = sort ? pk_itemsize(sort_type) : 0, kind_size = kinds ? pk_itemsize(kind_type) : 0;
+    void *d_ids = nullptr, *d_sort = nullptr, *d_kinds = nullptr;  // staged copies (TSFA_HOST only)
+    pk_u64 *hi[2] = {nullptr, nullptr}, *lo[2] = {nullptr, nullptr};
+    uint32_t *idx[2] = {nullptr, nullptr}, *counts = nullptr;
+    int64_t *d_offsets = nullptr, *d_rebased = nullptr, *d_krows = nullptr, *d_kgroups = nullptr;
+    void *d_uniq = nullptr, *d_kvals = nullptr, *d_psort = nullptr;
+    PkStats *d_st = nullptr;
+    PkSetStats *d_ks = nullptr;
+    PkStats st;
+    PkSetStats ks;
+    tsfa_pack_set *set = new tsfa_pack_set();
+    int cur = 0;
+    set->device = device; set->n_rows = n; set->id_type = id_type; set->sort_type = sort ? sort_type : 0;
+    set->kind_type = kinds ? kind_type : 0; set->has_kinds = kinds != nullptr;
+
+    PK_HIP(hipSetDevice(device));
+    if (space == TSFA_HOST) {
+        PK_ALLOC(d_ids, (size_t)n * id_size, "the id column");
+        PK_HIP(hipMemcpy(d_ids, ids, (size_t)n * id_size, hipMemcpyHostToDevice));
+        if (sort) {
+            PK_ALLOC(d_sort, (size_t)n * sort_size, "the sort column");
+            PK_HIP(hipMemcpy(d_sort, sort, (size_t)n * sort_size, hipMemcpyHostToDevice));
+        }
+        if (kinds) {
+            PK_ALLOC(d_kinds, (size_t)n * kind_size, "the kind column");
+            PK_HIP(hipMemcpy(d_kinds, kinds, (size_t)n * kind_size, hipMemcpyHostToDevice));
+        }
+        ids = d_ids; sort = d_sort; kinds = d_kinds;
+    }
+    PK_ALLOC(d_st, sizeof(PkStats), "the packer's counters");
+    PK_ALLOC(d_ks, sizeof(PkSetStats), "the packer's kind counters");
+    pk_stats_init(&st);
+    pk_set_stats_init(&ks);
+    PK_HIP(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
+    PK_HIP(hipMemcpy(d_ks, &ks, sizeof(ks), hipMemcpyHostToDevice));
+
+    // 1. min / max of the three keys, descents of (id, sort) and of (kind, id, sort)
+    k_pack_minmax<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, d_st);
+    if (kinds) k_pack_kind_minmax<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(kinds, kind_type, ids, id_type, sort, sort_type, n, d_ks);
+    PK_HIP(hipGetLastError());
+    PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
+    PK_HIP(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
+    {
+        const bool inner_in_order = st.descents == 0;                       // (id, sort): only the kind passes are left
+        const bool in_order = kinds ? ks.descents == 0 : inner_in_order;    // (kind, id, sort): nothing is sorted
+        if (in_order) set->flags |= TSFA_PACK_IN_ORDER;
+        // 2. id and sort keys, identity permutation, byte histograms
+        for (int k = 0; k < (in_order ? 1 : 2); ++k) {
+            PK_ALLOC(hi[k], (size_t)n * 8, "the id keys (sort scratch: 40 bytes per row in all)");
+            PK_ALLOC(lo[k], (size_t)n * 8, "the sort keys (sort scratch: 40 bytes per row in all)");
+            PK_ALLOC(idx[k], (size_t)n * 4, "the row indices (sort scratch: 40 bytes per row in all)");
+        }
+        PK_ALLOC(counts, (size_t)n_tiles * PK_RADIX * 4, "the per-tile digit counts");
+        const int inner_passes = (in_order || inner_in_order) ? 0 : 1;
+        k_pack_keys<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, st.kmin[0], sort ? st.kmin[1] : 0ull,
+                                                             pk_sig_bytes(st.kmax[0] - st.kmin[0]),
+                                                             sort ? pk_sig_bytes(st.kmax[1] - st.kmin[1]) : 0, inner_passes, hi[0],
+                                                             lo[0], idx[0], d_st);
+        if (kinds && !in_order)
+            k_pack_kind_hist<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(kinds, kind_type, n, ks.kmin, pk_sig_bytes(ks.kmax - ks.kmin), d_ks);
+        PK_HIP(hipGetLastError());
+        if (!in_order) {
+            // 3. the radix passes, least significant digit first: sort bytes, id bytes, kind bytes; constant digits are skipped
+            int pass_word[16], pass_byte[16], kind_byte[8];
+            PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
+            PK_HIP(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
+            const int np = inner_passes ? pk_plan_passes(&st, n, sort != nullptr, pass_word, pass_byte) : 0;
+            for (int p = 0; p < np; ++p) {
+                const pk_u64 *key = pass_word[p] ? lo[cur] : hi[cur];
+                const int shift = 8 * pass_byte[p];
+                k_pack_hist<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, counts);
+                k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles * PK_RADIX, nullptr);
+                k_pack_scatter<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, counts, hi[cur], lo[cur], idx[cur],
+                                                                         hi[cur ^ 1], lo[cur ^ 1], idx[cur ^ 1]);
+                PK_HIP(hipGetLastError());
+                cur ^= 1;
+            }
+            const int nkp = kinds ? pk_plan_kind_passes(&ks, n, kind_byte) : 0;
+            for (int p = 0; p < nkp; ++p) {
+                const PkKindDigit dg{kinds, kind_type, ks.kmin, idx[cur], 8 * kind_byte[p]};
+                k_pack_hist_kind<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, dg, n, counts);
+                k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles * PK_RADIX, nullptr);
+                k_pack_scatter_kind<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, dg, n, counts, hi[cur], lo[cur], idx[cur],
+                                                                              hi[cur ^ 1], lo[cur ^ 1], idx[cur ^ 1]);
+                PK_HIP(hipGetLastError());
+                cur ^= 1;
+            }
+            set->n_passes = np + nkp;
+        }
+    }
+    // 4. group and kind boundaries (counts is reused: [0, n_tiles) head counts, [n_tiles, 2 n_tiles) kind-head counts)
+    k_pack_set_heads<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi[cur], idx[cur], kinds, kind_type, n, counts, counts + n_tiles);
+    k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles, &d_st->n_groups);
+    k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts + n_tiles, (size_t)n_tiles, &d_ks->n_kinds);
+    PK_HIP(hipGetLastError());
+    PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
+    PK_HIP(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
+    if (ks.n_kinds > 0x7fffffffu) {
+        rc = tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_pack_set_create: more than 2 147 483 647 distinct kinds");
+        goto done;
+    }
+    set->n_groups = (int64_t)st.n_groups;
+    set->n_kinds = (int32_t)ks.n_kinds;
+    {
+        const int64_t nk = set->n_kinds, ng = set->n_groups;
+        PK_ALLOC(d_offsets, (size_t)(ng + 1) * 8, "the offsets");
+        PK_ALLOC(d_uniq, (size_t)ng * id_size, "the unique ids");
+        PK_ALLOC(d_krows, (size_t)(nk + 1) * 8, "the kinds' row ranges");
+        PK_ALLOC(d_kgroups, (size_t)(nk + 1) * 8, "the kinds' group ranges");
+        PK_ALLOC(d_kvals, (size_t)nk * kind_size, "the kind values");
+        k_pack_set_groups<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi[cur], idx[cur], kinds, kind_type, n, counts, counts + n_tiles, ng, nk,
+                                                                    ids, id_size, d_offsets, d_uniq, d_krows, d_kgroups, d_kvals);
+        PK_HIP(hipGetLastError());
+        if (nk > 1) {
+            PK_ALLOC(d_rebased, (size_t)(ng + nk) * 8, "the offsets of every kind");
+            k_pack_rebase<<<pk_grid(ng + nk), PK_GRID_THREADS, 0, 0>>>(d_offsets, d_krows, d_kgroups, nk, ng + nk, d_rebased);
+            PK_HIP(hipGetLastError());
+        }
+        if (options & TSFA_PACK_KEEP_SORT) {
+            PK_ALLOC(d_psort, (size_t)n * sort_size, "the packed sort column");
+            k_pack_gather_raw<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(sort, sort_size, idx[cur], n, d_psort);
+            PK_HIP(hipGetLastError());
+        }
+        set->kind_rows.resize((size_t)nk + 1);
+        set->kind_groups.resize((size_t)nk + 1);
+        set->kind_vals.resize((size_t)nk * kind_size);
+        PK_HIP(hipMemcpy(set->kind_rows.data(), d_krows, (size_t)(nk + 1) * 8, hipMemcpyDeviceToHost));  // (synchronises)
+        PK_HIP(hipMemcpy(set->kind_groups.data(), d_kgroups, (size_t)(nk + 1) * 8, hipMemcpyDeviceToHost));
+        if (kind_size) PK_HIP(hipMemcpy(set->kind_vals.data(), d_kvals, (size_t)nk * kind_size, hipMemcpyDeviceToHost));
+    }
+    // the set takes over what outlives the call
+    set->perm = pk_share(idx[cur], device); idx[cur] = nullptr;
+    set->offsets = pk_share(d_offsets, device); d_offsets = nullptr;
+    set->uniq = pk_share(d_uniq, device); d_uniq = nullptr;
+    if (d_rebased) { set->rebased = pk_share(d_rebased, device); d_rebased = nullptr; }
+    if (d_psort) { set->sort = pk_share(d_psort, device); d_psort = nullptr; }
+done:
+    for (int k = 0; k < 2; ++k) {
+        (void)hipFree(hi[k]); (void)hipFree(lo[k]); (void)hipFree(idx[k]);
+    }
+    (void)hipFree(counts); (void)hipFree(d_st); (void)hipFree(d_ks);
+    (void)hipFree(d_ids); (void)hipFree(d_sort); (void)hipFree(d_kinds);
+    (void)hipFree(d_offsets); (void)hipFree(d_rebased); (void)hipFree(d_krows); (void)hipFree(d_kgroups);
+    (void)hipFree(d_uniq); (void)hipFree(d_kvals); (void)hipFree(d_psort);
+    if (rc) {
+        delete set;
+        return rc;
+    }
+    *out_set = set;
+    return TSFA_OK;
+}
+
+extern "C" int32_t tsfa_pack_set_n_kinds(const tsfa_pack_set *set) { return set ? set->n_kinds : 0; }
+extern "C" int32_t tsfa_pack_set_flags(const tsfa_pack_set *set) { return set ? set->flags : 0; }
+extern "C" int32_t tsfa_pack_set_n_passes(const tsfa_pack_set *set) { return set ? set->n_passes : 0; }
+
+extern "C" int tsfa_pack_set_copy_kinds(const tsfa_pack_set *set, void *kinds_host) {
+    if (!set || !kinds_host) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_copy_kinds: null pointer");
+    if (!set->has_kinds) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_copy_kinds: the set was made without a kind column");
+    memcpy(kinds_host, set->kind_vals.data(), set->kind_vals.size());
+    return TSFA_OK;
+}
+
+#undef PK_WHO
+#define PK_WHO "tsfa_pack_set_values"
+extern "C" int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int32_t value_type, int32_t space, tsfa_pack **out_packs) {
+    if (!set || !values || !out_packs || (space != TSFA_HOST && space != TSFA_DEVICE))
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_values: bad arguments");
+    const int val_size = pk_itemsize(value_type);
+    if (val_size == 0) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_values: unknown element type of the value column");
+    const int64_t n = set->n_rows;
+    const int out_type = pk_out_type(value_type), out_size = pk_itemsize(out_type);
+    const int id_size = pk_itemsize(set->id_type), sort_size = pk_itemsize(set->sort_type);
+    void *d_vals = nullptr, *d_out = nullptr;
+    PkStats *d_st = nullptr;
+    unsigned int nan_flag = 0;
+    std::shared_ptr<void> out;
+    int rc = TSFA_OK;
+    for (int32_t k = 0; k < set->n_kinds; ++k) out_packs[k] = nullptr;
+
+    PK_HIP(hipSetDevice(set->device));
+    if (space == TSFA_HOST) {
+        PK_ALLOC(d_vals, (size_t)n * val_size, "the value column");
+        PK_HIP(hipMemcpy(d_vals, values, (size_t)n * val_size, hipMemcpyHostToDevice));
+        values = d_vals;
+    }
+    PK_ALLOC(d_st, sizeof(PkStats), "the packer's counters");
+    PK_HIP(hipMemset(d_st, 0, sizeof(PkStats)));
+    PK_ALLOC(d_out, (size_t)n * out_size, "the ragged sample buffer");
+    out = pk_share(d_out, set->device);
+    k_pack_gather<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(values, value_type, (const uint32_t *)set->perm.get(), n, d_out, d_st);
+    PK_HIP(hipGetLastError());
+    PK_HIP(hipMemcpy(&nan_flag, &d_st->nan_flag, sizeof(nan_flag), hipMemcpyDeviceToHost));  // (synchronises: the staged column may go)
+    for (int32_t k = 0; k < set->n_kinds; ++k) {
+        const int64_t r0 = set->kind_rows[(size_t)k], g0 = set->kind_groups[(size_t)k];
+        tsfa_pack *pk = new tsfa_pack();
+        pk->device = set->device;
+        pk->n_rows = set->kind_rows[(size_t)k + 1] - r0;
+        pk->n_groups = set->kind_groups[(size_t)k + 1] - g0;
+        pk->flags = set->flags | (nan_flag ? TSFA_PACK_VALUE_NAN : 0);
+        pk->n_passes = set->n_passes;
+        pk->id_type = set->id_type; pk->sort_type = set->sort_type; pk->out_type = out_type;
+        pk->values = (char *)d_out + (size_t)r0 * out_size;
+        pk->hold[0] = out;
+        // one kind: the set's own offsets; several: the kind's stretch of the rebased buffer (pk_rebase_body's layout)
+        pk->hold[1] = set->rebased ? set->rebased : set->offsets;
+        pk->offsets = (int64_t *)pk->hold[1].get() + (set->rebased ? g0 + k : 0);
+        pk->uniq = (char *)set->uniq.get() + (size_t)g0 * id_size;
+        pk->hold[2] = set->uniq;
+        if (set->sort) {
+            pk->sort = (char *)set->sort.get() + (size_t)r0 * sort_size;
+            pk->hold[3] = set->sort;
+        }
+        out_packs[k] = pk;
+    }
+done:
+    (void)hipFree(d_vals); (void)hipFree(d_st);
+    return rc;
+}
+
+extern "C" void tsfa_pack_set_destroy(tsfa_pack_set *set) { delete set; }

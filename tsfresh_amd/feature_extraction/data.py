@@ -9,6 +9,8 @@ layout the kernels consume.  Everything is vectorised (factorize + lexsort); no 
 A frame whose rows are NOT grouped by ascending id with every group in sort order (a sensor log written in time order, the
 long format, a shuffled frame) can be packed on the device instead (`pack="device"` / `"auto"`, `_native.DevicePack`): the
 columns are uploaded as they are, sorted and gathered there, and the ragged buffer goes to the kernels without returning.
+A frame of several kinds -- a long frame whose kinds interleave, a wide frame with several value columns -- is sorted ONCE
+(`_native.DevicePackSet`) and every kind is a view of that one sort.
 """
 import warnings
 
@@ -180,15 +182,9 @@ def _pack_presorted(kind, ids, values, sort_values, index, nan_name=None):
     return PackedKind(str(kind), uniques, vals, offsets, times, sv)
 
 
-def _device_pack_columns(ids, values, sort_values, index=None):
-    """What tsfa_pack_device would read for these columns: -> (None, (ids column, unique labels or None, sort column or
-    None, value column)), each column as `_native.pack_column` returns it, or (reason, None) when the frame keeps the host
-    route.  Eligible: integer ids (strings / objects are factorized to codes on the host first: that still leaves the
-    lexsort and the gather to the device); a sort column of an integer type, float32 / float64, datetime64 / timedelta64,
-    or none; a value column of bool, an integer type, float32 or float64.  NOT eligible, and follow-ups rather than part of
-    the device packer: float ids, float16 / longdouble values, sort values that do not compare element-wise (objects),
-    and frames with a DatetimeIndex (the `times` of linear_trend_timewise are pandas arithmetic, `_hours_since_first`).
-    `extract_rolled_features` needs the packed sort column on the host anyway and always packs there."""
+def _device_key_columns(ids, sort_values, index=None):
+    """The id and sort columns as the device packer reads them: -> (None, (ids column, unique labels or None, sort column or
+    None)) or (reason, None); see `_device_pack_columns`."""
     ids = np.asarray(ids)
     if index is not None:
         return "the frame has a DatetimeIndex (linear_trend_timewise's times are computed on the host)", None
@@ -213,6 +209,11 @@ def _device_pack_columns(ids, values, sort_values, index=None):
         sort_col = _native.pack_column(sv)
         if sort_col is None:
             return "the sort column has dtype {}".format(sv.dtype), None
+    return None, (id_col, labels, sort_col)
+
+
+def _device_value_column(values):
+    """A value column as the device packer reads it: -> (None, column) or (reason, None)."""
     raw = np.asarray(values)
     if raw.dtype.kind not in "biuf" or (raw.dtype.kind == "f" and raw.dtype.itemsize not in (4, 8)):
         return "the value column has dtype {} (bool, integers, float32 / float64 are packed on the device)".format(
@@ -220,7 +221,25 @@ def _device_pack_columns(ids, values, sort_values, index=None):
     val_col = _native.pack_column(raw)
     if val_col is None:
         return "the value column has dtype {}".format(raw.dtype), None
-    return None, (id_col, labels, sort_col, val_col)
+    return None, val_col
+
+
+def _device_pack_columns(ids, values, sort_values, index=None):
+    """What tsfa_pack_device would read for these columns: -> (None, (ids column, unique labels or None, sort column or
+    None, value column)), each column as `_native.pack_column` returns it, or (reason, None) when the frame keeps the host
+    route.  Eligible: integer ids (strings / objects are factorized to codes on the host first: that still leaves the
+    lexsort and the gather to the device); a sort column of an integer type, float32 / float64, datetime64 / timedelta64,
+    or none; a value column of bool, an integer type, float32 or float64.  NOT eligible, and follow-ups rather than part of
+    the device packer: float ids, float16 / longdouble values, sort values that do not compare element-wise (objects),
+    and frames with a DatetimeIndex (the `times` of linear_trend_timewise are pandas arithmetic, `_hours_since_first`).
+    `extract_rolled_features` needs the packed sort column on the host anyway and always packs there."""
+    reason, keys = _device_key_columns(ids, sort_values, index)
+    if reason is not None:
+        return reason, None
+    reason, val_col = _device_value_column(values)
+    if reason is not None:
+        return reason, None
+    return None, keys + (val_col,)
 
 
 def _pack_on_device(kind, columns, nan_name, device):
@@ -289,6 +308,94 @@ def _pack(kind, ids, values, sort_values, index=None, nan_name=None, pack="host"
                       None if sort_values is None else np.asarray(sort_values)[order])
 
 
+def _takes_device(pack, n_rows):
+    """The rule of `_pack` for a frame of n_rows rows that is not in packed order."""
+    return pack == "device" or (pack == "auto" and n_rows >= _DEVICE_PACK_MIN_ROWS and _native.device_count() > 0)
+
+
+def _view_kind(kind, dp, labels):
+    return PackedKind(str(kind), dp.ids if labels is None else labels[dp.ids], None, None, None, None, device_pack=dp)
+
+
+def _close_all(kinds):
+    for pk in kinds:
+        if pk is not None and pk.device_pack is not None:
+            pk.device_pack.close()
+
+
+def _pack_long_on_device(kuniq, kcodes, ids, values, sort_values, index, pack, device):
+    """A long frame whose kinds interleave, sorted ONCE on the device by (kind, id, sort) (`_native.DevicePackSet`): no
+    per-kind selection on the host, one upload, one sort, one gather; every kind is a view into the one gathered buffer.
+    -> [PackedKind per kind of kuniq], or None when the frame keeps the per-kind route (not eligible under "auto"; a device
+    allocation that failed, after one warning)."""
+    reason, columns = _device_pack_columns(ids, values, sort_values, index)
+    if reason is not None:
+        if pack == "device":
+            raise ValueError("pack='device': kind {!r} cannot be packed on the device: {}".format(str(kuniq[0]), reason))
+        return None
+    id_col, labels, sort_col, val_col = columns
+    n_kinds = len(kuniq)   # dense codes 0 .. n_kinds - 1 in the narrowest type: one radix pass per byte
+    kind_col = _native.pack_column(kcodes.astype(np.uint8 if n_kinds <= 1 << 8 else np.uint16 if n_kinds <= 1 << 16 else np.int64))
+    try:
+        with _native.DevicePackSet(id_col, sort_col, kind_col, device=device) as pack_set:
+            packs = pack_set.values(val_col)
+    except _native.NativeError as exc:
+        if pack == "device" or exc.code != _native.TSFA_ERR_HIP:
+            raise
+        warnings.warn("packing the frame's {} kinds on the device failed ({}); packing on the host instead".format(
+            n_kinds, exc), RuntimeWarning, stacklevel=3)
+        return None
+    return [_view_kind(kind, dp, labels) for kind, dp in zip(kuniq, packs)]
+
+
+def _pack_wide(columns, ids, sort_values, index, pack, device):
+    """The value columns of a wide frame: `columns` is [(name, values, nan_name or None)].  With at least two columns the
+    device packer takes and rows that are not in packed order, the id and sort columns are uploaded, keyed, sorted and
+    boundary-scanned ONCE (`_native.DevicePackSet` without a kind column) and every value column is one gather through the
+    stored permutation; the packs share the set's offsets and ids.  Everything else is `_pack` per column, as before."""
+    ids = np.asarray(ids)
+
+    def per_column(todo, mode):
+        return [_pack(name, ids, values, sort_values, index, nan_name=nan_name, pack=mode, device=device)
+                for name, values, nan_name in todo]
+
+    if len(columns) < 2 or pack == "host" or not _takes_device(pack, len(ids)):
+        return per_column(columns, pack)
+    name0, values0, nan_name0 = columns[0]
+    first = _pack_presorted(name0, ids, values0, sort_values, index, nan_name0)
+    if first is not None:   # the frame is in packed order: every column costs what it cost before
+        return [first] + per_column(columns[1:], pack)
+    reason, keys = _device_key_columns(ids, sort_values, index)
+    value_cols = [_device_value_column(values) for _, values, _ in columns]
+    if reason is not None or sum(r is None for r, _ in value_cols) < 2:
+        return per_column(columns, pack)   # (raises under "device" where a column is not eligible)
+    id_col, labels, sort_col = keys
+    packed = []
+    try:
+        with _native.DevicePackSet(id_col, sort_col, None, device=device) as pack_set:
+            for (name, values, nan_name), (why, val_col) in zip(columns, value_cols):
+                if why is not None:
+                    if pack == "device":
+                        raise ValueError("pack='device': kind {!r} cannot be packed on the device: {}".format(str(name), why))
+                    packed.append(_pack(name, ids, values, sort_values, index, nan_name=nan_name, pack="host"))
+                    continue
+                dp = pack_set.values(val_col)[0]
+                packed.append(_view_kind(name, dp, labels))
+                if dp.value_nan and nan_name is not None:
+                    raise ValueError("Column must not contain NaN values: {}".format(nan_name))
+    except _native.NativeError as exc:
+        _close_all(packed)
+        if pack == "device" or exc.code != _native.TSFA_ERR_HIP:
+            raise
+        warnings.warn("packing the frame's {} value columns on the device failed ({}); packing on the host instead".format(
+            len(columns), exc), RuntimeWarning, stacklevel=3)
+        return per_column(columns, "host")
+    except Exception:
+        _close_all(packed)
+        raise
+    return packed
+
+
 def _arrow_to_frame(table):
     """A pyarrow Table / RecordBatch as a DataFrame, column by column through numpy (no Python objects for primitive
     columns; pandas still consolidates the columns into its own blocks): the checks and the packing below then see an
@@ -337,7 +444,7 @@ def _pack_arrow_wide(table, column_id, column_kind, column_value, column_sort, p
         _raise_if_nan(arrays[name], name)
     ids = arrays[column_id]
     sort_all = arrays[column_sort] if column_sort is not None else None
-    packed = [_pack(c, ids, arrays[c], sort_all, None, nan_name=c, pack=pack, device=device) for c in value_columns]
+    packed = _pack_wide([(c, arrays[c], c) for c in value_columns], ids, sort_all, None, pack, device)
     return packed, ids.dtype, False
 
 
@@ -376,6 +483,14 @@ def pack_timeseries(container, column_id=None, column_kind=None, column_value=No
             ids_all = df[column_id].to_numpy()
             vals_all = df[column_value].to_numpy()
             sort_all = df[column_sort].to_numpy() if column_sort is not None else None
+            interleaved = len(kcodes) > 1 and not bool(np.all(kcodes[1:] >= kcodes[:-1]))
+            if interleaved and pack != "host" and _takes_device(pack, len(kcodes)):
+                # kinds that interleave (rows in (id, time) or time order): one sort of the whole frame on the device.
+                # A frame whose kinds come in blocks keeps the per-kind route below, where a packed block costs a proof.
+                views = _pack_long_on_device(kuniq, kcodes, ids_all, vals_all, sort_all, dt_index, pack, device)
+                if views is not None:
+                    return views, df[column_id].dtype, False
+                pack = "host"   # "auto": not eligible, or the allocation failed and the warning is out
             for k, kind in enumerate(kuniq):
                 sel = np.nonzero(kcodes == k)[0]
                 packed.append(_pack(kind, ids_all[sel], vals_all[sel], None if sort_all is None else sort_all[sel],
@@ -392,8 +507,8 @@ def pack_timeseries(container, column_id=None, column_kind=None, column_value=No
         ids_all = df[column_id].to_numpy()
         sort_all = df[column_sort].to_numpy() if column_sort is not None else None
         dt_index = df.index if isinstance(df.index, pd.DatetimeIndex) else None
-        packed = [_pack(col, ids_all, df[col].to_numpy(), sort_all, dt_index, nan_name=col if col in deferred else None,
-                        pack=pack, device=device) for col in value_columns]
+        packed = _pack_wide([(col, df[col].to_numpy(), col if col in deferred else None) for col in value_columns],
+                            ids_all, sort_all, dt_index, pack, device)
         return packed, df[column_id].dtype, isinstance(df.index, pd.DatetimeIndex)
     if isinstance(container, dict):
         # dict of frames, one per kind (data.py:294-338)
