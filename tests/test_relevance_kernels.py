@@ -1,0 +1,556 @@
+"""tsfresh_amd/csrc/tsfa_relevance.hip, kernel by kernel, against the brute-force statistics of tests/relevance_ref.py:
+every output field of the four relevance / impute entry points and of the gather / scatter pair, compared with `==` at
+the row counts where the device code changes shape (the 1024-thread chunks, the 2048 / 4096 sort tiles, zero to three
+merge-path levels of the inversion counter).  CPU: the references themselves against scipy."""
+import ctypes
+import functools
+import math
+import warnings
+
+import numpy as np
+import pandas as pd
+import pytest
+
+import relevance_ref as ref
+
+# 1024-thread chunking of k_rel_ks, both tile sizes (np2 2048 -> 4096), zero .. three merge-path levels (np2 4096 .. 32768)
+SIZES = (1, 2, 3, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097, 8191, 8192, 8193, 16385)
+TARGETS = ("normal", "rounded", "two_valued", "all_equal", "ramp")
+
+
+def _target(kind, n, rng):
+    if kind == "normal":
+        return rng.standard_normal(n)
+    if kind == "rounded":
+        return np.round(rng.standard_normal(n), 1)
+    if kind == "two_valued":
+        return rng.integers(0, 2, n).astype(np.float64)
+    if kind == "all_equal":
+        return np.full(n, 1.5)
+    return np.arange(n, dtype=np.float64)
+
+
+def _columns(n, y, rng):
+    """The eleven columns of the issue, 0-based here: iid, y, -y, few values, two-valued dependent on y, two-valued with
+    one high row, constant, +-inf cells, signed zeros plus one 1.0, sorted by row, tie groups of three across the seams."""
+    X = np.empty((n, 11))
+    X[:, 0] = rng.standard_normal(n)
+    X[:, 1] = y
+    X[:, 2] = -y
+    X[:, 3] = np.round(rng.standard_normal(n) + 0.3 * y, 0)
+    X[:, 4] = (y + rng.standard_normal(n) > np.median(y)) * 1.0
+    if n >= 2:
+        X[0, 4], X[-1, 4] = 0.0, 1.0          # both values present whatever the draw
+    X[:, 5] = 0.0
+    X[int(rng.integers(0, n)), 5] = 1.0       # n_hi = 1
+    X[:, 6] = 2.5
+    X[:, 7] = rng.standard_normal(n)
+    order = rng.permutation(n)
+    k = max(n // 10, 1 if n >= 3 else 0)
+    X[order[:k], 7] = np.inf                  # real +inf rows: in front of the +inf padding of the device sort
+    X[order[k:2 * k], 7] = -np.inf
+    X[:, 8] = 0.0
+    X[1::2, 8] = -0.0
+    if n >= 2:
+        X[n // 2, 8] = 1.0                    # {+-0.0, 1.0}: two values
+    X[:, 9] = np.sort(rng.standard_normal(n))
+    X[rng.permutation(n), 10] = np.floor(np.arange(n) / 3.0)
+    return X
+
+
+@functools.lru_cache(maxsize=None)
+def _real_inputs(n, kind):
+    rng = np.random.default_rng([n, TARGETS.index(kind)])
+    y = _target(kind, n, rng)
+    X = _columns(n, y, rng)
+    X.setflags(write=False)
+    y.setflags(write=False)
+    return X, y
+
+
+def _pairs():
+    """About 30 small (x, y): ties in both, in one, in neither."""
+    rng = np.random.default_rng(31)
+    out = []
+    for trial in range(32):
+        n = int(rng.integers(2, 601))
+        x, y = rng.standard_normal(n), rng.standard_normal(n) + (0.4 * rng.standard_normal(n) if trial % 2 else 0.0)
+        mode = trial % 4
+        if mode in (0, 1):
+            x = np.round(x, 1 if trial % 8 < 4 else 0)
+        if mode in (0, 2):
+            y = np.round(y, 1)
+        out.append((x, y))
+    return out
+
+
+# ------------------------------------------------------------------------------------------- CPU: the references
+
+
+def test_fast_discordant_count_equals_the_definition():
+    for x, y in _pairs():
+        assert ref.dis_fenwick(x, y) == ref.dis_brute(x, y)
+    # the extremes: no pair, every pair, every pair tied
+    r = np.arange(50.0)
+    assert ref.dis_fenwick(r, r) == ref.dis_brute(r, r) == 0
+    assert ref.dis_fenwick(r, -r) == ref.dis_brute(r, -r) == 50 * 49 // 2
+    assert ref.dis_fenwick(np.zeros(50), r) == ref.dis_brute(r, np.zeros(50)) == 0
+
+
+def test_ks_restatement_equals_scipy():
+    """Exact against ks_2samp(method="asymp"): scipy and the restatement both form one quotient per sample and one
+    difference.  With method="auto" scipy 1.15.3 takes the exact route at these sizes, and that route (since scipy
+    1.5) hands back the statistic re-formed as round(d * lcm) / lcm, which can differ from the difference of the two
+    quotients by the rounding of those quotients (values up to 1, half an ulp each, plus the rounding of h / lcm): that
+    one is compared to 2 ulp of the quotients, 2 * spacing(0.5)."""
+    from scipy import stats
+    rng = np.random.default_rng(32)
+    for trial in range(40):
+        n = int(rng.integers(2, 500))
+        v = rng.standard_normal(n) if trial % 2 else np.round(rng.standard_normal(n), 1)
+        split = rng.random(n) < rng.uniform(0.1, 0.9)
+        split[0], split[1] = True, False
+        want = stats.ks_2samp(v[split], v[~split], method="asymp").statistic
+        assert ref.ks_statistic(v[split], v[~split]) == want
+        auto = stats.ks_2samp(v[split], v[~split]).statistic
+        assert abs(want - auto) <= 2 * np.spacing(0.5)
+        codes = split.astype(np.int32)
+        got = ref.class_ks_stats(v, codes, 2)
+        assert got[1] == want and got[0] == stats.ks_2samp(v[~split], v[split], method="asymp").statistic
+
+
+def test_reference_fields_give_scipys_kendall_pvalue():
+    """The ten fields are what the host folds into the p-value: kendall_pvalue fed from real_column_stats against
+    scipy.stats.kendalltau(method="asymptotic")."""
+    from scipy import stats
+    from tsfresh_amd.feature_selection.significance_tests import kendall_pvalue, target_tie_statistics
+    for x, y in _pairs():
+        s = ref.real_column_stats(x, y)
+        ytie, y0, y1 = target_tie_statistics(ref.dense_rank(y))
+        got = kendall_pvalue(len(x), s["dis"], s["xtie"], s["ntie"], s["x0"], s["x1"], ytie, y0, y1)
+        want = stats.kendalltau(x, y, method="asymptotic").pvalue
+        assert (math.isnan(got) and math.isnan(want)) or got == pytest.approx(want, rel=1e-12, abs=1e-300)
+
+
+def test_reference_on_hand_counted_columns():
+    x = np.array([1.0, 1.0, 2.0, 2.0, 2.0, 3.0])
+    y = np.array([5.0, 5.0, 4.0, 4.0, 1.0, 9.0])
+    s = ref.real_column_stats(x, y)
+    assert (s["n_unique"], s["v_lo"], s["v_hi"], s["n_hi"], s["ks_d"]) == (3, 1.0, 3.0, 0, 0.0)
+    assert (s["xtie"], s["x0"], s["x1"]) == (1 + 3, 0.0 + 6.0, 2.0 * 9 + 6.0 * 11)
+    assert s["ntie"] == 1 + 1 and s["dis"] == 2 * 3
+    b = ref.real_column_stats(np.array([0.0, -0.0, 1.0, 0.0]), np.array([1.0, 2.0, 3.0, 4.0]))
+    assert (b["n_unique"], b["n_hi"]) == (2, 1) and b["ks_d"] == 2.0 / 3.0
+    assert ref.impute_stats([np.nan, np.inf, -np.inf]) == (0.0, 0.0, 0.0, 0)
+    assert ref.impute_stats([np.nan, 3.0, 1.0, np.inf]) == (3.0, 1.0, 2.0, 2)
+
+
+# ------------------------------------------------------------------------------------------- tsfa_relevance_real
+
+
+@functools.lru_cache(maxsize=None)
+def _real_reference(n, kind):
+    X, y = _real_inputs(n, kind)
+    return [ref.real_column_stats(X[:, c], y) for c in range(X.shape[1])]
+
+
+def _assert_same_records(a, b, what):
+    for f in ref.REAL_FIELDS:
+        assert np.array_equal(a[f], b[f]), (what, f, a[f].tolist(), b[f].tolist())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", SIZES)
+def test_gpu_relevance_real_fields_equal_the_brute_force(gpu, n):
+    """Gaps 1 and 2 of the issue: `tsfa_relevance_real` is never compared with anything directly, and the inversion
+    counter is never run at the seams of its two regimes.  All ten fields of every column, five targets, `==`.
+    x0 and x1 are sums of integers in float64: the largest term, t(t-1)(2t+5) of one tie group of all 16385 rows, is
+    8.8e12 < 1e13 and every partial sum stays far below 2^53, so the order of the device's atomic additions cannot
+    show and equality is the right comparison."""
+    from tsfresh_amd import _native
+    assert 16385 * 16384 * (2 * 16385 + 5) < 1e13
+    bad = []
+    for kind in TARGETS:
+        X, y = _real_inputs(n, kind)
+        got, _ = _native.relevance_real(X, y)
+        want = _real_reference(n, kind)
+        assert len(got) == X.shape[1]
+        for c in range(X.shape[1]):
+            for f in ref.REAL_FIELDS:
+                if not got[f][c] == want[c][f]:
+                    bad.append((kind, "column %d" % (c + 1), f, got[f][c].item(), want[c][f]))
+    assert not bad, bad[:20]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", SIZES)
+def test_gpu_relevance_real_is_invariant_under_a_row_permutation(gpu, n):
+    """Gap 1: the statistics are functions of the multiset of (x, y) rows -- the same call on jointly permuted rows."""
+    from tsfresh_amd import _native
+    for kind in TARGETS:
+        X, y = _real_inputs(n, kind)
+        p = np.random.default_rng(n).permutation(n)
+        a, _ = _native.relevance_real(X, y)
+        b, _ = _native.relevance_real(X[p], y[p])
+        _assert_same_records(a, b, kind)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", SIZES)
+def test_gpu_relevance_real_is_invariant_under_the_column_batch(gpu, n):
+    """Gap 1: column batches of 1 and of 4 (11 columns: a last batch of 3) against the single batch."""
+    from tsfresh_amd import _native
+    for kind in ("rounded", "two_valued"):
+        X, y = _real_inputs(n, kind)
+        a, _ = _native.relevance_real(X, y)
+        for batch in (1, 4):
+            _native.set_library_option("relevance_batch", batch)
+            try:
+                b, _ = _native.relevance_real(X, y)
+            finally:
+                _native.set_library_option("relevance_batch", 0)
+            _assert_same_records(a, b, (kind, batch))
+
+
+# ------------------------------------------------------------------------------------------- tsfa_relevance_classes(_ks)
+
+
+@functools.lru_cache(maxsize=None)
+def _class_inputs(n, C):
+    rng = np.random.default_rng([n, C, 7])
+    codes = rng.permutation(np.arange(n) % C).astype(np.int32)   # every class present as soon as n >= C
+    full = _columns(n, codes.astype(np.float64), rng)
+    X = np.ascontiguousarray(full[:, [0, 3, 4, 7, 8]])           # columns 1, 4, 5, 8, 9, driven by the class code
+    return X, codes
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [s for s in SIZES if s <= 8193])
+def test_gpu_class_ks_distances_equal_the_restatement(gpu, n):
+    """Gap 3: `k_rel_ks_classes` (the `smir` option) -- ks_d[c, k] against the restatement of ks_2samp's statistic of
+    x[codes == k] against x[codes != k], exactly, for 2, 3 and 7 classes; the other six outputs equal those of the
+    call without the distances.  With fewer rows than classes a class is empty and its distance is undefined (0 / 0):
+    there only the six other outputs are compared."""
+    from tsfresh_amd import _native
+    for C in (2, 3, 7):
+        X, codes = _class_inputs(n, C)
+        plain = _native.relevance_classes(X, codes, C)
+        with_ks = _native.relevance_classes(X, codes, C, with_ks=True)
+        assert len(plain) == 6 and len(with_ks) == 7
+        for u, v in zip(plain, with_ks):
+            assert np.array_equal(u, v)
+        if n < C:
+            continue
+        assert len(np.unique(codes)) == C
+        for c in range(X.shape[1]):
+            want = ref.class_ks_stats(X[:, c], codes, C)
+            assert with_ks[6][c].tolist() == want.tolist(), (C, c, with_ks[6][c].tolist(), want.tolist())
+
+
+@pytest.mark.gpu
+def test_gpu_relevance_classes_with_256_classes_and_refusal_of_257(gpu):
+    """Gap 4: all 256 LDS accumulators of `k_rel_stats` in use (4097 rows: the 4096 tile plus one), rank sums and
+    counts against scipy.stats.rankdata / np.unique; 257 classes are refused by the argument check."""
+    from scipy.stats import rankdata
+    from tsfresh_amd import _native
+    rng = np.random.default_rng(256)
+    n, C = 4097, 256
+    codes = rng.permutation(np.arange(n) % C).astype(np.int32)
+    X = rng.standard_normal((n, 4))
+    X[:, 1] = np.round(X[:, 1], 0)
+    X[rng.choice(n, 400, replace=False), 2] = np.inf
+    X[rng.choice(n, 400, replace=False), 2] = -np.inf
+    X[:, 3] = (X[:, 3] + 0.01 * codes > 1.0) * 1.0
+    nu, lo, hi, tie, rs, hc = _native.relevance_classes(X, codes, C)
+    onehot = np.zeros((n, C))
+    onehot[np.arange(n), codes] = 1.0
+    for c in range(X.shape[1]):
+        r = rankdata(X[:, c])
+        u, cnt = np.unique(X[:, c], return_counts=True)
+        assert nu[c] == len(u) and lo[c] == u[0] and hi[c] == u[-1]
+        assert tie[c] == float(np.sum(cnt.astype(float) ** 3 - cnt))
+        want_rs = np.array([r[codes == k].sum() for k in range(C)])   # mid-ranks: multiples of 0.5, exact sums
+        assert np.array_equal(rs[c], want_rs)
+        assert np.array_equal(hc[c], ((X[:, c] == u[-1]).astype(float) @ onehot).astype(np.int64))
+    codes257 = (np.arange(n) % 257).astype(np.int32)
+    with pytest.raises(_native.NativeError) as err:
+        _native.relevance_classes(X, codes257, 257)
+    assert err.value.code == _native.TSFA_ERR_UNSUPPORTED
+
+
+# ------------------------------------------------------------------------------------------- tsfa_impute
+
+
+def _numpy_impute(data):
+    from tsfresh_amd.utilities import dataframe_functions as ours
+    df = pd.DataFrame(data.copy())
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        mx, mn, med = ours.get_range_values_per_column(df)
+        ours.impute_dataframe_range(df, mx, mn, med)
+    return df.to_numpy()
+
+
+def _with_finite_cells(n, k, rng, value=None):
+    """A column of n cells of which exactly min(k, n) (at random rows) are finite; the rest cycle NaN, +inf, -inf."""
+    col = np.array([np.nan, np.inf, -np.inf] * (n // 3 + 1))[:n]
+    rows = rng.permutation(n)[:max(0, min(k, n))]
+    col[rows] = rng.standard_normal(len(rows)) if value is None else value
+    return col
+
+
+def _impute_matrix(n, rng):
+    X = np.empty((n, 11))
+    X[:, 0] = rng.standard_normal(n)
+    X[:, 1] = rng.standard_normal(n)
+    u = rng.random(n)
+    X[u < 0.05, 1] = np.nan
+    X[(u >= 0.05) & (u < 0.08), 1] = np.inf
+    X[(u >= 0.08) & (u < 0.11), 1] = -np.inf
+    X[:, 2] = _with_finite_cells(n, 1, rng)
+    X[:, 3] = _with_finite_cells(n, 2, rng)                       # the median is the mean of the two
+    X[:, 4] = _with_finite_cells(n, (n - 1) // 2 * 2, rng)        # the largest even count below n
+    X[:, 5] = _with_finite_cells(n, n - 1 - (n % 2), rng)         # the largest odd count below n
+    X[:, 6] = np.nan
+    X[:, 7] = np.inf
+    X[:, 8] = -np.inf
+    X[:, 9] = 4.25
+    X[int(rng.integers(0, n)), 9] = np.nan
+    zeros = np.where(rng.random(n) < 0.5, -0.0, 0.0)
+    zeros[rng.random(n) < 0.3] = np.nan
+    X[:, 10] = zeros
+    return X
+
+
+def _check_impute(data):
+    from tsfresh_amd import _native
+    got = data.copy()
+    mx, mn, med, cnt = _native.impute_matrix(got, device=0)
+    for c in range(data.shape[1]):
+        want = ref.impute_stats(data[:, c])
+        assert (mx[c], mn[c], med[c], cnt[c]) == want, (c, (mx[c], mn[c], med[c], cnt[c]), want)
+    assert np.array_equal(got, _numpy_impute(data))
+    assert np.isfinite(got).all()
+    return got, cnt
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 2, 3, 2047, 2048, 2049, 4096, 4097, 8193])
+def test_gpu_impute_statistics_and_patch_at_the_tile_boundaries(gpu, n):
+    """Gap 5: `tsfa_impute` with 1 and 2 finite cells, an even and an odd finite count next to the tile, columns of
+    only NaN / +inf / -inf, one row: max, min, median and finite count against np.median on the finite cells, the
+    patched matrix against the numpy path."""
+    data = _impute_matrix(n, np.random.default_rng([n, 4]))
+    got, cnt = _check_impute(data)
+    assert cnt[6] == cnt[7] == cnt[8] == 0 and not got[:, 6:9].any()   # no finite value: zeros, as the numpy path
+    assert cnt[0] == n and cnt[2] == 1 and cnt[3] == min(2, n)
+    if n > 3:
+        assert cnt[4] % 2 == 0 and cnt[5] % 2 == 1 and n - 2 <= cnt[4] < n and n - 2 <= cnt[5] < n
+
+
+@pytest.mark.gpu
+def test_gpu_impute_patch_wraps_the_grid_stride(gpu):
+    """Gap 5: 3000 x 200 = 600 000 cells, more than the 2048 x 256 = 524 288 threads of `k_imp_apply`."""
+    rng = np.random.default_rng(200)
+    data = rng.standard_normal((3000, 200))
+    u = rng.random(data.shape)
+    data[u < 0.02] = np.nan
+    data[(u >= 0.02) & (u < 0.03)] = np.inf
+    data[(u >= 0.03) & (u < 0.04)] = -np.inf
+    data[-40:, -3:] = np.nan        # the cells only the second trip of the grid-stride reaches
+    assert data.size > 2048 * 256
+    _check_impute(data)
+
+
+# ------------------------------------------------------------------------------------------- gather / scatter
+
+
+def _upload(lib, dm, host):
+    from tsfresh_amd import _native
+    host = np.ascontiguousarray(host, dtype=np.float64)
+    assert host.shape == dm.shape
+    _native._check(lib, lib.tsfa_device_copy(ctypes.c_void_p(dm.ptr), host.ctypes.data_as(ctypes.c_void_p), host.nbytes, 1,
+                                             dm.device))
+
+
+@pytest.mark.gpu
+def test_gpu_gather_and_scatter_columns(gpu):
+    """Gap 6: `tsfa_gather_columns` / `tsfa_scatter_columns` on their own -- duplicate and reversed indices, all
+    columns, none, an index equal to ld or negative refused, and 600 000 / 540 000 cells so that the grid-stride of
+    2048 x 256 threads wraps."""
+    from tsfresh_amd import _native
+    lib = _native.load()
+    rng = np.random.default_rng(55)
+    n, m = 3000, 200
+    host = rng.standard_normal((n, m))
+    dm = _native.DeviceMatrix(n, m)
+    src = _native.DeviceMatrix(n, 180)
+    try:
+        _upload(lib, dm, host)
+        assert np.array_equal(dm.to_host(), host)
+        subset = np.sort(rng.choice(m, 37, replace=False))
+        assert np.array_equal(dm.to_host(subset), host[:, subset])
+        dup = np.array([199, 150, 150, 7, 7, 7, 0, 0])
+        assert np.array_equal(dm.to_host(dup), host[:, dup])
+        assert np.array_equal(dm.to_host(np.arange(m)), host)
+        assert np.array_equal(dm.to_host(np.arange(m)[::-1]), host[:, ::-1])
+        none = dm.to_host([])
+        assert none.shape == (n, 0)
+        out = np.zeros((n, 2))
+        for bad_index in (m, -1):
+            idx = np.array([3, bad_index], dtype=np.int32)
+            rc = lib.tsfa_gather_columns(ctypes.c_void_p(dm.ptr), n, m, idx.ctypes.data_as(ctypes.c_void_p), 2,
+                                         out.ctypes.data_as(ctypes.c_void_p), 0)
+            assert rc == _native.TSFA_ERR_INVALID
+            rc = lib.tsfa_scatter_columns(ctypes.c_void_p(dm.ptr), m, idx.ctypes.data_as(ctypes.c_void_p),
+                                          ctypes.c_void_p(src.ptr), n, 2, 0)
+            assert rc == _native.TSFA_ERR_INVALID
+        assert not out.any() and np.array_equal(dm.to_host(), host)      # refused before anything ran
+        # scatter: 180 source columns into distinct columns of a sentinel-filled destination
+        sentinel = -777.25
+        block = rng.standard_normal((n, 180))
+        where = rng.permutation(m)[:180].astype(np.int32)
+        _upload(lib, src, block)
+        _upload(lib, dm, np.full((n, m), sentinel))
+        assert n * 180 > 2048 * 256
+        _native._check(lib, lib.tsfa_scatter_columns(ctypes.c_void_p(dm.ptr), dm.ld, where.ctypes.data_as(ctypes.c_void_p),
+                                                     ctypes.c_void_p(src.ptr), n, 180, 0))
+        want = np.full((n, m), sentinel)
+        want[:, where] = block
+        assert np.array_equal(dm.to_host(), want)
+    finally:
+        dm.free()
+        src.free()
+
+
+# ------------------------------------------------------------------------------------------- device space, ld > n_cols
+
+
+def _ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _device_relevance_real(lib, xptr, n, m, ld, y):
+    """tsfa_relevance_real on a device pointer; the target is prepared as _native.relevance_real prepares it."""
+    from tsfresh_amd import _native
+    y_rank = np.ascontiguousarray(np.unique(y, return_inverse=True)[1].reshape(-1), dtype=np.int32)
+    y_perm = np.ascontiguousarray(np.argsort(y, kind="stable"), dtype=np.int32)
+    ys = y[y_perm]
+    y_end = np.ones(n, dtype=np.uint8)
+    y_end[:-1] = ys[1:] != ys[:-1]
+    cols = np.zeros(m, dtype=_native._REAL_COL_DTYPE)
+    lib.tsfa_relevance_real.restype = ctypes.c_int32
+    lib.tsfa_relevance_real.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+    _native._check(lib, lib.tsfa_relevance_real(xptr, n, m, ld, _native.TSFA_DEVICE, _ptr(y_rank), _ptr(y_perm), _ptr(y_end),
+                                                0, _ptr(cols)))
+    return cols
+
+
+def _device_relevance_classes_ks(lib, xptr, n, m, ld, codes, C):
+    from tsfresh_amd import _native
+    rec = np.zeros(m, dtype=[("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("tie_term", "<f8")])
+    rs, hc, ks = np.zeros((m, C)), np.zeros((m, C), dtype=np.int64), np.zeros((m, C))
+    lib.tsfa_relevance_classes_ks.restype = ctypes.c_int32
+    lib.tsfa_relevance_classes_ks.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                              ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _native._check(lib, lib.tsfa_relevance_classes_ks(xptr, n, m, ld, _native.TSFA_DEVICE, _ptr(codes), C, 0, _ptr(rec),
+                                                      _ptr(rs), _ptr(hc), _ptr(ks)))
+    return rec["n_unique"], rec["v_lo"], rec["v_hi"], rec["tie_term"], rs, hc, ks
+
+
+def _device_impute(lib, xptr, n, m, ld):
+    from tsfresh_amd import _native
+    mx, mn, med, cnt = np.zeros(m), np.zeros(m), np.zeros(m), np.zeros(m, dtype=np.int32)
+    lib.tsfa_impute.restype = ctypes.c_int32
+    lib.tsfa_impute.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _native._check(lib, lib.tsfa_impute(xptr, n, m, ld, _native.TSFA_DEVICE, 0, _ptr(mx), _ptr(mn), _ptr(med), _ptr(cnt)))
+    return mx, mn, med, cnt
+
+
+@pytest.mark.gpu
+def test_gpu_device_space_column_block_inside_a_wider_matrix(gpu):
+    """Gap 7: the TSFA_DEVICE space with ld > n_cols -- columns 3 .. 9 of a 4097 x 13 device matrix (pointer advanced
+    by three columns, n_cols = 7, ld = 13) through tsfa_relevance_real, tsfa_relevance_classes_ks and tsfa_impute.
+    The statistics equal the host-space call on the block; tsfa_impute leaves the columns around the block
+    bit-identical, NaN cells included.  The relevance calls see the block without NaN (they are not defined on it);
+    the NaN cells of the block are uploaded before the impute call."""
+    from tsfresh_amd import _native
+    lib = _native.load()
+    _native._bind_device_api(lib)
+    rng = np.random.default_rng(13)
+    n, ld, c0, m = 4097, 13, 3, 7
+    y = np.round(rng.standard_normal(n), 1)
+    codes = rng.permutation(np.arange(n) % 3).astype(np.int32)
+    M = rng.standard_normal((n, ld))
+    M[:, c0:c0 + m] = _columns(n, y, rng)[:, [0, 3, 4, 6, 7, 8, 10]]
+    outside = [0, 1, 2, 10, 11, 12]
+    for c in outside:                                   # must never be read: NaN and +-inf would show in any statistic
+        M[rng.random(n) < 0.2, c] = np.nan
+        M[rng.random(n) < 0.1, c] = np.inf
+    block = np.ascontiguousarray(M[:, c0:c0 + m])
+    dm = _native.DeviceMatrix(n, ld)
+    try:
+        _upload(lib, dm, M)
+        xptr = ctypes.c_void_p(dm.ptr + 8 * c0)
+        want_real, _ = _native.relevance_real(block, y)
+        got_real = _device_relevance_real(lib, xptr, n, m, ld, y)
+        _assert_same_records(got_real, want_real, "device block")
+        assert [got_real[f].tolist() for f in ref.REAL_FIELDS] == \
+            [[ref.real_column_stats(block[:, c], y)[f] for c in range(m)] for f in ref.REAL_FIELDS]
+        want_cls = _native.relevance_classes(block, codes, 3, with_ks=True)
+        got_cls = _device_relevance_classes_ks(lib, xptr, n, m, ld, codes, 3)
+        for u, v in zip(got_cls, want_cls):
+            assert np.array_equal(u, v)
+        assert np.array_equal(dm.to_host().view(np.uint64), M.view(np.uint64))   # the relevance calls write nothing
+        # impute: NaN and +-inf cells inside the block as well
+        M2 = M.copy()
+        u = rng.random((n, m))
+        M2[:, c0:c0 + m][u < 0.05] = np.nan
+        M2[:, c0:c0 + m][(u >= 0.05) & (u < 0.08)] = -np.inf
+        M2[:, c0 + 3] = np.nan                          # a column without a finite value
+        _upload(lib, dm, M2)
+        host_block = np.ascontiguousarray(M2[:, c0:c0 + m])
+        want_stats = _native.impute_matrix(host_block, device=0)
+        got_stats = _device_impute(lib, xptr, n, m, ld)
+        for u_, v_ in zip(got_stats, want_stats):
+            assert np.array_equal(u_, v_)
+        for c in range(m):
+            assert (got_stats[0][c], got_stats[1][c], got_stats[2][c], got_stats[3][c]) == ref.impute_stats(M2[:, c0 + c])
+        after = dm.to_host()
+        assert np.array_equal(after[:, outside].view(np.uint64), M2[:, outside].view(np.uint64))
+        assert np.array_equal(after[:, c0:c0 + m], host_block)
+        assert np.array_equal(host_block, _numpy_impute(M2[:, c0:c0 + m]))
+    finally:
+        dm.free()
+
+
+# ------------------------------------------------------------------------------------------- one table at a seam
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [4097, 8193])
+def test_gpu_regression_table_matches_the_oracle_at_a_seam(gpu, n):
+    """Gap 2, end to end: calculate_relevance_table for regression one row past the 4096 tile and one row past the
+    first merge-path level, against the oracle under the comparison of the at-scale tests of test_selection.py."""
+    from oracle.selection import relevance_table
+    from tsfresh_amd.feature_selection import calculate_relevance_table
+    Xall, yv = _real_inputs(n, "rounded")
+    X = pd.DataFrame(np.ascontiguousarray(Xall[:, [0, 3, 4, 6]]), columns=["iid", "few_values", "two_valued", "constant"])
+    y = pd.Series(yv.copy())
+    tab = calculate_relevance_table(X, y)
+    want = relevance_table(X, y)
+    assert list(tab.loc[X.columns]["type"]) == ["real", "real", "binary", "constant"]
+    for f in X.columns:
+        for c, w in want[f].items():
+            g = tab.loc[f][c]
+            if isinstance(w, (bool, np.bool_)):
+                assert bool(g) == bool(w), (f, c, g, w)
+            elif isinstance(w, str):
+                assert g == w
+            elif isinstance(w, float) and math.isnan(w):
+                assert math.isnan(g)
+            else:
+                assert g == pytest.approx(w, rel=1e-9, abs=1e-300), (f, c, g, w)

@@ -220,7 +220,9 @@ def test_gpu_relevance_statistics_are_exact_with_infinities_and_ties():
     from scipy.stats import rankdata
     from tsfresh_amd import _native
     rng = np.random.default_rng(9)
-    for n, m, C in [(1, 2, 1), (7, 3, 2), (2049, 6, 3), (5000, 5, 2), (33000, 4, 4)]:
+    for n, m, C in [(1, 2, 1), (7, 3, 2), (2049, 6, 3), (5000, 5, 2), (33000, 4, 4),
+                    # both sides of the 2048 / 4096 sort tiles and of the first global merge level
+                    (2047, 4, 2), (2048, 4, 3), (4095, 4, 2), (4096, 4, 4), (4097, 4, 3), (8192, 4, 2), (8193, 4, 3)]:
         X = rng.standard_normal((n, m))
         X[:, 0] = np.round(X[:, 0], 0)
         if n > 4:
