@@ -66,3 +66,15 @@ def test_counting_filter_equals_the_oracle_on_the_device(gpu, dtype):
     bad = compare(list(names), got, want, [s.astype(np.float64) for s in series], skipped=skipped)
     assert not bad, bad[:10]
     assert len(skipped) <= 15, skipped
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_counts_on_tied_series_equal_the_emulation_on_the_device(gpu, dtype):
+    """The periodic, tiled, square-wave and quantized series above (5 of them are R8's: no reference count): device and
+    emulation return the count of one documented order (fam_cwt.h: taps ascending), so every cell is equal.  The first 400
+    samples of each as uniform rows, 310 .. 400 of them in the ragged run."""
+    from test_quantized_divergence import check_device_counts_equal_the_emulation
+    s = long_series()
+    tied = [s[i] for i in (3, 4, 5, 6, 7, 8, 11)]
+    check_device_counts_equal_the_emulation([[x[:400 - 15 * i] for i, x in enumerate(tied)], [x[:400] for x in tied]], dtype)

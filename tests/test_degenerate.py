@@ -3,19 +3,14 @@ constant, linear, periodic, ... series must return what the reference returns --
 (minimum-norm) solution with rank-aware AIC / degrees of freedom -- wherever the reference's answer is not itself
 round-off (tests/parity.py R4/R5 say where it is).  CPU: the g++ build of the kernel sources; the `-m gpu` twin is
 tests/test_gpu_parity.py::test_hip_matches_reference_golden[...]."""
-import math
-from fractions import Fraction
-
 import numpy as np
 import pytest
 
 import goldens
+from dd_cases import AR_ADF, ill_conditioned_series, perfect_fit_series, tiny_noise_ramp
 from engines import emul_engine, oracle_engine
 from parity import compare, excluded
 from tsfresh_amd.feature_extraction.settings import ComprehensiveFCParameters
-
-AR_ADF = {"ar_coefficient": [{"coeff": c, "k": 10} for c in range(11)],
-          "augmented_dickey_fuller": [{"attr": a, "autolag": "AIC"} for a in ("teststat", "pvalue", "usedlag")]}
 
 
 def _cells(pair, label, feature):
@@ -57,33 +52,12 @@ def test_perfect_fit_behaviour_is_pinned():
     """Where a lag-search regression fits perfectly the reference divides round-off by round-off (parity.py R5); the
     kernels treat the residual as the exact 0 it is: AIC = -inf (the first perfect lag wins), t = 0/0 or x/0."""
     adf = {"augmented_dickey_fuller": AR_ADF["augmented_dickey_fuller"]}
-    for x, want_lag in ((np.arange(64.0), 1), (5.0 - 0.5 * np.arange(100.0), 1), (np.tile([1.0, -1.0], 40), 0),
-                        (np.arange(200.0) ** 2, 1)):
+    for x, want_lag in perfect_fit_series():
         names, got = emul_engine(adf, x, np.array([0, len(x)]))
         row = dict(zip([n.split('attr_"')[1].split('"')[0] for n in names], got[0]))
         assert row["usedlag"] == want_lag, (row, want_lag)
         assert np.isnan(row["teststat"]) or np.isinf(row["teststat"]), row
         assert all(excluded(n, x) for n in names)  # and parity.py knows these are round-off in the reference
-
-
-def _exact_nested_ssr(X, y):
-    """Residual sums of squares of the nested fits y ~ X[:, :m], m = 1..p, in exact rational arithmetic (LDL^T)."""
-    Xf = [[Fraction(float(v)) for v in r] for r in X]
-    yf = [Fraction(float(v)) for v in y]
-    p = len(Xf[0])
-    G = [[sum(r[a] * r[c] for r in Xf) for c in range(p)] for a in range(p)]
-    g = [sum(r[a] * v for r, v in zip(Xf, yf)) for a in range(p)]
-    yy = sum(v * v for v in yf)
-    L = [[Fraction(0)] * p for _ in range(p)]
-    D, w, out, acc = [Fraction(0)] * p, [Fraction(0)] * p, [], Fraction(0)
-    for j in range(p):
-        D[j] = G[j][j] - sum(L[j][k] ** 2 * D[k] for k in range(j))
-        for i in range(j + 1, p):
-            L[i][j] = (G[i][j] - sum(L[i][k] * L[j][k] * D[k] for k in range(j))) / D[j]
-        w[j] = (g[j] - sum(L[j][k] * w[k] * D[k] for k in range(j))) / D[j]
-        acc += w[j] ** 2 * D[j]
-        out.append(float(yy - acc))
-    return out
 
 
 def test_near_degenerate_lag_search_agrees_with_exact_arithmetic():
@@ -92,16 +66,8 @@ def test_near_degenerate_lag_search_agrees_with_exact_arithmetic():
     why parity.py R4 excludes designs with singular values in (5e-16, 1e-8) s_max instead of calling them mismatches."""
     g = goldens.load("degenerate")
     i = g["labels"].index("tiny_noise_ramp_300")
-    x = g["series"][i]
+    x, exact_lag = tiny_noise_ramp()      # (the exact-rational lag search: tests/dd_cases.py)
     n = len(x)
-    M = min(n // 2 - 2, int(math.ceil(12.0 * (n / 100.0) ** 0.25)))
-    d = np.diff(x)
-    rows = np.arange(M, len(d))
-    X = np.column_stack([np.ones(len(rows)), x[rows]] + [d[rows - j] for j in range(1, M + 1)])
-    ssr = _exact_nested_ssr(X, d[rows])
-    nobs = len(rows)
-    aic = [nobs * math.log(ssr[m - 1] / nobs) + 2 * m for m in range(2, M + 3)]
-    exact_lag = int(np.argmin(aic))
     names, got = emul_engine({"augmented_dickey_fuller": [{"attr": "usedlag", "autolag": "AIC"}]}, x, np.array([0, n]))
     assert got[0, 0] == exact_lag == 12
     ref = g["matrix"][i, g["names"].index('value__augmented_dickey_fuller__attr_"usedlag"__autolag_"AIC"')]
@@ -112,16 +78,7 @@ def test_near_degenerate_lag_search_agrees_with_exact_arithmetic():
 def test_ill_conditioned_but_resolvable_series_match_the_oracle():
     """Designs between the float64 normal equations' reach (pivot test, ~3e4) and the reference's own (1e10): noiseless
     float32 sines, ramps with small noise, large offsets.  The second pass must agree with the oracle's SVD to 1e-6."""
-    rng = np.random.default_rng(11)
-    t = np.arange(600, dtype=np.float64)
-    cases = [
-        np.sin(0.07 * t[:512]).astype(np.float32).astype(np.float64),
-        (2.0 + np.cos(0.031 * t[:400])).astype(np.float32).astype(np.float64),
-        t[:300] + 1e-4 * rng.standard_normal(300),
-        3e4 + rng.standard_normal(256),
-        np.round(50 * np.sin(0.02 * t), 3),
-        np.concatenate([np.full(40, 2.0), 2.0 + 1e-3 * rng.standard_normal(80)]),
-    ]
+    cases = ill_conditioned_series()
     values = np.concatenate(cases)
     offsets = np.concatenate([[0], np.cumsum([len(c) for c in cases])]).astype(np.int64)
     names, got = emul_engine(AR_ADF, values, offsets)

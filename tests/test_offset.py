@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import goldens
-import polyfit_mp
+from dd_cases import langevin_second_pass_cases
 from engines import emul_engine, oracle_engine
 from parity import EPS, compare, excluded, feature_of
 
@@ -47,19 +47,7 @@ def _pack(series):
 def test_langevin_second_pass_agrees_with_60_digit_arithmetic():
     """fam_langevin_dd.h against np.polyfit's DEFINITION evaluated in 60 digits (scaled design, SVD, rank cut, minimum
     norm): the pass stays within 2 % of eps * kappa -- the reference's own float64 result is ~1 eps * kappa away."""
-    rng = np.random.default_rng(5)
-    series, want = [], []
-    for off in (1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8):
-        for kind in ("iid", "walk"):
-            e = rng.standard_normal(400)
-            x = off + (e if kind == "iid" else np.cumsum(e) * 0.1)
-            bm = polyfit_mp.bin_means(x, 30)
-            kappa, in_band = polyfit_mp.polyfit_conditioning(bm[0], 3)
-            if in_band:
-                continue
-            coef, _, rank = polyfit_mp.exact_polyfit(bm[0], bm[1], 3)
-            series.append(x)
-            want.append((coef, kappa, rank))
+    series, want = langevin_second_pass_cases()
     assert len(series) >= 10 and {w[2] for w in want} >= {2, 3, 4}     # full rank and both truncated ranks occur
     values, offsets = _pack(series)
     _, got = emul_engine({"friedrich_coefficients": LANGEVIN["friedrich_coefficients"]}, values, offsets)

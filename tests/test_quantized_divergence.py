@@ -56,3 +56,35 @@ def test_r8_fires_on_walks_and_not_on_rounded_noise():
     fam = _families(12, 300)
     fired = {k: sum(excluded("value__number_cwt_peaks__n_5", x) for x in v) for k, v in fam.items()}
     assert fired["rounded"] <= 1 and fired["walk"] >= 6, fired
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# R8 cells have no reference value, but they have ONE kernel value: the count of the documented order (README; fam_cwt.h:
+# taps ascending).  The g++ emulation builds the same body, so device and emulation are equal in every cell.
+# ---------------------------------------------------------------------------------------------------------------------
+CWT_PARAMS = {"number_cwt_peaks": [{"n": n} for n in (1, 3, 5)]}
+
+
+def check_device_counts_equal_the_emulation(batches, dtype):
+    """batches: lists of series (a ragged one, a uniform one); both engines read the values as `dtype` holds them."""
+    for batch in batches:
+        values = np.concatenate(batch).astype(dtype)
+        offsets = np.concatenate([[0], np.cumsum([len(x) for x in batch])]).astype(np.int64)
+        names, got = hip_engine(CWT_PARAMS, values, offsets)
+        enames, want = emul_engine(CWT_PARAMS, values.astype(np.float64), offsets)
+        assert list(names) == list(enames)
+        diff = np.argwhere(got != want)
+        assert len(diff) == 0, [(int(i), names[j], got[i, j], want[i, j]) for i, j in diff[:8]]
+    return names
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_hip_cwt_peak_counts_equal_the_emulation_on_tied_data(gpu, dtype):
+    fam = _families(12, 400)
+    uniform = fam["rounded"] + fam["poisson"] + fam["walk"]
+    ragged = [x[:400 - 7 * (i % 20)] if i % 3 else x for i, x in enumerate(uniform)]
+    names = check_device_counts_equal_the_emulation([ragged, uniform], dtype)
+    walks = [x.astype(dtype).astype(np.float64) for x in fam["walk"]]
+    fired = sum(excluded(n, x) for x in walks for n in names)
+    assert fired >= len(walks) * len(names) / 3.0, fired      # the cells parity skips are among the cells compared here
