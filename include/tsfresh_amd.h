@@ -147,6 +147,16 @@ int tsfa_extract_windows(tsfa_plan *plan, const void *values, int32_t dtype, con
                          int64_t ld_out, int32_t space, void *stream);
 
 /*
+ * The row chunks into which the TSFA_HOST form of tsfa_extract* cuts a batch of n_series series on this plan (at least 4096
+ * series each, at most 16; the plan's "host_chunks" option and profiling change them): cuts[c] .. cuts[c + 1] is chunk c.
+ * A launch sizes its workgroups by the lengths of ITS batch, and the workgroup size decides the association of the
+ * reductions: a caller that extracts the same series chunk by chunk with TSFA_DEVICE pointers gets, with these cuts, the
+ * launches of the TSFA_HOST form and bit-equal features.  cap: entries of `cuts` (>= n_chunks + 1, 17 always suffice).
+ * Returns the number of chunks (0 for n_series == 0) or a negative tsfa_status.
+ */
+int tsfa_extract_chunks(const tsfa_plan *plan, int64_t n_series, int64_t *cuts, int32_t cap);
+
+/*
  * Timing of the kernels of the last tsfa_extract on this plan, measured with HIP events on the
  * stream the kernels were launched on.  names[i] / ms[i] for i < returned count (<= cap).
  * Only recorded when tsfa_plan_set_profiling(plan, 1) was called before the extract.
@@ -282,6 +292,48 @@ int32_t tsfa_pack_set_flags(const tsfa_pack_set *set);
 int32_t tsfa_pack_set_n_passes(const tsfa_pack_set *set);
 int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int32_t value_type, int32_t space, tsfa_pack **out_packs);
 void tsfa_pack_set_destroy(tsfa_pack_set *set);
+
+/* Window builder: the rolled (forecasting) layout of one pack, built on the device from the pack's offsets.  Replaces, for a
+ * frame packed by tsfa_pack_device / tsfa_pack_set_*, the host's enumeration of n_series x n_shifts window candidates
+ * (tsfresh/utilities/dataframe_functions.py:340-358, _roll_out_time_series, for all shifts at once) and the upload of the
+ * starts and ends: the windows go from here to tsfa_extract_windows as TSFA_DEVICE pointers next to the pack's value buffer.
+ *   pack               a handle of tsfa_pack_device or a view of tsfa_pack_set_values
+ *   rolling_direction  != 0; its magnitude is the stride of the timeshifts
+ *   max_timeshift      > 0, or 0 for none
+ *   min_timeshift      >= 0
+ *   steps              the reference's prediction_steps (:546): the longest series of the whole FRAME over all kinds (of one
+ *                      entry for a dict container); the caller passes it because another kind may own the longest series
+ * The windows are those of the reference, in (series, ascending timeshift) order.  Series of `len` samples, a = |direction|,
+ * mts = max_timeshift or steps; no window when mts < min_timeshift; otherwise
+ *   direction > 0: every ts with ts = steps (mod a) and min_timeshift + 1 <= ts <= len gives [max(ts - mts - 1, 0), ts)
+ *   direction < 0: every frm = k a <= len - min_timeshift - 1 gives [frm, min(frm + mts + 1, len)), ts = frm + 1
+ * Three launches: a per-series count (O(1) per series), the packer's exclusive scan, a fill in which window w finds its series
+ * by bisection over the scanned counts.  A series has at most `len` windows, so a pack has fewer than 2^32 of them; every
+ * index is int64.  The handle owns, in device memory, n_windows int64 each of
+ *   starts / ends      indices into the pack's value buffer (offsets[s] + frm, offsets[s] + until)
+ *   series             the series index s of the window (row of the pack's ids)
+ *   timeshifts         ts
+ *   tsfa_windows_n_windows, tsfa_windows_starts / _ends (device pointers, NULL when there is no window)
+ *   tsfa_windows_copy_series / _timeshifts / _starts / _ends: copies to host arrays of n_windows int64
+ *   tsfa_roll_shift_values  the value of the pack's kept sort column that names each window -- sort[ends - 1] for a positive
+ *                      direction, sort[starts] for a negative one -- gathered on the device in the column's own element type;
+ *                      n_windows elements are copied to out_host.  `pack` is the pack the windows were built on.
+ *                      TSFA_ERR_INVALID for a pack without TSFA_PACK_KEEP_SORT.
+ * Synchronous.  TSFA_ERR_NO_DEVICE without a HIP device; TSFA_ERR_INVALID for direction 0, a negative max_timeshift or
+ * min_timeshift, or steps below the pack's longest series.  The windows do not keep the pack alive: destroy them first or
+ * not, but hand tsfa_extract_windows only live buffers. */
+typedef struct tsfa_windows tsfa_windows; /* opaque; owned by the library */
+int tsfa_roll_windows(const tsfa_pack *pack, int32_t rolling_direction, int64_t max_timeshift, int64_t min_timeshift,
+                      int64_t steps, tsfa_windows **out_windows);
+int64_t tsfa_windows_n_windows(const tsfa_windows *windows);
+const int64_t *tsfa_windows_starts(const tsfa_windows *windows);
+const int64_t *tsfa_windows_ends(const tsfa_windows *windows);
+int tsfa_windows_copy_series(const tsfa_windows *windows, int64_t *series_host);
+int tsfa_windows_copy_timeshifts(const tsfa_windows *windows, int64_t *timeshifts_host);
+int tsfa_windows_copy_starts(const tsfa_windows *windows, int64_t *starts_host);
+int tsfa_windows_copy_ends(const tsfa_windows *windows, int64_t *ends_host);
+int tsfa_roll_shift_values(const tsfa_windows *windows, const tsfa_pack *pack, void *out_host);
+void tsfa_windows_destroy(tsfa_windows *windows);
 
 /* Page-locked host memory for the TSFA_HOST form.  tsfa_extract* accepts ANY host pointer; from pageable memory the HIP
  * runtime stages every transfer through its own bounce buffers, from memory obtained here the copy engines read and

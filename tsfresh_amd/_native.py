@@ -30,6 +30,7 @@ EXPORTS = (
     "tsfa_version", "tsfa_device_count", "tsfa_last_error", "tsfa_calc_id", "tsfa_calc_name", "tsfa_calc_count",
     "tsfa_plan_create", "tsfa_plan_create_with_data", "tsfa_plan_n_cols", "tsfa_plan_destroy", "tsfa_extract", "tsfa_extract_timed",
     "tsfa_extract_windows",
+    "tsfa_extract_chunks",
     "tsfa_plan_set_profiling",
     "tsfa_plan_set_option",
     "tsfa_plan_last_timings",
@@ -56,6 +57,16 @@ EXPORTS = (
     "tsfa_pack_set_n_passes",
     "tsfa_pack_set_values",
     "tsfa_pack_set_destroy",
+    "tsfa_roll_windows",
+    "tsfa_windows_n_windows",
+    "tsfa_windows_starts",
+    "tsfa_windows_ends",
+    "tsfa_windows_copy_series",
+    "tsfa_windows_copy_timeshifts",
+    "tsfa_windows_copy_starts",
+    "tsfa_windows_copy_ends",
+    "tsfa_roll_shift_values",
+    "tsfa_windows_destroy",
     "tsfa_impute",
     "tsfa_relevance_classes",
     "tsfa_relevance_classes_ks",
@@ -480,6 +491,104 @@ class DevicePackSet:
             pass
 
 
+def _bind_roll_api(lib):
+    """The tsfa_roll_* / tsfa_windows_* prototypes, bound on first use (a diagnostics library given through TSFA_LIB may
+    predate them)."""
+    if getattr(lib, "_tsfa_roll_bound", False):
+        return
+    lib.tsfa_roll_windows.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                      ctypes.POINTER(ctypes.c_void_p)]
+    lib.tsfa_roll_windows.restype = ctypes.c_int
+    lib.tsfa_windows_n_windows.argtypes, lib.tsfa_windows_n_windows.restype = [ctypes.c_void_p], ctypes.c_int64
+    for name in ("starts", "ends"):
+        fn = getattr(lib, "tsfa_windows_" + name)
+        fn.argtypes, fn.restype = [ctypes.c_void_p], ctypes.c_void_p
+    for name in ("copy_series", "copy_timeshifts", "copy_starts", "copy_ends"):
+        fn = getattr(lib, "tsfa_windows_" + name)
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
+    lib.tsfa_roll_shift_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.tsfa_roll_shift_values.restype = ctypes.c_int
+    lib.tsfa_windows_destroy.argtypes = [ctypes.c_void_p]
+    lib.tsfa_windows_destroy.restype = None
+    lib._tsfa_roll_bound = True
+
+
+class DeviceWindows:
+    """Owns a `tsfa_windows*`: the rolled windows of one DevicePack, built on the device from the pack's offsets
+    (tsfa_roll_windows).  The starts and ends stay in HBM and go to `Plan.extract_windows_pack` as device pointers; the host
+    gets the series index and the timeshift of every window (`.series`, `.timeshifts`: what the window ids are built from),
+    `.shift_values()` (the kept sort column's value that names each window) and, only when asked, `.starts` / `.ends`.
+    steps: the reference's prediction_steps -- the longest series of the whole frame, which another kind may own.
+    The pack must stay open for as long as the windows are used."""
+
+    def __init__(self, pack, rolling_direction=1, max_timeshift=None, min_timeshift=0, steps=None):
+        lib = load()
+        _bind_device_api(lib)
+        _bind_roll_api(lib)
+        if steps is None:
+            steps = int(np.diff(pack.offsets).max()) if pack.n_series else 1
+        handle = ctypes.c_void_p()
+        _check(lib, lib.tsfa_roll_windows(pack._h, int(rolling_direction), int(max_timeshift or 0), int(min_timeshift),
+                                          int(steps), ctypes.byref(handle)))
+        self._lib, self._h, self._pack, self.device = lib, handle, pack, pack.device
+        self.rolling_direction = int(rolling_direction)
+        self.n_windows = int(lib.tsfa_windows_n_windows(handle))
+        self.starts_ptr = lib.tsfa_windows_starts(handle)
+        self.ends_ptr = lib.tsfa_windows_ends(handle)
+        self._host = {}
+
+    def _copy(self, what):
+        if what not in self._host:
+            out = np.empty(self.n_windows, dtype=np.int64)
+            fn = getattr(self._lib, "tsfa_windows_copy_" + what)
+            _check(self._lib, fn(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+            self._host[what] = out
+        return self._host[what]
+
+    @property
+    def series(self):
+        return self._copy("series")
+
+    @property
+    def timeshifts(self):
+        return self._copy("timeshifts")
+
+    @property
+    def starts(self):
+        return self._copy("starts")
+
+    @property
+    def ends(self):
+        return self._copy("ends")
+
+    def shift_values(self):
+        """sort[ends - 1] (positive direction) / sort[starts] (negative) of the pack's kept sort column, gathered on the
+        device: n_windows elements of the column's dtype come back, not the column."""
+        if self._pack._sort_dtype is None:
+            raise ValueError("the pack was made without keep_sort=True: it holds no sort column")
+        out = np.empty(self.n_windows, dtype=self._pack._sort_dtype)
+        _check(self._lib, self._lib.tsfa_roll_shift_values(self._h, self._pack._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.tsfa_windows_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            if not sys.is_finalizing():
+                self.close()
+        except Exception:
+            pass
+
+
 def _result_matrix(n_rows, n_cols):
     """The feature matrix of a host-side extraction: page-locked when it is large enough for the copy-out to matter."""
     if n_rows * n_cols * 8 >= (4 << 20) and os.environ.get("TSFRESH_AMD_PINNED", "1") != "0":
@@ -625,6 +734,48 @@ class Plan:
         try:
             self.extract_into(None, None, dm, pack=pack)
             dm.to_host(out=out)
+        finally:
+            dm.free()
+        return out
+
+    def extract_windows_pack(self, pack, windows, out=None, chunk_rows=None):
+        """The windows of a DeviceWindows over the samples of its DevicePack -> float64 [n_windows, n_cols] on the host:
+        tsfa_extract_windows with the pack's value pointer and the handle's starts / ends, nothing is uploaded.  The device
+        result matrix comes back in row chunks (chunk_rows windows each; default: the cuts of the TSFA_HOST pipeline, tsfa_extract_chunks, up to 16), so a
+        large window count does not need one n_windows x n_cols allocation next to the samples.
+        out: optional C-contiguous float64 [n_windows, n_cols] target."""
+        n = windows.n_windows
+        if pack.device != self.device or windows.device != self.device:
+            raise ValueError("the pack and the windows must live on the plan's device")
+        if out is None:
+            out = _result_matrix(n, self.n_cols)
+        elif out.dtype != np.float64 or out.shape != (n, self.n_cols) or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous float64 [n_windows, n_cols] matrix")
+        if n == 0 or self.n_cols == 0:
+            return out
+        if chunk_rows is None:
+            # the cuts of the TSFA_HOST pipeline, from the library: the same launches as extract_windows_host, bit-equal features
+            edges = (ctypes.c_int64 * 17)()
+            self._lib.tsfa_extract_chunks.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32]
+            self._lib.tsfa_extract_chunks.restype = ctypes.c_int
+            n_chunks = self._lib.tsfa_extract_chunks(self._h, n, edges, 17)
+            if n_chunks < 0:
+                _check(self._lib, n_chunks)
+            cuts = [(int(edges[c]), int(edges[c + 1])) for c in range(n_chunks)]
+        else:
+            chunk_rows = max(1, min(int(chunk_rows), n))
+            cuts = [(r0, min(r0 + chunk_rows, n)) for r0 in range(0, n, chunk_rows)]
+        dm = DeviceMatrix(max(r1 - r0 for r0, r1 in cuts), self.n_cols, self.device)
+        try:
+            for r0, r1 in cuts:
+                rows = r1 - r0
+                _check(self._lib, self._lib.tsfa_extract_windows(
+                    self._h, ctypes.c_void_p(pack.values_ptr), pack.values_type, None,
+                    ctypes.c_void_p(windows.starts_ptr + 8 * r0), ctypes.c_void_p(windows.ends_ptr + 8 * r0), rows,
+                    ctypes.c_void_p(dm.ptr), dm.ld, TSFA_DEVICE, None))
+                part = out[r0:r0 + rows]
+                _check(self._lib, self._lib.tsfa_device_copy(part.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(dm.ptr),
+                                                             part.nbytes, 0, self.device))
         finally:
             dm.free()
         return out

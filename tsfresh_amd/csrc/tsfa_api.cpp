@@ -547,6 +547,24 @@ static int host_len_stats(const int64_t *starts, const int64_t *ends, int64_t n,
     return 0;
 }
 
+// Row chunks of the TSFA_HOST pipeline: >= 4096 series each (a launch should fill the 256 CUs several times over), at most
+// TSFA_MAX_CHUNKS; chunk c is rows [n_series * c / n_chunks, n_series * (c + 1) / n_chunks).  tsfa_extract_chunks hands the
+// same cuts to callers that launch a batch chunk by chunk with TSFA_DEVICE pointers.
+static int host_chunk_count(const tsfa_plan *plan, int64_t n_series) {
+    int n_chunks = (int)std::min<int64_t>(TSFA_MAX_CHUNKS, std::max<int64_t>(1, n_series / 4096));
+    if (plan->opt.host_chunks >= 1) n_chunks = std::min(plan->opt.host_chunks, TSFA_MAX_CHUNKS);
+    if (plan->profiling) n_chunks = 1;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(n_chunks, n_series));
+}
+
+int tsfa_extract_chunks(const tsfa_plan *plan, int64_t n_series, int64_t *cuts, int32_t cap) {
+    if (!plan || !cuts || n_series < 0) return fail(TSFA_ERR_INVALID, "tsfa_extract_chunks: bad arguments");
+    const int n_chunks = n_series ? host_chunk_count(plan, n_series) : 0;
+    if (cap < n_chunks + 1) return fail(TSFA_ERR_INVALID, "tsfa_extract_chunks: cuts holds fewer than n_chunks + 1 entries");
+    for (int c = 0; c <= n_chunks; ++c) cuts[c] = n_chunks ? n_series * c / n_chunks : 0;
+    return n_chunks;
+}
+
 static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const double *d_times, const int64_t *d_starts,
                      const int64_t *d_ends, int64_t n_series, double *d_out, int64_t ld, const BatchShape &sh,
                      const int *d_sel, hipStream_t st, bool with_overlap) {
@@ -1195,11 +1213,7 @@ int tsfa_extract_windows(tsfa_plan *plan, const void *values, int32_t dtype, con
     double *d_out = (double *)plan->out.p;
     const int64_t ld = plan->n_cols;
 
-    // chunks: >= 4096 series each (a launch should fill the 256 CUs several times over), at most TSFA_MAX_CHUNKS
-    int n_chunks = (int)std::min<int64_t>(TSFA_MAX_CHUNKS, std::max<int64_t>(1, n_series / 4096));
-    if (plan->opt.host_chunks >= 1) n_chunks = std::min(plan->opt.host_chunks, TSFA_MAX_CHUNKS);
-    if (plan->profiling) n_chunks = 1;
-    n_chunks = (int)std::min<int64_t>(n_chunks, n_series);
+    const int n_chunks = host_chunk_count(plan, n_series);
 
     HIP_TRY(hipMemcpyAsync(plan->offsets.p, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice, plan->s_in));
     if (!ragged || n_chunks == 1) {

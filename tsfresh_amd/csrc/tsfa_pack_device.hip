@@ -1,5 +1,6 @@
 // Device packer of the C-ABI (include/tsfresh_amd.h: tsfa_pack_device*): the kernels around the bodies of pack_device.h
 // and the host code that strings them together.  See pack_device.h for the scratch formula and the sort's design.
+// The window builder (tsfa_roll_windows, roll_device.h) lives here as well: it reads a pack's buffers and reuses k_pack_scan.
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -7,6 +8,7 @@
 #include <vector>
 
 #include "pack_device.h"
+#include "roll_device.h"
 
 int tsfa_fail(int code, const char *msg);
 
@@ -630,3 +632,165 @@ done:
 }
 
 extern "C" void tsfa_pack_set_destroy(tsfa_pack_set *set) { delete set; }
+
+// ---------------------------------------------------------------------------------------------
+// Window builder: the rolled layout of one pack (roll_device.h), built from the pack's offsets on the device
+// ---------------------------------------------------------------------------------------------
+struct tsfa_windows {
+    int32_t device = 0;
+    int32_t positive = 0;
+    int64_t n_windows = 0;
+    int64_t *starts = nullptr, *ends = nullptr, *series = nullptr, *shifts = nullptr;  // n_windows int64 each, device memory
+};
+
+namespace {
+
+__global__ void __launch_bounds__(PK_GRID_THREADS) k_roll_count(const int64_t *offsets, int64_t n_series, RlParams p, uint32_t *counts,
+                                                                  RlStats *st) {
+    __shared__ pk_u64 red;
+    const PkBlk b{(int)threadIdx.x, (int)blockDim.x};
+    rl_count_body(b, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, offsets, n_series, p, counts, &red, st);
+}
+
+__global__ void __launch_bounds__(PK_GRID_THREADS) k_roll_fill(const int64_t *offsets, int64_t n_series, const uint32_t *scanned,
+                                                                 int64_t n_windows, RlParams p, int64_t *starts, int64_t *ends,
+                                                                 int64_t *series, int64_t *shifts) {
+    const PkBlk b{(int)threadIdx.x, (int)blockDim.x};
+    rl_fill_body(b, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, offsets, n_series, scanned, n_windows, p, starts,
+                 ends, series, shifts);
+}
+
+__global__ void __launch_bounds__(PK_GRID_THREADS) k_roll_shift_values(const void *sort, int itemsize, int64_t n_rows,
+                                                                         const int64_t *starts, const int64_t *ends, int positive,
+                                                                         int64_t n_windows, void *out) {
+    const PkBlk b{(int)threadIdx.x, (int)blockDim.x};
+    rl_shift_values_body(b, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, sort, itemsize, n_rows, starts, ends,
+                         positive, n_windows, out);
+}
+
+}  // namespace
+
+#undef PK_WHO
+#define PK_WHO "tsfa_roll_windows"
+extern "C" int tsfa_roll_windows(const tsfa_pack *pack, int32_t rolling_direction, int64_t max_timeshift, int64_t min_timeshift,
+                                 int64_t steps, tsfa_windows **out_windows) {
+    if (!out_windows) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_roll_windows: out_windows is NULL");
+    *out_windows = nullptr;
+    int ndev = 0;  // before the handle is looked at: without a device no pack can exist
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_roll_windows: no HIP device visible: tsfresh_amd has no CPU fallback");
+    if (!pack) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_roll_windows: pack is NULL");
+    RlParams p;
+    if (const char *why = rl_make_params(rolling_direction, max_timeshift, min_timeshift, steps, &p))
+        return tsfa_fail(TSFA_ERR_INVALID, (std::string("tsfa_roll_windows: ") + why).c_str());
+    const int64_t ns = pack->n_groups;
+    uint32_t *counts = nullptr;
+    RlStats *d_st = nullptr;
+    RlStats st;
+    tsfa_windows *win = new tsfa_windows();
+    int rc = TSFA_OK;
+    win->device = pack->device;
+    win->positive = p.positive;
+    memset(&st, 0, sizeof(st));
+
+    PK_HIP(hipSetDevice(pack->device));
+    if (ns > 0) {
+        PK_ALLOC(counts, (size_t)ns * 4, "the window counts");
+        PK_ALLOC(d_st, sizeof(RlStats), "the window builder's counters");
+        PK_HIP(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
+        k_roll_count<<<pk_grid(ns), PK_GRID_THREADS, 0, 0>>>(pack->offsets, ns, p, counts, d_st);
+        k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)ns, &d_st->total);
+        PK_HIP(hipGetLastError());
+        PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
+        if ((int64_t)st.max_len > steps) {
+            rc = tsfa_fail(TSFA_ERR_INVALID, ("tsfa_roll_windows: steps = " + std::to_string(steps) + " is below the pack's longest series (" +
+                                              std::to_string(st.max_len) + " samples)").c_str());
+            goto done;
+        }
+        win->n_windows = (int64_t)st.total;
+    }
+    if (win->n_windows > 0) {
+        const int64_t nw = win->n_windows;
+        PK_ALLOC(win->starts, (size_t)nw * 8, "the window starts");
+        PK_ALLOC(win->ends, (size_t)nw * 8, "the window ends");
+        PK_ALLOC(win->series, (size_t)nw * 8, "the windows' series indices");
+        PK_ALLOC(win->shifts, (size_t)nw * 8, "the windows' timeshifts");
+        k_roll_fill<<<pk_grid(nw), PK_GRID_THREADS, 0, 0>>>(pack->offsets, ns, counts, nw, p, win->starts, win->ends, win->series,
+                                                              win->shifts);
+        PK_HIP(hipGetLastError());
+        PK_HIP(hipDeviceSynchronize());
+    }
+done:
+    (void)hipFree(counts); (void)hipFree(d_st);
+    if (rc) {
+        tsfa_windows_destroy(win);
+        return rc;
+    }
+    *out_windows = win;
+    return TSFA_OK;
+}
+
+extern "C" int64_t tsfa_windows_n_windows(const tsfa_windows *windows) { return windows ? windows->n_windows : 0; }
+extern "C" const int64_t *tsfa_windows_starts(const tsfa_windows *windows) { return windows ? windows->starts : nullptr; }
+extern "C" const int64_t *tsfa_windows_ends(const tsfa_windows *windows) { return windows ? windows->ends : nullptr; }
+
+static int rl_copy_out(const tsfa_windows *windows, void *dst, const void *src, size_t bytes, const char *who) {
+    if (!windows || !dst) return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": null pointer").c_str());
+    if (!bytes) return TSFA_OK;
+    hipError_t e = hipSetDevice(windows->device);
+    if (e == hipSuccess) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? (int)TSFA_OK : pk_fail_hip("hipMemcpy", e, who);
+}
+
+extern "C" int tsfa_windows_copy_series(const tsfa_windows *windows, int64_t *series_host) {
+    return rl_copy_out(windows, series_host, windows ? windows->series : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+                       "tsfa_windows_copy_series");
+}
+
+extern "C" int tsfa_windows_copy_timeshifts(const tsfa_windows *windows, int64_t *timeshifts_host) {
+    return rl_copy_out(windows, timeshifts_host, windows ? windows->shifts : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+                       "tsfa_windows_copy_timeshifts");
+}
+
+extern "C" int tsfa_windows_copy_starts(const tsfa_windows *windows, int64_t *starts_host) {
+    return rl_copy_out(windows, starts_host, windows ? windows->starts : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+                       "tsfa_windows_copy_starts");
+}
+
+extern "C" int tsfa_windows_copy_ends(const tsfa_windows *windows, int64_t *ends_host) {
+    return rl_copy_out(windows, ends_host, windows ? windows->ends : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+                       "tsfa_windows_copy_ends");
+}
+
+#undef PK_WHO
+#define PK_WHO "tsfa_roll_shift_values"
+extern "C" int tsfa_roll_shift_values(const tsfa_windows *windows, const tsfa_pack *pack, void *out_host) {
+    if (!windows || !pack || !out_host) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_roll_shift_values: null pointer");
+    if (!pack->sort)
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_roll_shift_values: the pack was made without TSFA_PACK_KEEP_SORT: it holds no sort column");
+    if (pack->device != windows->device)
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_roll_shift_values: the windows and the pack live on different devices");
+    const int64_t nw = windows->n_windows;
+    if (nw == 0) return TSFA_OK;
+    const int itemsize = pk_itemsize(pack->sort_type);
+    void *d_out = nullptr;
+    int rc = TSFA_OK;
+    PK_HIP(hipSetDevice(pack->device));
+    PK_ALLOC(d_out, (size_t)nw * itemsize, "the windows' shift values");
+    k_roll_shift_values<<<pk_grid(nw), PK_GRID_THREADS, 0, 0>>>(pack->sort, itemsize, pack->n_rows, windows->starts, windows->ends,
+                                                                  windows->positive, nw, d_out);
+    PK_HIP(hipGetLastError());
+    PK_HIP(hipMemcpy(out_host, d_out, (size_t)nw * itemsize, hipMemcpyDeviceToHost));
+done:
+    (void)hipFree(d_out);
+    return rc;
+}
+
+extern "C" void tsfa_windows_destroy(tsfa_windows *windows) {
+    if (!windows) return;
+    if (windows->starts || windows->ends || windows->series || windows->shifts) {
+        (void)hipSetDevice(windows->device);
+        (void)hipFree(windows->starts); (void)hipFree(windows->ends); (void)hipFree(windows->series); (void)hipFree(windows->shifts);
+    }
+    delete windows;
+}

@@ -24,6 +24,10 @@ _NATIVE_SCAN_MIN_ROWS = 1 << 18  # below this the numpy passes are as fast as sp
 # power of two at which the device route's median is below the host route's (profiles/pack_device_timing.md: 4.7 ms against
 # 6.5 ms at 2^18 rows, 34 ms against 0.80 s at 2^24)
 _DEVICE_PACK_MIN_ROWS = 1 << 18
+# extract_rolled_features(pack="auto"): rows of the frame from which the device route (device packer + windows built on the
+# device) is taken.  None: not measured end to end yet (profiles/roll_device_timing.md), "auto" keeps the
+# host route; to be set to the smallest measured power of two at which the device median is below the host median.
+_DEVICE_ROLL_MIN_ROWS = None
 PACK_MODES = ("auto", "host", "device")
 
 
@@ -64,6 +68,7 @@ class PackedKind:
         self._offsets = offsets
         self.times = times  # float64 hours since each series' first timestamp (DatetimeIndex input only)
         self.sort = sort    # the sort column in packed order (None without column_sort); names rolled windows
+        self.sort_dtype = None   # device_pack made with keep_sort: the sort column's dtype (the pack keeps datetimes as ticks)
 
     @property
     def offsets(self):
@@ -232,7 +237,8 @@ def _device_pack_columns(ids, values, sort_values, index=None):
     or none; a value column of bool, an integer type, float32 or float64.  NOT eligible, and follow-ups rather than part of
     the device packer: float ids, float16 / longdouble values, sort values that do not compare element-wise (objects),
     and frames with a DatetimeIndex (the `times` of linear_trend_timewise are pandas arithmetic, `_hours_since_first`).
-    `extract_rolled_features` needs the packed sort column on the host anyway and always packs there."""
+    `extract_rolled_features` packs here as well (`keep_sort=True`: the packed sort column stays in HBM and only the stamps
+    that name the windows come back, `_native.DeviceWindows.shift_values`)."""
     reason, keys = _device_key_columns(ids, sort_values, index)
     if reason is not None:
         return reason, None
@@ -242,17 +248,21 @@ def _device_pack_columns(ids, values, sort_values, index=None):
     return None, keys + (val_col,)
 
 
-def _pack_on_device(kind, columns, nan_name, device):
+def _pack_on_device(kind, columns, nan_name, device, sort_dtype=None):
+    """sort_dtype: the sort column's dtype when the pack is to keep the packed sort column (keep_sort), else None."""
     id_col, labels, sort_col, val_col = columns
-    dp = _native.DevicePack(id_col, sort_col, val_col, device=device)
+    dp = _native.DevicePack(id_col, sort_col, val_col, device=device, keep_sort=sort_dtype is not None)
     if dp.value_nan and nan_name is not None:
         dp.close()
         raise ValueError("Column must not contain NaN values: {}".format(nan_name))
-    ids = dp.ids if labels is None else labels[dp.ids]
-    return PackedKind(str(kind), ids, None, None, None, None, device_pack=dp)
+    return _view_kind(kind, dp, labels, sort_dtype)
 
 
-def _pack(kind, ids, values, sort_values, index=None, nan_name=None, pack="host", device=0):
+def _kept_sort_dtype(keep_sort, sort_values):
+    return np.asarray(sort_values).dtype if keep_sort and sort_values is not None else None
+
+
+def _pack(kind, ids, values, sort_values, index=None, nan_name=None, pack="host", device=0, keep_sort=False):
     """Group `values` by `ids` (ascending), each group ordered by `sort_values` (stable).  `index`: the frame's
     DatetimeIndex (row-aligned with `values`) or None.  nan_name: the value column's name if its NaN check
     (data.py:148-167) has been left to this function.
@@ -260,26 +270,35 @@ def _pack(kind, ids, values, sort_values, index=None, nan_name=None, pack="host"
     sorted and gathered on HIP device `device` (ValueError naming the reason when it is not eligible, see
     `_device_pack_columns`); "auto" -- the device for eligible frames of at least _DEVICE_PACK_MIN_ROWS rows when a device
     is visible, the host otherwise and (with one warning) when the device allocation fails.  The proof that a frame is
-    already in packed order (`_pack_presorted`) always runs first: that layout costs what it cost before."""
+    already in packed order (`_pack_presorted`) always runs first: that layout costs what it cost before.
+    keep_sort: the caller (`extract_rolled_features`) wants the samples, the offsets AND the packed sort column in HBM: where
+    the device route is taken it is taken for a frame in packed order too (the packer proves the order itself and sorts
+    nothing), the pack keeps the sort column, and the proof on the host only runs when the device does not take the frame."""
     ids = np.asarray(ids)
-    fast = _pack_presorted(kind, ids, values, sort_values, index, nan_name)
+    postponed = keep_sort and _takes_device(pack, len(ids), True)
+    fast = None if postponed else _pack_presorted(kind, ids, values, sort_values, index, nan_name)
     if fast is not None:
         return fast
-    if pack == "device" or (pack == "auto" and len(ids) >= _DEVICE_PACK_MIN_ROWS and _native.device_count() > 0):
+    if postponed or (not keep_sort and _takes_device(pack, len(ids))):
+        sort_dtype = _kept_sort_dtype(keep_sort, sort_values)
         reason, columns = _device_pack_columns(ids, values, sort_values, index)
         if reason is not None:
             if pack == "device":
                 raise ValueError("pack='device': kind {!r} cannot be packed on the device: {}".format(str(kind), reason))
         elif pack == "device":
-            return _pack_on_device(kind, columns, nan_name, device)
+            return _pack_on_device(kind, columns, nan_name, device, sort_dtype)
         else:
             try:
-                return _pack_on_device(kind, columns, nan_name, device)
+                return _pack_on_device(kind, columns, nan_name, device, sort_dtype)
             except _native.NativeError as exc:
                 if exc.code != _native.TSFA_ERR_HIP:
                     raise
                 warnings.warn("kind {!r}: packing on the device failed ({}); packing on the host instead".format(
                     str(kind), exc), RuntimeWarning, stacklevel=2)
+        if postponed:   # the device did not take the frame: the proof it was spared
+            fast = _pack_presorted(kind, ids, values, sort_values, index, nan_name)
+            if fast is not None:
+                return fast
     _raise_if_nan(_as_values(values), nan_name)
     codes, uniques = pd.factorize(ids, sort=True)
     order = None
@@ -308,13 +327,17 @@ def _pack(kind, ids, values, sort_values, index=None, nan_name=None, pack="host"
                       None if sort_values is None else np.asarray(sort_values)[order])
 
 
-def _takes_device(pack, n_rows):
-    """The rule of `_pack` for a frame of n_rows rows that is not in packed order."""
-    return pack == "device" or (pack == "auto" and n_rows >= _DEVICE_PACK_MIN_ROWS and _native.device_count() > 0)
+def _takes_device(pack, n_rows, keep_sort=False):
+    """The rule of `_pack` for a frame of n_rows rows that is not in packed order.  keep_sort (the rolled extraction, where
+    the device route also builds the windows and takes frames in packed order): its own threshold."""
+    min_rows = _DEVICE_ROLL_MIN_ROWS if keep_sort else _DEVICE_PACK_MIN_ROWS
+    return pack == "device" or (pack == "auto" and min_rows is not None and n_rows >= min_rows and _native.device_count() > 0)
 
 
-def _view_kind(kind, dp, labels):
-    return PackedKind(str(kind), dp.ids if labels is None else labels[dp.ids], None, None, None, None, device_pack=dp)
+def _view_kind(kind, dp, labels, sort_dtype=None):
+    pk = PackedKind(str(kind), dp.ids if labels is None else labels[dp.ids], None, None, None, None, device_pack=dp)
+    pk.sort_dtype = sort_dtype
+    return pk
 
 
 def _close_all(kinds):
@@ -323,7 +346,7 @@ def _close_all(kinds):
             pk.device_pack.close()
 
 
-def _pack_long_on_device(kuniq, kcodes, ids, values, sort_values, index, pack, device):
+def _pack_long_on_device(kuniq, kcodes, ids, values, sort_values, index, pack, device, keep_sort=False):
     """A long frame whose kinds interleave, sorted ONCE on the device by (kind, id, sort) (`_native.DevicePackSet`): no
     per-kind selection on the host, one upload, one sort, one gather; every kind is a view into the one gathered buffer.
     -> [PackedKind per kind of kuniq], or None when the frame keeps the per-kind route (not eligible under "auto"; a device
@@ -337,7 +360,7 @@ def _pack_long_on_device(kuniq, kcodes, ids, values, sort_values, index, pack, d
     n_kinds = len(kuniq)   # dense codes 0 .. n_kinds - 1 in the narrowest type: one radix pass per byte
     kind_col = _native.pack_column(kcodes.astype(np.uint8 if n_kinds <= 1 << 8 else np.uint16 if n_kinds <= 1 << 16 else np.int64))
     try:
-        with _native.DevicePackSet(id_col, sort_col, kind_col, device=device) as pack_set:
+        with _native.DevicePackSet(id_col, sort_col, kind_col, device=device, keep_sort=keep_sort) as pack_set:
             packs = pack_set.values(val_col)
     except _native.NativeError as exc:
         if pack == "device" or exc.code != _native.TSFA_ERR_HIP:
@@ -345,24 +368,26 @@ def _pack_long_on_device(kuniq, kcodes, ids, values, sort_values, index, pack, d
         warnings.warn("packing the frame's {} kinds on the device failed ({}); packing on the host instead".format(
             n_kinds, exc), RuntimeWarning, stacklevel=3)
         return None
-    return [_view_kind(kind, dp, labels) for kind, dp in zip(kuniq, packs)]
+    sort_dtype = _kept_sort_dtype(keep_sort, sort_values)
+    return [_view_kind(kind, dp, labels, sort_dtype) for kind, dp in zip(kuniq, packs)]
 
 
-def _pack_wide(columns, ids, sort_values, index, pack, device):
+def _pack_wide(columns, ids, sort_values, index, pack, device, keep_sort=False):
     """The value columns of a wide frame: `columns` is [(name, values, nan_name or None)].  With at least two columns the
     device packer takes and rows that are not in packed order, the id and sort columns are uploaded, keyed, sorted and
     boundary-scanned ONCE (`_native.DevicePackSet` without a kind column) and every value column is one gather through the
-    stored permutation; the packs share the set's offsets and ids.  Everything else is `_pack` per column, as before."""
+    stored permutation; the packs share the set's offsets and ids.  Everything else is `_pack` per column, as before.
+    keep_sort: as in `_pack` -- the set keeps the packed sort column and a frame in packed order goes to the device as well."""
     ids = np.asarray(ids)
 
     def per_column(todo, mode):
-        return [_pack(name, ids, values, sort_values, index, nan_name=nan_name, pack=mode, device=device)
+        return [_pack(name, ids, values, sort_values, index, nan_name=nan_name, pack=mode, device=device, keep_sort=keep_sort)
                 for name, values, nan_name in todo]
 
-    if len(columns) < 2 or pack == "host" or not _takes_device(pack, len(ids)):
+    if len(columns) < 2 or pack == "host" or not _takes_device(pack, len(ids), keep_sort):
         return per_column(columns, pack)
     name0, values0, nan_name0 = columns[0]
-    first = _pack_presorted(name0, ids, values0, sort_values, index, nan_name0)
+    first = None if keep_sort else _pack_presorted(name0, ids, values0, sort_values, index, nan_name0)
     if first is not None:   # the frame is in packed order: every column costs what it cost before
         return [first] + per_column(columns[1:], pack)
     reason, keys = _device_key_columns(ids, sort_values, index)
@@ -370,9 +395,10 @@ def _pack_wide(columns, ids, sort_values, index, pack, device):
     if reason is not None or sum(r is None for r, _ in value_cols) < 2:
         return per_column(columns, pack)   # (raises under "device" where a column is not eligible)
     id_col, labels, sort_col = keys
+    sort_dtype = _kept_sort_dtype(keep_sort, sort_values)
     packed = []
     try:
-        with _native.DevicePackSet(id_col, sort_col, None, device=device) as pack_set:
+        with _native.DevicePackSet(id_col, sort_col, None, device=device, keep_sort=keep_sort) as pack_set:
             for (name, values, nan_name), (why, val_col) in zip(columns, value_cols):
                 if why is not None:
                     if pack == "device":
@@ -380,7 +406,7 @@ def _pack_wide(columns, ids, sort_values, index, pack, device):
                     packed.append(_pack(name, ids, values, sort_values, index, nan_name=nan_name, pack="host"))
                     continue
                 dp = pack_set.values(val_col)[0]
-                packed.append(_view_kind(name, dp, labels))
+                packed.append(_view_kind(name, dp, labels, sort_dtype))
                 if dp.value_nan and nan_name is not None:
                     raise ValueError("Column must not contain NaN values: {}".format(nan_name))
     except _native.NativeError as exc:
@@ -412,7 +438,7 @@ def _arrow_to_frame(table):
     return pd.DataFrame(cols, copy=False)
 
 
-def _pack_arrow_wide(table, column_id, column_kind, column_value, column_sort, pack="host", device=0):
+def _pack_arrow_wide(table, column_id, column_kind, column_value, column_sort, pack="host", device=0, keep_sort=False):
     """Wide-format pyarrow Table / RecordBatch with primitive, null-free columns: the Arrow buffers go to the packer as
     numpy views (zero copy) -- no pandas frame, no block consolidation.  None -> the caller converts to a DataFrame
     and takes the general route (strings, nulls, chunked columns that need a copy, the long format)."""
@@ -444,18 +470,19 @@ def _pack_arrow_wide(table, column_id, column_kind, column_value, column_sort, p
         _raise_if_nan(arrays[name], name)
     ids = arrays[column_id]
     sort_all = arrays[column_sort] if column_sort is not None else None
-    packed = _pack_wide([(c, arrays[c], c) for c in value_columns], ids, sort_all, None, pack, device)
+    packed = _pack_wide([(c, arrays[c], c) for c in value_columns], ids, sort_all, None, pack, device, keep_sort)
     return packed, ids.dtype, False
 
 
 def pack_timeseries(container, column_id=None, column_kind=None, column_value=None, column_sort=None, pack="host",
-                    device=0):
+                    device=0, keep_sort=False):
     """-> (list[PackedKind] in output-column order, dtype of the id column, has_datetime_index).
-    pack / device: see `_pack` ("host": every kind is packed in numpy, as before the device packer existed)."""
+    pack / device: see `_pack` ("host": every kind is packed in numpy, as before the device packer existed).
+    keep_sort: see `_pack` (only `extract_rolled_features` asks for it; the default leaves every route as it was)."""
     if pack not in PACK_MODES:
         raise ValueError("pack must be one of {}, not {!r}".format(", ".join(repr(m) for m in PACK_MODES), pack))
     if type(container).__module__.startswith("pyarrow") and hasattr(container, "schema"):
-        direct = _pack_arrow_wide(container, column_id, column_kind, column_value, column_sort, pack, device)
+        direct = _pack_arrow_wide(container, column_id, column_kind, column_value, column_sort, pack, device, keep_sort)
         if direct is not None:
             return direct
         container = _arrow_to_frame(container)
@@ -484,17 +511,18 @@ def pack_timeseries(container, column_id=None, column_kind=None, column_value=No
             vals_all = df[column_value].to_numpy()
             sort_all = df[column_sort].to_numpy() if column_sort is not None else None
             interleaved = len(kcodes) > 1 and not bool(np.all(kcodes[1:] >= kcodes[:-1]))
-            if interleaved and pack != "host" and _takes_device(pack, len(kcodes)):
+            if interleaved and pack != "host" and _takes_device(pack, len(kcodes), keep_sort):
                 # kinds that interleave (rows in (id, time) or time order): one sort of the whole frame on the device.
                 # A frame whose kinds come in blocks keeps the per-kind route below, where a packed block costs a proof.
-                views = _pack_long_on_device(kuniq, kcodes, ids_all, vals_all, sort_all, dt_index, pack, device)
+                views = _pack_long_on_device(kuniq, kcodes, ids_all, vals_all, sort_all, dt_index, pack, device, keep_sort)
                 if views is not None:
                     return views, df[column_id].dtype, False
                 pack = "host"   # "auto": not eligible, or the allocation failed and the warning is out
             for k, kind in enumerate(kuniq):
                 sel = np.nonzero(kcodes == k)[0]
                 packed.append(_pack(kind, ids_all[sel], vals_all[sel], None if sort_all is None else sort_all[sel],
-                                    None if dt_index is None else dt_index[sel], pack=pack, device=device))
+                                    None if dt_index is None else dt_index[sel], pack=pack, device=device,
+                                    keep_sort=keep_sort))
             return packed, df[column_id].dtype, isinstance(df.index, pd.DatetimeIndex)
         # wide format (data.py:181-230)
         _check_nan(df, column_id)
@@ -508,7 +536,7 @@ def pack_timeseries(container, column_id=None, column_kind=None, column_value=No
         sort_all = df[column_sort].to_numpy() if column_sort is not None else None
         dt_index = df.index if isinstance(df.index, pd.DatetimeIndex) else None
         packed = _pack_wide([(col, df[col].to_numpy(), col if col in deferred else None) for col in value_columns],
-                            ids_all, sort_all, dt_index, pack, device)
+                            ids_all, sort_all, dt_index, pack, device, keep_sort)
         return packed, df[column_id].dtype, isinstance(df.index, pd.DatetimeIndex)
     if isinstance(container, dict):
         # dict of frames, one per kind (data.py:294-338)
@@ -522,7 +550,8 @@ def pack_timeseries(container, column_id=None, column_kind=None, column_value=No
         for kind, frame in container.items():
             sort_vals = frame[column_sort].to_numpy() if column_sort is not None else None
             packed.append(_pack(kind, frame[column_id].to_numpy(), frame[column_value].to_numpy(), sort_vals,
-                                frame.index if isinstance(frame.index, pd.DatetimeIndex) else None, pack=pack, device=device))
+                                frame.index if isinstance(frame.index, pd.DatetimeIndex) else None, pack=pack, device=device,
+                                keep_sort=keep_sort))
             id_dtype = frame[column_id].dtype
             has_dt = has_dt or isinstance(frame.index, pd.DatetimeIndex)
         return packed, id_dtype, has_dt

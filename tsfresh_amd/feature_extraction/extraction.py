@@ -153,6 +153,11 @@ class _CompositePlan:
     def extract_windows_host(self, values, starts, ends, times=None):
         return self._gather(len(starts), lambda pl: pl.extract_windows_host(values, starts, ends, times=times))
 
+    def extract_windows_pack(self, pack, windows, chunk_rows=None):
+        """The windows of a `_native.DeviceWindows` over its `_native.DevicePack`: every part reads the same device buffers
+        (`Plan.extract_windows_pack`); the parts' columns meet on the host, as in `extract_windows_host`."""
+        return self._gather(windows.n_windows, lambda pl: pl.extract_windows_pack(pack, windows, chunk_rows=chunk_rows))
+
     def extract_pack(self, pack):
         """The series of a `_native.DevicePack`: every part reads the pack's device buffers; nothing is uploaded."""
         out = _native._result_matrix(pack.n_series, self.n_cols)
@@ -470,10 +475,35 @@ class _WindowBlock:
         self.ids = ids
 
 
+class _LazyWindowEdges:
+    """The starts or the ends of a `_native.DeviceWindows`, copied from the device the first time the host looks at them
+    (`check_reference_data_errors` does only for settings whose calculators can raise on the data)."""
+
+    def __init__(self, windows, what):
+        self._windows, self._what = windows, what
+
+    def __len__(self):
+        return self._windows.n_windows
+
+    def __getitem__(self, item):
+        return getattr(self._windows, self._what)[item]
+
+    def __array__(self, dtype=None, copy=None):
+        a = getattr(self._windows, self._what)
+        return a if dtype is None else a.astype(dtype, copy=False)
+
+
+def _window_ids(base_ids, shift_val):
+    ids = np.empty(len(base_ids), dtype=object)
+    for i in range(len(base_ids)):
+        ids[i] = (base_ids[i], shift_val[i])
+    return ids
+
+
 def extract_rolled_features(timeseries_container, column_id=None, column_sort=None, column_kind=None, column_value=None,
                             rolling_direction=1, max_timeshift=None, min_timeshift=0, default_fc_parameters=None,
                             kind_to_fc_parameters=None, impute_function=None, show_warnings=False, pivot=True,
-                            device=None):
+                            device=None, pack="auto"):
     """`extract_features(roll_time_series(container, ...), column_id="id", ...)` without building the rolled frame.
 
     The reference's forecasting workflow first copies every window into a new DataFrame
@@ -481,60 +511,103 @@ def extract_rolled_features(timeseries_container, column_id=None, column_sort=No
     packed and uploaded ONCE; the windows are `(start, end)` views into that buffer
     (`tsfresh_amd.utilities.dataframe_functions.roll_views` restates the reference's index arithmetic) and go to the
     kernels through `tsfa_extract_windows`.  Same rows, same ``(id, shift)`` index, same columns as the two-step form.
+
+    :param pack: where the frame is grouped and sorted AND where the windows are built.  "host": numpy (factorize + lexsort +
+        gather, `roll_views`), then one upload of samples, starts and ends.  "device": the device packer with the packed sort
+        column kept in HBM (`tsfa_pack_device` / `tsfa_pack_set_*`), the windows from the pack's offsets on the device
+        (`tsfa_roll_windows`), the kernels on those device buffers; the host receives the per-series offsets, the series
+        index and the shift value of every window, and the features.  A frame that is already in packed order is uploaded
+        and takes the same route (the packer proves the order and sorts nothing).  ValueError naming the reason for a frame
+        the device packer does not take (float ids, float16 / longdouble values, object sort values, a DatetimeIndex),
+        whatever its row order.  "auto" (default): the device route for eligible frames of at least
+        `data._DEVICE_ROLL_MIN_ROWS` rows when a device is visible, the host route otherwise; while that threshold is None
+        (no end-to-end measurement yet, profiles/roll_device_timing.md) "auto" is the host route.  The result does not depend
+        on the choice.  Under "auto" the packer falls back to the host when its device allocation fails; an allocation that
+        fails later, in the window builder or the extraction, is raised as it is on either mode.
     """
-    from tsfresh_amd.utilities.dataframe_functions import roll_views
+    from tsfresh_amd.utilities.dataframe_functions import check_roll_arguments, roll_views
     if default_fc_parameters is None and kind_to_fc_parameters is None:
         default_fc_parameters = ComprehensiveFCParameters()
     elif default_fc_parameters is None:
         default_fc_parameters = {}
+    if pack not in PACK_MODES:
+        raise ValueError("pack must be one of {}, not {!r}".format(", ".join(repr(m) for m in PACK_MODES), pack))
     if isinstance(timeseries_container, pd.DataFrame) and len(timeseries_container) <= 1:
         raise ValueError("Your time series container has zero or one rows!. Can not perform rolling.")
-    packed, id_dtype, _ = pack_timeseries(timeseries_container, column_id=column_id, column_kind=column_kind,
-                                          column_value=column_value, column_sort=column_sort)
     if device is None:
         device = _default_device()
+    packed, id_dtype, _ = pack_timeseries(timeseries_container, column_id=column_id, column_kind=column_kind,
+                                          column_value=column_value, column_sort=column_sort, pack=pack, device=device,
+                                          keep_sort=pack != "host")
     # prediction_steps is the longest series over ALL ids and kinds of ONE frame (dataframe_functions.py:546); a dict
     # container is rolled entry by entry (:430-445), each entry with the longest series of its own frame
+    # (a device-packed kind fetches its offsets here: n_series + 1 integers)
     per_kind_steps = isinstance(timeseries_container, dict)
     steps_all = max(int(np.diff(pk.offsets).max()) for pk in packed if pk.n_series)
     blocks, plan_cache, pins = [], {}, set()
-    with warnings.catch_warnings():
-        warnings.simplefilter("default" if show_warnings else "ignore")
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("default" if show_warnings else "ignore")
+            for pk in packed:
+                fc_parameters = kind_to_fc_parameters[pk.kind] if kind_to_fc_parameters and pk.kind in kind_to_fc_parameters \
+                    else default_fc_parameters
+                kind_has_dt = pk.times is not None
+                key = (id(fc_parameters), kind_has_dt)
+                if key not in plan_cache:
+                    fplan = compile_fc_parameters(fc_parameters, has_datetime_index=kind_has_dt)
+                    if fplan.host_calls:
+                        from tsfresh_amd.feature_extraction.registry import UnsupportedFeature
+                        raise UnsupportedFeature("custom (callable) calculators are evaluated per series on the host: roll the "
+                                                 "frame with roll_time_series and call extract_features on it")
+                    plan_cache[key] = (fplan, _acquire_plan(fplan, device, pins) if len(fplan) else None)
+                fplan, nplan = plan_cache[key]
+                if nplan is None:
+                    continue
+                lengths = np.diff(pk.offsets)
+                steps = int(lengths.max()) if per_kind_steps else steps_all
+                names = [pk.kind + "__" + n for n in fplan.names]
+                if pk.device_pack is not None:
+                    # the windows are built on the device from the pack's offsets and never visit the host
+                    dp = pk.device_pack
+                    check_roll_arguments(rolling_direction, max_timeshift, min_timeshift)   # (roll_views' on the host route)
+                    with _native.DeviceWindows(dp, rolling_direction, max_timeshift, min_timeshift, steps) as win:
+                        if pk.sort_dtype is not None:
+                            shift_val = win.shift_values()
+                            if pk.sort_dtype.kind in "mM":  # as roll_time_series: pandas Timestamps in the window ids
+                                shift_val = pd.Series(shift_val.view(pk.sort_dtype)).tolist()
+                        else:
+                            shift_val = win.timeshifts - 1
+                        ids = _window_ids(pk.ids[win.series], shift_val)
+                        matrix = nplan.extract_windows_pack(dp, win)
+                        check_reference_data_errors(fplan.specs, matrix, pk.values, _LazyWindowEdges(win, "starts"),
+                                                    _LazyWindowEdges(win, "ends"))
+                    dp.close()   # the kind's device buffers go as soon as its features are out
+                    if np.asarray(pk.ids).dtype.kind not in "iu":
+                        order = sorted(range(len(ids)), key=lambda i: ids[i])
+                        ids, matrix = ids[order], matrix[order]
+                    # (integer ids: the windows come out by ascending id and, inside a series, non-decreasing shift value, and
+                    # Python's sort is stable: the emitted order IS the sorted order)
+                    blocks.append((_WindowBlock(pk.kind, ids), names, matrix))
+                    continue
+                # roll_views sizes its shifts from the longest series it is given: append a phantom of `steps` samples
+                gi, frm, until, ts = roll_views(np.concatenate([lengths, [steps]]), rolling_direction, max_timeshift, min_timeshift)
+                keep = gi < len(lengths)
+                gi, frm, until, ts = gi[keep], frm[keep], until[keep], ts[keep]
+                starts, ends = pk.offsets[gi] + frm, pk.offsets[gi] + until
+                if pk.sort is not None:
+                    shift_val = pk.sort[ends - 1] if rolling_direction > 0 else pk.sort[starts]
+                    if shift_val.dtype.kind in "mM":  # as roll_time_series: pandas Timestamps in the window ids
+                        shift_val = pd.Series(shift_val).tolist()
+                else:
+                    shift_val = ts - 1
+                ids = _window_ids(pk.ids[gi], shift_val)
+                matrix = nplan.extract_windows_host(pk.values, starts, ends, times=pk.times)
+                check_reference_data_errors(fplan.specs, matrix, pk.values, starts, ends)
+                order = sorted(range(len(ids)), key=lambda i: ids[i])
+                blocks.append((_WindowBlock(pk.kind, ids[order]), names, matrix[order]))
+            _trim_cache(_thread_cache())
+    finally:
         for pk in packed:
-            fc_parameters = kind_to_fc_parameters[pk.kind] if kind_to_fc_parameters and pk.kind in kind_to_fc_parameters \
-                else default_fc_parameters
-            kind_has_dt = pk.times is not None
-            key = (id(fc_parameters), kind_has_dt)
-            if key not in plan_cache:
-                fplan = compile_fc_parameters(fc_parameters, has_datetime_index=kind_has_dt)
-                if fplan.host_calls:
-                    from tsfresh_amd.feature_extraction.registry import UnsupportedFeature
-                    raise UnsupportedFeature("custom (callable) calculators are evaluated per series on the host: roll the "
-                                             "frame with roll_time_series and call extract_features on it")
-                plan_cache[key] = (fplan, _acquire_plan(fplan, device, pins) if len(fplan) else None)
-            fplan, nplan = plan_cache[key]
-            if nplan is None:
-                continue
-            lengths = np.diff(pk.offsets)
-            steps = int(lengths.max()) if per_kind_steps else steps_all
-            # roll_views sizes its shifts from the longest series it is given: append a phantom of `steps` samples
-            gi, frm, until, ts = roll_views(np.concatenate([lengths, [steps]]), rolling_direction, max_timeshift, min_timeshift)
-            keep = gi < len(lengths)
-            gi, frm, until, ts = gi[keep], frm[keep], until[keep], ts[keep]
-            starts, ends = pk.offsets[gi] + frm, pk.offsets[gi] + until
-            if pk.sort is not None:
-                shift_val = pk.sort[ends - 1] if rolling_direction > 0 else pk.sort[starts]
-                if shift_val.dtype.kind in "mM":  # as roll_time_series: pandas Timestamps in the window ids
-                    shift_val = pd.Series(shift_val).tolist()
-            else:
-                shift_val = ts - 1
-            ids = np.empty(len(gi), dtype=object)
-            base_ids = pk.ids[gi]
-            for i in range(len(gi)):
-                ids[i] = (base_ids[i], shift_val[i])
-            matrix = nplan.extract_windows_host(pk.values, starts, ends, times=pk.times)
-            check_reference_data_errors(fplan.specs, matrix, pk.values, starts, ends)
-            order = sorted(range(len(ids)), key=lambda i: ids[i])
-            blocks.append((_WindowBlock(pk.kind, ids[order]), [pk.kind + "__" + n for n in fplan.names], matrix[order]))
-        _trim_cache(_thread_cache())
+            if pk.device_pack is not None:
+                pk.device_pack.close()
     return _assemble(blocks, np.dtype(object), pivot, impute_function)

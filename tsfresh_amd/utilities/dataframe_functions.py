@@ -16,18 +16,23 @@ import numpy as np
 import pandas as pd
 
 
-def roll_views(lengths, rolling_direction=1, max_timeshift=None, min_timeshift=0):
-    """Window views of series with the given lengths.
-
-    Restates the index arithmetic of `_roll_out_time_series` (dataframe_functions.py:340-358) for all shifts at once.
-    -> (series index, first row, end row (exclusive), timeshift) as int64 arrays, ordered by (series, timeshift).
-    """
+def check_roll_arguments(rolling_direction, max_timeshift, min_timeshift):
+    """The reference's ValueErrors for the rolling arguments (dataframe_functions.py:377 ff.)."""
     if rolling_direction == 0:
         raise ValueError("Rolling direction of 0 is not possible")
     if max_timeshift is not None and max_timeshift <= 0:
         raise ValueError("max_timeshift needs to be positive!")
     if min_timeshift < 0:
         raise ValueError("min_timeshift needs to be positive or zero!")
+
+
+def roll_views(lengths, rolling_direction=1, max_timeshift=None, min_timeshift=0):
+    """Window views of series with the given lengths.
+
+    Restates the index arithmetic of `_roll_out_time_series` (dataframe_functions.py:340-358) for all shifts at once.
+    -> (series index, first row, end row (exclusive), timeshift) as int64 arrays, ordered by (series, timeshift).
+    """
+    check_roll_arguments(rolling_direction, max_timeshift, min_timeshift)
     lengths = np.asarray(lengths, dtype=np.int64)
     if lengths.size == 0:
         z = np.zeros(0, dtype=np.int64)
