@@ -165,6 +165,38 @@ int tsfa_plan_set_profiling(tsfa_plan *plan, int32_t enable);
 int32_t tsfa_plan_last_timings(const tsfa_plan *plan, const char **names, float *ms, int32_t cap);
 
 /*
+ * What the last tsfa_extract* on this plan launched: one record per (kernel family, launch group), in launch order, written
+ * just before the family's launch when every launch parameter has its final value.  Read-only diagnostics (the tests read
+ * which build, workgroup size and scratch layout a length was routed to); recording changes no launch.  The list is cleared at
+ * the start of every extract; the TSFA_HOST form appends the records of its row chunks one after the other.
+ *   family        0 BASIC, 1 SORT, 2 SPECTRAL, 3 AR, 4 ENTROPY, 5 CWT (number_cwt_peaks), 6 SEQ, 7 TREND, 8 MPROFILE
+ *   length_class  index of the launch group (0 when the batch is one group)
+ *   max_len       longest series of the group: what the carve is sized for
+ *   n_series      series of the group
+ *   threads       workgroup size of the family kernel
+ *   lds_bytes     the family's carve for max_len with 8-byte samples, the number the route is decided by: bytes of LDS in the
+ *                 LDS build, bytes of a workgroup's HBM scratch slot (before rounding to 256) in the long-series build
+ *   long_build    1: the HBM-scratch build (tsfa_kernels_long.hip) runs, 0: the LDS build
+ *   variant       ENTROPY: the sweep (0 / 1 pair sweeps, 2 / 3 bit-matrix sweeps, 4 the bit-matrix sweep over HBM)
+ *                 CWT: bit 0 the row values are kept in LDS, bit 1 the matrix-core convolutions
+ *                 SEQ: `bins` values parsed per launch | (symbol rows in HBM) << 8
+ *                 SPECTRAL: 1 chirp-z scratch attached      SORT: 1 a k_perm launch is queued for the group
+ *                 AR: 1 the second pass works in HBM scratch    others: 0
+ * Returns the number of records; at most `cap` are written to `out` (cap = 0 or out = NULL only counts).
+ */
+typedef struct tsfa_launch_info {
+    int32_t family;
+    int32_t length_class;
+    int32_t max_len;
+    int32_t threads;
+    int64_t n_series;
+    int64_t lds_bytes;
+    int32_t long_build;
+    int32_t variant;
+} tsfa_launch_info;
+int32_t tsfa_plan_last_launches(const tsfa_plan *plan, tsfa_launch_info *out, int32_t cap);
+
+/*
  * Launch options of one plan, set by the caller who owns it.  The library reads NO environment variable that can change a
  * result; what used to be debugging switches of the environment are named options here, each an alternative ROUTE to the same
  * numbers (the tests compare both ways) or a diagnostic pre-fill:

@@ -55,9 +55,10 @@ def emul_engine(fc_parameters, values, offsets, kind="value", times=None):
     return emul_extract(fc_parameters, values, offsets, kind=kind, times=times)
 
 
-def hip_engine(fc_parameters, values, offsets, kind="value", device=0, times=None, options=None):
+def hip_engine(fc_parameters, values, offsets, kind="value", device=0, times=None, options=None, launches=None):
     """times: float64 hours since each series' first timestamp (DatetimeIndex data) -> linear_trend_timewise
-    options: {name: value} for tsfa_plan_set_option (an alternative route to the same numbers: the A/B tests)"""
+    options: {name: value} for tsfa_plan_set_option (an alternative route to the same numbers: the A/B tests)
+    launches: optional list that receives Plan.last_launches() of the extract (what each family launched)"""
     from tsfresh_amd import _native
     from tsfresh_amd.feature_extraction.plan import compile_fc_parameters
     fplan = compile_fc_parameters(fc_parameters, has_datetime_index=times is not None)
@@ -66,6 +67,8 @@ def hip_engine(fc_parameters, values, offsets, kind="value", device=0, times=Non
         plan.set_option(name, value)
     try:
         out = plan.extract_host(values, np.asarray(offsets, dtype=np.int64), times=times)
+        if launches is not None:
+            launches.extend(plan.last_launches())
     finally:
         plan.close()
     return [kind + "__" + n for n in fplan.names], out

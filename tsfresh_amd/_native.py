@@ -34,6 +34,7 @@ EXPORTS = (
     "tsfa_plan_set_profiling",
     "tsfa_plan_set_option",
     "tsfa_plan_last_timings",
+    "tsfa_plan_last_launches",
     "tsfa_plan_set_length_hint",
     "tsfa_host_alloc",
     "tsfa_host_free",
@@ -87,6 +88,17 @@ class FeatureSpec(ctypes.Structure):
 class RelevanceCol(ctypes.Structure):
     _fields_ = [("n_unique", ctypes.c_int64), ("v_lo", ctypes.c_double), ("v_hi", ctypes.c_double),
                 ("tie_term", ctypes.c_double)]
+
+
+class LaunchInfo(ctypes.Structure):
+    """tsfa_launch_info: what one (kernel family, launch group) of the last extract launched (Plan.last_launches)."""
+    _fields_ = [("family", ctypes.c_int32), ("length_class", ctypes.c_int32), ("max_len", ctypes.c_int32),
+                ("threads", ctypes.c_int32), ("n_series", ctypes.c_int64), ("lds_bytes", ctypes.c_int64),
+                ("long_build", ctypes.c_int32), ("variant", ctypes.c_int32)]
+
+
+# enum tsfa_family (csrc/tsfa_specs.h), by number
+FAMILY_NAMES = ("BASIC", "SORT", "SPECTRAL", "AR", "ENTROPY", "CWT", "SEQ", "TREND", "MPROFILE")
 
 
 class NativeError(RuntimeError):
@@ -660,6 +672,18 @@ class Plan:
         ms = (ctypes.c_float * cap)()
         n = self._lib.tsfa_plan_last_timings(self._h, names, ms, cap)
         return [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+    def last_launches(self):
+        """One dict per (kernel family, launch group) of the last extract on this plan, in launch order: family (a name of
+        FAMILY_NAMES), length_class, max_len, n_series, threads, lds_bytes, long_build, variant (include/tsfresh_amd.h:
+        tsfa_plan_last_launches).  Read-only."""
+        fn = self._lib.tsfa_plan_last_launches
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.POINTER(LaunchInfo), ctypes.c_int32], ctypes.c_int32
+        n = fn(self._h, None, 0)
+        arr = (LaunchInfo * max(n, 1))()
+        n = min(n, fn(self._h, arr, n))
+        return [dict({name: int(getattr(arr[i], name)) for name, _ in LaunchInfo._fields_}, family=FAMILY_NAMES[arr[i].family])
+                for i in range(n)]
 
     def extract_host(self, values, offsets, times=None, out=None):
         """values: 1-D float32/float64 ndarray; offsets: int64 ndarray (n_series + 1) -> float64 [n_series, n_cols].

@@ -137,6 +137,7 @@ struct tsfa_plan {
     hipEvent_t ev_fork = nullptr, ev_join[TSFA_MAX_AUX] = {nullptr};
     bool profiling = false;
     std::vector<Timing> timings;
+    std::vector<tsfa_launch_info> launches;     // tsfa_plan_last_launches: one record per (family, launch group) of the last extract
     long long hint_min_len = 0, hint_max_len = 0;  // tsfa_plan_set_length_hint: skip the length scan (and its host sync)
     // Every family kernel writes every one of its columns for every series (NaN where the reference yields NaN): audited
     // with a sentinel pre-fill over lengths 1 .. 8192, three parameter sets, both sample types, constant / non-finite
@@ -447,6 +448,13 @@ int32_t tsfa_plan_last_timings(const tsfa_plan *plan, const char **names, float 
         if (ms) ms[n] = t.ms;
         ++n;
     }
+    return n;
+}
+
+int32_t tsfa_plan_last_launches(const tsfa_plan *plan, tsfa_launch_info *out, int32_t cap) {
+    if (!plan) return 0;
+    const int32_t n = (int32_t)plan->launches.size();
+    for (int32_t i = 0; out && i < n && i < cap; ++i) out[i] = plan->launches[(size_t)i];
     return n;
 }
 
@@ -936,6 +944,24 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                     }
                 }
             }
+            // tsfa_plan_last_launches: what this (family, group) is about to launch (a group k_stream already served launches nothing)
+            if (!(plan->stream_ok && (f == TSFA_FAM_SORT || f == TSFA_FAM_BASIC) && maxn <= 2048 && g <= TSFA_N_LEN_CLASSES && stream_done[g])) {
+                tsfa_launch_info li;
+                li.family = f;
+                li.length_class = g;
+                li.max_len = maxn;
+                li.threads = a.nt;
+                li.n_series = a.n_series;
+                li.lds_bytes = (int64_t)lds;
+                li.long_build = use_long ? 1 : 0;
+                li.variant = (f == TSFA_FAM_ENTROPY) ? a.ent_cnt
+                             : (f == TSFA_FAM_CWT) ? a.cwt_rowv
+                             : (f == TSFA_FAM_SEQ) ? (seq_group | (seq_grows << 8))
+                             : (f == TSFA_FAM_SPECTRAL) ? (a.gscratch != nullptr ? 1 : 0)
+                             : (f == TSFA_FAM_SORT) ? (a.hint_d != 0 ? 1 : 0)
+                             : (f == TSFA_FAM_AR) ? (a.dd_scratch != nullptr ? 1 : 0) : 0;
+                plan->launches.push_back(li);
+            }
             int rc = 0;
             if (plan->stream_ok && (f == TSFA_FAM_SORT || f == TSFA_FAM_BASIC) && maxn <= 2048 && g <= TSFA_N_LEN_CLASSES) {
                 if (stream_done[g]) continue;   // BASIC's turn after the SORT family's launch served both
@@ -1088,6 +1114,7 @@ int tsfa_extract_windows(tsfa_plan *plan, const void *values, int32_t dtype, con
     if (dtype != TSFA_F32 && dtype != TSFA_F64) return fail(TSFA_ERR_INVALID, "dtype must be TSFA_F32 or TSFA_F64");
     if (space != TSFA_HOST && space != TSFA_DEVICE) return fail(TSFA_ERR_INVALID, "space must be TSFA_HOST or TSFA_DEVICE");
     if (n_series < 0) return fail(TSFA_ERR_INVALID, "n_series < 0");
+    plan->launches.clear();
     if (n_series == 0 || plan->n_cols == 0) return TSFA_OK;
     if (!values || !starts || !ends || !out) return fail(TSFA_ERR_INVALID, "NULL buffer");
     if (ld_out < plan->n_cols) return fail(TSFA_ERR_INVALID, "ld_out < n_cols");
