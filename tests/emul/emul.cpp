@@ -75,6 +75,14 @@ extern "C" int tsfa_emul_extract_timed(const tsfa_feature_spec *specs, int n_spe
 static std::vector<double> g_pool;
 extern "C" void tsfa_emul_set_pool(const double *data, int64_t n) { g_pool.assign(data, data + (n > 0 ? n : 0)); }
 
+// change_quantiles: how many corridors were swept a second time about their own mean since the last call (fam_sort.h,
+// TSFA_CQ_REFINE); reading resets the count
+extern "C" int64_t tsfa_emul_cq_refined() {
+    const int64_t r = g_tsfa_cq_refined;
+    g_tsfa_cq_refined = 0;
+    return r;
+}
+
 extern "C" int tsfa_emul_extract(const tsfa_feature_spec *specs, int n_specs, const double *values,
                                  const int64_t *offsets, int64_t n_series, double *out, int64_t ld, char *err,
                                  int errlen) {

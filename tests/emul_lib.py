@@ -45,7 +45,14 @@ def load():
     lib.tsfa_emul_extract_timed.restype = ctypes.c_int
     lib.tsfa_emul_set_pool.argtypes = [ctypes.c_void_p, ctypes.c_int64]
     lib.tsfa_emul_set_pool.restype = None
+    lib.tsfa_emul_cq_refined.argtypes = []
+    lib.tsfa_emul_cq_refined.restype = ctypes.c_int64
     return lib
+
+
+def cq_refined():
+    """change_quantiles corridors the emulation swept a second time since the last call (fam_sort.h, TSFA_CQ_REFINE)."""
+    return int(load().tsfa_emul_cq_refined())
 
 
 def emul_extract_specs(specs, values, offsets, times=None):

@@ -545,6 +545,49 @@ TSFA_DEV void friedrich_coeffs(const Blk &b, XS xs, int n, S1 srt1, int m, int r
 //     The cancellation in `var` costs eps * (mean - s)^2 <= eps * (4 max|x|)^2, seven decades below the parity bar's absolute
 //     floor for a quadratic feature (tests/parity.py: 1e-9 max|x|^2); a second masked pass about each corridor's own mean
 //     (what np.var does, and what this function did until round 6) doubled the predicate evaluations and the sample reads.
+//   * That floor is no bound where the changes inside a corridor are nearly constant (a sawtooth's rising flank: the
+//     corridor's mean change is the slope, far from the series' mean change s, and the variance a jitter twelve decades
+//     below slope^2).  The relative error of the one-pass form is K eps R, R = (S2 / c) / var the cancellation ratio; K
+//     measured 7 .. 20 on 300 .. 8197 samples (profiles/shift_invariance.md: 5.4e-10 at R = 3.4e5, 1.4e-5 at 3.4e9, 7e-2
+//     at 3.3e13).  A corridor whose one-pass variance comes out below TSFA_CQ_REFINE = 2^-20 of S2 / c (R > 1e6: the
+//     one-pass error reaches 5e-9 there, 200 times inside the 1e-6 bar, and the gate itself is read from a variance that is
+//     still good to 5e-9) is swept again about its own mean.  Noise never asks: R is 1 + mean^2 / var, below 3 for the absolute changes
+//     of iid normal samples, 1 for the signed ones (tests/test_shift_invariance.py counts the sweeps of a batch: none), and
+//     a corridor that does not ask keeps its bits.  What does ask besides a jittered flank: two or more changes inside a
+//     corridor that are EXACTLY equal while their mean differs from s (a piecewise-linear series) -- the one-pass variance is
+//     then 0 or round-off, indistinguishable from a cancelled 1e-20, and the sweep is paid to return 0; a corridor holding
+//     a single change is left alone.
+#define TSFA_CQ_REFINE 9.5367431640625e-07   // 2^-20
+#ifdef TSFA_EMUL
+static long long g_tsfa_cq_refined = 0;   // the emulation counts the second sweeps (tsfa_emul_cq_refined)
+#define TSFA_CQ_REFINE_NOTE() (++g_tsfa_cq_refined)
+#else
+#define TSFA_CQ_REFINE_NOTE() ((void)0)
+#endif
+// The second sweep of one corridor [l, h]: the variances of the changes and of the absolute changes about the corridor's own
+// means mu1, mu2 (c changes inside), in the corrected two-pass form -- the sums of the residuals are the round-off of the means
+// and take it out again.  Block-uniform: every thread calls it.
+struct CqRefined { double v, va; };
+template <class XS>
+TSFA_DEVN CqRefined cq_refine_corridor(const Blk &b, XS xs, int n, double l, double h, double mu1, double mu2, double c) {
+    double e[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = b.tid; i < n - 1; i += b.nt) {
+        const double x0 = xs[i], x1 = xs[i + 1];
+        if (x0 >= l && x0 <= h && x1 >= l && x1 <= h) {
+            const double d = x1 - x0;
+            const double e1 = d - mu1, e2 = fabs(d) - mu2;
+            e[0] += e1;
+            e[1] += e1 * e1;
+            e[2] += e2;
+            e[3] += e2 * e2;
+        }
+    }
+    blk_sum_multi<4>(b, e);
+    CqRefined r;
+    r.v = (e[1] - e[0] * e[0] / c) / c;
+    r.va = (e[3] - e[2] * e[2] / c) / c;
+    return r;
+}
 template <class XS, class SS>
 TSFA_DEV void cq_fill_all(const Blk &b, XS xs, SS srt, int n, const TsfaCqPlan &plan, double *cq) {
     TSFA_TICKER(tkq, 0);
@@ -609,6 +652,41 @@ TSFA_DEV void cq_fill_all(const Blk &b, XS xs, SS srt, int n, const TsfaCqPlan &
         TSFA_TICK(tkq, b, 221);
         blk_sum_multi<20>(b, a);
         TSFA_TICK(tkq, b, 222);
+        // The refinement.  Every thread holds the block's sums, so the gate is block-uniform: bit j asks for the signed
+        // variance of corridor j about its own mean, bit 4 + j for that of the absolute changes (c^2 times the gate above,
+        // no division; a NaN or an empty corridor asks for nothing).
+        int refine = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double c = a[5 * j], q1 = a[5 * j + 3] * c, q2 = a[5 * j + 4] * c;
+            const bool many = c > 1.0;   // (a single change has the variance 0 in either form)
+            refine |= (many && q1 - a[5 * j + 1] * a[5 * j + 1] < TSFA_CQ_REFINE * q1) ? (1 << j) : 0;
+            refine |= (many && q2 - a[5 * j + 2] * a[5 * j + 2] < TSFA_CQ_REFINE * q2) ? (16 << j) : 0;
+        }
+#if TSFA_GPU
+        refine = __builtin_amdgcn_readfirstlane(refine);   // a scalar branch around the sweep and its barriers
+#endif
+        for (int j = 0; refine != 0 && j < ng; ++j) {
+            if (((refine >> j) & 0x11) == 0) continue;
+            TSFA_CQ_REFINE_NOTE();
+            double l = lo[0], h = hi[0], c = a[0], t1 = a[1], t2 = a[2];
+#pragma unroll
+            for (int jj = 1; jj < 4; ++jj) {   // (selects between wave-uniform values: lo[j] would move the arrays to scratch)
+                l = (jj == j) ? lo[jj] : l;
+                h = (jj == j) ? hi[jj] : h;
+                c = (jj == j) ? a[5 * jj] : c;
+                t1 = (jj == j) ? a[5 * jj + 1] : t1;
+                t2 = (jj == j) ? a[5 * jj + 2] : t2;
+            }
+            // (a call, not inline code: the sweep that every series runs keeps the registers it had without the refinement)
+            const CqRefined w = cq_refine_corridor(b, xs, n, l, h, s + t1 / c, sa + t2 / c, c);
+            const double w1 = w.v, w2 = w.va;
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                a[5 * jj + 3] = (jj == j && ((refine >> jj) & 1)) ? w1 : a[5 * jj + 3];
+                a[5 * jj + 4] = (jj == j && ((refine >> jj) & 16)) ? w2 : a[5 * jj + 4];
+            }
+        }
         blk_sync();   // every thread has read this sweep's edges
         if (b.tid == 0) {
 #pragma unroll
@@ -621,7 +699,9 @@ TSFA_DEV void cq_fill_all(const Blk &b, XS xs, SS srt, int n, const TsfaCqPlan &
                     o[0] = c;
                     o[1] = any ? s + m1 : 0.0;
                     o[2] = any ? sa + m2 : 0.0;
-                    const double v1 = a[5 * j + 3] / c - m1 * m1, v2 = a[5 * j + 4] / c - m2 * m2;
+                    double v1 = a[5 * j + 3] / c - m1 * m1, v2 = a[5 * j + 4] / c - m2 * m2;
+                    v1 = ((refine >> j) & 1) ? a[5 * j + 3] : v1;     // (refined: the slot holds the variance itself)
+                    v2 = ((refine >> j) & 16) ? a[5 * j + 4] : v2;
                     o[3] = any ? ((v1 < 0.0) ? 0.0 : v1) : 0.0;   // (a NaN stays a NaN: inf - inf changes inside the corridor)
                     o[4] = any ? ((v2 < 0.0) ? 0.0 : v2) : 0.0;
                 }
