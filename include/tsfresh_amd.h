@@ -39,10 +39,13 @@ typedef enum tsfa_status {
 
 /* element type of the ragged value buffer */
 /* (tsfa_extract* take TSFA_F32 / TSFA_F64 samples; the integer types and TSFA_BOOL name id / sort-key columns and the value
- * columns tsfa_pack_device converts to float64) */
+ * columns tsfa_pack_device converts to float64; TSFA_F16 / TSFA_BF16 are accepted by tsfa_pack_dense ONLY, which converts them
+ * to float32 -- every other entry point refuses them as it refuses an unknown type) */
 typedef enum tsfa_dtype {
     TSFA_F32 = 0, TSFA_F64 = 1, TSFA_I64 = 2, TSFA_I32 = 3,
-    TSFA_I8 = 4, TSFA_I16 = 5, TSFA_U8 = 6, TSFA_U16 = 7, TSFA_U32 = 8, TSFA_U64 = 9, TSFA_BOOL = 10 /* one byte, 0 | 1 */
+    TSFA_I8 = 4, TSFA_I16 = 5, TSFA_U8 = 6, TSFA_U16 = 7, TSFA_U32 = 8, TSFA_U64 = 9, TSFA_BOOL = 10, /* one byte, 0 | 1 */
+    TSFA_F16 = 11,  /* IEEE binary16 */
+    TSFA_BF16 = 12  /* bfloat16: the upper half of a binary32 */
 } tsfa_dtype;
 
 /* where the caller's buffers live */
@@ -324,6 +327,39 @@ int32_t tsfa_pack_set_flags(const tsfa_pack_set *set);
 int32_t tsfa_pack_set_n_passes(const tsfa_pack_set *set);
 int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int32_t value_type, int32_t space, tsfa_pack **out_packs);
 void tsfa_pack_set_destroy(tsfa_pack_set *set);
+
+/* Dense packer: the ragged layout for a batch that already IS an array in device memory -- (n_batch, n_channels, n_time) with
+ * any non-negative element strides: [B, C, n], the channels-last [B, n, C] of a multivariate recording, [B, n] (one channel,
+ * stride_channel 0), sliced, stepped and expanded (stride 0) views.  Replaces WideTsFrameAdapter (data.py:181-230: one
+ * groupby of the id column per value column) for a container that is already an array: there is nothing to group or to sort,
+ * series b of channel c is row (b, c), and the only work is the copy into the layout tsfa_extract* reads, fused with the
+ * conversion of the element type.
+ *   x, x_type        TSFA_F64 stays float64, TSFA_F32 stays float32, TSFA_F16 and TSFA_BF16 become float32 (both exact:
+ *                    subnormals and +-inf keep their value)
+ *   lengths          NULL, or n_batch entries of lengths_type (TSFA_I32 | TSFA_I64): series b is its first lengths[b] samples,
+ *                    1 <= lengths[b] <= n_time (a right-padded batch)
+ *   values_out       channel c occupies elements [c * channel_stride_out, c * channel_stride_out + T) of the output type,
+ *                    T = sum of the lengths (n_batch * n_time without lengths), the series back to back in batch order;
+ *                    channel_stride_out >= n_batch * n_time
+ *   offsets_out      n_batch + 1 int64 shared by every channel: b * n_time without lengths, else the exclusive scan of the
+ *                    lengths (one workgroup, 64 bits wide; no workgroup waits on another)
+ *   flags_out        one int32 the call ORs into (the caller clears it): TSFA_PACK_VALUE_NAN a sample that was copied is NaN
+ *                    (the caller raises the reference's ValueError, data.py:148-167); TSFA_DENSE_BAD_LENGTH a length is
+ *                    outside [1, n_time] -- it was clamped into [0, n_time] before use, so whatever `lengths` holds nothing
+ *                    outside x is read and nothing outside [0, T) of a channel is written
+ * Channel c of the result goes to tsfa_extract* as (values_out + c * channel_stride_out, offsets_out, n_batch, TSFA_DEVICE).
+ * Three kernels, chosen from the strides: stride_time == 1 copies rows with consecutive lanes on consecutive samples;
+ * stride_channel == 1 with several channels turns [time x channel] tiles through LDS so that both the reads and the writes
+ * are unit-stride; anything else is a strided gather.  All pointers are device pointers on `device`; nothing is allocated.
+ *   stream           a hipStream_t: the call returns after enqueueing.  NULL: the library's own (the null) stream, and the
+ *                    call returns when the work is done.
+ * TSFA_ERR_INVALID: a null pointer, a type outside the lists above, a negative stride, a dimension below 1,
+ * channel_stride_out below n_batch * n_time, or an extent beyond 2^62 elements.  TSFA_ERR_TOO_LONG: n_time > 33 554 431.
+ * TSFA_ERR_NO_DEVICE: no HIP device (there is no CPU route in the library). */
+#define TSFA_DENSE_BAD_LENGTH 8
+int tsfa_pack_dense(const void *x, int32_t x_type, int64_t n_batch, int64_t n_channels, int64_t n_time, int64_t stride_batch,
+                    int64_t stride_channel, int64_t stride_time, const void *lengths, int32_t lengths_type, void *values_out,
+                    int64_t channel_stride_out, int64_t *offsets_out, int32_t *flags_out, int32_t device, void *stream);
 
 /* Window builder: the rolled (forecasting) layout of one pack, built on the device from the pack's offsets.  Replaces, for a
  * frame packed by tsfa_pack_device / tsfa_pack_set_*, the host's enumeration of n_series x n_shifts window candidates

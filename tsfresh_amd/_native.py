@@ -21,7 +21,9 @@ TSFA_ERR_HIP = -4
 TSFA_ERR_TOO_LONG = -5
 TSFA_F32, TSFA_F64, TSFA_I64, TSFA_I32 = 0, 1, 2, 3
 TSFA_I8, TSFA_I16, TSFA_U8, TSFA_U16, TSFA_U32, TSFA_U64, TSFA_BOOL = 4, 5, 6, 7, 8, 9, 10
+TSFA_F16, TSFA_BF16 = 11, 12   # tsfa_pack_dense only
 TSFA_PACK_UNSORTED, TSFA_PACK_VALUE_NAN, TSFA_PACK_IN_ORDER = 1, 2, 4
+TSFA_DENSE_BAD_LENGTH = 8
 TSFA_PACK_KEEP_SORT = 1
 TSFA_HOST, TSFA_DEVICE = 0, 1
 
@@ -58,6 +60,7 @@ EXPORTS = (
     "tsfa_pack_set_n_passes",
     "tsfa_pack_set_values",
     "tsfa_pack_set_destroy",
+    "tsfa_pack_dense",
     "tsfa_roll_windows",
     "tsfa_windows_n_windows",
     "tsfa_windows_starts",
@@ -501,6 +504,62 @@ class DevicePackSet:
                 self.close()
         except Exception:
             pass
+
+
+def _bind_pack_dense_api(lib):
+    """The tsfa_pack_dense prototype, bound on first use (a diagnostics library given through TSFA_LIB may predate it)."""
+    if getattr(lib, "_tsfa_pack_dense_bound", False):
+        return
+    lib.tsfa_pack_dense.argtypes = [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_int64] * 6 + [
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+        ctypes.c_void_p]
+    lib.tsfa_pack_dense.restype = ctypes.c_int
+    lib._tsfa_pack_dense_bound = True
+
+
+def pack_dense(x_ptr, x_type, shape, strides, values_ptr, channel_stride_out, offsets_ptr, flags_ptr, device=0,
+               lengths_ptr=None, lengths_type=0, stream=None):
+    """tsfa_pack_dense on raw device pointers (ints): the array of logical `shape` (n_batch, n_channels, n_time) and element
+    `strides` at x_ptr -> the ragged layout in caller-provided buffers: channel c at values_ptr + c * channel_stride_out
+    elements (float64 for TSFA_F64 input, float32 otherwise), n_batch + 1 int64 offsets shared by the channels, one int32
+    flag word the call ORs into.  lengths_ptr: n_batch int32 / int64 (lengths_type TSFA_I32 / TSFA_I64) or None.
+    stream: a hipStream_t as an int (the call only enqueues) or None (the call returns when the work is done)."""
+    lib = load()
+    _bind_pack_dense_api(lib)
+    (n_batch, n_channels, n_time), (sb, sc, st) = shape, strides
+    _check(lib, lib.tsfa_pack_dense(
+        ctypes.c_void_p(x_ptr), int(x_type), int(n_batch), int(n_channels), int(n_time), int(sb), int(sc), int(st),
+        ctypes.c_void_p(lengths_ptr) if lengths_ptr else None, int(lengths_type), ctypes.c_void_p(values_ptr),
+        int(channel_stride_out), ctypes.c_void_p(offsets_ptr), ctypes.c_void_p(flags_ptr), int(device),
+        ctypes.c_void_p(stream) if stream else None))
+
+
+class DensePack:
+    """One channel of a tsfa_pack_dense result, as `Plan.extract_into(pack=...)` and `extract_parts_into(pack=...)` read a
+    pack: the channel's stretch of the value buffer, the offsets every channel shares, the series count.  A view: the
+    buffers belong to `owner` (whatever must stay alive while the view is used), nothing is freed here."""
+
+    def __init__(self, values_ptr, values_type, offsets_ptr, n_series, device, owner=None):
+        self.values_ptr, self.values_type = int(values_ptr), int(values_type)
+        self.offsets_ptr, self.n_series, self.device = int(offsets_ptr), int(n_series), int(device)
+        self.values_dtype = np.dtype(np.float32 if self.values_type == TSFA_F32 else np.float64)
+        self.owner = owner
+
+    def close(self):
+        self.owner = None
+
+
+class BorrowedMatrix:
+    """Row-major float64 [n_rows, >= n_cols] device memory someone else owns (a torch tensor), with the attributes the
+    extract paths read of a DeviceMatrix: `.ptr`, `.ld`, `.shape`, `.device`.  Frees nothing; `owner` keeps the memory's
+    owner alive for as long as the wrapper lives."""
+
+    def __init__(self, ptr, n_rows, n_cols, device, ld=None, owner=None):
+        self.ptr, self.shape, self.device = int(ptr), (int(n_rows), int(n_cols)), int(device)
+        self.ld = int(n_cols if ld is None else ld)
+        if self.ld < self.shape[1]:
+            raise ValueError("the leading dimension is below the number of columns")
+        self.owner = owner
 
 
 def _bind_roll_api(lib):
