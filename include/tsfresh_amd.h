@@ -179,11 +179,14 @@ int32_t tsfa_plan_last_timings(const tsfa_plan *plan, const char **names, float 
  *   threads       workgroup size of the family kernel
  *   lds_bytes     the family's carve for max_len with 8-byte samples, the number the route is decided by: bytes of LDS in the
  *                 LDS build, bytes of a workgroup's HBM scratch slot (before rounding to 256) in the long-series build
+ *                 (SORT, LDS build: what the launch really carves, in the input precision)
  *   long_build    1: the HBM-scratch build (tsfa_kernels_long.hip) runs, 0: the LDS build
  *   variant       ENTROPY: the sweep (0 / 1 pair sweeps, 2 / 3 bit-matrix sweeps, 4 the bit-matrix sweep over HBM)
  *                 CWT: bit 0 the row values are kept in LDS, bit 1 the matrix-core convolutions
  *                 SEQ: `bins` values parsed per launch | (symbol rows in HBM) << 8
- *                 SPECTRAL: 1 chirp-z scratch attached      SORT: 1 a k_perm launch is queued for the group
+ *                 SPECTRAL: 1 chirp-z scratch attached
+ *                 SORT: bit 0 a k_perm launch is queued for the group, bit 1 one wavefront per series with a sorted copy,
+ *                       bit 2 one wavefront per series with the entropy kernel's 16-bit order in its place
  *                 AR: 1 the second pass works in HBM scratch    others: 0
  * Returns the number of records; at most `cap` are written to `out` (cap = 0 or out = NULL only counts).
  */
@@ -215,6 +218,7 @@ int32_t tsfa_plan_last_launches(const tsfa_plan *plan, tsfa_launch_info *out, in
  *   "entropy_route"  0|1|2 bit-matrix sweep | windowed pair sweep | general kernel
  *   "force_long"     0|1   the HBM-scratch build of the family kernels whatever the length
  *   "row_form"       0|1   BASIC / TREND columns of series of <= 256 samples four series to a wavefront (1)
+ *   "sort_waves"     1|2   k_sort up to 2048 samples: one wavefront per series (1), or the two-wavefront form it replaced (2)
  *   "seq_rows"       -1|0|1 lempel_ziv_complexity's symbol rows in LDS (0), in HBM (1), or in HBM where that puts more series on a CU (-1, default)
  *   "host_chunks"    n     row chunks of the TSFA_HOST pipeline (0: by batch size)
  *   "fill" v / "fill_off"  pre-fill the result matrix with v before the kernels run (audits: every cell is written anyway)

@@ -27,20 +27,7 @@ TSFA_DEV int adf_maxlag_for(int n) {
 TSFA_DEV int ar_tri(int i, int j) { return ((i * (i + 1)) >> 1) + j; }
 TSFA_DEV int ar_tri_doubles(int P) { return (P * (P - 1)) / 2; }
 
-// LDS exchange inside the family.  A one-wavefront workgroup (every launch group up to 2048 samples) needs no s_barrier:
-// its LDS instructions complete in issue order, so waiting for its own (lgkmcnt) orders a lane's read after another
-// lane's write, and the "memory" clobber keeps the compiler from moving LDS accesses across the wait.  The family never
-// reads back what it stores to global memory, so no vmcnt wait is needed either.
-TSFA_DEV void ar_sync(const Blk &b) {
-#if TSFA_GPU && !defined(TSFA_LONG)
-    if (b.nt <= 64) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        return;
-    }
-#endif
-    (void)b;
-    blk_sync();
-}
+// LDS exchange inside the family: ar_sync (tsfa_common.h) -- every launch group up to 2048 samples is one wavefront.
 
 // Cholesky factorization G = L L^T (packed lower triangle, in place).  Serial.
 TSFA_DEV bool chol_factor(double *G, int p) {

@@ -81,6 +81,7 @@ struct PlanOptions {
     bool length_classes = true;   // launch a batch whose lengths span more than 2x class by class
     bool stats_share = true;      // k_basic's per-series statistics record serves the ENTROPY / AR / SEQ / SORT families
     bool perm_share = true;       // k_entropy_bits' sample order serves k_sort
+    int sort_waves = 1;           // SORT, groups up to 2048 samples: 1 = one wavefront per series; 2 = the two-wavefront form it replaced
     bool select = true;           // median / quantile-only plans: order statistics by selection (k_order_stats)
     bool bluestein = true;        // chirp-z transform for long non-power-of-two spectra
     bool cwt_mfma = false;        // number_cwt_peaks' Ricker convolutions on v_mfma_f64_16x16x4_f64
@@ -417,6 +418,7 @@ int tsfa_plan_set_option(tsfa_plan *plan, const char *name, double value) {
     else if (n == "row_form") o.row_form = on;
     else if (n == "seq_rows") o.seq_rows = (value < 0.0) ? -1 : (on ? 1 : 0);
     else if (n == "entropy_route") { if (value != 0.0 && value != 1.0 && value != 2.0) return fail(TSFA_ERR_INVALID, "entropy_route: 0, 1 or 2"); o.entropy_route = (int)value; }
+    else if (n == "sort_waves") { if (value != 1.0 && value != 2.0) return fail(TSFA_ERR_INVALID, "sort_waves: 1 or 2"); o.sort_waves = (int)value; }
     else if (n == "bluestein_min") o.bluestein_min = value > 0.0 ? (int)std::min(value, 32767.0) : 0;
     else if (n == "gscratch_slots") o.gscratch_slots = value > 0.0 ? (int)std::min(value, 2147483647.0) : 0;
     else if (n == "host_chunks") o.host_chunks = value > 0.0 ? (int)std::min(value, (double)TSFA_MAX_CHUNKS) : 0;
@@ -673,9 +675,15 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                 // AR: one wavefront per series.  Its time is serial linear algebra that a second wavefront only repeated,
                 // and its layout (10 144 B at 1024 samples) puts 16 one-wavefront series on a CU; the workgroup size is
                 // then the same for every length up to 2048, so a series gives the same bits in whatever group it lands.
-                static const int pref[TSFA_N_FAMILIES] = {64, 128, 128, 64, 256, 256, 128, 64, 256};
+                // SORT: one wavefront per series as well (round 8).  Its sweeps are short, and what lies between them -- the
+                // corridor edges with lane = edge, the reductions' exchange through LDS, the refinement gate, the Householder
+                // fit of wavefront 0, the lane = column epilogue -- a second wavefront waited for or repeated.  9 744 B at
+                // 1024 float32 samples (the sorted series as a 16-bit order): 16 series per CU, and no dependence of the bits
+                // on the launch group's longest series.  The plan option sort_waves = 2 keeps the 128-thread form reachable.
+                static const int pref[TSFA_N_FAMILIES] = {64, 64, 128, 64, 256, 256, 128, 64, 256};
                 const int cap = std::max(64, ((maxn / 4 + 63) / 64) * 64);
                 a.nt = std::min(pref[f], cap);
+                if (f == TSFA_FAM_SORT && plan->opt.sort_waves == 2) a.nt = std::min(128, cap);
             }
             if (TSFA_LAB_ONLY(plan->opt.nt[f] >= 64)) a.nt = plan->opt.nt[f];   // lab build: workgroup size of a family
             a.stream = fst;
@@ -944,6 +952,14 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                     }
                 }
             }
+            if (f == TSFA_FAM_SORT && !use_long) {
+                // one wavefront per series (k_sort<T, 1>); where k_entropy_bits left the sample order and k_perm takes the
+                // permutation_entropy columns (a dimension >= 8 would borrow the sorted copy's storage), the sorted series is
+                // that order in LDS and not a copy (k_sort<T, 2>).  The layout follows: the kernel carves with these arguments.
+                a.sort_mode = (maxn <= 2048 && a.nt == 64 && plan->opt.sort_waves == 1 && !TSFA_LAB_ONLY(plan->opt.nt[f] >= 64))
+                                  ? ((a.perm_buf != nullptr && a.hint_d != 0) ? 2 : 1) : 0;
+                lds = tsfa_sort_lds_bytes(a, dtype == TSFA_F32 ? 4 : 8);
+            }
             // tsfa_plan_last_launches: what this (family, group) is about to launch (a group k_stream already served launches nothing)
             if (!(plan->stream_ok && (f == TSFA_FAM_SORT || f == TSFA_FAM_BASIC) && maxn <= 2048 && g <= TSFA_N_LEN_CLASSES && stream_done[g])) {
                 tsfa_launch_info li;
@@ -958,7 +974,7 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                              : (f == TSFA_FAM_CWT) ? a.cwt_rowv
                              : (f == TSFA_FAM_SEQ) ? (seq_group | (seq_grows << 8))
                              : (f == TSFA_FAM_SPECTRAL) ? (a.gscratch != nullptr ? 1 : 0)
-                             : (f == TSFA_FAM_SORT) ? (a.hint_d != 0 ? 1 : 0)
+                             : (f == TSFA_FAM_SORT) ? ((a.hint_d != 0 ? 1 : 0) | (a.sort_mode << 1))   // bit 1: one wavefront, bit 2: ... with the 16-bit order
                              : (f == TSFA_FAM_AR) ? (a.dd_scratch != nullptr ? 1 : 0) : 0;
                 plan->launches.push_back(li);
             }

@@ -151,6 +151,23 @@ TSFA_DEV void blk_sync_all() {
 #endif
 }
 
+// LDS exchange of a family whose launch groups up to 2048 samples are ONE wavefront (AR, SORT).  Such a workgroup needs no
+// s_barrier: its LDS instructions complete in issue order, so waiting for its own (lgkmcnt) orders a lane's read after
+// another lane's write, and the "memory" clobber keeps the compiler from moving LDS accesses across the wait.  (Not left to
+// __syncthreads(): for a one-wavefront workgroup the compiler lowers it to a wave barrier with no wait at all.)  These
+// families never read back what they store to global memory, so no vmcnt wait is needed either.  Larger
+// workgroups, and the long-series build whose working set lives in HBM, take blk_sync().
+TSFA_DEV void ar_sync(const Blk &b) {
+#if TSFA_GPU && !defined(TSFA_LONG)
+    if (b.nt <= 64) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        return;
+    }
+#endif
+    (void)b;
+    blk_sync();
+}
+
 // ---------------------------------------------------------------------------------------------
 // reductions: every thread receives the result
 // ---------------------------------------------------------------------------------------------
@@ -853,7 +870,7 @@ template <typename K>
 TSFA_DEV void blk_bitonic_sort(const Blk &b, K *a, int npow2) {
     for (int k = 2; k <= npow2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
-            blk_sync();
+            ar_sync(b);
             for (int t = b.tid; t < (npow2 >> 1); t += b.nt) {
                 // index of the lower element of pair t for stride j
                 const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
@@ -867,7 +884,7 @@ TSFA_DEV void blk_bitonic_sort(const Blk &b, K *a, int npow2) {
             }
         }
     }
-    blk_sync();
+    ar_sync(b);
 }
 
 // perm[0 .. np2) = indices 0 .. n-1 sorted ascending by key[index] (ties by index), padded with the index type's largest
@@ -1157,10 +1174,10 @@ TSFA_DEV void blk_sort_keys_regs(const Blk &b, K (&key)[E], K *xchg) {
                 default: sortk_stage_lanes<E, 32>(key, g0, k, j); break;
                 }
             } else {
-                blk_sync();
+                ar_sync(b);
 #pragma unroll
                 for (int e = 0; e < E; ++e) xchg[g0 + e] = key[e];
-                blk_sync();
+                ar_sync(b);
                 const bool lower = ((g0 & j) == 0);
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
@@ -1183,10 +1200,10 @@ TSFA_DEVN void blk_sorted_copy_regs_e(const Blk &b, const K *src, int n, K *dst)
         key[e] = (g < n) ? src[g] : (K)TSFA_INF;
     }
     blk_sort_keys_regs<E>(b, key, dst);
-    blk_sync();
+    ar_sync(b);
 #pragma unroll
     for (int e = 0; e < E; ++e) dst[b.tid * E + e] = key[e];
-    blk_sync();
+    ar_sync(b);
 }
 template <typename K>
 TSFA_DEV bool blk_sorted_copy_regs(const Blk &b, const K *src, int n, K *dst, int np2) {

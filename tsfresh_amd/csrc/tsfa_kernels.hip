@@ -227,7 +227,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TSFA_RO
 }
 #endif
 
-template <typename T>
+// MODE 0: as many wavefronts as the launch gives (groups beyond 2048 samples, the long-series build, and the two-wavefront
+//         form of the groups up to 2048 samples that the plan option sort_waves = 2 keeps reachable).
+// MODE 1: ONE wavefront per series (every group up to 2048 samples): the workgroup size is a constant of the instantiation, so
+//         every blk_* reduction is its in-register path and every exchange through LDS the wave-local wait (ar_sync).
+// MODE 2: MODE 1 with the sorted series kept as the 16-bit order another family left in perm_buf (fam_sort.h: OrdView) --
+//         the launch chooses it where that order exists and no column needs the sorted copy's storage.
+template <typename T, int MODE>
 __global__ void __launch_bounds__(1024) k_sort(const T *__restrict__ values, const int64_t *__restrict__ starts, const int64_t *__restrict__ ends, int64_t n_series, const int *__restrict__ sel,
                        const TsfaSpec *__restrict__ specs, int nspecs, double *__restrict__ out, int64_t ld, int maxn,
                        const TsfaCqPlan cqplan, int n_loop, int w_doubles, double *__restrict__ pf_buf,
@@ -236,17 +242,18 @@ __global__ void __launch_bounds__(1024) k_sort(const T *__restrict__ values, con
     TSFA_SERIES_BEGIN
     const int64_t off = starts[sidx];
     const int n = (int)(ends[sidx] - off);
+    const int nt = (MODE != 0) ? 64 : (int)blockDim.x;
     SortLds L;
-    L.carve(tsfa_base, maxn, blockDim.x, (int)sizeof(T), w_doubles);
+    L.carve(tsfa_base, maxn, nt, (int)sizeof(T), w_doubles, MODE == 2 ? 1 : 0, stats_in == nullptr ? 1 : 0);
     TSFA_TICKS_BEGIN();
-    Blk b{(int)threadIdx.x, (int)blockDim.x, L.red, L.np};
+    Blk b{(int)threadIdx.x, nt, L.red, L.np};
     T *xs = (T *)L.xs;  // resident in the input precision, like its sorted copy
     {
         const T *__restrict__ g = values + off;
         for (int i = b.tid; i < n; i += b.nt) xs[i] = g[i];
-        blk_sync();
+        ar_sync(b);
     }
-    fam_sort_series<T>(b, xs, n, specs, nspecs, out + sidx * ld, (T *)L.srt, L.w, L.iw, cqplan, L.cq, L.stage,
+    fam_sort_series<T, MODE == 2>(b, xs, n, specs, nspecs, out + sidx * ld, (T *)L.srt, L.w, L.iw, cqplan, L.cq, L.stage,
                        n_loop, L.ctx, w_doubles, FrDefer{pf_buf, pf_count, pf_slot, (long long)sidx, 0, pf_cap},
                        perm_buf ? perm_buf + (size_t)sidx * (size_t)perm_stride : nullptr,
                        stats_in ? stats_in + sidx * TSFA_STATS_N : nullptr, pe_hint);
@@ -1080,11 +1087,24 @@ static int launch_all_t(const TsfaLaunch &a, const T *values) {
         TSFA_KLAUNCH(k_trend<T>, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn,
                      a.hint_b, a.times, a.alt, a.hint_c, a.skip_le);
     } else if (a.fam == TSFA_FAM_SORT) {
-        SortLds L;
         const int wd = (a.hint_a >= 320) ? a.hint_a : 1280;
-        const size_t lds = L.carve(nullptr, a.maxn, nt, (int)sizeof(T), wd);
-        TSFA_KLAUNCH(k_sort<T>, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, a.cq,
-                     a.hint_c, wd, a.pf_buf, a.pf_count, a.pf_slot, a.pf_cap, a.perm_buf, a.perm_stride, a.stats_in, a.hint_d);
+        const size_t lds = tsfa_sort_lds_bytes(a, (int)sizeof(T));   // (the same carve call as the kernel's, with its arguments)
+#if !defined(TSFA_LONG)
+        if (a.sort_mode == 2) {
+            auto kfn = k_sort<T, 2>;
+            TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, a.cq,
+                         a.hint_c, wd, a.pf_buf, a.pf_count, a.pf_slot, a.pf_cap, a.perm_buf, a.perm_stride, a.stats_in, a.hint_d);
+        } else if (a.sort_mode == 1) {
+            auto kfn = k_sort<T, 1>;
+            TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, a.cq,
+                         a.hint_c, wd, a.pf_buf, a.pf_count, a.pf_slot, a.pf_cap, a.perm_buf, a.perm_stride, a.stats_in, a.hint_d);
+        } else
+#endif
+        {
+            auto kfn = k_sort<T, 0>;
+            TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, a.cq,
+                         a.hint_c, wd, a.pf_buf, a.pf_count, a.pf_slot, a.pf_cap, a.perm_buf, a.perm_stride, a.stats_in, a.hint_d);
+        }
     } else if (a.fam == TSFA_FAM_SPECTRAL) {
         SpectralLds L;
         const size_t lds = L.carve(nullptr, a.maxn, a.dft_n, (int)sizeof(T));
@@ -1332,6 +1352,12 @@ size_t tsfa_entropy_lds_bytes(int maxn, int with_cnt) {
 size_t tsfa_seq_lds_bytes(const TsfaSeqGroup &g) {
     SeqLds L;
     return L.carve(nullptr, g.grows ? 0 : 1, g.stride, g.ttotal, g.etotal);
+}
+
+size_t tsfa_sort_lds_bytes(const TsfaLaunch &a, int xs_bytes) {
+    SortLds L;
+    return L.carve(nullptr, a.maxn, a.nt, xs_bytes, (a.hint_a >= 320) ? a.hint_a : 1280, a.sort_mode == 2 ? 1 : 0,
+                   a.stats_in == nullptr ? 1 : 0);
 }
 
 size_t tsfa_family_lds_bytes(int fam, int maxn, int nt, int aux) {

@@ -76,6 +76,7 @@ struct TsfaLaunch {
     size_t long_bytes;            // ... and its size: slots of one working set each, one per resident workgroup
     int ent_cnt;            // ENTROPY: per-template LDS counters (symmetric sweep)
     int ent_fast;           // ENTROPY: only m = 2 specs and ent_cnt: the kernel variant without the fallback sweeps
+    int sort_mode;          // SORT: k_sort's instantiation -- 0: nt threads; 1: one wavefront; 2: one wavefront, the sorted series as a 16-bit order
 };
 
 struct TsfaCwtLaunch {
@@ -95,6 +96,7 @@ struct TsfaCwtLaunch {
 size_t tsfa_family_lds_bytes(int fam, int maxn, int nt, int aux);
 size_t tsfa_entropy_lds_bytes(int maxn, int with_cnt);
 size_t tsfa_seq_lds_bytes(const TsfaSeqGroup &g);
+size_t tsfa_sort_lds_bytes(const TsfaLaunch &a, int xs_bytes);   // k_sort's layout for this launch: SortLds::carve with the kernel's own arguments
 int tsfa_launch_family(const TsfaLaunch &a);         // (TSFA_FAM_MPROFILE: k_mprofile reads specs / nspecs / maxn only; its aux is the sample size)
 int tsfa_launch_rows(const TsfaLaunch &a);          // BASIC / TREND: the series of at most TSFA_ROW_MAXN samples, four per wavefront (k_basic_rows / k_trend_rows)
 int tsfa_launch_family_long(const TsfaLaunch &a);   // working set in a.long_scratch instead of LDS (any length <= 65535)

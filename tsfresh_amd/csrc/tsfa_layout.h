@@ -108,14 +108,30 @@ struct SortLds {
     // w_doubles: scratch of the Langevin fit (6 r + 16 + r (m + 1) doubles for the plan's largest (m, r): tsfa_prepare_family),
     //            at least 320; the ordinal-pattern histogram of permutation_entropy takes what is there and sweeps the
     //            pattern space in as many passes as it needs (fam_sort.h)
-    TSFA_HD size_t carve(unsigned char *base, int maxn, int nt, int xs_bytes = 8, int w_doubles = 1280) {
-        (void)nt;
+    // nt <= 64 (one wavefront per series: every launch group up to 2048 samples unless the plan asks for two): the
+    //   cross-wavefront scratch is two slots (every blk_* reduction tests nt > 64 first), and the numpy-order scratch --
+    //   used by the mean of symmetry_looking alone, and only where k_basic left no statistics (with_np) -- shares w, which
+    //   is dead between two columns.  ord16: `srt` is the 16-bit sample order (fam_sort.h: OrdView), maxn entries.
+    //   1024 float32 samples, Comprehensive: 16 + 4096 + 2048 + 2560 + 960 + 64 = 9 744 B, 16 series per CU.
+    // nt > 64: the layout of the two-wavefront form, unchanged (15 664 B at the same shape).
+    TSFA_HD size_t carve(unsigned char *base, int maxn, int nt, int xs_bytes = 8, int w_doubles = 1280, int ord16 = 0,
+                         int with_np = 1) {
         LdsCarve c{base, 0};
-        red = c.take<double>(TSFA_RED_DOUBLES);
-        np = c.take<NpScratch>(1);
+        const bool one_wave = nt <= 64;
+        red = c.take<double>(one_wave ? 2 : TSFA_RED_DOUBLES);
+        np = one_wave ? nullptr : c.take<NpScratch>(1);
         xs = c.take<unsigned char>((size_t)maxn * xs_bytes);
-        srt = c.take<unsigned char>((size_t)tsfa_pow2_ceil(maxn) * xs_bytes);
-        w = c.take<double>(w_doubles);
+        srt = (one_wave && ord16) ? c.take<unsigned char>((size_t)maxn * sizeof(unsigned short))
+                                  : c.take<unsigned char>((size_t)tsfa_pow2_ceil(maxn) * xs_bytes);
+        if (one_wave) {
+            size_t wb = (size_t)w_doubles * sizeof(double);
+            if (with_np && wb < sizeof(NpScratch)) wb = sizeof(NpScratch);
+            unsigned char *u = c.take<unsigned char>(wb);
+            w = (double *)u;
+            np = with_np ? (NpScratch *)u : nullptr;
+        } else {
+            w = c.take<double>(w_doubles);
+        }
         iw = (int *)w;              // ... aliased with the ordinal-pattern histogram: never live together
         cq = c.take<double>(5 * TSFA_CQ_MAX);  // change_quantiles results per corridor
         ctx = c.take<double>(8);               // TSFA_SORT_CTX: values read by the epilogue columns
