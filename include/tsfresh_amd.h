@@ -407,6 +407,34 @@ int tsfa_windows_copy_ends(const tsfa_windows *windows, int64_t *ends_host);
 int tsfa_roll_shift_values(const tsfa_windows *windows, const tsfa_pack *pack, void *out_host);
 void tsfa_windows_destroy(tsfa_windows *windows);
 
+/* The same windows, in the same order and with the same meaning of every roll argument, for a batch that is no pack: the
+ * offsets tsfa_pack_dense wrote (or any n_series + 1 ascending int64 in device memory) in, caller-owned device buffers out.
+ * All pointers are device pointers on `device`; nothing is allocated beyond one counter word inside tsfa_roll_count.
+ * Two routes, chosen by `scanned`:
+ *   scanned != NULL  a ragged batch.  tsfa_roll_count writes every series' window count into scanned[n_series], scans it in
+ *                    place (exclusive) and returns the total in *n_windows_host; tsfa_roll_fill finds window w's series by
+ *                    bisection over `scanned`.  series_len is ignored.
+ *   scanned == NULL  a uniform batch: every series has series_len samples, offsets[s] = offsets[0] + s * series_len (offsets
+ *                    may be NULL for offsets[0] = 0).  The count per series is a closed form the host evaluates:
+ *                    tsfa_roll_count launches nothing and reads nothing back, tsfa_roll_fill is one launch in which window w
+ *                    belongs to series w / c with shift index w % c.  tsfa_roll_fill refuses an n_windows that is not the
+ *                    one tsfa_roll_count returns for the same arguments.
+ *   starts / ends / series / timeshifts   n_windows int64 each, as the handle of tsfa_roll_windows holds them; cells beyond
+ *                    n_windows are not written.  With n_windows == 0 nothing is launched and the pointers may be NULL.
+ *   stream           a hipStream_t: tsfa_roll_fill returns after enqueueing; tsfa_roll_count's ragged route enqueues on it and
+ *                    then waits for it, because the total is its result.  NULL: the null stream, and both return when the work
+ *                    is done.
+ * TSFA_ERR_TOO_LONG, before anything is launched: a batch of 2^32 samples or more -- offsets[n_series] - offsets[0] (two words
+ * read back) or n_series * series_len; the counts are 32 bits wide, which suffices because no series has more windows than
+ * samples.  TSFA_ERR_INVALID: direction 0, a negative max_timeshift or min_timeshift, steps below the longest series
+ * (below series_len), a null pointer that is needed.  TSFA_ERR_NO_DEVICE without a HIP device. */
+int tsfa_roll_count(const int64_t *offsets, int64_t n_series, int64_t series_len, int32_t rolling_direction,
+                    int64_t max_timeshift, int64_t min_timeshift, int64_t steps, uint32_t *scanned, int64_t *n_windows_host,
+                    int32_t device, void *stream);
+int tsfa_roll_fill(const int64_t *offsets, int64_t n_series, const uint32_t *scanned, int64_t series_len, int64_t n_windows,
+                   int32_t rolling_direction, int64_t max_timeshift, int64_t min_timeshift, int64_t steps, int64_t *starts,
+                   int64_t *ends, int64_t *series, int64_t *timeshifts, int32_t device, void *stream);
+
 /* Page-locked host memory for the TSFA_HOST form.  tsfa_extract* accepts ANY host pointer; from pageable memory the HIP
  * runtime stages every transfer through its own bounce buffers, from memory obtained here the copy engines read and
  * write it directly, so the chunked copy-in / compute / copy-out pipeline of tsfa_extract runs at PCIe rate.  The

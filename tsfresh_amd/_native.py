@@ -71,6 +71,8 @@ EXPORTS = (
     "tsfa_windows_copy_ends",
     "tsfa_roll_shift_values",
     "tsfa_windows_destroy",
+    "tsfa_roll_count",
+    "tsfa_roll_fill",
     "tsfa_impute",
     "tsfa_relevance_classes",
     "tsfa_relevance_classes_ks",
@@ -581,7 +583,48 @@ def _bind_roll_api(lib):
     lib.tsfa_roll_shift_values.restype = ctypes.c_int
     lib.tsfa_windows_destroy.argtypes = [ctypes.c_void_p]
     lib.tsfa_windows_destroy.restype = None
+    lib.tsfa_roll_count.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                    ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32,
+                                    ctypes.c_void_p]
+    lib.tsfa_roll_count.restype = ctypes.c_int
+    lib.tsfa_roll_fill.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [ctypes.c_int32,
+                                                                                                         ctypes.c_void_p]
+    lib.tsfa_roll_fill.restype = ctypes.c_int
     lib._tsfa_roll_bound = True
+
+
+def _ptr(p):
+    return ctypes.c_void_p(p) if p else None
+
+
+def roll_count(offsets_ptr, n_series, rolling_direction=1, max_timeshift=None, min_timeshift=0, steps=1, scanned_ptr=None,
+               series_len=0, device=0, stream=None):
+    """tsfa_roll_count on raw device pointers (ints) -> the number of windows of the batch whose n_series + 1 int64 offsets
+    lie at offsets_ptr.  scanned_ptr: n_series uint32 of the caller's (a ragged batch: they receive the exclusive scan of the
+    per-series counts, which `roll_fill` reads; the call waits for its stream), or None for a uniform batch of series_len
+    samples per series (the closed form: nothing is launched or read back, offsets_ptr may be None)."""
+    lib = load()
+    _bind_roll_api(lib)
+    total = ctypes.c_int64(0)
+    _check(lib, lib.tsfa_roll_count(_ptr(offsets_ptr), int(n_series), int(series_len), int(rolling_direction),
+                                    int(max_timeshift or 0), int(min_timeshift), int(steps), _ptr(scanned_ptr),
+                                    ctypes.byref(total), int(device), _ptr(stream)))
+    return int(total.value)
+
+
+def roll_fill(offsets_ptr, n_series, n_windows, starts_ptr, ends_ptr, series_ptr, timeshifts_ptr, rolling_direction=1,
+              max_timeshift=None, min_timeshift=0, steps=1, scanned_ptr=None, series_len=0, device=0, stream=None):
+    """tsfa_roll_fill on raw device pointers (ints): the n_windows windows `roll_count` counted for the same arguments, as
+    four int64 arrays of the caller's -- starts / ends (indices into a channel's value buffer), series, timeshifts -- in
+    (series, ascending timeshift) order.  stream: a hipStream_t as an int (the call only enqueues) or None (the call
+    returns when the work is done)."""
+    lib = load()
+    _bind_roll_api(lib)
+    _check(lib, lib.tsfa_roll_fill(_ptr(offsets_ptr), int(n_series), _ptr(scanned_ptr), int(series_len), int(n_windows),
+                                   int(rolling_direction), int(max_timeshift or 0), int(min_timeshift), int(steps),
+                                   _ptr(starts_ptr), _ptr(ends_ptr), _ptr(series_ptr), _ptr(timeshifts_ptr), int(device),
+                                   _ptr(stream)))
 
 
 class DeviceWindows:
@@ -863,6 +906,19 @@ class Plan:
             dm.free()
         return out
 
+    def extract_windows_into(self, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=0):
+        """Device pointers (ints) in, columns [col0, col0 + n_cols) of the DeviceMatrix / BorrowedMatrix `matrix` out: window
+        w is the view [starts[w], ends[w]) of the value buffer at values_ptr (TSFA_F32 / TSFA_F64), all of it on the matrix'
+        device -- one tsfa_extract_windows call with TSFA_DEVICE pointers, nothing is uploaded and the rows stay in HBM."""
+        n_windows = int(n_windows)
+        if matrix.device != self.device or matrix.shape[0] != n_windows or col0 < 0 or col0 + self.n_cols > matrix.shape[1]:
+            raise ValueError("the device matrix does not hold [n_windows, col0 + n_cols] cells on the plan's device")
+        if n_windows == 0 or self.n_cols == 0:
+            return
+        _check(self._lib, self._lib.tsfa_extract_windows(
+            self._h, ctypes.c_void_p(values_ptr), int(values_type), None, ctypes.c_void_p(starts_ptr), ctypes.c_void_p(ends_ptr),
+            n_windows, ctypes.c_void_p(matrix.ptr + 8 * col0), matrix.ld, TSFA_DEVICE, None))
+
     def extract_into(self, values, offsets, matrix, col0=0, times=None, pack=None):
         """Host arrays in, columns [col0, col0 + n_cols) of the DeviceMatrix `matrix` out: the samples are copied to the
         device once and the feature rows stay there (tsfa_extract / tsfa_extract_timed with TSFA_DEVICE pointers).
@@ -1028,6 +1084,33 @@ def extract_parts_into(parts, values, offsets, matrix, col0=0, times=None, pack=
             bf.free()
         if tmp is not None:
             tmp.free()
+
+
+def extract_parts_windows_into(parts, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=0):
+    """The window twin of `extract_parts_into(pack=...)`: several native plans over the same device buffers.  Every part's
+    block of the windows [starts[w], ends[w]) of the value buffer at values_ptr is extracted into a transient device matrix
+    and scattered (tsfa_scatter_columns) into columns col0 + cols of `matrix` (a DeviceMatrix or a BorrowedMatrix)."""
+    lib = load()
+    _bind_device_api(lib)
+    n_windows = int(n_windows)
+    if matrix.shape[0] != n_windows:
+        raise ValueError("the device matrix does not hold one row per window")
+    if col0 < 0 or any(len(cols) and int(col0) + int(max(cols)) >= matrix.shape[1] for _, cols in parts):
+        raise ValueError("the device matrix does not hold the parts' columns from col0 on")
+    if n_windows == 0:
+        return
+    tmp = DeviceMatrix(n_windows, max(plan.n_cols for plan, _ in parts), matrix.device)
+    try:
+        for plan, cols in parts:
+            if plan.n_cols == 0:
+                continue
+            plan.extract_windows_into(values_ptr, values_type, starts_ptr, ends_ptr, n_windows,
+                                      BorrowedMatrix(tmp.ptr, n_windows, plan.n_cols, matrix.device, owner=tmp))
+            idx = np.ascontiguousarray(np.asarray(cols, dtype=np.int64) + int(col0), dtype=np.int32)
+            _check(lib, lib.tsfa_scatter_columns(ctypes.c_void_p(matrix.ptr), matrix.ld, idx.ctypes.data_as(ctypes.c_void_p),
+                                                 ctypes.c_void_p(tmp.ptr), n_windows, plan.n_cols, matrix.device))
+    finally:
+        tmp.free()
 
 
 def _bind_device_api(lib):

@@ -22,8 +22,15 @@
 // A series of len samples has at most len windows, so the counts and their total fit the packer's 32-bit scan (a pack holds
 // fewer than 2^32 rows); every index a window carries is int64.
 //
+// The same windows for a batch that is no pack (tsfa_roll_count / tsfa_roll_fill: raw offsets in, caller-owned buffers out) take
+// one of two routes.  Ragged: steps 1-3 above, with the counts scanned in place in the caller's `scanned` buffer.  Uniform (every
+// series has n samples, offsets[s] = offsets[0] + s n): the count per series c = rl_count(p, n) is known on the host, so
+// n_windows = n_series * c, window w belongs to series w / c with shift index w % c, and one launch of rl_fill_uniform_body is the
+// whole build: no counts, no scan, no bisection, nothing read back.  The host side of both (rl_check_extent, rl_uniform_count)
+// lives here too, so that the emulation runs the driver's checks and not a copy of them.
+//
 // Compiled two ways like pack_device.h: by hipcc for gfx950 and by g++ -DTSFA_EMUL with one thread per workgroup
-// (tests/emul/emul_roll.cpp).  The bodies are grid-stride loops without ballots or DPP (one LDS word collects a workgroup's
+// (tests/emul/emul_roll.cpp, tests/emul/emul_roll_dense.cpp).  The bodies are grid-stride loops without ballots or DPP (one LDS word collects a workgroup's
 // maximum length): the emulation sees all of their arithmetic.  No workgroup waits on another; the maximum length is the only
 // atomic and does not depend on arrival order.
 #ifndef TSFA_ROLL_DEVICE_H
@@ -61,14 +68,15 @@ static inline const char *rl_make_params(int32_t rolling_direction, int64_t max_
 }
 
 // first valid timeshift (direction > 0) of a series; only meaningful where rl_count > 0
-TSFA_DEV int64_t rl_first_shift(const RlParams &p) {
+// (PK_HD: the uniform route of tsfa_roll_count / tsfa_roll_fill evaluates the two closed forms on the host as well)
+PK_HD int64_t rl_first_shift(const RlParams &p) {
     const int64_t lo = p.min_ts + 1;                       // the smallest admissible ts
     int64_t d = (p.steps - lo) % p.amount;                 // (C++ remainder: negative when lo > steps) -> the residue
     if (d < 0) d += p.amount;
     return lo + d;                                         // the smallest ts >= lo with ts = steps (mod amount)
 }
 
-TSFA_DEV int64_t rl_count(const RlParams &p, int64_t len) {
+PK_HD int64_t rl_count(const RlParams &p, int64_t len) {
     if (p.mts < p.min_ts) return 0;
     if (p.positive) {
         const int64_t first = rl_first_shift(p);
@@ -128,6 +136,76 @@ TSFA_DEV void rl_fill_body(const PkBlk &b, int64_t first, int64_t stride, const 
         series[w] = lo;
         shifts[w] = ts;
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// 3u. the windows of a batch of n_series series of n samples each, c = rl_count(p, n) > 0 windows per series, n_windows =
+//     n_series * c.  offsets: the batch's offsets (only offsets[0], the base, is read) or NULL for base 0.
+//     (grid-stride over the windows)
+// ---------------------------------------------------------------------------------------------
+TSFA_DEV void rl_fill_uniform_body(const PkBlk &b, int64_t first, int64_t stride, const int64_t *offsets, int64_t n, int64_t c,
+                                   int64_t n_windows, RlParams p, int64_t *starts, int64_t *ends, int64_t *series,
+                                   int64_t *shifts) {
+    const int64_t base = offsets ? offsets[0] : 0;
+    for (int64_t w = first + b.tid; w < n_windows; w += stride) {
+        const int64_t s = w / c, j = w - s * c, o = base + s * n;
+        int64_t ts, frm, until;
+        if (p.positive) {
+            ts = rl_first_shift(p) + j * p.amount;
+            until = ts;
+            frm = ts - p.mts - 1;
+            if (frm < 0) frm = 0;
+        } else {
+            frm = j * p.amount;
+            ts = frm + 1;
+            until = frm + p.mts + 1;
+            if (until > n) until = n;
+        }
+        starts[w] = o + frm;
+        ends[w] = o + until;
+        series[w] = s;
+        shifts[w] = ts;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Host code of tsfa_roll_count / tsfa_roll_fill (the .hip driver and the emulation share it).  The counts and their scan are
+// 32 bits wide, which holds because no series has more windows than samples: a batch of 2^32 or more samples is refused.
+// ---------------------------------------------------------------------------------------------
+#define RL_MAX_SAMPLES 0xffffffffll
+
+// extent = offsets[n_series] - offsets[0] of a ragged batch: a tsfa_status, *why set when it is not TSFA_OK
+static inline int rl_check_extent(int64_t extent, const char **why) {
+    if (extent < 0) {
+        *why = "offsets[n_series] is below offsets[0]";
+        return TSFA_ERR_INVALID;
+    }
+    if (extent > RL_MAX_SAMPLES) {
+        *why = "4 294 967 296 or more samples (the window counts are 32 bits wide)";
+        return TSFA_ERR_TOO_LONG;
+    }
+    return TSFA_OK;
+}
+
+// The uniform route: n_series series of series_len samples -> *per_series = rl_count(p, series_len) and *n_windows, their
+// product (below 2^32, as the samples are).  A tsfa_status, *why set when it is not TSFA_OK.
+static inline int rl_uniform_count(const RlParams &p, int64_t n_series, int64_t series_len, int64_t *per_series, int64_t *n_windows,
+                                   const char **why) {
+    if (n_series < 0 || series_len < 1) {
+        *why = "n_series is negative or series_len is below 1";
+        return TSFA_ERR_INVALID;
+    }
+    if (series_len > p.steps) {
+        *why = "steps is below series_len";
+        return TSFA_ERR_INVALID;
+    }
+    if (n_series > RL_MAX_SAMPLES / series_len) {   // n_series * series_len >= 2^32, without forming the product
+        *why = "4 294 967 296 or more samples (the window counts are 32 bits wide)";
+        return TSFA_ERR_TOO_LONG;
+    }
+    *per_series = rl_count(p, series_len);          // <= series_len: the product below cannot overflow
+    *n_windows = n_series * *per_series;
+    return TSFA_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

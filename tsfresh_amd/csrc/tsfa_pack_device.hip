@@ -660,6 +660,14 @@ __global__ void __launch_bounds__(PK_GRID_THREADS) k_roll_fill(const int64_t *of
                  ends, series, shifts);
 }
 
+__global__ void __launch_bounds__(PK_GRID_THREADS) k_roll_fill_uniform(const int64_t *offsets, int64_t n, int64_t c, int64_t n_windows,
+                                                                         RlParams p, int64_t *starts, int64_t *ends, int64_t *series,
+                                                                         int64_t *shifts) {
+    const PkBlk b{(int)threadIdx.x, (int)blockDim.x};
+    rl_fill_uniform_body(b, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, offsets, n, c, n_windows, p, starts, ends,
+                         series, shifts);
+}
+
 __global__ void __launch_bounds__(PK_GRID_THREADS) k_roll_shift_values(const void *sort, int itemsize, int64_t n_rows,
                                                                          const int64_t *starts, const int64_t *ends, int positive,
                                                                          int64_t n_windows, void *out) {
@@ -760,6 +768,114 @@ extern "C" int tsfa_windows_copy_starts(const tsfa_windows *windows, int64_t *st
 extern "C" int tsfa_windows_copy_ends(const tsfa_windows *windows, int64_t *ends_host) {
     return rl_copy_out(windows, ends_host, windows ? windows->ends : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
                        "tsfa_windows_copy_ends");
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same windows for a batch that is no pack: raw offsets in, caller-owned buffers out (see roll_device.h for the two routes)
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+int rl_check_device(const char *who, int32_t device) {
+    int ndev = 0;  // before the arguments are looked at: without a device no device pointer can exist
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return tsfa_fail(TSFA_ERR_NO_DEVICE, (std::string(who) + ": no HIP device visible: tsfresh_amd has no CPU fallback").c_str());
+    if (device < 0 || device >= ndev) return tsfa_fail(TSFA_ERR_NO_DEVICE, (std::string(who) + ": no such HIP device").c_str());
+    return TSFA_OK;
+}
+
+}  // namespace
+
+#undef PK_WHO
+#define PK_WHO "tsfa_roll_count"
+extern "C" int tsfa_roll_count(const int64_t *offsets, int64_t n_series, int64_t series_len, int32_t rolling_direction,
+                               int64_t max_timeshift, int64_t min_timeshift, int64_t steps, uint32_t *scanned,
+                               int64_t *n_windows_host, int32_t device, void *stream) {
+    int rc = rl_check_device(PK_WHO, device);
+    if (rc) return rc;
+    if (!n_windows_host) return tsfa_fail(TSFA_ERR_INVALID, PK_WHO ": n_windows_host is NULL");
+    *n_windows_host = 0;
+    RlParams p;
+    const char *why = rl_make_params(rolling_direction, max_timeshift, min_timeshift, steps, &p);
+    if (why) return tsfa_fail(TSFA_ERR_INVALID, (std::string(PK_WHO ": ") + why).c_str());
+    if (!scanned) {  // the uniform route: the closed form on the host, nothing is launched
+        int64_t per_series = 0;
+        if ((rc = rl_uniform_count(p, n_series, series_len, &per_series, n_windows_host, &why)))
+            return tsfa_fail(rc, (std::string(PK_WHO ": ") + why).c_str());
+        return TSFA_OK;
+    }
+    if (!offsets || n_series < 0) return tsfa_fail(TSFA_ERR_INVALID, PK_WHO ": offsets is NULL or n_series is negative");
+    if (n_series == 0) return TSFA_OK;
+    hipStream_t st = (hipStream_t)stream;  // NULL: the null stream
+    int64_t edge[2] = {0, 0};
+    RlStats *d_st = nullptr;
+    RlStats hst;
+    memset(&hst, 0, sizeof(hst));
+
+    PK_HIP(hipSetDevice(device));
+    // the extent the offsets claim, before anything is launched on them
+    PK_HIP(hipMemcpyAsync(&edge[0], offsets, 8, hipMemcpyDeviceToHost, st));
+    PK_HIP(hipMemcpyAsync(&edge[1], offsets + n_series, 8, hipMemcpyDeviceToHost, st));
+    PK_HIP(hipStreamSynchronize(st));
+    if ((rc = rl_check_extent(edge[1] - edge[0], &why))) {
+        rc = tsfa_fail(rc, (std::string(PK_WHO ": ") + why).c_str());
+        goto done;
+    }
+    PK_ALLOC(d_st, sizeof(RlStats), "the window builder's counters");
+    PK_HIP(hipMemsetAsync(d_st, 0, sizeof(RlStats), st));
+    k_roll_count<<<pk_grid(n_series), PK_GRID_THREADS, 0, st>>>(offsets, n_series, p, scanned, d_st);
+    k_pack_scan<<<1, PK_SCAN_THREADS, 0, st>>>(scanned, (size_t)n_series, &d_st->total);
+    PK_HIP(hipGetLastError());
+    PK_HIP(hipMemcpyAsync(&hst, d_st, sizeof(hst), hipMemcpyDeviceToHost, st));
+    PK_HIP(hipStreamSynchronize(st));  // the total is the call's result: this route waits for the stream whoever owns it
+    if ((int64_t)hst.max_len > steps) {
+        rc = tsfa_fail(TSFA_ERR_INVALID, (PK_WHO ": steps = " + std::to_string(steps) + " is below the batch's longest series (" +
+                                          std::to_string(hst.max_len) + " samples)").c_str());
+        goto done;
+    }
+    *n_windows_host = (int64_t)hst.total;
+done:
+    (void)hipFree(d_st);
+    return rc;
+}
+
+#undef PK_WHO
+#define PK_WHO "tsfa_roll_fill"
+extern "C" int tsfa_roll_fill(const int64_t *offsets, int64_t n_series, const uint32_t *scanned, int64_t series_len,
+                              int64_t n_windows, int32_t rolling_direction, int64_t max_timeshift, int64_t min_timeshift,
+                              int64_t steps, int64_t *starts, int64_t *ends, int64_t *series, int64_t *timeshifts, int32_t device,
+                              void *stream) {
+    int rc = rl_check_device(PK_WHO, device);
+    if (rc) return rc;
+    RlParams p;
+    const char *why = rl_make_params(rolling_direction, max_timeshift, min_timeshift, steps, &p);
+    if (why) return tsfa_fail(TSFA_ERR_INVALID, (std::string(PK_WHO ": ") + why).c_str());
+    if (n_windows < 0 || n_series < 0) return tsfa_fail(TSFA_ERR_INVALID, PK_WHO ": n_windows or n_series is negative");
+    int64_t per_series = 0;
+    if (!scanned) {
+        int64_t expect = 0;
+        if ((rc = rl_uniform_count(p, n_series, series_len, &per_series, &expect, &why)))
+            return tsfa_fail(rc, (std::string(PK_WHO ": ") + why).c_str());
+        if (n_windows != expect)
+            return tsfa_fail(TSFA_ERR_INVALID, (PK_WHO ": n_windows = " + std::to_string(n_windows) + ", but " + std::to_string(n_series) +
+                                                " series of " + std::to_string(series_len) + " samples have " + std::to_string(expect) +
+                                                " windows").c_str());
+    } else if (!offsets || n_windows > RL_MAX_SAMPLES) {
+        return tsfa_fail(TSFA_ERR_INVALID, PK_WHO ": offsets is NULL, or n_windows is beyond what tsfa_roll_count returns");
+    }
+    if (n_windows == 0) return TSFA_OK;
+    if (n_series < 1 || !starts || !ends || !series || !timeshifts)
+        return tsfa_fail(TSFA_ERR_INVALID, PK_WHO ": windows without a series, or an output pointer is NULL");
+    hipStream_t st = (hipStream_t)stream;  // NULL: the null stream
+    PK_HIP(hipSetDevice(device));
+    if (scanned)
+        k_roll_fill<<<pk_grid(n_windows), PK_GRID_THREADS, 0, st>>>(offsets, n_series, scanned, n_windows, p, starts, ends, series, timeshifts);
+    else
+        k_roll_fill_uniform<<<pk_grid(n_windows), PK_GRID_THREADS, 0, st>>>(offsets, series_len, per_series, n_windows, p, starts, ends,
+                                                                             series, timeshifts);
+    PK_HIP(hipGetLastError());
+    if (!stream) PK_HIP(hipStreamSynchronize(st));
+done:
+    return rc;
 }
 
 #undef PK_WHO

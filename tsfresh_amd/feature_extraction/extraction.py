@@ -175,6 +175,11 @@ class _CompositePlan:
         pack: a `_native.DevicePack` instead of host `values` / `offsets`."""
         _native.extract_parts_into(self.parts, values, offsets, matrix, col0=col0, times=times, pack=pack)
 
+    def extract_windows_into(self, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=0):
+        """Columns [col0, col0 + n_cols) of the device matrix `matrix` for windows held as device pointers
+        (`Plan.extract_windows_into`): the parts' blocks are scattered into the caller's column order in HBM."""
+        _native.extract_parts_windows_into(self.parts, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=col0)
+
 
 def _split_native_specs(specs):
     """-> [(sub-list of specs, their column indices)]: one part unless augmented_dickey_fuller columns name several lag

@@ -1,10 +1,12 @@
-"""`extract_features_tensor`: features of a batch that already is a tensor, without pandas.
+"""`extract_features_tensor` and `extract_rolled_features_tensor`: features of a batch that already is a tensor, without pandas.
 
 `extract_features` takes the reference's containers: a batch held as `[B, C, n]`, `[B, n, C]` or a right-padded `[B, n_max]`
 with `lengths[B]` on the GPU would have to be copied to the host, written out as a DataFrame and sorted back into the layout
 it already had.  Here the tensor goes to the dense packer (`tsfa_pack_dense`: one fused copy / transpose / convert kernel,
 include/tsfresh_amd.h) and from there to the kernels `extract_features` runs, through the same FCParameters handling, the
 same plan cache and the same composite plans (feature_extraction/extraction.py); the feature matrix stays on the device.
+The rolled entry adds the window builder between the two (`tsfa_roll_count` / `tsfa_roll_fill` on the packer's offsets) and
+hands the kernels `(start, end)` views instead of whole series (`tsfa_extract_windows` with device pointers).
 """
 import numpy as np
 
@@ -49,42 +51,11 @@ def _dense_pack(torch, x3, lengths, device):
     return packs, flag
 
 
-def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, default_fc_parameters=None,
-                            kind_to_fc_parameters=None, device=None, check_nan=True, show_warnings=False):
-    """Extract features from a batch of equally sampled series held as a tensor; the feature matrix stays on the GPU.
-
-    :param x: `torch.Tensor` (on the GPU or on the CPU) or numpy array of dtype float64, float32, float16 or bfloat16 and
-        shape `(B, n)` (one kind), `(B, C, n)`, or `(B, n, C)` with `channels_last=True`: B series of n samples for each of C
-        kinds.  Any strides are taken as they are (sliced, stepped, permuted and expanded views are not copied first).  A CPU
-        tensor or a numpy array is moved to `device` with torch.  float16 and bfloat16 samples are converted to float32
-        (exactly) on the way into the packed layout, and the result equals that of the float32 samples.
-    :param lengths: optional 1-D integer tensor or array of B entries: series b is its first `lengths[b]` samples (a
-        right-padded batch), 1 <= lengths[b] <= n.  What lies beyond a series' length is never read.
-    :param kinds: C names, default "0" ... "C-1"; the rules of a wide frame's value columns apply (no "__", no trailing "_").
-    :param default_fc_parameters, kind_to_fc_parameters: as in `extract_features` (default `ComprehensiveFCParameters()`).
-        Custom calculators (callable keys) are evaluated on the host per series and raise `UnsupportedFeature` here.
-    :param device: HIP device ordinal.  Default: the device `x` lives on; for a CPU tensor or an array the rule of
-        `extract_features` ($TSFRESH_AMD_DEVICE, else $LOCAL_RANK, else 0).
-    :param check_nan: True (default): a NaN among the samples raises the reference's
-        `ValueError("Column must not contain NaN values: <kind>")`; False skips the check and its read-back of one word.
-    :return: `(features, columns)`: a `torch.float64` tensor `[B, number of columns]` on the device and the list of column
-        names ``"{kind}__{feature}"``, in exactly the order `extract_features` gives for the equivalent wide frame.
-
-    Ordering (this version is synchronous): `x` is read only after everything queued on torch's current stream at the time of
-    the call has finished -- the call synchronises with that stream explicitly, because the library's streams do not
-    synchronise with it implicitly -- and when the call returns `features` is complete and safe to use on any stream.
-    Enqueue-only operation on the caller's stream is a follow-up.
-
-    Not mirrored: the reference's exceptions that depend on the samples -- an infinite sample under `binned_entropy` or
-    `ar_coefficient`, a `query_similarity_count` query longer than a series (feature_extraction/reference_errors.py raises
-    them for `extract_features`).  Finding them needs the samples on the host; here those cells hold the kernels' NaN.
-    """
-    import torch
-
+def _batch_arguments(torch, x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device):
+    """The checks both entries make on their batch -> (x3: the (B, C, n) view of x, lengths: None or a contiguous int32 /
+    int64 tensor, kinds, default_fc_parameters, device).  Nothing has moved to the device yet."""
     from tsfresh_amd.feature_extraction import extraction
     from tsfresh_amd.feature_extraction.data import _check_colname
-    from tsfresh_amd.feature_extraction.plan import compile_fc_parameters
-    from tsfresh_amd.feature_extraction.registry import UnsupportedFeature
     from tsfresh_amd.feature_extraction.settings import ComprehensiveFCParameters
 
     if isinstance(x, np.ndarray):
@@ -130,41 +101,106 @@ def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, de
         default_fc_parameters = {}
     if device is None:
         device = x.device.index if x.is_cuda else extraction._default_device()
-    device = int(device)
+    return x3, lengths, kinds, default_fc_parameters, int(device)
+
+
+def _kind_jobs(kinds, default_fc_parameters, kind_to_fc_parameters, device, pins, instead):
+    """The plans of the kinds that have columns -> ([(channel, kind, fplan, native plan, first column)], number of columns,
+    column names).  A settings object the kernels do not serve, or a box without a device, fails here, before anything
+    moves.  instead: what the UnsupportedFeature of a callable calculator tells the caller to do."""
+    from tsfresh_amd.feature_extraction import extraction
+    from tsfresh_amd.feature_extraction.plan import compile_fc_parameters
+    from tsfresh_amd.feature_extraction.registry import UnsupportedFeature
+
+    plan_cache, jobs, n_cols = {}, [], 0
+    for c, kind in enumerate(kinds):
+        fc_parameters = kind_to_fc_parameters[kind] if kind_to_fc_parameters and kind in kind_to_fc_parameters \
+            else default_fc_parameters
+        key = id(fc_parameters)
+        if key not in plan_cache:
+            fplan = compile_fc_parameters(fc_parameters, has_datetime_index=False)
+            if fplan.host_calls:
+                raise UnsupportedFeature("custom (callable) calculators are evaluated per series on the host: " + instead)
+            plan_cache[key] = (fplan, extraction._acquire_plan(fplan, device, pins) if fplan.names else None)
+        fplan, nplan = plan_cache[key]
+        if nplan is None:
+            continue
+        jobs.append((c, kind, fplan, nplan, n_cols))
+        n_cols += len(fplan.names)
+    columns = [kind + "__" + name for _, kind, fplan, _, _ in jobs for name in fplan.names]
+    return jobs, n_cols, columns
+
+
+def _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=False):
+    """`_dense_pack` of the batch on `device` and its flag word's errors -> (x3 and lengths on the device, packs, steps).
+    steps (want_steps): the longest series, n without lengths -- with lengths their maximum, which comes back in the same
+    read as the flag word."""
+    n = x3.shape[2]
+    x3 = _to_device(x3, device)
+    if lengths is not None:
+        lengths = _to_device(lengths, device)
+    packs, flag = _dense_pack(torch, x3, lengths, device)
+    steps = n
+    if lengths is not None or check_nan:
+        if want_steps and lengths is not None:
+            # one read for both words, before any extraction kernel is launched
+            flags, steps = torch.stack([flag.reshape(()).to(torch.int64), lengths.max().to(torch.int64)]).tolist()
+        else:
+            flags = int(flag.item())   # one word back, before any extraction kernel is launched
+        if flags & _native.TSFA_DENSE_BAD_LENGTH:
+            raise ValueError("lengths must lie in [1, {}] (the samples per series of x)".format(n))
+        if check_nan and flags & _native.TSFA_PACK_VALUE_NAN:
+            raise ValueError("Column must not contain NaN values: {}".format(_first_nan_kind(torch, x3, lengths, kinds)))
+    return x3, lengths, packs, int(steps)
+
+
+def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, default_fc_parameters=None,
+                            kind_to_fc_parameters=None, device=None, check_nan=True, show_warnings=False):
+    """Extract features from a batch of equally sampled series held as a tensor; the feature matrix stays on the GPU.
+
+    :param x: `torch.Tensor` (on the GPU or on the CPU) or numpy array of dtype float64, float32, float16 or bfloat16 and
+        shape `(B, n)` (one kind), `(B, C, n)`, or `(B, n, C)` with `channels_last=True`: B series of n samples for each of C
+        kinds.  Any strides are taken as they are (sliced, stepped, permuted and expanded views are not copied first).  A CPU
+        tensor or a numpy array is moved to `device` with torch.  float16 and bfloat16 samples are converted to float32
+        (exactly) on the way into the packed layout, and the result equals that of the float32 samples.
+    :param lengths: optional 1-D integer tensor or array of B entries: series b is its first `lengths[b]` samples (a
+        right-padded batch), 1 <= lengths[b] <= n.  What lies beyond a series' length is never read.
+    :param kinds: C names, default "0" ... "C-1"; the rules of a wide frame's value columns apply (no "__", no trailing "_").
+    :param default_fc_parameters, kind_to_fc_parameters: as in `extract_features` (default `ComprehensiveFCParameters()`).
+        Custom calculators (callable keys) are evaluated on the host per series and raise `UnsupportedFeature` here.
+    :param device: HIP device ordinal.  Default: the device `x` lives on; for a CPU tensor or an array the rule of
+        `extract_features` ($TSFRESH_AMD_DEVICE, else $LOCAL_RANK, else 0).
+    :param check_nan: True (default): a NaN among the samples raises the reference's
+        `ValueError("Column must not contain NaN values: <kind>")`; False skips the check and its read-back of one word.
+    :return: `(features, columns)`: a `torch.float64` tensor `[B, number of columns]` on the device and the list of column
+        names ``"{kind}__{feature}"``, in exactly the order `extract_features` gives for the equivalent wide frame.
+
+    Ordering (this version is synchronous): `x` is read only after everything queued on torch's current stream at the time of
+    the call has finished -- the call synchronises with that stream explicitly, because the library's streams do not
+    synchronise with it implicitly -- and when the call returns `features` is complete and safe to use on any stream.
+    Enqueue-only operation on the caller's stream is a follow-up.
+
+    Not mirrored: the reference's exceptions that depend on the samples -- an infinite sample under `binned_entropy` or
+    `ar_coefficient`, a `query_similarity_count` query longer than a series (feature_extraction/reference_errors.py raises
+    them for `extract_features`).  Finding them needs the samples on the host; here those cells hold the kernels' NaN.
+    """
+    import torch
+
+    from tsfresh_amd.feature_extraction import extraction
+
+    x3, lengths, kinds, default_fc_parameters, device = _batch_arguments(
+        torch, x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device)
+    B = x3.shape[0]
 
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("default" if show_warnings else "ignore")
-        # plans first: a settings object the kernels do not serve, or a box without a device, fails before anything moves
-        plan_cache, pins, jobs, n_cols = {}, set(), [], 0
-        for c, kind in enumerate(kinds):
-            fc_parameters = kind_to_fc_parameters[kind] if kind_to_fc_parameters and kind in kind_to_fc_parameters \
-                else default_fc_parameters
-            key = id(fc_parameters)
-            if key not in plan_cache:
-                fplan = compile_fc_parameters(fc_parameters, has_datetime_index=False)
-                if fplan.host_calls:
-                    raise UnsupportedFeature("custom (callable) calculators are evaluated per series on the host: build a "
-                                             "DataFrame and call extract_features on it")
-                plan_cache[key] = (fplan, extraction._acquire_plan(fplan, device, pins) if fplan.names else None)
-            fplan, nplan = plan_cache[key]
-            if nplan is None:
-                continue
-            jobs.append((c, kind, fplan, nplan, n_cols))
-            n_cols += len(fplan.names)
-        columns = [kind + "__" + name for _, kind, fplan, _, _ in jobs for name in fplan.names]
-
+        pins = set()
+        jobs, n_cols, columns = _kind_jobs(kinds, default_fc_parameters, kind_to_fc_parameters, device, pins,
+                                           "build a DataFrame and call extract_features on it")
         x3 = _to_device(x3, device)
-        if lengths is not None:
-            lengths = _to_device(lengths, device)
         features = torch.empty((B, n_cols), dtype=torch.float64, device=x3.device)
-        packs, flag = _dense_pack(torch, x3, lengths, device)
-        if lengths is not None or check_nan:
-            flags = int(flag.item())   # one word back, before any extraction kernel is launched
-            if flags & _native.TSFA_DENSE_BAD_LENGTH:
-                raise ValueError("lengths must lie in [1, {}] (the samples per series of x)".format(n))
-            if check_nan and flags & _native.TSFA_PACK_VALUE_NAN:
-                raise ValueError("Column must not contain NaN values: {}".format(_first_nan_kind(torch, x3, lengths, kinds)))
+        x3, lengths, packs, _ = _pack_checked(torch, x3, lengths, kinds, device, check_nan)
         if n_cols:
             matrix = _native.BorrowedMatrix(features.data_ptr(), B, n_cols, device, owner=features)
             for c, kind, fplan, nplan, col0 in jobs:
@@ -174,6 +210,105 @@ def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, de
             pack.close()
         extraction._trim_cache(extraction._thread_cache())
     return features, columns
+
+
+def _roll_windows(torch, pack, series_len, rolling_direction, max_timeshift, min_timeshift, steps):
+    """The rolled windows of a dense-packed batch, built on the device from the offsets its channels share -> (starts, ends,
+    series, timeshifts): four int64 tensors of n_windows entries on the pack's device, in (series, ascending timeshift)
+    order; starts / ends index every channel's own value buffer.  series_len: the samples of every series of a batch
+    without `lengths` (the closed form: one launch, nothing read back), or None for a ragged batch (count, scan, fill: the
+    window count comes back).  With no window nothing is launched."""
+    dev = "cuda:%d" % pack.device
+    B = pack.n_series
+    roll = dict(rolling_direction=rolling_direction, max_timeshift=max_timeshift, min_timeshift=min_timeshift, steps=steps,
+                device=pack.device)
+    scanned = None
+    if series_len is None:
+        scanned = torch.empty(B, dtype=torch.int32, device=dev)   # (uint32 to the library: 4 bytes per series)
+        roll["scanned_ptr"] = scanned.data_ptr()
+        _synchronize(torch, pack.device)   # (the allocator may hand out memory that work queued on torch's stream still uses)
+    else:
+        roll["series_len"] = series_len
+    n_windows = _native.roll_count(pack.offsets_ptr, B, **roll)
+    out = torch.empty((4, n_windows), dtype=torch.int64, device=dev)
+    _synchronize(torch, pack.device)
+    _native.roll_fill(pack.offsets_ptr, B, n_windows, *(out[k].data_ptr() for k in range(4)), **roll)
+    return out[0], out[1], out[2], out[3]
+
+
+def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=False, rolling_direction=1, max_timeshift=None,
+                                   min_timeshift=0, default_fc_parameters=None, kind_to_fc_parameters=None, device=None,
+                                   check_nan=True, show_warnings=False):
+    """`extract_rolled_features` for a batch that already is a tensor: sliding-window (forecasting) features of every series,
+    without pandas; the windows are built in HBM and the feature matrix stays there.
+
+    :param x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device, check_nan: exactly as in
+        `extract_features_tensor`.  Custom calculators (callable keys) raise `UnsupportedFeature` here as well.
+    :param rolling_direction, max_timeshift, min_timeshift: as in `roll_time_series` / `extract_rolled_features`; the
+        reference's three `ValueError`s for them are raised before anything moves.  A window of w samples at every step is
+        `max_timeshift=w - 1, min_timeshift=w - 1`.
+    :return: `(features, columns, series, positions)`, all tensors on the device:
+        `features` `torch.float64` `[n_windows, number of columns]`; `columns` the names ``"{kind}__{feature}"`` in exactly the
+        order `extract_rolled_features` gives for the equivalent wide frame; `series` `torch.int64` `[n_windows]`, the batch
+        index of each window; `positions` `torch.int64` `[n_windows]`, `timeshift - 1`: the second half of the reference's
+        window id `(id, shift)` when the sort column is `0 .. len - 1` -- the index of the window's last sample for a positive
+        direction, of its first sample for a negative one.  Rows are in `(series, ascending position)` order, the sorted order
+        of the reference's `(id, shift)` index for integer ids.  For a batch without `lengths` every series has the same
+        windows, so `features.view(B, n_windows // B, -1)` is the dense `[B, W, F]` form.  With no window at all (for example
+        `min_timeshift` at or above every length) the tensors are empty, of shapes `(0, number of columns)` and `(0,)`, and
+        nothing is launched.
+
+    The windows are built once for all kinds (the channels share their offsets): for a batch without `lengths` in one launch
+    from a closed form, with nothing read back; with `lengths` the longest length comes back with the packer's flag word
+    (`ts = steps (mod |rolling_direction|)` decides the shifts, so the true maximum is needed) and the window count after a
+    count and a scan.
+
+    Memory: the result matrix is allocated whole, `n_windows * number of columns * 8` bytes, and is the caller's to budget.
+    1000 series of 1024 samples at window 128 are 1000 * (1024 - 127) = 897 000 windows: with the 777 columns of
+    `EfficientFCParameters` 5.58 GB, next to 4 * 8 bytes per window of starts, ends, series and positions (28.7 MB).  Roll a
+    slice of the batch at a time when that is too much.
+
+    Ordering: synchronous, like `extract_features_tensor` -- `x` is read after everything queued on torch's current stream
+    has finished, and the results are complete when the call returns.
+
+    Not mirrored, as in `extract_features_tensor`: the reference's exceptions that depend on the samples (an infinite sample
+    under `binned_entropy` or `ar_coefficient`, a `query_similarity_count` query longer than a window); those cells hold the
+    kernels' NaN.
+    """
+    import torch
+
+    from tsfresh_amd.feature_extraction import extraction
+    from tsfresh_amd.utilities.dataframe_functions import check_roll_arguments
+
+    check_roll_arguments(rolling_direction, max_timeshift, min_timeshift)
+    x3, lengths, kinds, default_fc_parameters, device = _batch_arguments(
+        torch, x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device)
+    n = x3.shape[2]
+
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("default" if show_warnings else "ignore")
+        pins = set()
+        jobs, n_cols, columns = _kind_jobs(kinds, default_fc_parameters, kind_to_fc_parameters, device, pins,
+                                           "build a DataFrame, roll it with roll_time_series and call extract_features on it")
+        x3, lengths, packs, steps = _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=True)
+        # once for all kinds: the channels share their offsets, and starts / ends count from each channel's own base
+        starts, ends, series, shifts = _roll_windows(torch, packs[0], n if lengths is None else None, int(rolling_direction),
+                                                     max_timeshift, int(min_timeshift), steps)
+        n_windows = int(series.shape[0])
+        features = torch.empty((n_windows, n_cols), dtype=torch.float64, device=x3.device)
+        if n_windows and n_cols:
+            matrix = _native.BorrowedMatrix(features.data_ptr(), n_windows, n_cols, device, owner=features)
+            _synchronize(torch, device)
+            for c, kind, fplan, nplan, col0 in jobs:
+                nplan.extract_windows_into(packs[c].values_ptr, packs[c].values_type, starts.data_ptr(), ends.data_ptr(),
+                                           n_windows, matrix, col0=col0)
+        positions = shifts - 1
+        _synchronize(torch, device)
+        for pack in packs:
+            pack.close()
+        extraction._trim_cache(extraction._thread_cache())
+    return features, columns, series, positions
 
 
 def _first_nan_kind(torch, x3, lengths, kinds):
