@@ -519,6 +519,59 @@ double tsfa_ks_outer_prob(int64_t m, int64_t n, int64_t g, int64_t h);
 int tsfa_impute(double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, int32_t device, double *col_max,
                 double *col_min, double *col_median, int32_t *finite_count);
 
+/* ---- selection on the device: p-value tails, FDR step-up, mask, gather (csrc/rel_tails.h) ----
+ * The chain impute -> relevance table -> selection for a matrix that stays in HBM: the statistics of tsfa_relevance_*
+ * are not copied out but turned into p-values where they are, the Benjamini-Hochberg / Benjamini-Yekutieli step-up runs
+ * on the p-value array, and the selected columns are gathered into another device matrix.  What comes back to the host is
+ * the count of host-route cells, the count of selected columns, and whatever the caller asks for.
+ *
+ * Every p-value cell has a route: who evaluates its tail (significance_tests.py mannwhitney_pvalue / fisher_exact_pvalue /
+ * kendall_pvalue restated in float64; Fisher by one wavefront per cell, the closed forms by one lane per cell).  The two
+ * HOST routes are left to the caller: the kernel writes NaN, counts the cell, and the caller overwrites p before
+ * tsfa_relevance_fdr -- the exact Mann-Whitney distribution (a class or its complement with <= 8 rows, no ties) and every
+ * Kolmogorov-Smirnov tail (with_ks, and two-valued columns under a real target). */
+enum tsfa_route {
+    TSFA_ROUTE_NONE = 0,           /* constant column: p = NaN */
+    TSFA_ROUTE_MWU_NORMAL = 1,
+    TSFA_ROUTE_FISHER = 2,
+    TSFA_ROUTE_KENDALL = 3,
+    TSFA_ROUTE_HOST_MWU_EXACT = 4,
+    TSFA_ROUTE_HOST_KS = 5
+};
+/* X, y_codes, n_classes as tsfa_relevance_classes; with_ks != 0 additionally runs the sweep of tsfa_relevance_classes_ks and
+ * routes every real cell to TSFA_ROUTE_HOST_KS.  Device outputs: p[n_cols * n_classes], route[n_cols * n_classes],
+ * type[n_cols] (0 constant, 1 binary, 2 real).  Optional host outputs (NULL: not copied): cols, rank_sums, hi_counts, ks_d
+ * (only with with_ks) as tsfa_relevance_classes_ks fills them, and n_host_cells, the number of HOST-route cells.
+ * Synchronous, on the null stream. */
+int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                 const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t device, double *p,
+                                 unsigned char *route, unsigned char *type, tsfa_relevance_col *cols, double *rank_sums,
+                                 int64_t *hi_counts, double *ks_d, int64_t *n_host_cells);
+/* The same for a real target (y_rank, y_perm, y_end as tsfa_relevance_real; ytie, y0, y1: the target's tied pairs,
+ * sum t(t-1)(t-2) and sum t(t-1)(2t+5) over its tie groups).  Device outputs p[n_cols], route[n_cols], type[n_cols]; optional
+ * host outputs cols[n_cols] and n_host_cells. */
+int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
+                              const int32_t *y_perm, const unsigned char *y_end, int64_t ytie, double y0, double y1,
+                              int32_t device, double *p, unsigned char *route, unsigned char *type,
+                              tsfa_relevance_real_col *cols, int64_t *n_host_cells);
+/* statsmodels' multipletests "fdr_bh" / "fdr_by" per table and relevance.py's combination of the tables.  All pointers are
+ * device pointers.  p[n_cols * n_tables] (n_tables <= 256: the classes, or 1), type[n_cols].  Per table the columns whose type
+ * is not 0 are tested (m of them); their p-values are sorted (NaN last, never rejected) and everything up to the largest
+ * sorted position k with  p_(k) <= ((k / (double)m) / c_m) * alpha  is rejected.  c_m: 1.0 for Benjamini-Hochberg,
+ * sum_{i=1..m} 1/i (as the caller's arithmetic adds it) for Benjamini-Yekutieli.
+ * Outputs: relevant_per_table[n_cols * n_tables], n_significant_out[n_cols] (tables that reject the column), p_min[n_cols]
+ * (smallest p-value over the tables, NaN when there is none), relevant[n_cols]: n_significant_out >= n_significant with
+ * multiclass != 0, n_significant_out > 0 otherwise.  Synchronous. */
+int tsfa_relevance_fdr(const double *p, const unsigned char *type, int64_t n_cols, int32_t n_tables, double alpha, double c_m,
+                       int32_t n_significant, int32_t multiclass, int32_t device, unsigned char *relevant_per_table,
+                       unsigned char *relevant, int32_t *n_significant_out, double *p_min);
+/* indices[0 .. *count) = the positions of the non-zero bytes of mask[n], ascending (mask and indices: device memory,
+ * indices has room for n entries and is written only up to *count; count: host). */
+int tsfa_compact_mask(const unsigned char *mask, int64_t n, int32_t *indices, int64_t *count, int32_t device);
+/* tsfa_gather_columns within HBM: out[r * ld_out + c] = X[r * ld + cols[c]], cols in device memory. */
+int tsfa_gather_columns_device(const double *X, int64_t n_rows, int64_t ld, const int32_t *cols, int64_t n_sel, double *out,
+                               int64_t ld_out, int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,12 @@ from tsfresh_amd.feature_extraction.settings import (  # noqa: F401
 )
 
 from tsfresh_amd.tensor import extract_features_tensor, extract_rolled_features_tensor  # noqa: F401,E402
+from tsfresh_amd.tensor_selection import (  # noqa: F401,E402
+    calculate_relevance_tensor,
+    extract_relevant_features_tensor,
+    impute_tensor,
+    select_features_tensor,
+)
 from tsfresh_amd.feature_selection import calculate_relevance_table, select_features  # noqa: F401,E402
 from tsfresh_amd.convenience import extract_relevant_features  # noqa: F401,E402
 

@@ -26,6 +26,9 @@ TSFA_PACK_UNSORTED, TSFA_PACK_VALUE_NAN, TSFA_PACK_IN_ORDER = 1, 2, 4
 TSFA_DENSE_BAD_LENGTH = 8
 TSFA_PACK_KEEP_SORT = 1
 TSFA_HOST, TSFA_DEVICE = 0, 1
+# enum tsfa_route: who evaluates the tail of a p-value cell (tsfa_relevance_tails_*)
+(TSFA_ROUTE_NONE, TSFA_ROUTE_MWU_NORMAL, TSFA_ROUTE_FISHER, TSFA_ROUTE_KENDALL, TSFA_ROUTE_HOST_MWU_EXACT,
+ TSFA_ROUTE_HOST_KS) = range(6)
 
 # every symbol include/tsfresh_amd.h declares
 EXPORTS = (
@@ -83,6 +86,11 @@ EXPORTS = (
     "tsfa_device_copy",
     "tsfa_gather_columns",
     "tsfa_scatter_columns",
+    "tsfa_relevance_tails_classes",
+    "tsfa_relevance_tails_real",
+    "tsfa_relevance_fdr",
+    "tsfa_compact_mask",
+    "tsfa_gather_columns_device",
 )
 
 
@@ -1207,13 +1215,7 @@ def relevance_real(X, y, device=0):
     if y.shape != (n,):
         raise ValueError("one target value per row")
     # the target is one vector: its dense ranks / sorted order are prepared here once for all columns
-    uniq, inverse = np.unique(y, return_inverse=True)
-    y_rank = np.ascontiguousarray(inverse, dtype=np.int32)
-    y_perm = np.ascontiguousarray(np.argsort(y, kind="stable"), dtype=np.int32)
-    ys = y[y_perm]
-    y_end = np.ones(n, dtype=np.uint8)
-    if n > 1:
-        y_end[:-1] = ys[1:] != ys[:-1]
+    y_rank, y_perm, y_end = target_order(y)
     cols = np.zeros(max(m, 1), dtype=_REAL_COL_DTYPE)
     lib.tsfa_relevance_real.restype = ctypes.c_int32
     lib.tsfa_relevance_real.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
@@ -1249,8 +1251,132 @@ def impute_matrix(X, device=0):
     return cmax, cmin, cmed, cnt
 
 
+def impute_ptr(x_ptr, n_rows, n_cols, ld, space, device=0):
+    """tsfa_impute in place on the float64 matrix at x_ptr (host or device memory by `space`), leading dimension ld."""
+    lib = load()
+    lib.tsfa_impute.restype = ctypes.c_int32
+    lib.tsfa_impute.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib, lib.tsfa_impute(ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), int(space), int(device), None, None,
+                                None, None))
+
+
 def ks_outer_prob(m, n, g, h):
     lib = load()
     lib.tsfa_ks_outer_prob.restype = ctypes.c_double
     lib.tsfa_ks_outer_prob.argtypes = [ctypes.c_int64] * 4
     return float(lib.tsfa_ks_outer_prob(int(m), int(n), int(g), int(h)))
+
+
+# ---- selection on the device (tsfa_relevance_tails_* / tsfa_relevance_fdr / tsfa_compact_mask / tsfa_gather_columns_device):
+# the matrix and every output are device pointers (ints, e.g. torch's `.data_ptr()`) owned by the caller ----
+
+def _bind_select_api(lib):
+    if getattr(lib, "_tsfa_select_api_bound", False):
+        return
+    i64, i32, f64, ptr = ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p
+    lib.tsfa_relevance_tails_classes.restype = i32
+    lib.tsfa_relevance_tails_classes.argtypes = [ptr, i64, i64, i64, i32, ptr, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr,
+                                                 ctypes.POINTER(i64)]
+    lib.tsfa_relevance_tails_real.restype = i32
+    lib.tsfa_relevance_tails_real.argtypes = [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i64, f64, f64, i32, ptr, ptr, ptr, ptr,
+                                              ctypes.POINTER(i64)]
+    lib.tsfa_relevance_fdr.restype = i32
+    lib.tsfa_relevance_fdr.argtypes = [ptr, ptr, i64, i32, f64, f64, i32, i32, i32, ptr, ptr, ptr, ptr]
+    lib.tsfa_compact_mask.restype = i32
+    lib.tsfa_compact_mask.argtypes = [ptr, i64, ptr, ctypes.POINTER(i64), i32]
+    lib.tsfa_gather_columns_device.restype = i32
+    lib.tsfa_gather_columns_device.argtypes = [ptr, i64, i64, ptr, i64, ptr, i64, i32]
+    lib._tsfa_select_api_bound = True
+
+
+def relevance_tails_classes(x_ptr, n_rows, n_cols, ld, y_codes, n_classes, p_ptr, route_ptr, type_ptr, device=0, with_ks=False,
+                            want_stats=False):
+    """The class tables of the device matrix at x_ptr, left on the device: p [m, C] float64, route [m, C] uint8, type [m]
+    uint8 -> (host-route cells, statistics).  statistics (want_stats): what `relevance_classes` returns, for the caller's
+    host routes; None otherwise (nothing but the cell count is copied)."""
+    lib = load()
+    _bind_select_api(lib)
+    y_codes = np.ascontiguousarray(y_codes, dtype=np.int32)
+    if y_codes.shape != (n_rows,):
+        raise ValueError("one class code per row")
+    n_host = ctypes.c_int64(0)
+    cols = rank_sums = hi_counts = ks_d = None
+    if want_stats:
+        cols = np.zeros(max(n_cols, 1), dtype=[("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("tie_term", "<f8")])
+        rank_sums = np.zeros((n_cols, n_classes), dtype=np.float64)
+        hi_counts = np.zeros((n_cols, n_classes), dtype=np.int64)
+        ks_d = np.zeros((n_cols, n_classes), dtype=np.float64) if with_ks else None
+    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    _check(lib, lib.tsfa_relevance_tails_classes(
+        ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_codes.ctypes.data_as(ctypes.c_void_p),
+        int(n_classes), int(bool(with_ks)), int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr),
+        ctypes.c_void_p(type_ptr), hp(cols), hp(rank_sums), hp(hi_counts), hp(ks_d), ctypes.byref(n_host)))
+    stats = None
+    if want_stats:
+        stats = (cols["n_unique"][:n_cols].copy(), cols["tie_term"][:n_cols].copy(), rank_sums, hi_counts, ks_d)
+    return int(n_host.value), stats
+
+
+def target_order(y):
+    """(dense ranks, ascending order, tie-group ends) of a real target: what tsfa_relevance_real takes."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    n = y.shape[0]
+    _, inverse = np.unique(y, return_inverse=True)
+    y_rank = np.ascontiguousarray(inverse, dtype=np.int32)
+    y_perm = np.ascontiguousarray(np.argsort(y, kind="stable"), dtype=np.int32)
+    ys = y[y_perm]
+    y_end = np.ones(n, dtype=np.uint8)
+    if n > 1:
+        y_end[:-1] = ys[1:] != ys[:-1]
+    return y_rank, y_perm, y_end
+
+
+def relevance_tails_real(x_ptr, n_rows, n_cols, ld, y, tie_statistics, p_ptr, route_ptr, type_ptr, device=0, want_stats=False):
+    """The table of a real target for the device matrix at x_ptr, left on the device: p [m], route [m], type [m] ->
+    (host-route cells, records).  tie_statistics: callable dense ranks -> (ytie, y0, y1).  records (want_stats): the
+    structured array `relevance_real` returns."""
+    lib = load()
+    _bind_select_api(lib)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.shape != (n_rows,):
+        raise ValueError("one target value per row")
+    y_rank, y_perm, y_end = target_order(y)
+    ytie, y0, y1 = tie_statistics(y_rank)
+    n_host = ctypes.c_int64(0)
+    cols = np.zeros(max(n_cols, 1), dtype=_REAL_COL_DTYPE) if want_stats else None
+    _check(lib, lib.tsfa_relevance_tails_real(
+        ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_rank.ctypes.data_as(ctypes.c_void_p),
+        y_perm.ctypes.data_as(ctypes.c_void_p), y_end.ctypes.data_as(ctypes.c_void_p), int(ytie), float(y0), float(y1),
+        int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr), ctypes.c_void_p(type_ptr),
+        None if cols is None else cols.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_host)))
+    return int(n_host.value), (None if cols is None else cols[:n_cols])
+
+
+def relevance_fdr(p_ptr, type_ptr, n_cols, n_tables, alpha, c_m, n_significant, multiclass, rel_table_ptr, relevant_ptr,
+                  n_significant_ptr, p_min_ptr, device=0):
+    """tsfa_relevance_fdr: the step-up per table and the combination of the tables, device arrays in and out."""
+    lib = load()
+    _bind_select_api(lib)
+    _check(lib, lib.tsfa_relevance_fdr(ctypes.c_void_p(p_ptr), ctypes.c_void_p(type_ptr), int(n_cols), int(n_tables), float(alpha),
+                                       float(c_m), int(n_significant), int(bool(multiclass)), int(device),
+                                       ctypes.c_void_p(rel_table_ptr), ctypes.c_void_p(relevant_ptr),
+                                       ctypes.c_void_p(n_significant_ptr), ctypes.c_void_p(p_min_ptr)))
+
+
+def compact_mask(mask_ptr, n, indices_ptr, device=0):
+    """tsfa_compact_mask: ascending int32 indices of the non-zero bytes of the device mask -> their count."""
+    lib = load()
+    _bind_select_api(lib)
+    count = ctypes.c_int64(0)
+    _check(lib, lib.tsfa_compact_mask(ctypes.c_void_p(mask_ptr), int(n), ctypes.c_void_p(indices_ptr), ctypes.byref(count),
+                                      int(device)))
+    return int(count.value)
+
+
+def gather_columns_device(x_ptr, n_rows, ld, cols_ptr, n_sel, out_ptr, ld_out, device=0):
+    """tsfa_gather_columns_device: out[r, c] = X[r, cols[c]] within HBM."""
+    lib = load()
+    _bind_select_api(lib)
+    _check(lib, lib.tsfa_gather_columns_device(ctypes.c_void_p(x_ptr), int(n_rows), int(ld), ctypes.c_void_p(cols_ptr), int(n_sel),
+                                               ctypes.c_void_p(out_ptr), int(ld_out), int(device)))

@@ -8,7 +8,8 @@
 // 4096-element tiles finished in LDS, only the strides >= 4096 as global passes), then ranks them (ties found by
 // binary search in the sorted column) and accumulates rank sums / counts per class with LDS atomics.  The sums are
 // exact (mid-ranks are multiples of 0.5, totals < 2^53), so the order of the atomics does not matter.
-// The p-value tails (O(1) per feature) are the host's: tsfresh_amd/feature_selection/significance_tests.py.
+// The p-value tails are the host's for the frame entry points (tsfresh_amd/feature_selection/significance_tests.py) and
+// device code for the tensor entry points (rel_tails.h, tsfa_relevance_tails_* below).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -18,8 +19,10 @@
 #include <vector>
 
 #include "../../include/tsfresh_amd.h"
+#include "rel_tails.h"
 
 int tsfa_fail(int code, const char *msg);  // tsfa_api.cpp: records the thread-local message, returns code
+static int rel_check_device(int32_t device, const char *who);
 
 #define REL_NT 1024
 #define REL_TILE 4096
@@ -420,10 +423,45 @@ extern "C" int tsfa_relevance_classes_ks(const double *X, int64_t n_rows, int64_
     return relevance_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, device, cols, rank_sums, hi_counts, ks_d);
 }
 
+// The device side of one statistics sweep: what the sweep allocates, and what it leaves in HBM for the caller -- the
+// host copies of tsfa_relevance_classes*, or the tails kernels of tsfa_relevance_tails_classes.
+struct RelClassesDev {
+    double *dX = nullptr, *dkeys = nullptr, *drs = nullptr, *dks = nullptr;
+    uint32_t *didx = nullptr;
+    int32_t *dy = nullptr;
+    int64_t *dhc = nullptr;
+    tsfa_relevance_col *dcols = nullptr;
+    void release() {
+        (void)hipFree(dX); (void)hipFree(dkeys); (void)hipFree(didx); (void)hipFree(dy); (void)hipFree(drs); (void)hipFree(dhc);
+        (void)hipFree(dcols); (void)hipFree(dks);
+        *this = RelClassesDev();
+    }
+};
+
+static int rel_classes_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_codes,
+                             int32_t n_classes, int32_t device, bool with_ks, RelClassesDev &d);
+
 static int relevance_classes_impl(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
                                   const int32_t *y_codes, int32_t n_classes, int32_t device, tsfa_relevance_col *cols,
                                   double *rank_sums, int64_t *hi_counts, double *ks_d) {
-    if (!X || !y_codes || !cols || !rank_sums || !hi_counts || n_rows < 1 || n_cols < 0 || ld < n_cols)
+    if (!cols || !rank_sums || !hi_counts) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_classes: null pointer or bad shape");
+    RelClassesDev d;
+    int rc = rel_classes_sweep(X, n_rows, n_cols, ld, space, y_codes, n_classes, device, ks_d != nullptr, d);
+    if (rc != TSFA_OK || n_cols == 0) { d.release(); return rc; }
+    REL_HIP(hipMemcpy(cols, d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_col), hipMemcpyDeviceToHost));
+    REL_HIP(hipMemcpy(rank_sums, d.drs, (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
+    REL_HIP(hipMemcpy(hi_counts, d.dhc, (size_t)n_cols * n_classes * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (ks_d) REL_HIP(hipMemcpy(ks_d, d.dks, (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
+done:
+    d.release();
+    return rc;
+}
+
+// validates, allocates and runs the sweep on the null stream; on return (any status) the caller releases `d`.  With
+// TSFA_OK and n_cols > 0 the kernels are queued (not waited for) and d.dcols / d.drs / d.dhc (/ d.dks) will hold the statistics.
+static int rel_classes_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_codes,
+                             int32_t n_classes, int32_t device, bool with_ks, RelClassesDev &d) {
+    if (!X || !y_codes || n_rows < 1 || n_cols < 0 || ld < n_cols)
         return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_classes: null pointer or bad shape");
     if (n_classes < 1 || n_classes > REL_MAXC) return tsfa_fail(TSFA_ERR_UNSUPPORTED, "tsfa_relevance_classes: 1 .. 256 classes");
     if (n_rows >= (1ll << 31)) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_relevance_classes: more than 2^31 rows");
@@ -438,11 +476,6 @@ static int relevance_classes_impl(const double *X, int64_t n_rows, int64_t n_col
     while (np2 < n_rows) np2 <<= 1;
     const int tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
     int64_t batch = rel_batch_columns(np2, n_cols);
-    double *dX = nullptr, *dkeys = nullptr, *drs = nullptr, *dks = nullptr;
-    uint32_t *didx = nullptr;
-    int32_t *dy = nullptr;
-    int64_t *dhc = nullptr;
-    tsfa_relevance_col *dcols = nullptr;
     const double *Xd = X;
     int64_t ldd = ld;   // leading dimension of the matrix the kernels work on (a host matrix is staged dense)
     REL_HIP(hipSetDevice(device));
@@ -451,45 +484,68 @@ static int relevance_classes_impl(const double *X, int64_t n_rows, int64_t n_col
     // read nor written back
     if (space == TSFA_HOST) {
         ldd = n_cols;
-        REL_HIP(hipMalloc((void **)&dX, (size_t)n_rows * n_cols * sizeof(double)));
-        REL_HIP(hipMemcpy2D(dX, (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
+        REL_HIP(hipMalloc((void **)&d.dX, (size_t)n_rows * n_cols * sizeof(double)));
+        REL_HIP(hipMemcpy2D(d.dX, (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
                             (size_t)n_rows, hipMemcpyHostToDevice));
-        Xd = dX;
+        Xd = d.dX;
     }
-    REL_HIP(hipMalloc((void **)&dkeys, (size_t)batch * np2 * sizeof(double)));
-    REL_HIP(hipMalloc((void **)&didx, (size_t)batch * np2 * sizeof(uint32_t)));
-    REL_HIP(hipMalloc((void **)&dy, (size_t)n_rows * sizeof(int32_t)));
-    REL_HIP(hipMalloc((void **)&drs, (size_t)n_cols * n_classes * sizeof(double)));
-    REL_HIP(hipMalloc((void **)&dhc, (size_t)n_cols * n_classes * sizeof(int64_t)));
-    REL_HIP(hipMalloc((void **)&dcols, (size_t)n_cols * sizeof(tsfa_relevance_col)));
-    if (ks_d) REL_HIP(hipMalloc((void **)&dks, (size_t)n_cols * n_classes * sizeof(double)));
-    REL_HIP(hipMemcpy(dy, y_codes, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    REL_HIP(hipMalloc((void **)&d.dkeys, (size_t)batch * np2 * sizeof(double)));
+    REL_HIP(hipMalloc((void **)&d.didx, (size_t)batch * np2 * sizeof(uint32_t)));
+    REL_HIP(hipMalloc((void **)&d.dy, (size_t)n_rows * sizeof(int32_t)));
+    REL_HIP(hipMalloc((void **)&d.drs, (size_t)n_cols * n_classes * sizeof(double)));
+    REL_HIP(hipMalloc((void **)&d.dhc, (size_t)n_cols * n_classes * sizeof(int64_t)));
+    REL_HIP(hipMalloc((void **)&d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_col)));
+    if (with_ks) REL_HIP(hipMalloc((void **)&d.dks, (size_t)n_cols * n_classes * sizeof(double)));
+    REL_HIP(hipMemcpy(d.dy, y_codes, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
     {
         const size_t lds = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
         REL_HIP(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         for (int64_t c0 = 0; c0 < n_cols; c0 += batch) {
             const int64_t nb = (n_cols - c0 < batch) ? (n_cols - c0) : batch;
-            k_rel_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, dkeys, didx, np2);
-            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(dkeys, didx, np2, tile);
-            k_rel_stats<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dkeys, didx, np2, n_rows, dy, n_classes, c0, dcols, drs, dhc);
-            if (ks_d) k_rel_ks_classes<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dkeys, didx, np2, n_rows, dy, n_classes, c0, dks);
+            k_rel_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, d.dkeys, d.didx, np2);
+            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(d.dkeys, d.didx, np2, tile);
+            k_rel_stats<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys, d.didx, np2, n_rows, d.dy, n_classes, c0, d.dcols, d.drs, d.dhc);
+            if (with_ks) k_rel_ks_classes<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys, d.didx, np2, n_rows, d.dy, n_classes, c0, d.dks);
             REL_HIP(hipGetLastError());
         }
     }
-    REL_HIP(hipMemcpy(cols, dcols, (size_t)n_cols * sizeof(tsfa_relevance_col), hipMemcpyDeviceToHost));
-    REL_HIP(hipMemcpy(rank_sums, drs, (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
-    REL_HIP(hipMemcpy(hi_counts, dhc, (size_t)n_cols * n_classes * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (ks_d) REL_HIP(hipMemcpy(ks_d, dks, (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
 done:
-    (void)hipFree(dX); (void)hipFree(dkeys); (void)hipFree(didx); (void)hipFree(dy); (void)hipFree(drs); (void)hipFree(dhc); (void)hipFree(dcols);
-    (void)hipFree(dks);
     return rc;
 }
+
+// The device side of tsfa_relevance_real's sweep, as RelClassesDev
+struct RelRealDev {
+    double *dX = nullptr, *dkeys = nullptr;
+    uint32_t *didx = nullptr;
+    int32_t *dyr = nullptr, *dyp = nullptr;
+    unsigned char *dye = nullptr;
+    tsfa_relevance_real_col *dcols = nullptr;
+    void release() {
+        (void)hipFree(dX); (void)hipFree(dkeys); (void)hipFree(didx); (void)hipFree(dyr); (void)hipFree(dyp); (void)hipFree(dye);
+        (void)hipFree(dcols);
+        *this = RelRealDev();
+    }
+};
+
+static int rel_real_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
+                          const int32_t *y_perm, const unsigned char *y_end, int32_t device, RelRealDev &d);
 
 extern "C" int tsfa_relevance_real(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
                                    const int32_t *y_rank, const int32_t *y_perm, const unsigned char *y_end, int32_t device,
                                    tsfa_relevance_real_col *cols) {
-    if (!X || !y_rank || !y_perm || !y_end || !cols || n_rows < 1 || n_cols < 0 || ld < n_cols)
+    if (!cols) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_real: null pointer or bad shape");
+    RelRealDev d;
+    int rc = rel_real_sweep(X, n_rows, n_cols, ld, space, y_rank, y_perm, y_end, device, d);
+    if (rc != TSFA_OK || n_cols == 0) { d.release(); return rc; }
+    REL_HIP(hipMemcpy(cols, d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_real_col), hipMemcpyDeviceToHost));
+done:
+    d.release();
+    return rc;
+}
+
+static int rel_real_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
+                          const int32_t *y_perm, const unsigned char *y_end, int32_t device, RelRealDev &d) {
+    if (!X || !y_rank || !y_perm || !y_end || n_rows < 1 || n_cols < 0 || ld < n_cols)
         return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_real: null pointer or bad shape");
     if (n_rows >= (1ll << 31)) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_relevance_real: more than 2^31 rows");
     int ndev = 0;
@@ -501,11 +557,6 @@ extern "C" int tsfa_relevance_real(const double *X, int64_t n_rows, int64_t n_co
     while (np2 < n_rows) np2 <<= 1;
     const int tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
     int64_t batch = rel_batch_columns(np2, n_cols);
-    double *dX = nullptr, *dkeys = nullptr;
-    uint32_t *didx = nullptr;
-    int32_t *dyr = nullptr, *dyp = nullptr;
-    unsigned char *dye = nullptr;
-    tsfa_relevance_real_col *dcols = nullptr;
     const double *Xd = X;
     int64_t ldd = ld;   // leading dimension of the matrix the kernels work on (a host matrix is staged dense)
     REL_HIP(hipSetDevice(device));
@@ -514,20 +565,20 @@ extern "C" int tsfa_relevance_real(const double *X, int64_t n_rows, int64_t n_co
     // read nor written back
     if (space == TSFA_HOST) {
         ldd = n_cols;
-        REL_HIP(hipMalloc((void **)&dX, (size_t)n_rows * n_cols * sizeof(double)));
-        REL_HIP(hipMemcpy2D(dX, (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
+        REL_HIP(hipMalloc((void **)&d.dX, (size_t)n_rows * n_cols * sizeof(double)));
+        REL_HIP(hipMemcpy2D(d.dX, (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
                             (size_t)n_rows, hipMemcpyHostToDevice));
-        Xd = dX;
+        Xd = d.dX;
     }
-    REL_HIP(hipMalloc((void **)&dkeys, (size_t)batch * np2 * sizeof(double)));
-    REL_HIP(hipMalloc((void **)&didx, (size_t)batch * np2 * sizeof(uint32_t)));
-    REL_HIP(hipMalloc((void **)&dyr, (size_t)n_rows * sizeof(int32_t)));
-    REL_HIP(hipMalloc((void **)&dyp, (size_t)n_rows * sizeof(int32_t)));
-    REL_HIP(hipMalloc((void **)&dye, (size_t)n_rows));
-    REL_HIP(hipMalloc((void **)&dcols, (size_t)n_cols * sizeof(tsfa_relevance_real_col)));
-    REL_HIP(hipMemcpy(dyr, y_rank, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
-    REL_HIP(hipMemcpy(dyp, y_perm, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
-    REL_HIP(hipMemcpy(dye, y_end, (size_t)n_rows, hipMemcpyHostToDevice));
+    REL_HIP(hipMalloc((void **)&d.dkeys, (size_t)batch * np2 * sizeof(double)));
+    REL_HIP(hipMalloc((void **)&d.didx, (size_t)batch * np2 * sizeof(uint32_t)));
+    REL_HIP(hipMalloc((void **)&d.dyr, (size_t)n_rows * sizeof(int32_t)));
+    REL_HIP(hipMalloc((void **)&d.dyp, (size_t)n_rows * sizeof(int32_t)));
+    REL_HIP(hipMalloc((void **)&d.dye, (size_t)n_rows));
+    REL_HIP(hipMalloc((void **)&d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_real_col)));
+    REL_HIP(hipMemcpy(d.dyr, y_rank, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    REL_HIP(hipMemcpy(d.dyp, y_perm, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    REL_HIP(hipMemcpy(d.dye, y_end, (size_t)n_rows, hipMemcpyHostToDevice));
     {
         const size_t lds_sort = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
         const size_t lds_inv = (size_t)tile * 2 * sizeof(uint32_t);
@@ -535,20 +586,272 @@ extern "C" int tsfa_relevance_real(const double *X, int64_t n_rows, int64_t n_co
         REL_HIP(hipFuncSetAttribute((const void *)k_rel_inversions, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
         for (int64_t c0 = 0; c0 < n_cols; c0 += batch) {
             const int64_t nb = (n_cols - c0 < batch) ? (n_cols - c0) : batch;
-            k_rel_stage_real<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, dyr, dkeys, didx, np2);
-            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds_sort, 0>>>(dkeys, didx, np2, tile);
-            k_rel_xties<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dkeys, didx, np2, n_rows, c0, dcols);
+            k_rel_stage_real<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, d.dyr, d.dkeys, d.didx, np2);
+            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds_sort, 0>>>(d.dkeys, d.didx, np2, tile);
+            k_rel_xties<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys, d.didx, np2, n_rows, c0, d.dcols);
             // the sorted values are dead now: their storage is the second buffer of the merge sort (np2 words per column
             // out of the np2 doubles)
-            k_rel_inversions<<<dim3((unsigned)nb), REL_NT, lds_inv, 0>>>(didx, (uint32_t *)dkeys, np2, tile, c0, dcols);
+            k_rel_inversions<<<dim3((unsigned)nb), REL_NT, lds_inv, 0>>>(d.didx, (uint32_t *)d.dkeys, np2, tile, c0, d.dcols);
             REL_HIP(hipGetLastError());
         }
-        k_rel_ks<<<dim3((unsigned)n_cols), REL_NT, 0, 0>>>(Xd, n_rows, ldd, dyp, dye, dcols);
+        k_rel_ks<<<dim3((unsigned)n_cols), REL_NT, 0, 0>>>(Xd, n_rows, ldd, d.dyp, d.dye, d.dcols);
         REL_HIP(hipGetLastError());
     }
-    REL_HIP(hipMemcpy(cols, dcols, (size_t)n_cols * sizeof(tsfa_relevance_real_col), hipMemcpyDeviceToHost));
 done:
-    (void)hipFree(dX); (void)hipFree(dkeys); (void)hipFree(didx); (void)hipFree(dyr); (void)hipFree(dyp); (void)hipFree(dye); (void)hipFree(dcols);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// p-value tails, FDR step-up, mask compaction and the device gather (rel_tails.h): the decision of the selection -- a
+// mask over the columns -- is taken where the statistics are, so the device-resident chain reads back the constant
+// columns' names and one count.  A wavefront serves a Fisher cell, a lane every closed-form cell; the two host routes
+// (exact Mann-Whitney, Kolmogorov-Smirnov) get NaN and are counted for the caller.
+// ---------------------------------------------------------------------------------------------------------------------
+#define RT_THREADS 256
+
+// closed forms and routes of the class tables: thread = cell (column, class); also the column types
+__global__ void __launch_bounds__(RT_THREADS) k_tails_classes(const tsfa_relevance_col *__restrict__ cols, const double *__restrict__ rank_sums,
+                                                              const int64_t *__restrict__ class_n, int64_t n_rows, int64_t n_cols,
+                                                              int n_classes, int with_ks, double *__restrict__ p,
+                                                              unsigned char *__restrict__ route, unsigned char *__restrict__ type,
+                                                              unsigned long long *__restrict__ n_host) {
+    const int64_t cell = (int64_t)blockIdx.x * RT_THREADS + threadIdx.x;
+    if (cell >= n_cols * n_classes) return;
+    if (rt_tails_classes_cell(cols, rank_sums, class_n, n_rows, n_classes, with_ks, cell, p, route, type)) atomicAdd(n_host, 1ull);
+}
+
+// Fisher cells: wavefront = cell; cells of other routes leave at once (wave-uniform)
+__global__ void __launch_bounds__(RT_THREADS) k_tails_fisher(const tsfa_relevance_col *__restrict__ cols, const int64_t *__restrict__ hi_counts,
+                                                             const int64_t *__restrict__ class_n, int64_t n_rows, int64_t n_cols,
+                                                             int n_classes, double *__restrict__ p) {
+    const int64_t cell = (int64_t)blockIdx.x * (RT_THREADS / 64) + (threadIdx.x >> 6);
+    if (cell >= n_cols * n_classes) return;
+    rt_tails_fisher_cell(cols, hi_counts, class_n, n_rows, n_classes, cell, p);
+}
+
+__global__ void __launch_bounds__(RT_THREADS) k_tails_real(const tsfa_relevance_real_col *__restrict__ cols, int64_t n_rows, int64_t n_cols,
+                                                           int64_t ytie, double y0, double y1, double *__restrict__ p,
+                                                           unsigned char *__restrict__ route, unsigned char *__restrict__ type,
+                                                           unsigned long long *__restrict__ n_host) {
+    const int64_t c = (int64_t)blockIdx.x * RT_THREADS + threadIdx.x;
+    if (c >= n_cols) return;
+    if (rt_tails_real_cell(cols, n_rows, ytie, y0, y1, c, p, route, type)) atomicAdd(n_host, 1ull);
+}
+
+extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                            const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t device, double *p,
+                                            unsigned char *route, unsigned char *type, tsfa_relevance_col *cols, double *rank_sums,
+                                            int64_t *hi_counts, double *ks_d, int64_t *n_host_cells) {
+    if (n_host_cells) *n_host_cells = 0;
+    if (n_cols > 0 && (!p || !route || !type)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: null output pointer");
+    if (ks_d && !with_ks) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: ks_d without with_ks");
+    RelClassesDev d;
+    int64_t *dcn = nullptr;
+    unsigned long long *dnh = nullptr, nh = 0ull;
+    std::vector<int64_t> class_n;
+    int rc = rel_classes_sweep(X, n_rows, n_cols, ld, space, y_codes, n_classes, device, with_ks != 0, d);
+    if (rc != TSFA_OK || n_cols == 0) { d.release(); return rc; }
+    class_n.assign((size_t)n_classes, 0);
+    for (int64_t r = 0; r < n_rows; ++r) ++class_n[(size_t)y_codes[r]];
+    REL_HIP(hipMalloc((void **)&dcn, (size_t)n_classes * sizeof(int64_t)));
+    REL_HIP(hipMalloc((void **)&dnh, sizeof(unsigned long long)));
+    REL_HIP(hipMemcpy(dcn, class_n.data(), (size_t)n_classes * sizeof(int64_t), hipMemcpyHostToDevice));
+    REL_HIP(hipMemset(dnh, 0, sizeof(unsigned long long)));
+    {
+        const int64_t cells = n_cols * n_classes;
+        k_tails_classes<<<dim3((unsigned)((cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(
+            d.dcols, d.drs, dcn, n_rows, n_cols, n_classes, with_ks, p, route, type, dnh);
+        REL_HIP(hipGetLastError());
+        k_tails_fisher<<<dim3((unsigned)((cells + RT_THREADS / 64 - 1) / (RT_THREADS / 64))), RT_THREADS, 0, 0>>>(
+            d.dcols, d.dhc, dcn, n_rows, n_cols, n_classes, p);
+        REL_HIP(hipGetLastError());
+    }
+    REL_HIP(hipMemcpy(&nh, dnh, sizeof(nh), hipMemcpyDeviceToHost));
+    if (n_host_cells) *n_host_cells = (int64_t)nh;
+    if (cols) REL_HIP(hipMemcpy(cols, d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_col), hipMemcpyDeviceToHost));
+    if (rank_sums) REL_HIP(hipMemcpy(rank_sums, d.drs, (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
+    if (hi_counts) REL_HIP(hipMemcpy(hi_counts, d.dhc, (size_t)n_cols * n_classes * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (ks_d) REL_HIP(hipMemcpy(ks_d, d.dks, (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
+done:
+    (void)hipFree(dcn); (void)hipFree(dnh);
+    d.release();
+    return rc;
+}
+
+extern "C" int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                         const int32_t *y_rank, const int32_t *y_perm, const unsigned char *y_end, int64_t ytie,
+                                         double y0, double y1, int32_t device, double *p, unsigned char *route, unsigned char *type,
+                                         tsfa_relevance_real_col *cols, int64_t *n_host_cells) {
+    if (n_host_cells) *n_host_cells = 0;
+    if (n_cols > 0 && (!p || !route || !type)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_real: null output pointer");
+    RelRealDev d;
+    unsigned long long *dnh = nullptr, nh = 0ull;
+    int rc = rel_real_sweep(X, n_rows, n_cols, ld, space, y_rank, y_perm, y_end, device, d);
+    if (rc != TSFA_OK || n_cols == 0) { d.release(); return rc; }
+    REL_HIP(hipMalloc((void **)&dnh, sizeof(unsigned long long)));
+    REL_HIP(hipMemset(dnh, 0, sizeof(unsigned long long)));
+    k_tails_real<<<dim3((unsigned)((n_cols + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(d.dcols, n_rows, n_cols, ytie, y0, y1, p,
+                                                                                              route, type, dnh);
+    REL_HIP(hipGetLastError());
+    REL_HIP(hipMemcpy(&nh, dnh, sizeof(nh), hipMemcpyDeviceToHost));
+    if (n_host_cells) *n_host_cells = (int64_t)nh;
+    if (cols) REL_HIP(hipMemcpy(cols, d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_real_col), hipMemcpyDeviceToHost));
+done:
+    (void)hipFree(dnh);
+    d.release();
+    return rc;
+}
+
+// masked sort keys of the p-value matrix (rt_fdr_key): what k_rel_stage / k_rel_sort then order, one key column per table
+__global__ void __launch_bounds__(RT_THREADS) k_fdr_keys(const double *__restrict__ p, const unsigned char *__restrict__ type, int64_t n_cols,
+                                                         int n_tables, double *__restrict__ keys) {
+    const int64_t cell = (int64_t)blockIdx.x * RT_THREADS + threadIdx.x;
+    if (cell >= n_cols * n_tables) return;
+    keys[cell] = rt_fdr_key(p[cell], type[cell / n_tables]);
+}
+
+// one workgroup per sorted key column (table t0 + blockIdx.x): m = the columns that are not constant, the largest sorted
+// position that meets its threshold, and the flag of every column of the table
+__global__ void __launch_bounds__(REL_NT) k_fdr_stepup(const double *__restrict__ keys, const uint32_t *__restrict__ idx, int64_t np2,
+                                                        const unsigned char *__restrict__ type, int64_t n_cols, int n_tables, int t0,
+                                                        double alpha, double c_m, unsigned char *__restrict__ rel_t) {
+    __shared__ unsigned long long s_m;
+    __shared__ long long s_last;
+    const double *K = keys + (int64_t)blockIdx.x * np2;
+    const uint32_t *I = idx + (int64_t)blockIdx.x * np2;
+    if (threadIdx.x == 0) { s_m = 0ull; s_last = -1ll; }
+    __syncthreads();
+    unsigned long long cnt = 0ull;
+    for (int64_t c = threadIdx.x; c < n_cols; c += REL_NT) cnt += (type[c] != 0) ? 1ull : 0ull;
+    atomicAdd(&s_m, cnt);
+    __syncthreads();
+    const int64_t m = (int64_t)s_m;
+    long long last = -1ll;
+    for (int64_t i = threadIdx.x; i < m; i += REL_NT)   // (positions m .. n_cols - 1 hold the constant columns' +inf)
+        if (K[i] <= rt_fdr_threshold(i + 1, m, c_m, alpha)) last = i;
+    atomicMax(&s_last, last);
+    __syncthreads();
+    last = s_last;
+    for (int64_t i = threadIdx.x; i < n_cols; i += REL_NT) rel_t[(int64_t)I[i] * n_tables + t0 + blockIdx.x] = (i <= last) ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(RT_THREADS) k_fdr_combine(const double *__restrict__ p, const unsigned char *__restrict__ rel_t,
+                                                            const unsigned char *__restrict__ type, int64_t n_cols, int n_tables,
+                                                            int multiclass, int n_significant, unsigned char *__restrict__ relevant,
+                                                            int32_t *__restrict__ n_sig, double *__restrict__ p_min) {
+    const int64_t c = (int64_t)blockIdx.x * RT_THREADS + threadIdx.x;
+    if (c >= n_cols) return;
+    rt_fdr_combine(p + c * n_tables, rel_t + c * n_tables, n_tables, type[c], multiclass, n_significant, relevant + c, n_sig + c, p_min + c);
+}
+
+extern "C" int tsfa_relevance_fdr(const double *p, const unsigned char *type, int64_t n_cols, int32_t n_tables, double alpha,
+                                  double c_m, int32_t n_significant, int32_t multiclass, int32_t device,
+                                  unsigned char *relevant_per_table, unsigned char *relevant, int32_t *n_significant_out,
+                                  double *p_min) {
+    if (n_cols < 0 || n_tables < 1 || n_tables > REL_MAXC || !(c_m > 0.0) ||
+        (n_cols > 0 && (!p || !type || !relevant_per_table || !relevant || !n_significant_out || !p_min)))
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_fdr: null pointer, bad shape, more than 256 tables or c_m <= 0");
+    if (n_cols >= (1ll << 31)) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_relevance_fdr: more than 2^31 columns");
+    int rc = rel_check_device(device, "tsfa_relevance_fdr");
+    if (rc || n_cols == 0) return rc;
+    int64_t np2 = 2048;
+    while (np2 < n_cols) np2 <<= 1;
+    const int tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
+    const int64_t batch = rel_batch_columns(np2, n_tables);
+    const int64_t cells = n_cols * n_tables;
+    double *dmask = nullptr, *dkeys = nullptr;
+    uint32_t *didx = nullptr;
+    REL_HIP(hipSetDevice(device));
+    REL_HIP(hipMalloc((void **)&dmask, (size_t)cells * sizeof(double)));
+    REL_HIP(hipMalloc((void **)&dkeys, (size_t)batch * np2 * sizeof(double)));
+    REL_HIP(hipMalloc((void **)&didx, (size_t)batch * np2 * sizeof(uint32_t)));
+    {
+        const size_t lds = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
+        REL_HIP(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k_fdr_keys<<<dim3((unsigned)((cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(p, type, n_cols, n_tables, dmask);
+        REL_HIP(hipGetLastError());
+        for (int64_t t0 = 0; t0 < n_tables; t0 += batch) {
+            const int64_t nb = (n_tables - t0 < batch) ? (n_tables - t0) : batch;
+            // the key matrix is [n_cols, n_tables]: a table is a column of it, its rows are the feature columns
+            k_rel_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dmask, n_cols, n_tables, t0, dkeys, didx, np2);
+            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(dkeys, didx, np2, tile);
+            k_fdr_stepup<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dkeys, didx, np2, type, n_cols, n_tables, (int)t0, alpha, c_m,
+                                                              relevant_per_table);
+            REL_HIP(hipGetLastError());
+        }
+        k_fdr_combine<<<dim3((unsigned)((n_cols + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(
+            p, relevant_per_table, type, n_cols, n_tables, multiclass, n_significant, relevant, n_significant_out, p_min);
+        REL_HIP(hipGetLastError());
+    }
+    REL_HIP(hipDeviceSynchronize());
+done:
+    (void)hipFree(dmask); (void)hipFree(dkeys); (void)hipFree(didx);
+    return rc;
+}
+
+// one workgroup: slice counts, their exclusive scan (thread 0, as the KS kernels above), the writes
+__global__ void __launch_bounds__(REL_NT) k_compact_mask(const unsigned char *__restrict__ mask, int64_t n, int32_t *__restrict__ indices,
+                                                          long long *__restrict__ count) {
+    __shared__ int32_t s_cnt[REL_NT];
+    s_cnt[threadIdx.x] = rt_compact_count(mask, n, (int)threadIdx.x, REL_NT);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t acc = 0;
+        for (int t = 0; t < REL_NT; ++t) { const int32_t v = s_cnt[t]; s_cnt[t] = acc; acc += v; }
+        *count = acc;
+    }
+    __syncthreads();
+    rt_compact_write(mask, n, (int)threadIdx.x, REL_NT, s_cnt[threadIdx.x], indices);
+}
+
+extern "C" int tsfa_compact_mask(const unsigned char *mask, int64_t n, int32_t *indices, int64_t *count, int32_t device) {
+    if (!count || n < 0 || (n > 0 && (!mask || !indices))) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_compact_mask: null pointer or bad shape");
+    *count = 0;
+    if (n >= (1ll << 31)) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_compact_mask: more than 2^31 entries");
+    int rc = rel_check_device(device, "tsfa_compact_mask");
+    if (rc || n == 0) return rc;
+    long long *dcount = nullptr, got = 0;
+    REL_HIP(hipSetDevice(device));
+    REL_HIP(hipMalloc((void **)&dcount, sizeof(long long)));
+    k_compact_mask<<<1, REL_NT, 0, 0>>>(mask, n, indices, dcount);
+    REL_HIP(hipGetLastError());
+    REL_HIP(hipMemcpy(&got, dcount, sizeof(got), hipMemcpyDeviceToHost));
+    *count = (int64_t)got;
+done:
+    (void)hipFree(dcount);
+    return rc;
+}
+
+// k_gather_columns with the indices read from HBM, a leading dimension of the destination, and a flag for an index
+// outside [0, ld) (nothing is read or written for it)
+__global__ void __launch_bounds__(256) k_gather_columns_device(const double *__restrict__ X, int64_t n_rows, int64_t ld,
+                                                                const int32_t *__restrict__ cols, int64_t n_sel,
+                                                                double *__restrict__ out, int64_t ld_out, int *__restrict__ bad) {
+    const int64_t total = n_rows * n_sel;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / n_sel, c = i - r * n_sel;
+        const int32_t src = cols[c];
+        if (src < 0 || src >= ld) { *bad = 1; continue; }
+        out[r * ld_out + c] = X[r * ld + src];
+    }
+}
+
+extern "C" int tsfa_gather_columns_device(const double *X, int64_t n_rows, int64_t ld, const int32_t *cols, int64_t n_sel,
+                                          double *out, int64_t ld_out, int32_t device) {
+    if (n_rows < 0 || n_sel < 0 || ld_out < n_sel || ((n_rows && n_sel) && (!X || !cols || !out)))
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_gather_columns_device: null pointer or bad shape");
+    int rc = rel_check_device(device, "tsfa_gather_columns_device");
+    if (rc || n_rows == 0 || n_sel == 0) return rc;
+    int *dbad = nullptr, bad = 0;
+    REL_HIP(hipSetDevice(device));
+    REL_HIP(hipMalloc((void **)&dbad, sizeof(int)));
+    REL_HIP(hipMemset(dbad, 0, sizeof(int)));
+    k_gather_columns_device<<<2048, 256, 0, 0>>>(X, n_rows, ld, cols, n_sel, out, ld_out, dbad);
+    REL_HIP(hipGetLastError());
+    REL_HIP(hipMemcpy(&bad, dbad, sizeof(int), hipMemcpyDeviceToHost));
+    if (bad) rc = tsfa_fail(TSFA_ERR_INVALID, "tsfa_gather_columns_device: column index out of range");
+done:
+    (void)hipFree(dbad);
     return rc;
 }
 
