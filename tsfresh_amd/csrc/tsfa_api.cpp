@@ -7,10 +7,12 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/tsfresh_amd.h"
+#include "tsfa_devmem.h"
 #include "tsfa_host_tables.h"
 #include "tsfa_launch.h"
 #include "fam_seq.h"
@@ -23,43 +25,8 @@ static int fail(int code, const std::string &msg) {
     return code;
 }
 
-// for the other translation units of the library (tsfa_relevance.hip)
+// for the other translation units of the library and the macros of tsfa_devmem.h
 int tsfa_fail(int code, const char *msg) { return fail(code, std::string(msg ? msg : "")); }
-#define HIP_TRY(expr)                                                                                    \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return fail(TSFA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return 0;
-        // the larger buffer first: a failed request leaves the old one (and its contents' owner) intact, and the
-        // out-of-memory error is taken off the thread -- callers with a fallback (chirp-z scratch -> Goertzel sweep) go on
-        // to launch kernels, whose launch check reads hipGetLastError (round-5 ADVICE)
-        size_t want = bytes + bytes / 8 + 4096;
-        void *q = nullptr;
-        if (hipMalloc(&q, want) != hipSuccess) {
-            (void)hipGetLastError();
-            if (p) { (void)hipFree(p); p = nullptr; cap = 0; }   // second try with the old buffer's bytes returned
-            if (hipMalloc(&q, want) != hipSuccess) {
-                (void)hipGetLastError();
-                return -1;
-            }
-        }
-        if (p) (void)hipFree(p);
-        p = q;
-        cap = want;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 #define TSFA_MAX_AUX 3
 #define TSFA_MAX_CHUNKS 16
@@ -67,8 +34,16 @@ struct DevBuf {
 
 struct Timing {
     std::string name;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;   // owned: a slot that plan->timings.resize() trims destroys its events
     float ms = 0.f;
+    Timing() = default;
+    // move construction is all std::vector::resize needs; there is no copy and no assignment on purpose, so that code
+    // which would duplicate or overwrite the handles does not compile
+    Timing(Timing &&o) noexcept : name(std::move(o.name)), e0(o.e0), e1(o.e1), ms(o.ms) { o.e0 = o.e1 = nullptr; }
+    ~Timing() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
 };
 
 // Launch options of a plan (tsfa_plan_set_option): each names an alternative ROUTE to the same numbers -- every one has a test
@@ -111,21 +86,24 @@ struct tsfa_plan {
     hipStream_t stream = nullptr;
     int n_cols = 0;
     std::vector<TsfaSpec> fam_specs[TSFA_N_FAMILIES];  // CWT slot: number_cwt_peaks specs only
-    TsfaSpec *d_specs[TSFA_N_FAMILIES] = {nullptr};
+    // Device memory is held by owners (tsfa_devmem.h) that go with the plan; the streams and events below are released by
+    // ~tsfa_plan, which also makes `device` current before any member is freed.
+    DevPtr<TsfaSpec> d_specs[TSFA_N_FAMILIES];
     TsfaFamHints hints[TSFA_N_FAMILIES];
     TsfaCwtBank bank;  // cwt_coefficients
-    double *d_W = nullptr;
-    int *d_cols = nullptr, *d_coeff = nullptr;
-    double *d_dectab = nullptr, *d_twc = nullptr, *d_tws = nullptr, *d_consts = nullptr;
-    long long *d_stats = nullptr;
+    DevPtr<double> d_W;
+    DevPtr<int> d_cols, d_coeff;
+    DevPtr<double> d_dectab, d_twc, d_tws, d_consts;
+    DevPtr<long long> d_stats;
+    // (long_scratch: the HBM slots of every long-series family, k_mprofile's among them)
     DevBuf values, offsets, out, gscratch, times, deg_list, sel, long_scratch, pf_buf, perm_buf, stats_buf, dd_scratch, gen_scratch, seq_rows;
     // k_general (fam_general.h): the columns of the calculators whose parameters lie beyond the tuned kernels' tables
     std::vector<TsfaSpec> gen_specs;
-    TsfaSpec *d_gen_specs = nullptr;
+    DevPtr<TsfaSpec> d_gen_specs;
     TsfaGenPlan gen_plan;
-    double *d_pool = nullptr;                   // array-valued parameters (tsfa_plan_create_with_data): query_similarity_count's queries
-    int *d_deg_count = nullptr;
-    int *d_cursor = nullptr;                    // per-launch-group fill cursors (k_class_fill)
+    DevPtr<double> d_pool;                      // array-valued parameters (tsfa_plan_create_with_data): query_similarity_count's queries
+    DevPtr<int> d_deg_count;
+    DevPtr<int> d_cursor;                       // per-launch-group fill cursors (k_class_fill)
     hipStream_t s_in = nullptr, s_out = nullptr;  // copy-in / copy-out streams of the host pipeline
     hipEvent_t ev_in[TSFA_MAX_CHUNKS] = {nullptr}, ev_k[TSFA_MAX_CHUNKS] = {nullptr};
     std::vector<int64_t> h_rel;                 // offsets relative to the staged span
@@ -158,16 +136,32 @@ struct tsfa_plan {
     hipEvent_t ev_side_fork = nullptr, ev_side_join = nullptr;
     unsigned side_mask = 0;              // bit f: family f runs on the side lane
     double fill_value = __builtin_nan("");   // TSFA_DEBUG_FILL=<value>: a sentinel instead (profiles/fill_audit.py)
+
+    // the body runs before the members' destructors: everything the plan owns is freed on its own device
+    ~tsfa_plan() {
+        // `stream` is the first thing a create makes: without it nothing else exists, and a create that was refused on its
+        // arguments leaves the caller's current device alone
+        if (!stream) return;
+        (void)hipSetDevice(device);
+        auto drop_event = [](hipEvent_t e) { if (e) (void)hipEventDestroy(e); };
+        auto drop_stream = [](hipStream_t s) { if (s) (void)hipStreamDestroy(s); };
+        for (hipEvent_t e : ev_in) drop_event(e);
+        for (hipEvent_t e : ev_k) drop_event(e);
+        for (hipEvent_t e : ev_join) drop_event(e);
+        for (hipEvent_t e : {ev_fork, ev_side_fork, ev_side_join}) drop_event(e);
+        for (hipStream_t s : aux) drop_stream(s);
+        for (hipStream_t s : {s_in, s_out, side, stream}) drop_stream(s);
+    }
 };
 
 static const char *fam_names[TSFA_N_FAMILIES] = {"k_basic", "k_sort", "k_spectral", "k_ar", "k_entropy", "k_cwtpeaks", "k_seq", "k_trend", "k_mprofile"};
 
 template <class T>
-static int upload(const std::vector<T> &h, T **d) {
-    *d = nullptr;
+static int upload(const std::vector<T> &h, DevPtr<T> &d) {
+    d.reset();
     if (h.empty()) return 0;
-    if (hipMalloc((void **)d, h.size() * sizeof(T)) != hipSuccess) return -1;
-    if (hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (d.alloc(h.size() * sizeof(T)) != hipSuccess) return -1;
+    if (hipMemcpy(d.get(), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return -1;
     return 0;
 }
 
@@ -204,56 +198,7 @@ const char *tsfa_calc_name(int calc) { return (calc >= 0 && calc < TSFA_N_CALCS)
 int tsfa_calc_count(void) { return TSFA_N_CALCS; }
 
 void tsfa_plan_destroy(tsfa_plan *plan) {
-    if (!plan) return;
-    (void)hipSetDevice(plan->device);
-    for (int f = 0; f < TSFA_N_FAMILIES; ++f)
-        if (plan->d_specs[f]) (void)hipFree(plan->d_specs[f]);
-    if (plan->d_W) (void)hipFree(plan->d_W);
-    if (plan->d_cols) (void)hipFree(plan->d_cols);
-    if (plan->d_coeff) (void)hipFree(plan->d_coeff);
-    if (plan->d_dectab) (void)hipFree(plan->d_dectab);
-    if (plan->d_twc) (void)hipFree(plan->d_twc);
-    if (plan->d_tws) (void)hipFree(plan->d_tws);
-    if (plan->d_consts) (void)hipFree(plan->d_consts);
-    if (plan->d_stats) (void)hipFree(plan->d_stats);
-    if (plan->d_deg_count) (void)hipFree(plan->d_deg_count);
-    if (plan->d_cursor) (void)hipFree(plan->d_cursor);
-    plan->deg_list.release();
-    plan->pf_buf.release();
-    plan->stats_buf.release();
-    plan->perm_buf.release();
-    plan->sel.release();
-    plan->long_scratch.release();   // (the HBM slots of every long-series family, k_mprofile's among them)
-    plan->seq_rows.release();
-    for (int i = 0; i < TSFA_MAX_CHUNKS; ++i) {
-        if (plan->ev_in[i]) (void)hipEventDestroy(plan->ev_in[i]);
-        if (plan->ev_k[i]) (void)hipEventDestroy(plan->ev_k[i]);
-    }
-    if (plan->s_in) (void)hipStreamDestroy(plan->s_in);
-    if (plan->s_out) (void)hipStreamDestroy(plan->s_out);
-    plan->times.release();
-    plan->values.release();
-    plan->offsets.release();
-    plan->out.release();
-    plan->gscratch.release();
-    plan->dd_scratch.release();
-    plan->gen_scratch.release();
-    if (plan->d_gen_specs) (void)hipFree(plan->d_gen_specs);
-    if (plan->d_pool) (void)hipFree(plan->d_pool);
-    for (auto &t : plan->timings) {
-        if (t.e0) (void)hipEventDestroy(t.e0);
-        if (t.e1) (void)hipEventDestroy(t.e1);
-    }
-    for (int i = 0; i < TSFA_MAX_AUX; ++i) {
-        if (plan->aux[i]) (void)hipStreamDestroy(plan->aux[i]);
-        if (plan->ev_join[i]) (void)hipEventDestroy(plan->ev_join[i]);
-    }
-    if (plan->ev_fork) (void)hipEventDestroy(plan->ev_fork);
-    if (plan->side) (void)hipStreamDestroy(plan->side);
-    if (plan->ev_side_fork) (void)hipEventDestroy(plan->ev_side_fork);
-    if (plan->ev_side_join) (void)hipEventDestroy(plan->ev_side_join);
-    if (plan->stream) (void)hipStreamDestroy(plan->stream);
-    delete plan;
+    if (plan) delete plan;   // ~tsfa_plan and the members' owners release everything
 }
 
 int tsfa_plan_create(const tsfa_feature_spec *specs, int32_t n_specs, int32_t device, tsfa_plan **out_plan) {
@@ -270,7 +215,7 @@ int tsfa_plan_create_with_data(const tsfa_feature_spec *specs, int32_t n_specs, 
     if (ndev <= 0) return fail(TSFA_ERR_NO_DEVICE, "no HIP device visible: tsfresh_amd has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(TSFA_ERR_INVALID, "device ordinal out of range");
 
-    tsfa_plan *plan = new tsfa_plan();
+    std::unique_ptr<tsfa_plan> plan(new tsfa_plan());   // goes with any early return below
     plan->device = device;
     plan->n_cols = n_specs;
     std::vector<TsfaSpec> cwt_coef;
@@ -281,49 +226,31 @@ int tsfa_plan_create_with_data(const tsfa_feature_spec *specs, int32_t n_specs, 
         s.calc = specs[i].calc;
         s.col = i;
         for (int k = 0; k < 4; ++k) s.p[k] = specs[i].p[k];
-        if (s.calc < 0 || s.calc >= TSFA_N_CALCS) {
-            delete plan;
+        if (s.calc < 0 || s.calc >= TSFA_N_CALCS)
             return fail(TSFA_ERR_UNSUPPORTED, "spec " + std::to_string(i) + ": unknown calculator id " + std::to_string(s.calc));
-        }
         const std::string why = tsfa_validate_spec(s);
-        if (!why.empty()) {
-            delete plan;
+        if (!why.empty())
             return fail(TSFA_ERR_UNSUPPORTED, std::string("spec ") + std::to_string(i) + " (" + tsfa_calc_table[s.calc].name + "): " + why);
-        }
-        if (s.calc == TSFA_C_QUERY_SIMILARITY_COUNT && s.p[3] > 0 && !(s.p[2] + s.p[3] <= (double)n_data)) {
-            delete plan;
+        if (s.calc == TSFA_C_QUERY_SIMILARITY_COUNT && s.p[3] > 0 && !(s.p[2] + s.p[3] <= (double)n_data))
             return fail(TSFA_ERR_INVALID, "spec " + std::to_string(i) + " (query_similarity_count): the query lies outside the data pool");
-        }
         if (s.calc == TSFA_C_LINEAR_TREND_TIMEWISE) plan->needs_times = true;
         if (s.calc == TSFA_C_CWT_COEFFICIENTS) cwt_coef.push_back(s);
         else if (general[s.calc]) plan->gen_specs.push_back(s);
         else plan->fam_specs[tsfa_calc_table[s.calc].family].push_back(s);
     }
     plan->gen_plan = tsfa_prepare_general(plan->gen_specs);
-    if (cwt_coef.size() > 128) {
-        delete plan;
-        return fail(TSFA_ERR_UNSUPPORTED, "more than 128 cwt_coefficients columns in one plan");
-    }
+    if (cwt_coef.size() > 128) return fail(TSFA_ERR_UNSUPPORTED, "more than 128 cwt_coefficients columns in one plan");
     {
         std::vector<TsfaSpec> all;
         for (int f = 0; f < TSFA_N_FAMILIES; ++f) all.insert(all.end(), plan->fam_specs[f].begin(), plan->fam_specs[f].end());
         const std::string why = tsfa_validate_plan(all.data(), (int)all.size());
-        if (!why.empty()) {
-            delete plan;
-            return fail(TSFA_ERR_UNSUPPORTED, why);
-        }
+        if (!why.empty()) return fail(TSFA_ERR_UNSUPPORTED, why);
     }
     if (!cwt_coef.empty()) {
         const std::string why = plan->bank.build(cwt_coef);
-        if (!why.empty()) {
-            delete plan;
-            return fail(TSFA_ERR_UNSUPPORTED, why);
-        }
+        if (!why.empty()) return fail(TSFA_ERR_UNSUPPORTED, why);
     }
-    if (hipSetDevice(device) != hipSuccess) {
-        delete plan;
-        return fail(TSFA_ERR_HIP, "hipSetDevice failed");
-    }
+    if (hipSetDevice(device) != hipSuccess) return fail(TSFA_ERR_HIP, "hipSetDevice failed");
     for (int f = 0; f < TSFA_N_FAMILIES; ++f) tsfa_prepare_family(f, plan->fam_specs[f], plan->hints[f]);
     plan->sort_only_order_stats = !plan->fam_specs[TSFA_FAM_SORT].empty();
     for (const auto &sp : plan->fam_specs[TSFA_FAM_SORT])
@@ -335,25 +262,25 @@ int tsfa_plan_create_with_data(const tsfa_feature_spec *specs, int32_t n_specs, 
     for (const auto &sp : plan->fam_specs[TSFA_FAM_SORT])
         if (sp.calc != TSFA_C_MEDIAN) plan->stream_ok = false;
     bool ok = hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking) == hipSuccess;
-    for (int f = 0; ok && f < TSFA_N_FAMILIES; ++f) ok = upload(plan->fam_specs[f], &plan->d_specs[f]) == 0;
-    if (ok) ok = upload(plan->gen_specs, &plan->d_gen_specs) == 0;
-    if (ok && n_data > 0) ok = upload(std::vector<double>(data, data + n_data), &plan->d_pool) == 0;
+    for (int f = 0; ok && f < TSFA_N_FAMILIES; ++f) ok = upload(plan->fam_specs[f], plan->d_specs[f]) == 0;
+    if (ok) ok = upload(plan->gen_specs, plan->d_gen_specs) == 0;
+    if (ok && n_data > 0) ok = upload(std::vector<double>(data, data + n_data), plan->d_pool) == 0;
     if (ok && !cwt_coef.empty()) {
-        ok = upload(plan->bank.W, &plan->d_W) == 0 && upload(plan->bank.cols, &plan->d_cols) == 0 &&
-             upload(plan->bank.coeff_idx, &plan->d_coeff) == 0;
+        ok = upload(plan->bank.W, plan->d_W) == 0 && upload(plan->bank.cols, plan->d_cols) == 0 &&
+             upload(plan->bank.coeff_idx, plan->d_coeff) == 0;
     }
     if (ok) {
         std::vector<double> dt, twc, tws;
         tsfa_build_dectab(dt);
         tsfa_build_twiddles(twc, tws);
-        ok = upload(dt, &plan->d_dectab) == 0 && upload(twc, &plan->d_twc) == 0 && upload(tws, &plan->d_tws) == 0;
+        ok = upload(dt, plan->d_dectab) == 0 && upload(twc, plan->d_twc) == 0 && upload(tws, plan->d_tws) == 0;
         std::vector<double> consts;
         tsfa_build_consts(consts);
-        ok = ok && upload(consts, &plan->d_consts) == 0;
+        ok = ok && upload(consts, plan->d_consts) == 0;
     }
-    if (ok) ok = hipMalloc((void **)&plan->d_stats, TSFA_LEN_STATS * sizeof(long long)) == hipSuccess;
-    if (ok) ok = hipMalloc((void **)&plan->d_deg_count, 2 * sizeof(int)) == hipSuccess;   // [k_ar_degenerate, k_langevin_dd]
-    if (ok) ok = hipMalloc((void **)&plan->d_cursor, TSFA_N_LEN_CLASSES * sizeof(int)) == hipSuccess;
+    if (ok) ok = plan->d_stats.alloc(TSFA_LEN_STATS * sizeof(long long)) == hipSuccess;
+    if (ok) ok = plan->d_deg_count.alloc(2 * sizeof(int)) == hipSuccess;   // [k_ar_degenerate, k_langevin_dd]
+    if (ok) ok = plan->d_cursor.alloc(TSFA_N_LEN_CLASSES * sizeof(int)) == hipSuccess;
     if (ok) ok = hipStreamCreateWithFlags(&plan->s_in, hipStreamNonBlocking) == hipSuccess &&
                  hipStreamCreateWithFlags(&plan->s_out, hipStreamNonBlocking) == hipSuccess;
     for (int i = 0; ok && i < TSFA_MAX_CHUNKS; ++i)
@@ -380,11 +307,8 @@ int tsfa_plan_create_with_data(const tsfa_feature_spec *specs, int32_t n_specs, 
         }
     }
     if (const char *e = getenv("TSFA_HOST_CHUNKS")) plan->opt.host_chunks = std::max(atoi(e), 0);
-    if (!ok) {
-        tsfa_plan_destroy(plan);
-        return fail(TSFA_ERR_HIP, "device allocation/upload failed while creating the plan");
-    }
-    *out_plan = plan;
+    if (!ok) return fail(TSFA_ERR_HIP, "device allocation/upload failed while creating the plan");
+    *out_plan = plan.release();
     return TSFA_OK;
 }
 
@@ -653,7 +577,7 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
             a.ends = d_ends;
             a.n_series = sh.g_count[g];
             a.sel = (sh.n_groups > 1) ? d_sel + sh.map.base[g] : nullptr;
-            a.specs = plan->d_specs[f];
+            a.specs = plan->d_specs[f].get();
             a.nspecs = (int)plan->fam_specs[f].size();
             a.out = d_out;
             a.ld = ld;
@@ -687,11 +611,11 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
             }
             if (TSFA_LAB_ONLY(plan->opt.nt[f] >= 64)) a.nt = plan->opt.nt[f];   // lab build: workgroup size of a family
             a.stream = fst;
-            a.dectab = plan->d_dectab;
+            a.dectab = plan->d_dectab.get();
             a.times = d_times;
-            a.twc = plan->d_twc;
-            a.consts = plan->d_consts;
-            a.tws = plan->d_tws;
+            a.twc = plan->d_twc.get();
+            a.consts = plan->d_consts.get();
+            a.tws = plan->d_tws.get();
             a.hint_a = plan->hints[f].a;
             a.hint_b = plan->hints[f].b;
             a.hint_c = plan->hints[f].c;
@@ -776,13 +700,13 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                     }
                 }
                 a.deg_list = (long long *)plan->deg_list.p;
-                a.deg_count = plan->d_deg_count;
-                HIP_TRY(hipMemsetAsync(plan->d_deg_count, 0, sizeof(int), fst));
+                a.deg_count = plan->d_deg_count.get();
+                HIP_TRY(hipMemsetAsync(plan->d_deg_count.get(), 0, sizeof(int), fst));
             } else if (f == TSFA_FAM_SORT && plan->hints[f].b > 0) {
                 // Langevin fits: ill-conditioned ones are recorded for the double-double pass (fam_langevin_dd.h)
                 a.pf_slot = tsfa_pf_slot_doubles(plan->hints[f].b);
                 a.pf_buf = (double *)plan->pf_buf.p;
-                a.pf_count = plan->d_deg_count + 1;
+                a.pf_count = plan->d_deg_count.get() + 1;
                 a.pf_cap = (int)std::min<long long>((long long)n_series * std::max(1, plan->hints[f].e), 2147483647LL);
                 HIP_TRY(hipMemsetAsync(a.pf_count, 0, sizeof(int), fst));
             } else if (f == TSFA_FAM_ENTROPY) {
@@ -982,9 +906,9 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
             if (plan->stream_ok && (f == TSFA_FAM_SORT || f == TSFA_FAM_BASIC) && maxn <= 2048 && g <= TSFA_N_LEN_CLASSES) {
                 if (stream_done[g]) continue;   // BASIC's turn after the SORT family's launch served both
                 TsfaLaunch sa = a;
-                sa.specs = plan->d_specs[TSFA_FAM_SORT];
+                sa.specs = plan->d_specs[TSFA_FAM_SORT].get();
                 sa.nspecs = (int)plan->fam_specs[TSFA_FAM_SORT].size();
-                sa.bspecs = plan->d_specs[TSFA_FAM_BASIC];
+                sa.bspecs = plan->d_specs[TSFA_FAM_BASIC].get();
                 sa.nbspecs = (int)plan->fam_specs[TSFA_FAM_BASIC].size();
                 rc = tsfa_launch_stream(sa);
                 stream_done[g] = true;
@@ -1052,11 +976,11 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
         c.starts = d_starts;
         c.ends = d_ends;
         c.n_series = n_series;
-        c.W = plan->d_W;
+        c.W = plan->d_W.get();
         c.S4 = plan->bank.S4;
         c.C = plan->bank.C;
-        c.cols = plan->d_cols;
-        c.coeff_idx = plan->d_coeff;
+        c.cols = plan->d_cols.get();
+        c.coeff_idx = plan->d_coeff.get();
         c.out = d_out;
         c.ld = ld;
         c.stream = st;
@@ -1084,14 +1008,14 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
         a.starts = d_starts;
         a.ends = d_ends;
         a.n_series = n_series;
-        a.specs = plan->d_gen_specs;
+        a.specs = plan->d_gen_specs.get();
         a.nspecs = (int)plan->gen_specs.size();
         a.out = d_out;
         a.ld = ld;
         a.maxn = maxn;
         a.stream = st;
         if (record(plan, st, slot, "k_general", true)) return fail(TSFA_ERR_HIP, "event record failed");
-        if (tsfa_launch_general(a, plan->gen_plan, (double *)plan->gen_scratch.p, slot_doubles, slots, plan->d_pool))
+        if (tsfa_launch_general(a, plan->gen_plan, (double *)plan->gen_scratch.p, slot_doubles, slots, plan->d_pool.get()))
             return fail(TSFA_ERR_HIP, "k_general launch failed");
         if (record(plan, st, slot, "k_general", false)) return fail(TSFA_ERR_HIP, "event record failed");
         ++slot;
@@ -1114,8 +1038,8 @@ static int check_shape(const tsfa_plan *plan, const BatchShape &sh) {
 static int build_sel(tsfa_plan *plan, const int64_t *d_starts, const int64_t *d_ends, int64_t n_series, const BatchShape &sh,
                      int *d_sel, hipStream_t st) {
     if (sh.n_groups <= 1) return TSFA_OK;
-    HIP_TRY(hipMemsetAsync(plan->d_cursor, 0, TSFA_N_LEN_CLASSES * sizeof(int), st));
-    if (tsfa_launch_class_fill(d_starts, d_ends, n_series, sh.map, plan->d_cursor, d_sel, st))
+    HIP_TRY(hipMemsetAsync(plan->d_cursor.get(), 0, TSFA_N_LEN_CLASSES * sizeof(int), st));
+    if (tsfa_launch_class_fill(d_starts, d_ends, n_series, sh.map, plan->d_cursor.get(), d_sel, st))
         return fail(TSFA_ERR_HIP, "class_fill launch failed");
     return TSFA_OK;
 }
@@ -1176,9 +1100,9 @@ int tsfa_extract_windows(tsfa_plan *plan, const void *values, int32_t dtype, con
             sh.g_has_short[0] = plan->hint_min_len <= TSFA_ROW_MAXN;
             memset(&sh.map, 0, sizeof sh.map);
         } else {
-            HIP_TRY(hipMemcpyAsync(plan->d_stats, h_stats, sizeof h_stats, hipMemcpyHostToDevice, st));
-            if (tsfa_launch_len_stats(starts, ends, n_series, plan->d_stats, st)) return fail(TSFA_ERR_HIP, "len_stats launch failed");
-            HIP_TRY(hipMemcpyAsync(h_stats, plan->d_stats, sizeof h_stats, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(plan->d_stats.get(), h_stats, sizeof h_stats, hipMemcpyHostToDevice, st));
+            if (tsfa_launch_len_stats(starts, ends, n_series, plan->d_stats.get(), st)) return fail(TSFA_ERR_HIP, "len_stats launch failed");
+            HIP_TRY(hipMemcpyAsync(h_stats, plan->d_stats.get(), sizeof h_stats, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             shape_from_stats(h_stats, n_series, sh, plan->opt.length_classes);
         }

@@ -9,17 +9,16 @@
 
 #include "pack_device.h"
 #include "roll_device.h"
-
-int tsfa_fail(int code, const char *msg);
+#include "tsfa_devmem.h"
 
 struct tsfa_pack {
     int32_t device = 0;
     int64_t n_rows = 0, n_groups = 0;
     int32_t flags = 0, n_passes = 0;
     int32_t id_type = 0, sort_type = 0, out_type = TSFA_F64;
-    // device buffers.  A pack made by tsfa_pack_device owns all four: tsfa_pack_device_destroy frees them.  A pack handed
-    // out by tsfa_pack_set_values is a VIEW: the pointers look into buffers it shares with the set and with its sibling
-    // packs, hold[k] keeps buffer k alive, and destroying the pack only drops those references.
+    // device buffers: the pointers are the views the accessors return, hold[k] keeps buffer k alive (pk_share).  A pack made
+    // by tsfa_pack_device is the only holder of its four; one handed out by tsfa_pack_set_values looks into buffers it
+    // shares with the set and with its sibling packs.  Either way destroying the pack only drops its references.
     void *values = nullptr;      // ragged buffer, n_rows x out_type
     int64_t *offsets = nullptr;  // n_groups + 1
     void *uniq = nullptr;        // n_groups x id_type
@@ -165,34 +164,17 @@ __global__ void __launch_bounds__(PK_GRID_THREADS) k_pack_rebase(const int64_t *
                    out);
 }
 
-int pk_fail_hip(const char *what, hipError_t e, const char *who = "tsfa_pack_device") {
-    return tsfa_fail(TSFA_ERR_HIP, (std::string(who) + ": " + what + ": " + hipGetErrorString(e)).c_str());
+// the function HIP_TRY and HIP_TRY_ALLOC name in their messages (redefined in front of every entry point below)
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_pack_device"
+
+// a device buffer as several holders keep it: freed on its device when the last of them goes
+std::shared_ptr<void> pk_share(void *p, int32_t device) {
+    return std::shared_ptr<void>(p, [device](void *q) {
+        (void)hipSetDevice(device);
+        (void)hipFree(q);
+    });
 }
-
-// the function the two macros below name in their messages (redefined in front of tsfa_pack_set_*)
-#define PK_WHO "tsfa_pack_device"
-
-#define PK_HIP(expr)                                        \
-    do {                                                    \
-        hipError_t e_ = (expr);                             \
-        if (e_ != hipSuccess) {                             \
-            rc = pk_fail_hip(#expr, e_, PK_WHO);                 \
-            goto done;                                      \
-        }                                                   \
-    } while (0)
-
-// hipMalloc that names the byte count when it fails
-#define PK_ALLOC(ptr, bytes, what)                                                                                        \
-    do {                                                                                                                  \
-        const size_t nb_ = (size_t)(bytes);                                                                               \
-        hipError_t e_ = hipMalloc((void **)&(ptr), nb_ ? nb_ : 1);                                                        \
-        if (e_ != hipSuccess) {                                                                                           \
-            (ptr) = nullptr;                                                                                              \
-            rc = tsfa_fail(TSFA_ERR_HIP, (std::string(PK_WHO ": cannot allocate ") + std::to_string(nb_) +                 \
-                                          " bytes of device memory for " + (what) + ": " + hipGetErrorString(e_)).c_str()); \
-            goto done;                                                                                                    \
-        }                                                                                                                 \
-    } while (0)
 
 int pk_check_device(int32_t device) {
     int ndev = 0;
@@ -230,100 +212,98 @@ extern "C" int tsfa_pack_device(const void *ids, int32_t id_type, const void *so
     const int64_t n = n_rows, n_tiles = (n + PK_TILE - 1) / PK_TILE;
     const int id_size = pk_itemsize(id_type), sort_size = sort ? pk_itemsize(sort_type) : 0, val_size = pk_itemsize(value_type);
     const int out_type = pk_out_type(value_type);
-    void *d_ids = nullptr, *d_sort = nullptr, *d_vals = nullptr;  // staged copies (TSFA_HOST only)
-    pk_u64 *hi[2] = {nullptr, nullptr}, *lo[2] = {nullptr, nullptr};
-    uint32_t *idx[2] = {nullptr, nullptr}, *counts = nullptr;
-    PkStats *d_st = nullptr;
     PkStats st;
-    tsfa_pack *pk = new tsfa_pack();
+    std::unique_ptr<tsfa_pack, void (*)(tsfa_pack *)> pk(new tsfa_pack(), tsfa_pack_device_destroy);
     int cur = 0;
     pk->device = device; pk->n_rows = n; pk->id_type = id_type; pk->sort_type = sort ? sort_type : 0; pk->out_type = out_type;
 
-    PK_HIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
+    DevPtr<void> d_ids, d_sort, d_vals;  // staged copies (TSFA_HOST only)
     if (space == TSFA_HOST) {
-        PK_ALLOC(d_ids, (size_t)n * id_size, "the id column");
-        PK_HIP(hipMemcpy(d_ids, ids, (size_t)n * id_size, hipMemcpyHostToDevice));
+        HIP_TRY_ALLOC(d_ids, (size_t)n * id_size, "the id column");
+        HIP_TRY(hipMemcpy(d_ids.get(), ids, (size_t)n * id_size, hipMemcpyHostToDevice));
         if (sort) {
-            PK_ALLOC(d_sort, (size_t)n * sort_size, "the sort column");
-            PK_HIP(hipMemcpy(d_sort, sort, (size_t)n * sort_size, hipMemcpyHostToDevice));
+            HIP_TRY_ALLOC(d_sort, (size_t)n * sort_size, "the sort column");
+            HIP_TRY(hipMemcpy(d_sort.get(), sort, (size_t)n * sort_size, hipMemcpyHostToDevice));
         }
-        PK_ALLOC(d_vals, (size_t)n * val_size, "the value column");
-        PK_HIP(hipMemcpy(d_vals, values, (size_t)n * val_size, hipMemcpyHostToDevice));
-        ids = d_ids; sort = d_sort; values = d_vals;
+        HIP_TRY_ALLOC(d_vals, (size_t)n * val_size, "the value column");
+        HIP_TRY(hipMemcpy(d_vals.get(), values, (size_t)n * val_size, hipMemcpyHostToDevice));
+        ids = d_ids.get(); sort = d_sort.get(); values = d_vals.get();
     }
-    PK_ALLOC(d_st, sizeof(PkStats), "the packer's counters");
+    DevPtr<PkStats> d_st_own;
+    HIP_TRY_ALLOC(d_st_own, sizeof(PkStats), "the packer's counters");
+    PkStats *const d_st = d_st_own.get();
     pk_stats_init(&st);
-    PK_HIP(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
 
     // 1. min / max of both keys, descents
     k_pack_minmax<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, d_st);
-    PK_HIP(hipGetLastError());
-    PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
-    {
-        const bool in_order = st.descents == 0;
-        if (in_order) pk->flags |= TSFA_PACK_IN_ORDER;
-        // 2. keys, identity permutation, byte histograms.  An ordered frame needs one set of buffers only.
-        for (int k = 0; k < (in_order ? 1 : 2); ++k) {
-            PK_ALLOC(hi[k], (size_t)n * 8, "the id keys (sort scratch: 40 bytes per row in all)");
-            PK_ALLOC(lo[k], (size_t)n * 8, "the sort keys (sort scratch: 40 bytes per row in all)");
-            PK_ALLOC(idx[k], (size_t)n * 4, "the row indices (sort scratch: 40 bytes per row in all)");
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
+    const bool in_order = st.descents == 0;
+    if (in_order) pk->flags |= TSFA_PACK_IN_ORDER;
+    // 2. keys, identity permutation, byte histograms.  An ordered frame needs one set of buffers only.
+    DevPtr<pk_u64> d_hi[2], d_lo[2];
+    DevPtr<uint32_t> d_idx[2], d_counts;
+    for (int k = 0; k < (in_order ? 1 : 2); ++k) {
+        HIP_TRY_ALLOC(d_hi[k], (size_t)n * 8, "the id keys (sort scratch: 40 bytes per row in all)");
+        HIP_TRY_ALLOC(d_lo[k], (size_t)n * 8, "the sort keys (sort scratch: 40 bytes per row in all)");
+        HIP_TRY_ALLOC(d_idx[k], (size_t)n * 4, "the row indices (sort scratch: 40 bytes per row in all)");
+    }
+    HIP_TRY_ALLOC(d_counts, (size_t)n_tiles * PK_RADIX * 4, "the per-tile digit counts");
+    pk_u64 *const hi[2] = {d_hi[0].get(), d_hi[1].get()}, *const lo[2] = {d_lo[0].get(), d_lo[1].get()};   // what the launches pass
+    uint32_t *const idx[2] = {d_idx[0].get(), d_idx[1].get()}, *const counts = d_counts.get();
+    k_pack_keys<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, st.kmin[0], sort ? st.kmin[1] : 0ull,
+                                                         pk_sig_bytes(st.kmax[0] - st.kmin[0]),
+                                                         sort ? pk_sig_bytes(st.kmax[1] - st.kmin[1]) : 0, in_order ? 0 : 1, hi[0], lo[0],
+                                                         idx[0], d_st);
+    HIP_TRY(hipGetLastError());
+    if (!in_order) {
+        // 3. the radix passes, least significant digit first; constant digits are skipped
+        int pass_word[16], pass_byte[16];
+        HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
+        const int np = pk_plan_passes(&st, n, sort != nullptr, pass_word, pass_byte);
+        for (int p = 0; p < np; ++p) {
+            const pk_u64 *key = pass_word[p] ? lo[cur] : hi[cur];
+            const int shift = 8 * pass_byte[p];
+            k_pack_hist<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, counts);
+            k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles * PK_RADIX, nullptr);
+            k_pack_scatter<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, counts, hi[cur], lo[cur], idx[cur],
+                                                                     hi[cur ^ 1], lo[cur ^ 1], idx[cur ^ 1]);
+            HIP_TRY(hipGetLastError());
+            cur ^= 1;
         }
-        PK_ALLOC(counts, (size_t)n_tiles * PK_RADIX * 4, "the per-tile digit counts");
-        k_pack_keys<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, st.kmin[0], sort ? st.kmin[1] : 0ull,
-                                                             pk_sig_bytes(st.kmax[0] - st.kmin[0]),
-                                                             sort ? pk_sig_bytes(st.kmax[1] - st.kmin[1]) : 0, in_order ? 0 : 1, hi[0],
-                                                             lo[0], idx[0], d_st);
-        PK_HIP(hipGetLastError());
-        if (!in_order) {
-            // 3. the radix passes, least significant digit first; constant digits are skipped
-            int pass_word[16], pass_byte[16];
-            PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
-            const int np = pk_plan_passes(&st, n, sort != nullptr, pass_word, pass_byte);
-            for (int p = 0; p < np; ++p) {
-                const pk_u64 *key = pass_word[p] ? lo[cur] : hi[cur];
-                const int shift = 8 * pass_byte[p];
-                k_pack_hist<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, counts);
-                k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles * PK_RADIX, nullptr);
-                k_pack_scatter<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, counts, hi[cur], lo[cur], idx[cur],
-                                                                         hi[cur ^ 1], lo[cur ^ 1], idx[cur ^ 1]);
-                PK_HIP(hipGetLastError());
-                cur ^= 1;
-            }
-            pk->n_passes = np;
-        }
+        pk->n_passes = np;
     }
     // 4. group boundaries (counts is reused for the per-tile head counts)
     k_pack_heads<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi[cur], n, counts);
     k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles, &d_st->n_groups);
-    PK_HIP(hipGetLastError());
-    PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
     pk->n_groups = (int64_t)st.n_groups;
-    PK_ALLOC(pk->offsets, (size_t)(pk->n_groups + 1) * 8, "the offsets");
-    PK_ALLOC(pk->uniq, (size_t)pk->n_groups * id_size, "the unique ids");
-    k_pack_groups<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi[cur], idx[cur], n, counts, pk->n_groups, ids, id_size, pk->offsets, pk->uniq);
-    PK_HIP(hipGetLastError());
+    DevPtr<int64_t> d_offsets;
+    DevPtr<void> d_uniq, d_out, d_psort;
+    HIP_TRY_ALLOC(d_offsets, (size_t)(pk->n_groups + 1) * 8, "the offsets");
+    HIP_TRY_ALLOC(d_uniq, (size_t)pk->n_groups * id_size, "the unique ids");
+    k_pack_groups<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi[cur], idx[cur], n, counts, pk->n_groups, ids, id_size, d_offsets.get(), d_uniq.get());
+    HIP_TRY(hipGetLastError());
     // 5. gather
-    PK_ALLOC(pk->values, (size_t)n * pk_itemsize(out_type), "the ragged sample buffer");
-    k_pack_gather<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(values, value_type, idx[cur], n, pk->values, d_st);
-    PK_HIP(hipGetLastError());
+    HIP_TRY_ALLOC(d_out, (size_t)n * pk_itemsize(out_type), "the ragged sample buffer");
+    k_pack_gather<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(values, value_type, idx[cur], n, d_out.get(), d_st);
+    HIP_TRY(hipGetLastError());
     if (options & TSFA_PACK_KEEP_SORT) {
-        PK_ALLOC(pk->sort, (size_t)n * sort_size, "the packed sort column");
-        k_pack_gather_raw<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(sort, sort_size, idx[cur], n, pk->sort);
-        PK_HIP(hipGetLastError());
+        HIP_TRY_ALLOC(d_psort, (size_t)n * sort_size, "the packed sort column");
+        k_pack_gather_raw<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(sort, sort_size, idx[cur], n, d_psort.get());
+        HIP_TRY(hipGetLastError());
     }
-    PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));  // (synchronises: the staged columns may go)
+    HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));  // (synchronises: the staged columns may go)
     if (st.nan_flag) pk->flags |= TSFA_PACK_VALUE_NAN;
-done:
-    for (int k = 0; k < 2; ++k) {
-        (void)hipFree(hi[k]); (void)hipFree(lo[k]); (void)hipFree(idx[k]);
-    }
-    (void)hipFree(counts); (void)hipFree(d_st);
-    (void)hipFree(d_ids); (void)hipFree(d_sort); (void)hipFree(d_vals);
-    if (rc) {
-        tsfa_pack_device_destroy(pk);
-        return rc;
-    }
-    *out_pack = pk;
+    // the pack takes over what outlives the call
+    pk->values = d_out.get(); pk->hold[0] = pk_share(d_out.release(), device);
+    pk->offsets = d_offsets.get(); pk->hold[1] = pk_share(d_offsets.release(), device);
+    pk->uniq = d_uniq.get(); pk->hold[2] = pk_share(d_uniq.release(), device);
+    if (d_psort) { pk->sort = d_psort.get(); pk->hold[3] = pk_share(d_psort.release(), device); }
+    *out_pack = pk.release();
     return TSFA_OK;
 }
 
@@ -346,7 +326,7 @@ static int pk_copy_out(const tsfa_pack *pack, void *dst, const void *src, size_t
     if (!src) return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": the pack does not hold that buffer").c_str());
     hipError_t e = hipSetDevice(pack->device);
     if (e == hipSuccess) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? (int)TSFA_OK : pk_fail_hip(who, e);
+    return e == hipSuccess ? (int)TSFA_OK : tsfa_fail_hip("tsfa_pack_device", who, e);
 }
 
 extern "C" int tsfa_pack_device_copy_ids(const tsfa_pack *pack, void *ids_host) {
@@ -366,31 +346,15 @@ extern "C" int tsfa_pack_device_copy_sort(const tsfa_pack *pack, void *sort_host
 
 extern "C" void tsfa_pack_device_destroy(tsfa_pack *pack) {
     if (!pack) return;
-    void *const bufs[4] = {pack->values, pack->offsets, pack->uniq, pack->sort};
-    for (int k = 0; k < 4; ++k) {
-        if (pack->hold[k] || !bufs[k]) continue;  // a view: the reference goes with `delete`
-        (void)hipSetDevice(pack->device);
-        (void)hipFree(bufs[k]);
-    }
-    delete pack;
+    (void)hipSetDevice(pack->device);
+    delete pack;  // drops the references; a buffer goes with its last holder
 }
 
 // ---------------------------------------------------------------------------------------------
 // Pack set: one sort per frame, one ordinary tsfa_pack per kind and value column
 // ---------------------------------------------------------------------------------------------
-namespace {
-
-std::shared_ptr<void> pk_share(void *p, int32_t device) {
-    return std::shared_ptr<void>(p, [device](void *q) {
-        (void)hipSetDevice(device);
-        (void)hipFree(q);
-    });
-}
-
-}  // namespace
-
-#undef PK_WHO
-#define PK_WHO "tsfa_pack_set_create"
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_pack_set_create"
 extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void *sort, int32_t sort_type, const void *kinds,
                                     int32_t kind_type, int64_t n_rows, int32_t space, int32_t options, int32_t device,
                                     tsfa_pack_set **out_set) {
@@ -412,58 +376,60 @@ extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void
 
     const int64_t n = n_rows, n_tiles = (n + PK_TILE - 1) / PK_TILE;
     const int id_size = pk_itemsize(id_type), sort_size = sort ? pk_itemsize(sort_type) : 0, kind_size = kinds ? pk_itemsize(kind_type) : 0;
-    void *d_ids = nullptr, *d_sort = nullptr, *d_kinds = nullptr;  // staged copies (TSFA_HOST only)
-    pk_u64 *hi[2] = {nullptr, nullptr}, *lo[2] = {nullptr, nullptr};
-    uint32_t *idx[2] = {nullptr, nullptr}, *counts = nullptr;
-    int64_t *d_offsets = nullptr, *d_rebased = nullptr, *d_krows = nullptr, *d_kgroups = nullptr;
-    void *d_uniq = nullptr, *d_kvals = nullptr, *d_psort = nullptr;
-    PkStats *d_st = nullptr;
-    PkSetStats *d_ks = nullptr;
     PkStats st;
     PkSetStats ks;
-    tsfa_pack_set *set = new tsfa_pack_set();
+    std::unique_ptr<tsfa_pack_set, void (*)(tsfa_pack_set *)> set(new tsfa_pack_set(), tsfa_pack_set_destroy);
     int cur = 0;
     set->device = device; set->n_rows = n; set->id_type = id_type; set->sort_type = sort ? sort_type : 0;
     set->kind_type = kinds ? kind_type : 0; set->has_kinds = kinds != nullptr;
 
-    PK_HIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
+    DevPtr<void> d_ids, d_sort, d_kinds;  // staged copies (TSFA_HOST only)
     if (space == TSFA_HOST) {
-        PK_ALLOC(d_ids, (size_t)n * id_size, "the id column");
-        PK_HIP(hipMemcpy(d_ids, ids, (size_t)n * id_size, hipMemcpyHostToDevice));
+        HIP_TRY_ALLOC(d_ids, (size_t)n * id_size, "the id column");
+        HIP_TRY(hipMemcpy(d_ids.get(), ids, (size_t)n * id_size, hipMemcpyHostToDevice));
         if (sort) {
-            PK_ALLOC(d_sort, (size_t)n * sort_size, "the sort column");
-            PK_HIP(hipMemcpy(d_sort, sort, (size_t)n * sort_size, hipMemcpyHostToDevice));
+            HIP_TRY_ALLOC(d_sort, (size_t)n * sort_size, "the sort column");
+            HIP_TRY(hipMemcpy(d_sort.get(), sort, (size_t)n * sort_size, hipMemcpyHostToDevice));
         }
         if (kinds) {
-            PK_ALLOC(d_kinds, (size_t)n * kind_size, "the kind column");
-            PK_HIP(hipMemcpy(d_kinds, kinds, (size_t)n * kind_size, hipMemcpyHostToDevice));
+            HIP_TRY_ALLOC(d_kinds, (size_t)n * kind_size, "the kind column");
+            HIP_TRY(hipMemcpy(d_kinds.get(), kinds, (size_t)n * kind_size, hipMemcpyHostToDevice));
         }
-        ids = d_ids; sort = d_sort; kinds = d_kinds;
+        ids = d_ids.get(); sort = d_sort.get(); kinds = d_kinds.get();
     }
-    PK_ALLOC(d_st, sizeof(PkStats), "the packer's counters");
-    PK_ALLOC(d_ks, sizeof(PkSetStats), "the packer's kind counters");
+    DevPtr<PkStats> d_st_own;
+    DevPtr<PkSetStats> d_ks_own;
+    HIP_TRY_ALLOC(d_st_own, sizeof(PkStats), "the packer's counters");
+    HIP_TRY_ALLOC(d_ks_own, sizeof(PkSetStats), "the packer's kind counters");
+    PkStats *const d_st = d_st_own.get();
+    PkSetStats *const d_ks = d_ks_own.get();
     pk_stats_init(&st);
     pk_set_stats_init(&ks);
-    PK_HIP(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
-    PK_HIP(hipMemcpy(d_ks, &ks, sizeof(ks), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ks, &ks, sizeof(ks), hipMemcpyHostToDevice));
 
     // 1. min / max of the three keys, descents of (id, sort) and of (kind, id, sort)
     k_pack_minmax<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, d_st);
     if (kinds) k_pack_kind_minmax<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(kinds, kind_type, ids, id_type, sort, sort_type, n, d_ks);
-    PK_HIP(hipGetLastError());
-    PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
-    PK_HIP(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
+    const bool inner_in_order = st.descents == 0;                       // (id, sort): only the kind passes are left
+    const bool in_order = kinds ? ks.descents == 0 : inner_in_order;    // (kind, id, sort): nothing is sorted
+    if (in_order) set->flags |= TSFA_PACK_IN_ORDER;
+    // 2. id and sort keys, identity permutation, byte histograms
+    DevPtr<pk_u64> d_hi[2], d_lo[2];
+    DevPtr<uint32_t> d_idx[2], d_counts;
+    for (int k = 0; k < (in_order ? 1 : 2); ++k) {
+        HIP_TRY_ALLOC(d_hi[k], (size_t)n * 8, "the id keys (sort scratch: 40 bytes per row in all)");
+        HIP_TRY_ALLOC(d_lo[k], (size_t)n * 8, "the sort keys (sort scratch: 40 bytes per row in all)");
+        HIP_TRY_ALLOC(d_idx[k], (size_t)n * 4, "the row indices (sort scratch: 40 bytes per row in all)");
+    }
+    HIP_TRY_ALLOC(d_counts, (size_t)n_tiles * PK_RADIX * 4, "the per-tile digit counts");
+    pk_u64 *const hi[2] = {d_hi[0].get(), d_hi[1].get()}, *const lo[2] = {d_lo[0].get(), d_lo[1].get()};   // what the launches pass
+    uint32_t *const idx[2] = {d_idx[0].get(), d_idx[1].get()}, *const counts = d_counts.get();
     {
-        const bool inner_in_order = st.descents == 0;                       // (id, sort): only the kind passes are left
-        const bool in_order = kinds ? ks.descents == 0 : inner_in_order;    // (kind, id, sort): nothing is sorted
-        if (in_order) set->flags |= TSFA_PACK_IN_ORDER;
-        // 2. id and sort keys, identity permutation, byte histograms
-        for (int k = 0; k < (in_order ? 1 : 2); ++k) {
-            PK_ALLOC(hi[k], (size_t)n * 8, "the id keys (sort scratch: 40 bytes per row in all)");
-            PK_ALLOC(lo[k], (size_t)n * 8, "the sort keys (sort scratch: 40 bytes per row in all)");
-            PK_ALLOC(idx[k], (size_t)n * 4, "the row indices (sort scratch: 40 bytes per row in all)");
-        }
-        PK_ALLOC(counts, (size_t)n_tiles * PK_RADIX * 4, "the per-tile digit counts");
         const int inner_passes = (in_order || inner_in_order) ? 0 : 1;
         k_pack_keys<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, st.kmin[0], sort ? st.kmin[1] : 0ull,
                                                              pk_sig_bytes(st.kmax[0] - st.kmin[0]),
@@ -471,12 +437,12 @@ extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void
                                                              lo[0], idx[0], d_st);
         if (kinds && !in_order)
             k_pack_kind_hist<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(kinds, kind_type, n, ks.kmin, pk_sig_bytes(ks.kmax - ks.kmin), d_ks);
-        PK_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         if (!in_order) {
             // 3. the radix passes, least significant digit first: sort bytes, id bytes, kind bytes; constant digits are skipped
             int pass_word[16], pass_byte[16], kind_byte[8];
-            PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
-            PK_HIP(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
             const int np = inner_passes ? pk_plan_passes(&st, n, sort != nullptr, pass_word, pass_byte) : 0;
             for (int p = 0; p < np; ++p) {
                 const pk_u64 *key = pass_word[p] ? lo[cur] : hi[cur];
@@ -485,7 +451,7 @@ extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void
                 k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles * PK_RADIX, nullptr);
                 k_pack_scatter<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, counts, hi[cur], lo[cur], idx[cur],
                                                                          hi[cur ^ 1], lo[cur ^ 1], idx[cur ^ 1]);
-                PK_HIP(hipGetLastError());
+                HIP_TRY(hipGetLastError());
                 cur ^= 1;
             }
             const int nkp = kinds ? pk_plan_kind_passes(&ks, n, kind_byte) : 0;
@@ -495,7 +461,7 @@ extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void
                 k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles * PK_RADIX, nullptr);
                 k_pack_scatter_kind<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, dg, n, counts, hi[cur], lo[cur], idx[cur],
                                                                               hi[cur ^ 1], lo[cur ^ 1], idx[cur ^ 1]);
-                PK_HIP(hipGetLastError());
+                HIP_TRY(hipGetLastError());
                 cur ^= 1;
             }
             set->n_passes = np + nkp;
@@ -505,61 +471,50 @@ extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void
     k_pack_set_heads<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi[cur], idx[cur], kinds, kind_type, n, counts, counts + n_tiles);
     k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles, &d_st->n_groups);
     k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts + n_tiles, (size_t)n_tiles, &d_ks->n_kinds);
-    PK_HIP(hipGetLastError());
-    PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
-    PK_HIP(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
-    if (ks.n_kinds > 0x7fffffffu) {
-        rc = tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_pack_set_create: more than 2 147 483 647 distinct kinds");
-        goto done;
-    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
+    if (ks.n_kinds > 0x7fffffffu) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_pack_set_create: more than 2 147 483 647 distinct kinds");
     set->n_groups = (int64_t)st.n_groups;
     set->n_kinds = (int32_t)ks.n_kinds;
+    DevPtr<int64_t> d_offsets, d_rebased, d_krows, d_kgroups;
+    DevPtr<void> d_uniq, d_kvals, d_psort;
     {
         const int64_t nk = set->n_kinds, ng = set->n_groups;
-        PK_ALLOC(d_offsets, (size_t)(ng + 1) * 8, "the offsets");
-        PK_ALLOC(d_uniq, (size_t)ng * id_size, "the unique ids");
-        PK_ALLOC(d_krows, (size_t)(nk + 1) * 8, "the kinds' row ranges");
-        PK_ALLOC(d_kgroups, (size_t)(nk + 1) * 8, "the kinds' group ranges");
-        PK_ALLOC(d_kvals, (size_t)nk * kind_size, "the kind values");
+        HIP_TRY_ALLOC(d_offsets, (size_t)(ng + 1) * 8, "the offsets");
+        HIP_TRY_ALLOC(d_uniq, (size_t)ng * id_size, "the unique ids");
+        HIP_TRY_ALLOC(d_krows, (size_t)(nk + 1) * 8, "the kinds' row ranges");
+        HIP_TRY_ALLOC(d_kgroups, (size_t)(nk + 1) * 8, "the kinds' group ranges");
+        HIP_TRY_ALLOC(d_kvals, (size_t)nk * kind_size, "the kind values");
         k_pack_set_groups<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi[cur], idx[cur], kinds, kind_type, n, counts, counts + n_tiles, ng, nk,
-                                                                    ids, id_size, d_offsets, d_uniq, d_krows, d_kgroups, d_kvals);
-        PK_HIP(hipGetLastError());
+                                                                    ids, id_size, d_offsets.get(), d_uniq.get(), d_krows.get(),
+                                                                    d_kgroups.get(), d_kvals.get());
+        HIP_TRY(hipGetLastError());
         if (nk > 1) {
-            PK_ALLOC(d_rebased, (size_t)(ng + nk) * 8, "the offsets of every kind");
-            k_pack_rebase<<<pk_grid(ng + nk), PK_GRID_THREADS, 0, 0>>>(d_offsets, d_krows, d_kgroups, nk, ng + nk, d_rebased);
-            PK_HIP(hipGetLastError());
+            HIP_TRY_ALLOC(d_rebased, (size_t)(ng + nk) * 8, "the offsets of every kind");
+            k_pack_rebase<<<pk_grid(ng + nk), PK_GRID_THREADS, 0, 0>>>(d_offsets.get(), d_krows.get(), d_kgroups.get(), nk, ng + nk,
+                                                                        d_rebased.get());
+            HIP_TRY(hipGetLastError());
         }
         if (options & TSFA_PACK_KEEP_SORT) {
-            PK_ALLOC(d_psort, (size_t)n * sort_size, "the packed sort column");
-            k_pack_gather_raw<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(sort, sort_size, idx[cur], n, d_psort);
-            PK_HIP(hipGetLastError());
+            HIP_TRY_ALLOC(d_psort, (size_t)n * sort_size, "the packed sort column");
+            k_pack_gather_raw<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(sort, sort_size, idx[cur], n, d_psort.get());
+            HIP_TRY(hipGetLastError());
         }
         set->kind_rows.resize((size_t)nk + 1);
         set->kind_groups.resize((size_t)nk + 1);
         set->kind_vals.resize((size_t)nk * kind_size);
-        PK_HIP(hipMemcpy(set->kind_rows.data(), d_krows, (size_t)(nk + 1) * 8, hipMemcpyDeviceToHost));  // (synchronises)
-        PK_HIP(hipMemcpy(set->kind_groups.data(), d_kgroups, (size_t)(nk + 1) * 8, hipMemcpyDeviceToHost));
-        if (kind_size) PK_HIP(hipMemcpy(set->kind_vals.data(), d_kvals, (size_t)nk * kind_size, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(set->kind_rows.data(), d_krows.get(), (size_t)(nk + 1) * 8, hipMemcpyDeviceToHost));  // (synchronises)
+        HIP_TRY(hipMemcpy(set->kind_groups.data(), d_kgroups.get(), (size_t)(nk + 1) * 8, hipMemcpyDeviceToHost));
+        if (kind_size) HIP_TRY(hipMemcpy(set->kind_vals.data(), d_kvals.get(), (size_t)nk * kind_size, hipMemcpyDeviceToHost));
     }
     // the set takes over what outlives the call
-    set->perm = pk_share(idx[cur], device); idx[cur] = nullptr;
-    set->offsets = pk_share(d_offsets, device); d_offsets = nullptr;
-    set->uniq = pk_share(d_uniq, device); d_uniq = nullptr;
-    if (d_rebased) { set->rebased = pk_share(d_rebased, device); d_rebased = nullptr; }
-    if (d_psort) { set->sort = pk_share(d_psort, device); d_psort = nullptr; }
-done:
-    for (int k = 0; k < 2; ++k) {
-        (void)hipFree(hi[k]); (void)hipFree(lo[k]); (void)hipFree(idx[k]);
-    }
-    (void)hipFree(counts); (void)hipFree(d_st); (void)hipFree(d_ks);
-    (void)hipFree(d_ids); (void)hipFree(d_sort); (void)hipFree(d_kinds);
-    (void)hipFree(d_offsets); (void)hipFree(d_rebased); (void)hipFree(d_krows); (void)hipFree(d_kgroups);
-    (void)hipFree(d_uniq); (void)hipFree(d_kvals); (void)hipFree(d_psort);
-    if (rc) {
-        delete set;
-        return rc;
-    }
-    *out_set = set;
+    set->perm = pk_share(d_idx[cur].release(), device);
+    set->offsets = pk_share(d_offsets.release(), device);
+    set->uniq = pk_share(d_uniq.release(), device);
+    if (d_rebased) set->rebased = pk_share(d_rebased.release(), device);
+    if (d_psort) set->sort = pk_share(d_psort.release(), device);
+    *out_set = set.release();
     return TSFA_OK;
 }
 
@@ -574,8 +529,8 @@ extern "C" int tsfa_pack_set_copy_kinds(const tsfa_pack_set *set, void *kinds_ho
     return TSFA_OK;
 }
 
-#undef PK_WHO
-#define PK_WHO "tsfa_pack_set_values"
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_pack_set_values"
 extern "C" int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int32_t value_type, int32_t space, tsfa_pack **out_packs) {
     if (!set || !values || !out_packs || (space != TSFA_HOST && space != TSFA_DEVICE))
         return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_values: bad arguments");
@@ -584,26 +539,26 @@ extern "C" int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int3
     const int64_t n = set->n_rows;
     const int out_type = pk_out_type(value_type), out_size = pk_itemsize(out_type);
     const int id_size = pk_itemsize(set->id_type), sort_size = pk_itemsize(set->sort_type);
-    void *d_vals = nullptr, *d_out = nullptr;
-    PkStats *d_st = nullptr;
     unsigned int nan_flag = 0;
-    std::shared_ptr<void> out;
-    int rc = TSFA_OK;
     for (int32_t k = 0; k < set->n_kinds; ++k) out_packs[k] = nullptr;
 
-    PK_HIP(hipSetDevice(set->device));
+    HIP_TRY(hipSetDevice(set->device));
+    DevPtr<void> d_vals, d_out_own;
+    DevPtr<PkStats> d_st_own;
     if (space == TSFA_HOST) {
-        PK_ALLOC(d_vals, (size_t)n * val_size, "the value column");
-        PK_HIP(hipMemcpy(d_vals, values, (size_t)n * val_size, hipMemcpyHostToDevice));
-        values = d_vals;
+        HIP_TRY_ALLOC(d_vals, (size_t)n * val_size, "the value column");
+        HIP_TRY(hipMemcpy(d_vals.get(), values, (size_t)n * val_size, hipMemcpyHostToDevice));
+        values = d_vals.get();
     }
-    PK_ALLOC(d_st, sizeof(PkStats), "the packer's counters");
-    PK_HIP(hipMemset(d_st, 0, sizeof(PkStats)));
-    PK_ALLOC(d_out, (size_t)n * out_size, "the ragged sample buffer");
-    out = pk_share(d_out, set->device);
+    HIP_TRY_ALLOC(d_st_own, sizeof(PkStats), "the packer's counters");
+    PkStats *const d_st = d_st_own.get();
+    HIP_TRY(hipMemset(d_st, 0, sizeof(PkStats)));
+    HIP_TRY_ALLOC(d_out_own, (size_t)n * out_size, "the ragged sample buffer");
+    void *const d_out = d_out_own.get();
+    const std::shared_ptr<void> out = pk_share(d_out_own.release(), set->device);
     k_pack_gather<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(values, value_type, (const uint32_t *)set->perm.get(), n, d_out, d_st);
-    PK_HIP(hipGetLastError());
-    PK_HIP(hipMemcpy(&nan_flag, &d_st->nan_flag, sizeof(nan_flag), hipMemcpyDeviceToHost));  // (synchronises: the staged column may go)
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&nan_flag, &d_st->nan_flag, sizeof(nan_flag), hipMemcpyDeviceToHost));  // (synchronises: the staged column may go)
     for (int32_t k = 0; k < set->n_kinds; ++k) {
         const int64_t r0 = set->kind_rows[(size_t)k], g0 = set->kind_groups[(size_t)k];
         tsfa_pack *pk = new tsfa_pack();
@@ -626,9 +581,7 @@ extern "C" int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int3
         }
         out_packs[k] = pk;
     }
-done:
-    (void)hipFree(d_vals); (void)hipFree(d_st);
-    return rc;
+    return TSFA_OK;
 }
 
 extern "C" void tsfa_pack_set_destroy(tsfa_pack_set *set) { delete set; }
@@ -640,7 +593,7 @@ struct tsfa_windows {
     int32_t device = 0;
     int32_t positive = 0;
     int64_t n_windows = 0;
-    int64_t *starts = nullptr, *ends = nullptr, *series = nullptr, *shifts = nullptr;  // n_windows int64 each, device memory
+    DevPtr<int64_t> starts, ends, series, shifts;  // n_windows int64 each; freed on `device` (tsfa_windows_destroy)
 };
 
 namespace {
@@ -678,8 +631,8 @@ __global__ void __launch_bounds__(PK_GRID_THREADS) k_roll_shift_values(const voi
 
 }  // namespace
 
-#undef PK_WHO
-#define PK_WHO "tsfa_roll_windows"
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_roll_windows"
 extern "C" int tsfa_roll_windows(const tsfa_pack *pack, int32_t rolling_direction, int64_t max_timeshift, int64_t min_timeshift,
                                  int64_t steps, tsfa_windows **out_windows) {
     if (!out_windows) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_roll_windows: out_windows is NULL");
@@ -692,81 +645,72 @@ extern "C" int tsfa_roll_windows(const tsfa_pack *pack, int32_t rolling_directio
     if (const char *why = rl_make_params(rolling_direction, max_timeshift, min_timeshift, steps, &p))
         return tsfa_fail(TSFA_ERR_INVALID, (std::string("tsfa_roll_windows: ") + why).c_str());
     const int64_t ns = pack->n_groups;
-    uint32_t *counts = nullptr;
-    RlStats *d_st = nullptr;
     RlStats st;
-    tsfa_windows *win = new tsfa_windows();
-    int rc = TSFA_OK;
+    std::unique_ptr<tsfa_windows, void (*)(tsfa_windows *)> win(new tsfa_windows(), tsfa_windows_destroy);
     win->device = pack->device;
     win->positive = p.positive;
     memset(&st, 0, sizeof(st));
 
-    PK_HIP(hipSetDevice(pack->device));
+    HIP_TRY(hipSetDevice(pack->device));
+    DevPtr<uint32_t> counts;
+    DevPtr<RlStats> d_st;
     if (ns > 0) {
-        PK_ALLOC(counts, (size_t)ns * 4, "the window counts");
-        PK_ALLOC(d_st, sizeof(RlStats), "the window builder's counters");
-        PK_HIP(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
-        k_roll_count<<<pk_grid(ns), PK_GRID_THREADS, 0, 0>>>(pack->offsets, ns, p, counts, d_st);
-        k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)ns, &d_st->total);
-        PK_HIP(hipGetLastError());
-        PK_HIP(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
-        if ((int64_t)st.max_len > steps) {
-            rc = tsfa_fail(TSFA_ERR_INVALID, ("tsfa_roll_windows: steps = " + std::to_string(steps) + " is below the pack's longest series (" +
-                                              std::to_string(st.max_len) + " samples)").c_str());
-            goto done;
-        }
+        HIP_TRY_ALLOC(counts, (size_t)ns * 4, "the window counts");
+        HIP_TRY_ALLOC(d_st, sizeof(RlStats), "the window builder's counters");
+        HIP_TRY(hipMemcpy(d_st.get(), &st, sizeof(st), hipMemcpyHostToDevice));
+        k_roll_count<<<pk_grid(ns), PK_GRID_THREADS, 0, 0>>>(pack->offsets, ns, p, counts.get(), d_st.get());
+        k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts.get(), (size_t)ns, &d_st.get()->total);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(&st, d_st.get(), sizeof(st), hipMemcpyDeviceToHost));
+        if ((int64_t)st.max_len > steps)
+            return tsfa_fail(TSFA_ERR_INVALID, ("tsfa_roll_windows: steps = " + std::to_string(steps) + " is below the pack's longest series (" +
+                                                std::to_string(st.max_len) + " samples)").c_str());
         win->n_windows = (int64_t)st.total;
     }
     if (win->n_windows > 0) {
         const int64_t nw = win->n_windows;
-        PK_ALLOC(win->starts, (size_t)nw * 8, "the window starts");
-        PK_ALLOC(win->ends, (size_t)nw * 8, "the window ends");
-        PK_ALLOC(win->series, (size_t)nw * 8, "the windows' series indices");
-        PK_ALLOC(win->shifts, (size_t)nw * 8, "the windows' timeshifts");
-        k_roll_fill<<<pk_grid(nw), PK_GRID_THREADS, 0, 0>>>(pack->offsets, ns, counts, nw, p, win->starts, win->ends, win->series,
-                                                              win->shifts);
-        PK_HIP(hipGetLastError());
-        PK_HIP(hipDeviceSynchronize());
+        HIP_TRY_ALLOC(win->starts, (size_t)nw * 8, "the window starts");
+        HIP_TRY_ALLOC(win->ends, (size_t)nw * 8, "the window ends");
+        HIP_TRY_ALLOC(win->series, (size_t)nw * 8, "the windows' series indices");
+        HIP_TRY_ALLOC(win->shifts, (size_t)nw * 8, "the windows' timeshifts");
+        k_roll_fill<<<pk_grid(nw), PK_GRID_THREADS, 0, 0>>>(pack->offsets, ns, counts.get(), nw, p, win->starts.get(), win->ends.get(),
+                                                              win->series.get(), win->shifts.get());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
     }
-done:
-    (void)hipFree(counts); (void)hipFree(d_st);
-    if (rc) {
-        tsfa_windows_destroy(win);
-        return rc;
-    }
-    *out_windows = win;
+    *out_windows = win.release();
     return TSFA_OK;
 }
 
 extern "C" int64_t tsfa_windows_n_windows(const tsfa_windows *windows) { return windows ? windows->n_windows : 0; }
-extern "C" const int64_t *tsfa_windows_starts(const tsfa_windows *windows) { return windows ? windows->starts : nullptr; }
-extern "C" const int64_t *tsfa_windows_ends(const tsfa_windows *windows) { return windows ? windows->ends : nullptr; }
+extern "C" const int64_t *tsfa_windows_starts(const tsfa_windows *windows) { return windows ? windows->starts.get() : nullptr; }
+extern "C" const int64_t *tsfa_windows_ends(const tsfa_windows *windows) { return windows ? windows->ends.get() : nullptr; }
 
 static int rl_copy_out(const tsfa_windows *windows, void *dst, const void *src, size_t bytes, const char *who) {
     if (!windows || !dst) return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": null pointer").c_str());
     if (!bytes) return TSFA_OK;
     hipError_t e = hipSetDevice(windows->device);
     if (e == hipSuccess) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? (int)TSFA_OK : pk_fail_hip("hipMemcpy", e, who);
+    return e == hipSuccess ? (int)TSFA_OK : tsfa_fail_hip(who, "hipMemcpy", e);
 }
 
 extern "C" int tsfa_windows_copy_series(const tsfa_windows *windows, int64_t *series_host) {
-    return rl_copy_out(windows, series_host, windows ? windows->series : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+    return rl_copy_out(windows, series_host, windows ? windows->series.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
                        "tsfa_windows_copy_series");
 }
 
 extern "C" int tsfa_windows_copy_timeshifts(const tsfa_windows *windows, int64_t *timeshifts_host) {
-    return rl_copy_out(windows, timeshifts_host, windows ? windows->shifts : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+    return rl_copy_out(windows, timeshifts_host, windows ? windows->shifts.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
                        "tsfa_windows_copy_timeshifts");
 }
 
 extern "C" int tsfa_windows_copy_starts(const tsfa_windows *windows, int64_t *starts_host) {
-    return rl_copy_out(windows, starts_host, windows ? windows->starts : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+    return rl_copy_out(windows, starts_host, windows ? windows->starts.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
                        "tsfa_windows_copy_starts");
 }
 
 extern "C" int tsfa_windows_copy_ends(const tsfa_windows *windows, int64_t *ends_host) {
-    return rl_copy_out(windows, ends_host, windows ? windows->ends : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+    return rl_copy_out(windows, ends_host, windows ? windows->ends.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
                        "tsfa_windows_copy_ends");
 }
 
@@ -785,101 +729,93 @@ int rl_check_device(const char *who, int32_t device) {
 
 }  // namespace
 
-#undef PK_WHO
-#define PK_WHO "tsfa_roll_count"
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_roll_count"
 extern "C" int tsfa_roll_count(const int64_t *offsets, int64_t n_series, int64_t series_len, int32_t rolling_direction,
                                int64_t max_timeshift, int64_t min_timeshift, int64_t steps, uint32_t *scanned,
                                int64_t *n_windows_host, int32_t device, void *stream) {
-    int rc = rl_check_device(PK_WHO, device);
+    int rc = rl_check_device(TSFA_WHO, device);
     if (rc) return rc;
-    if (!n_windows_host) return tsfa_fail(TSFA_ERR_INVALID, PK_WHO ": n_windows_host is NULL");
+    if (!n_windows_host) return tsfa_fail(TSFA_ERR_INVALID, TSFA_WHO ": n_windows_host is NULL");
     *n_windows_host = 0;
     RlParams p;
     const char *why = rl_make_params(rolling_direction, max_timeshift, min_timeshift, steps, &p);
-    if (why) return tsfa_fail(TSFA_ERR_INVALID, (std::string(PK_WHO ": ") + why).c_str());
+    if (why) return tsfa_fail(TSFA_ERR_INVALID, (std::string(TSFA_WHO ": ") + why).c_str());
     if (!scanned) {  // the uniform route: the closed form on the host, nothing is launched
         int64_t per_series = 0;
         if ((rc = rl_uniform_count(p, n_series, series_len, &per_series, n_windows_host, &why)))
-            return tsfa_fail(rc, (std::string(PK_WHO ": ") + why).c_str());
+            return tsfa_fail(rc, (std::string(TSFA_WHO ": ") + why).c_str());
         return TSFA_OK;
     }
-    if (!offsets || n_series < 0) return tsfa_fail(TSFA_ERR_INVALID, PK_WHO ": offsets is NULL or n_series is negative");
+    if (!offsets || n_series < 0) return tsfa_fail(TSFA_ERR_INVALID, TSFA_WHO ": offsets is NULL or n_series is negative");
     if (n_series == 0) return TSFA_OK;
     hipStream_t st = (hipStream_t)stream;  // NULL: the null stream
     int64_t edge[2] = {0, 0};
-    RlStats *d_st = nullptr;
     RlStats hst;
     memset(&hst, 0, sizeof(hst));
 
-    PK_HIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     // the extent the offsets claim, before anything is launched on them
-    PK_HIP(hipMemcpyAsync(&edge[0], offsets, 8, hipMemcpyDeviceToHost, st));
-    PK_HIP(hipMemcpyAsync(&edge[1], offsets + n_series, 8, hipMemcpyDeviceToHost, st));
-    PK_HIP(hipStreamSynchronize(st));
-    if ((rc = rl_check_extent(edge[1] - edge[0], &why))) {
-        rc = tsfa_fail(rc, (std::string(PK_WHO ": ") + why).c_str());
-        goto done;
-    }
-    PK_ALLOC(d_st, sizeof(RlStats), "the window builder's counters");
-    PK_HIP(hipMemsetAsync(d_st, 0, sizeof(RlStats), st));
-    k_roll_count<<<pk_grid(n_series), PK_GRID_THREADS, 0, st>>>(offsets, n_series, p, scanned, d_st);
-    k_pack_scan<<<1, PK_SCAN_THREADS, 0, st>>>(scanned, (size_t)n_series, &d_st->total);
-    PK_HIP(hipGetLastError());
-    PK_HIP(hipMemcpyAsync(&hst, d_st, sizeof(hst), hipMemcpyDeviceToHost, st));
-    PK_HIP(hipStreamSynchronize(st));  // the total is the call's result: this route waits for the stream whoever owns it
-    if ((int64_t)hst.max_len > steps) {
-        rc = tsfa_fail(TSFA_ERR_INVALID, (PK_WHO ": steps = " + std::to_string(steps) + " is below the batch's longest series (" +
-                                          std::to_string(hst.max_len) + " samples)").c_str());
-        goto done;
-    }
+    HIP_TRY(hipMemcpyAsync(&edge[0], offsets, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&edge[1], offsets + n_series, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = rl_check_extent(edge[1] - edge[0], &why))) return tsfa_fail(rc, (std::string(TSFA_WHO ": ") + why).c_str());
+    DevPtr<RlStats> d_st;
+    HIP_TRY_ALLOC(d_st, sizeof(RlStats), "the window builder's counters");
+    HIP_TRY(hipMemsetAsync(d_st.get(), 0, sizeof(RlStats), st));
+    k_roll_count<<<pk_grid(n_series), PK_GRID_THREADS, 0, st>>>(offsets, n_series, p, scanned, d_st.get());
+    k_pack_scan<<<1, PK_SCAN_THREADS, 0, st>>>(scanned, (size_t)n_series, &d_st.get()->total);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&hst, d_st.get(), sizeof(hst), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the total is the call's result: this route waits for the stream whoever owns it
+    if ((int64_t)hst.max_len > steps)
+        return tsfa_fail(TSFA_ERR_INVALID, (TSFA_WHO ": steps = " + std::to_string(steps) + " is below the batch's longest series (" +
+                                            std::to_string(hst.max_len) + " samples)").c_str());
     *n_windows_host = (int64_t)hst.total;
-done:
-    (void)hipFree(d_st);
-    return rc;
+    return TSFA_OK;
 }
 
-#undef PK_WHO
-#define PK_WHO "tsfa_roll_fill"
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_roll_fill"
 extern "C" int tsfa_roll_fill(const int64_t *offsets, int64_t n_series, const uint32_t *scanned, int64_t series_len,
                               int64_t n_windows, int32_t rolling_direction, int64_t max_timeshift, int64_t min_timeshift,
                               int64_t steps, int64_t *starts, int64_t *ends, int64_t *series, int64_t *timeshifts, int32_t device,
                               void *stream) {
-    int rc = rl_check_device(PK_WHO, device);
+    int rc = rl_check_device(TSFA_WHO, device);
     if (rc) return rc;
     RlParams p;
     const char *why = rl_make_params(rolling_direction, max_timeshift, min_timeshift, steps, &p);
-    if (why) return tsfa_fail(TSFA_ERR_INVALID, (std::string(PK_WHO ": ") + why).c_str());
-    if (n_windows < 0 || n_series < 0) return tsfa_fail(TSFA_ERR_INVALID, PK_WHO ": n_windows or n_series is negative");
+    if (why) return tsfa_fail(TSFA_ERR_INVALID, (std::string(TSFA_WHO ": ") + why).c_str());
+    if (n_windows < 0 || n_series < 0) return tsfa_fail(TSFA_ERR_INVALID, TSFA_WHO ": n_windows or n_series is negative");
     int64_t per_series = 0;
     if (!scanned) {
         int64_t expect = 0;
         if ((rc = rl_uniform_count(p, n_series, series_len, &per_series, &expect, &why)))
-            return tsfa_fail(rc, (std::string(PK_WHO ": ") + why).c_str());
+            return tsfa_fail(rc, (std::string(TSFA_WHO ": ") + why).c_str());
         if (n_windows != expect)
-            return tsfa_fail(TSFA_ERR_INVALID, (PK_WHO ": n_windows = " + std::to_string(n_windows) + ", but " + std::to_string(n_series) +
+            return tsfa_fail(TSFA_ERR_INVALID, (TSFA_WHO ": n_windows = " + std::to_string(n_windows) + ", but " + std::to_string(n_series) +
                                                 " series of " + std::to_string(series_len) + " samples have " + std::to_string(expect) +
                                                 " windows").c_str());
     } else if (!offsets || n_windows > RL_MAX_SAMPLES) {
-        return tsfa_fail(TSFA_ERR_INVALID, PK_WHO ": offsets is NULL, or n_windows is beyond what tsfa_roll_count returns");
+        return tsfa_fail(TSFA_ERR_INVALID, TSFA_WHO ": offsets is NULL, or n_windows is beyond what tsfa_roll_count returns");
     }
     if (n_windows == 0) return TSFA_OK;
     if (n_series < 1 || !starts || !ends || !series || !timeshifts)
-        return tsfa_fail(TSFA_ERR_INVALID, PK_WHO ": windows without a series, or an output pointer is NULL");
+        return tsfa_fail(TSFA_ERR_INVALID, TSFA_WHO ": windows without a series, or an output pointer is NULL");
     hipStream_t st = (hipStream_t)stream;  // NULL: the null stream
-    PK_HIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     if (scanned)
         k_roll_fill<<<pk_grid(n_windows), PK_GRID_THREADS, 0, st>>>(offsets, n_series, scanned, n_windows, p, starts, ends, series, timeshifts);
     else
         k_roll_fill_uniform<<<pk_grid(n_windows), PK_GRID_THREADS, 0, st>>>(offsets, series_len, per_series, n_windows, p, starts, ends,
                                                                              series, timeshifts);
-    PK_HIP(hipGetLastError());
-    if (!stream) PK_HIP(hipStreamSynchronize(st));
-done:
-    return rc;
+    HIP_TRY(hipGetLastError());
+    if (!stream) HIP_TRY(hipStreamSynchronize(st));
+    return TSFA_OK;
 }
 
-#undef PK_WHO
-#define PK_WHO "tsfa_roll_shift_values"
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_roll_shift_values"
 extern "C" int tsfa_roll_shift_values(const tsfa_windows *windows, const tsfa_pack *pack, void *out_host) {
     if (!windows || !pack || !out_host) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_roll_shift_values: null pointer");
     if (!pack->sort)
@@ -889,24 +825,18 @@ extern "C" int tsfa_roll_shift_values(const tsfa_windows *windows, const tsfa_pa
     const int64_t nw = windows->n_windows;
     if (nw == 0) return TSFA_OK;
     const int itemsize = pk_itemsize(pack->sort_type);
-    void *d_out = nullptr;
-    int rc = TSFA_OK;
-    PK_HIP(hipSetDevice(pack->device));
-    PK_ALLOC(d_out, (size_t)nw * itemsize, "the windows' shift values");
-    k_roll_shift_values<<<pk_grid(nw), PK_GRID_THREADS, 0, 0>>>(pack->sort, itemsize, pack->n_rows, windows->starts, windows->ends,
-                                                                  windows->positive, nw, d_out);
-    PK_HIP(hipGetLastError());
-    PK_HIP(hipMemcpy(out_host, d_out, (size_t)nw * itemsize, hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(d_out);
-    return rc;
+    HIP_TRY(hipSetDevice(pack->device));
+    DevPtr<void> d_out;
+    HIP_TRY_ALLOC(d_out, (size_t)nw * itemsize, "the windows' shift values");
+    k_roll_shift_values<<<pk_grid(nw), PK_GRID_THREADS, 0, 0>>>(pack->sort, itemsize, pack->n_rows, windows->starts.get(),
+                                                                  windows->ends.get(), windows->positive, nw, d_out.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out_host, d_out.get(), (size_t)nw * itemsize, hipMemcpyDeviceToHost));
+    return TSFA_OK;
 }
 
 extern "C" void tsfa_windows_destroy(tsfa_windows *windows) {
     if (!windows) return;
-    if (windows->starts || windows->ends || windows->series || windows->shifts) {
-        (void)hipSetDevice(windows->device);
-        (void)hipFree(windows->starts); (void)hipFree(windows->ends); (void)hipFree(windows->series); (void)hipFree(windows->shifts);
-    }
+    (void)hipSetDevice(windows->device);
     delete windows;
 }

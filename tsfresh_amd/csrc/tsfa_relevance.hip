@@ -20,8 +20,8 @@
 
 #include "../../include/tsfresh_amd.h"
 #include "rel_tails.h"
+#include "tsfa_devmem.h"
 
-int tsfa_fail(int code, const char *msg);  // tsfa_api.cpp: records the thread-local message, returns code
 static int rel_check_device(int32_t device, const char *who);
 
 #define REL_NT 1024
@@ -400,12 +400,6 @@ static int64_t rel_batch_columns(int64_t np2, int64_t n_cols) {
     return batch;
 }
 
-#define REL_HIP(call)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) { rc = tsfa_fail(TSFA_ERR_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); goto done; } \
-    } while (0)
-
 static int relevance_classes_impl(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
                                   const int32_t *y_codes, int32_t n_classes, int32_t device, tsfa_relevance_col *cols,
                                   double *rank_sums, int64_t *hi_counts, double *ks_d);
@@ -426,16 +420,11 @@ extern "C" int tsfa_relevance_classes_ks(const double *X, int64_t n_rows, int64_
 // The device side of one statistics sweep: what the sweep allocates, and what it leaves in HBM for the caller -- the
 // host copies of tsfa_relevance_classes*, or the tails kernels of tsfa_relevance_tails_classes.
 struct RelClassesDev {
-    double *dX = nullptr, *dkeys = nullptr, *drs = nullptr, *dks = nullptr;
-    uint32_t *didx = nullptr;
-    int32_t *dy = nullptr;
-    int64_t *dhc = nullptr;
-    tsfa_relevance_col *dcols = nullptr;
-    void release() {
-        (void)hipFree(dX); (void)hipFree(dkeys); (void)hipFree(didx); (void)hipFree(dy); (void)hipFree(drs); (void)hipFree(dhc);
-        (void)hipFree(dcols); (void)hipFree(dks);
-        *this = RelClassesDev();
-    }
+    DevPtr<double> dX, dkeys, drs, dks;
+    DevPtr<uint32_t> didx;
+    DevPtr<int32_t> dy;
+    DevPtr<int64_t> dhc;
+    DevPtr<tsfa_relevance_col> dcols;
 };
 
 static int rel_classes_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_codes,
@@ -447,18 +436,17 @@ static int relevance_classes_impl(const double *X, int64_t n_rows, int64_t n_col
     if (!cols || !rank_sums || !hi_counts) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_classes: null pointer or bad shape");
     RelClassesDev d;
     int rc = rel_classes_sweep(X, n_rows, n_cols, ld, space, y_codes, n_classes, device, ks_d != nullptr, d);
-    if (rc != TSFA_OK || n_cols == 0) { d.release(); return rc; }
-    REL_HIP(hipMemcpy(cols, d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_col), hipMemcpyDeviceToHost));
-    REL_HIP(hipMemcpy(rank_sums, d.drs, (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
-    REL_HIP(hipMemcpy(hi_counts, d.dhc, (size_t)n_cols * n_classes * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (ks_d) REL_HIP(hipMemcpy(ks_d, d.dks, (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
-done:
-    d.release();
-    return rc;
+    if (rc != TSFA_OK || n_cols == 0) return rc;
+    HIP_TRY(hipMemcpy(cols, d.dcols.get(), (size_t)n_cols * sizeof(tsfa_relevance_col), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rank_sums, d.drs.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hi_counts, d.dhc.get(), (size_t)n_cols * n_classes * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (ks_d) HIP_TRY(hipMemcpy(ks_d, d.dks.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
+    return TSFA_OK;
 }
 
-// validates, allocates and runs the sweep on the null stream; on return (any status) the caller releases `d`.  With
-// TSFA_OK and n_cols > 0 the kernels are queued (not waited for) and d.dcols / d.drs / d.dhc (/ d.dks) will hold the statistics.
+// validates, allocates and runs the sweep on the null stream; on return (any status) the caller owns `d`, and what the
+// sweep allocated goes with it.  With TSFA_OK and n_cols > 0 the kernels are queued (not waited for) and d.dcols / d.drs /
+// d.dhc (/ d.dks) will hold the statistics.
 static int rel_classes_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_codes,
                              int32_t n_classes, int32_t device, bool with_ks, RelClassesDev &d) {
     if (!X || !y_codes || n_rows < 1 || n_cols < 0 || ld < n_cols)
@@ -471,60 +459,56 @@ static int rel_classes_sweep(const double *X, int64_t n_rows, int64_t n_cols, in
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
         return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_relevance_classes: no such HIP device (there is no CPU path)");
     if (n_cols == 0) return TSFA_OK;
-    int rc = TSFA_OK;
     int64_t np2 = 2048;
     while (np2 < n_rows) np2 <<= 1;
     const int tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
     int64_t batch = rel_batch_columns(np2, n_cols);
     const double *Xd = X;
     int64_t ldd = ld;   // leading dimension of the matrix the kernels work on (a host matrix is staged dense)
-    REL_HIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     // a host matrix may be a row-strided VIEW (ld > n_cols) that ends with its last row: only the n_cols-wide rows are
     // the caller's -- the device copy is dense (leading dimension n_cols) and the columns between the rows are never
     // read nor written back
     if (space == TSFA_HOST) {
         ldd = n_cols;
-        REL_HIP(hipMalloc((void **)&d.dX, (size_t)n_rows * n_cols * sizeof(double)));
-        REL_HIP(hipMemcpy2D(d.dX, (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
+        HIP_TRY_MALLOC(d.dX, (size_t)n_rows * n_cols * sizeof(double));
+        HIP_TRY(hipMemcpy2D(d.dX.get(), (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
                             (size_t)n_rows, hipMemcpyHostToDevice));
-        Xd = d.dX;
+        Xd = d.dX.get();
     }
-    REL_HIP(hipMalloc((void **)&d.dkeys, (size_t)batch * np2 * sizeof(double)));
-    REL_HIP(hipMalloc((void **)&d.didx, (size_t)batch * np2 * sizeof(uint32_t)));
-    REL_HIP(hipMalloc((void **)&d.dy, (size_t)n_rows * sizeof(int32_t)));
-    REL_HIP(hipMalloc((void **)&d.drs, (size_t)n_cols * n_classes * sizeof(double)));
-    REL_HIP(hipMalloc((void **)&d.dhc, (size_t)n_cols * n_classes * sizeof(int64_t)));
-    REL_HIP(hipMalloc((void **)&d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_col)));
-    if (with_ks) REL_HIP(hipMalloc((void **)&d.dks, (size_t)n_cols * n_classes * sizeof(double)));
-    REL_HIP(hipMemcpy(d.dy, y_codes, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY_MALLOC(d.dkeys, (size_t)batch * np2 * sizeof(double));
+    HIP_TRY_MALLOC(d.didx, (size_t)batch * np2 * sizeof(uint32_t));
+    HIP_TRY_MALLOC(d.dy, (size_t)n_rows * sizeof(int32_t));
+    HIP_TRY_MALLOC(d.drs, (size_t)n_cols * n_classes * sizeof(double));
+    HIP_TRY_MALLOC(d.dhc, (size_t)n_cols * n_classes * sizeof(int64_t));
+    HIP_TRY_MALLOC(d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_col));
+    if (with_ks) HIP_TRY_MALLOC(d.dks, (size_t)n_cols * n_classes * sizeof(double));
+    HIP_TRY(hipMemcpy(d.dy.get(), y_codes, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
     {
         const size_t lds = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
-        REL_HIP(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         for (int64_t c0 = 0; c0 < n_cols; c0 += batch) {
             const int64_t nb = (n_cols - c0 < batch) ? (n_cols - c0) : batch;
-            k_rel_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, d.dkeys, d.didx, np2);
-            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(d.dkeys, d.didx, np2, tile);
-            k_rel_stats<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys, d.didx, np2, n_rows, d.dy, n_classes, c0, d.dcols, d.drs, d.dhc);
-            if (with_ks) k_rel_ks_classes<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys, d.didx, np2, n_rows, d.dy, n_classes, c0, d.dks);
-            REL_HIP(hipGetLastError());
+            k_rel_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, d.dkeys.get(), d.didx.get(), np2);
+            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(d.dkeys.get(), d.didx.get(), np2, tile);
+            k_rel_stats<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys.get(), d.didx.get(), np2, n_rows, d.dy.get(), n_classes, c0,
+                                                              d.dcols.get(), d.drs.get(), d.dhc.get());
+            if (with_ks)
+                k_rel_ks_classes<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys.get(), d.didx.get(), np2, n_rows, d.dy.get(), n_classes, c0,
+                                                                       d.dks.get());
+            HIP_TRY(hipGetLastError());
         }
     }
-done:
-    return rc;
+    return TSFA_OK;
 }
 
 // The device side of tsfa_relevance_real's sweep, as RelClassesDev
 struct RelRealDev {
-    double *dX = nullptr, *dkeys = nullptr;
-    uint32_t *didx = nullptr;
-    int32_t *dyr = nullptr, *dyp = nullptr;
-    unsigned char *dye = nullptr;
-    tsfa_relevance_real_col *dcols = nullptr;
-    void release() {
-        (void)hipFree(dX); (void)hipFree(dkeys); (void)hipFree(didx); (void)hipFree(dyr); (void)hipFree(dyp); (void)hipFree(dye);
-        (void)hipFree(dcols);
-        *this = RelRealDev();
-    }
+    DevPtr<double> dX, dkeys;
+    DevPtr<uint32_t> didx;
+    DevPtr<int32_t> dyr, dyp;
+    DevPtr<unsigned char> dye;
+    DevPtr<tsfa_relevance_real_col> dcols;
 };
 
 static int rel_real_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
@@ -536,11 +520,9 @@ extern "C" int tsfa_relevance_real(const double *X, int64_t n_rows, int64_t n_co
     if (!cols) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_real: null pointer or bad shape");
     RelRealDev d;
     int rc = rel_real_sweep(X, n_rows, n_cols, ld, space, y_rank, y_perm, y_end, device, d);
-    if (rc != TSFA_OK || n_cols == 0) { d.release(); return rc; }
-    REL_HIP(hipMemcpy(cols, d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_real_col), hipMemcpyDeviceToHost));
-done:
-    d.release();
-    return rc;
+    if (rc != TSFA_OK || n_cols == 0) return rc;
+    HIP_TRY(hipMemcpy(cols, d.dcols.get(), (size_t)n_cols * sizeof(tsfa_relevance_real_col), hipMemcpyDeviceToHost));
+    return TSFA_OK;
 }
 
 static int rel_real_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
@@ -552,53 +534,51 @@ static int rel_real_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
         return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_relevance_real: no such HIP device (there is no CPU path)");
     if (n_cols == 0) return TSFA_OK;
-    int rc = TSFA_OK;
     int64_t np2 = 2048;
     while (np2 < n_rows) np2 <<= 1;
     const int tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
     int64_t batch = rel_batch_columns(np2, n_cols);
     const double *Xd = X;
     int64_t ldd = ld;   // leading dimension of the matrix the kernels work on (a host matrix is staged dense)
-    REL_HIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     // a host matrix may be a row-strided VIEW (ld > n_cols) that ends with its last row: only the n_cols-wide rows are
     // the caller's -- the device copy is dense (leading dimension n_cols) and the columns between the rows are never
     // read nor written back
     if (space == TSFA_HOST) {
         ldd = n_cols;
-        REL_HIP(hipMalloc((void **)&d.dX, (size_t)n_rows * n_cols * sizeof(double)));
-        REL_HIP(hipMemcpy2D(d.dX, (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
+        HIP_TRY_MALLOC(d.dX, (size_t)n_rows * n_cols * sizeof(double));
+        HIP_TRY(hipMemcpy2D(d.dX.get(), (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
                             (size_t)n_rows, hipMemcpyHostToDevice));
-        Xd = d.dX;
+        Xd = d.dX.get();
     }
-    REL_HIP(hipMalloc((void **)&d.dkeys, (size_t)batch * np2 * sizeof(double)));
-    REL_HIP(hipMalloc((void **)&d.didx, (size_t)batch * np2 * sizeof(uint32_t)));
-    REL_HIP(hipMalloc((void **)&d.dyr, (size_t)n_rows * sizeof(int32_t)));
-    REL_HIP(hipMalloc((void **)&d.dyp, (size_t)n_rows * sizeof(int32_t)));
-    REL_HIP(hipMalloc((void **)&d.dye, (size_t)n_rows));
-    REL_HIP(hipMalloc((void **)&d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_real_col)));
-    REL_HIP(hipMemcpy(d.dyr, y_rank, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
-    REL_HIP(hipMemcpy(d.dyp, y_perm, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
-    REL_HIP(hipMemcpy(d.dye, y_end, (size_t)n_rows, hipMemcpyHostToDevice));
+    HIP_TRY_MALLOC(d.dkeys, (size_t)batch * np2 * sizeof(double));
+    HIP_TRY_MALLOC(d.didx, (size_t)batch * np2 * sizeof(uint32_t));
+    HIP_TRY_MALLOC(d.dyr, (size_t)n_rows * sizeof(int32_t));
+    HIP_TRY_MALLOC(d.dyp, (size_t)n_rows * sizeof(int32_t));
+    HIP_TRY_MALLOC(d.dye, (size_t)n_rows);
+    HIP_TRY_MALLOC(d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_real_col));
+    HIP_TRY(hipMemcpy(d.dyr.get(), y_rank, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.dyp.get(), y_perm, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.dye.get(), y_end, (size_t)n_rows, hipMemcpyHostToDevice));
     {
         const size_t lds_sort = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
         const size_t lds_inv = (size_t)tile * 2 * sizeof(uint32_t);
-        REL_HIP(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort));
-        REL_HIP(hipFuncSetAttribute((const void *)k_rel_inversions, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
+        HIP_TRY(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort));
+        HIP_TRY(hipFuncSetAttribute((const void *)k_rel_inversions, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
         for (int64_t c0 = 0; c0 < n_cols; c0 += batch) {
             const int64_t nb = (n_cols - c0 < batch) ? (n_cols - c0) : batch;
-            k_rel_stage_real<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, d.dyr, d.dkeys, d.didx, np2);
-            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds_sort, 0>>>(d.dkeys, d.didx, np2, tile);
-            k_rel_xties<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys, d.didx, np2, n_rows, c0, d.dcols);
+            k_rel_stage_real<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, d.dyr.get(), d.dkeys.get(), d.didx.get(), np2);
+            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds_sort, 0>>>(d.dkeys.get(), d.didx.get(), np2, tile);
+            k_rel_xties<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys.get(), d.didx.get(), np2, n_rows, c0, d.dcols.get());
             // the sorted values are dead now: their storage is the second buffer of the merge sort (np2 words per column
             // out of the np2 doubles)
-            k_rel_inversions<<<dim3((unsigned)nb), REL_NT, lds_inv, 0>>>(d.didx, (uint32_t *)d.dkeys, np2, tile, c0, d.dcols);
-            REL_HIP(hipGetLastError());
+            k_rel_inversions<<<dim3((unsigned)nb), REL_NT, lds_inv, 0>>>(d.didx.get(), (uint32_t *)d.dkeys.get(), np2, tile, c0, d.dcols.get());
+            HIP_TRY(hipGetLastError());
         }
-        k_rel_ks<<<dim3((unsigned)n_cols), REL_NT, 0, 0>>>(Xd, n_rows, ldd, d.dyp, d.dye, d.dcols);
-        REL_HIP(hipGetLastError());
+        k_rel_ks<<<dim3((unsigned)n_cols), REL_NT, 0, 0>>>(Xd, n_rows, ldd, d.dyp.get(), d.dye.get(), d.dcols.get());
+        HIP_TRY(hipGetLastError());
     }
-done:
-    return rc;
+    return TSFA_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -646,36 +626,34 @@ extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int
     if (n_cols > 0 && (!p || !route || !type)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: null output pointer");
     if (ks_d && !with_ks) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: ks_d without with_ks");
     RelClassesDev d;
-    int64_t *dcn = nullptr;
-    unsigned long long *dnh = nullptr, nh = 0ull;
+    unsigned long long nh = 0ull;
     std::vector<int64_t> class_n;
     int rc = rel_classes_sweep(X, n_rows, n_cols, ld, space, y_codes, n_classes, device, with_ks != 0, d);
-    if (rc != TSFA_OK || n_cols == 0) { d.release(); return rc; }
+    if (rc != TSFA_OK || n_cols == 0) return rc;
     class_n.assign((size_t)n_classes, 0);
     for (int64_t r = 0; r < n_rows; ++r) ++class_n[(size_t)y_codes[r]];
-    REL_HIP(hipMalloc((void **)&dcn, (size_t)n_classes * sizeof(int64_t)));
-    REL_HIP(hipMalloc((void **)&dnh, sizeof(unsigned long long)));
-    REL_HIP(hipMemcpy(dcn, class_n.data(), (size_t)n_classes * sizeof(int64_t), hipMemcpyHostToDevice));
-    REL_HIP(hipMemset(dnh, 0, sizeof(unsigned long long)));
+    DevPtr<int64_t> dcn;
+    DevPtr<unsigned long long> dnh;
+    HIP_TRY_MALLOC(dcn, (size_t)n_classes * sizeof(int64_t));
+    HIP_TRY_MALLOC(dnh, sizeof(unsigned long long));
+    HIP_TRY(hipMemcpy(dcn.get(), class_n.data(), (size_t)n_classes * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dnh.get(), 0, sizeof(unsigned long long)));
     {
         const int64_t cells = n_cols * n_classes;
         k_tails_classes<<<dim3((unsigned)((cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(
-            d.dcols, d.drs, dcn, n_rows, n_cols, n_classes, with_ks, p, route, type, dnh);
-        REL_HIP(hipGetLastError());
+            d.dcols.get(), d.drs.get(), dcn.get(), n_rows, n_cols, n_classes, with_ks, p, route, type, dnh.get());
+        HIP_TRY(hipGetLastError());
         k_tails_fisher<<<dim3((unsigned)((cells + RT_THREADS / 64 - 1) / (RT_THREADS / 64))), RT_THREADS, 0, 0>>>(
-            d.dcols, d.dhc, dcn, n_rows, n_cols, n_classes, p);
-        REL_HIP(hipGetLastError());
+            d.dcols.get(), d.dhc.get(), dcn.get(), n_rows, n_cols, n_classes, p);
+        HIP_TRY(hipGetLastError());
     }
-    REL_HIP(hipMemcpy(&nh, dnh, sizeof(nh), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&nh, dnh.get(), sizeof(nh), hipMemcpyDeviceToHost));
     if (n_host_cells) *n_host_cells = (int64_t)nh;
-    if (cols) REL_HIP(hipMemcpy(cols, d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_col), hipMemcpyDeviceToHost));
-    if (rank_sums) REL_HIP(hipMemcpy(rank_sums, d.drs, (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
-    if (hi_counts) REL_HIP(hipMemcpy(hi_counts, d.dhc, (size_t)n_cols * n_classes * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (ks_d) REL_HIP(hipMemcpy(ks_d, d.dks, (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(dcn); (void)hipFree(dnh);
-    d.release();
-    return rc;
+    if (cols) HIP_TRY(hipMemcpy(cols, d.dcols.get(), (size_t)n_cols * sizeof(tsfa_relevance_col), hipMemcpyDeviceToHost));
+    if (rank_sums) HIP_TRY(hipMemcpy(rank_sums, d.drs.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
+    if (hi_counts) HIP_TRY(hipMemcpy(hi_counts, d.dhc.get(), (size_t)n_cols * n_classes * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (ks_d) HIP_TRY(hipMemcpy(ks_d, d.dks.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
+    return TSFA_OK;
 }
 
 extern "C" int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
@@ -685,21 +663,19 @@ extern "C" int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_
     if (n_host_cells) *n_host_cells = 0;
     if (n_cols > 0 && (!p || !route || !type)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_real: null output pointer");
     RelRealDev d;
-    unsigned long long *dnh = nullptr, nh = 0ull;
+    unsigned long long nh = 0ull;
     int rc = rel_real_sweep(X, n_rows, n_cols, ld, space, y_rank, y_perm, y_end, device, d);
-    if (rc != TSFA_OK || n_cols == 0) { d.release(); return rc; }
-    REL_HIP(hipMalloc((void **)&dnh, sizeof(unsigned long long)));
-    REL_HIP(hipMemset(dnh, 0, sizeof(unsigned long long)));
-    k_tails_real<<<dim3((unsigned)((n_cols + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(d.dcols, n_rows, n_cols, ytie, y0, y1, p,
-                                                                                              route, type, dnh);
-    REL_HIP(hipGetLastError());
-    REL_HIP(hipMemcpy(&nh, dnh, sizeof(nh), hipMemcpyDeviceToHost));
+    if (rc != TSFA_OK || n_cols == 0) return rc;
+    DevPtr<unsigned long long> dnh;
+    HIP_TRY_MALLOC(dnh, sizeof(unsigned long long));
+    HIP_TRY(hipMemset(dnh.get(), 0, sizeof(unsigned long long)));
+    k_tails_real<<<dim3((unsigned)((n_cols + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(d.dcols.get(), n_rows, n_cols, ytie, y0, y1, p,
+                                                                                              route, type, dnh.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&nh, dnh.get(), sizeof(nh), hipMemcpyDeviceToHost));
     if (n_host_cells) *n_host_cells = (int64_t)nh;
-    if (cols) REL_HIP(hipMemcpy(cols, d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_real_col), hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(dnh);
-    d.release();
-    return rc;
+    if (cols) HIP_TRY(hipMemcpy(cols, d.dcols.get(), (size_t)n_cols * sizeof(tsfa_relevance_real_col), hipMemcpyDeviceToHost));
+    return TSFA_OK;
 }
 
 // masked sort keys of the p-value matrix (rt_fdr_key): what k_rel_stage / k_rel_sort then order, one key column per table
@@ -759,34 +735,32 @@ extern "C" int tsfa_relevance_fdr(const double *p, const unsigned char *type, in
     const int tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
     const int64_t batch = rel_batch_columns(np2, n_tables);
     const int64_t cells = n_cols * n_tables;
-    double *dmask = nullptr, *dkeys = nullptr;
-    uint32_t *didx = nullptr;
-    REL_HIP(hipSetDevice(device));
-    REL_HIP(hipMalloc((void **)&dmask, (size_t)cells * sizeof(double)));
-    REL_HIP(hipMalloc((void **)&dkeys, (size_t)batch * np2 * sizeof(double)));
-    REL_HIP(hipMalloc((void **)&didx, (size_t)batch * np2 * sizeof(uint32_t)));
+    HIP_TRY(hipSetDevice(device));
+    DevPtr<double> dmask, dkeys;
+    DevPtr<uint32_t> didx;
+    HIP_TRY_MALLOC(dmask, (size_t)cells * sizeof(double));
+    HIP_TRY_MALLOC(dkeys, (size_t)batch * np2 * sizeof(double));
+    HIP_TRY_MALLOC(didx, (size_t)batch * np2 * sizeof(uint32_t));
     {
         const size_t lds = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
-        REL_HIP(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_fdr_keys<<<dim3((unsigned)((cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(p, type, n_cols, n_tables, dmask);
-        REL_HIP(hipGetLastError());
+        HIP_TRY(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k_fdr_keys<<<dim3((unsigned)((cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(p, type, n_cols, n_tables, dmask.get());
+        HIP_TRY(hipGetLastError());
         for (int64_t t0 = 0; t0 < n_tables; t0 += batch) {
             const int64_t nb = (n_tables - t0 < batch) ? (n_tables - t0) : batch;
             // the key matrix is [n_cols, n_tables]: a table is a column of it, its rows are the feature columns
-            k_rel_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dmask, n_cols, n_tables, t0, dkeys, didx, np2);
-            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(dkeys, didx, np2, tile);
-            k_fdr_stepup<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dkeys, didx, np2, type, n_cols, n_tables, (int)t0, alpha, c_m,
+            k_rel_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dmask.get(), n_cols, n_tables, t0, dkeys.get(), didx.get(), np2);
+            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(dkeys.get(), didx.get(), np2, tile);
+            k_fdr_stepup<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dkeys.get(), didx.get(), np2, type, n_cols, n_tables, (int)t0, alpha, c_m,
                                                               relevant_per_table);
-            REL_HIP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         k_fdr_combine<<<dim3((unsigned)((n_cols + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(
             p, relevant_per_table, type, n_cols, n_tables, multiclass, n_significant, relevant, n_significant_out, p_min);
-        REL_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    REL_HIP(hipDeviceSynchronize());
-done:
-    (void)hipFree(dmask); (void)hipFree(dkeys); (void)hipFree(didx);
-    return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return TSFA_OK;
 }
 
 // one workgroup: slice counts, their exclusive scan (thread 0, as the KS kernels above), the writes
@@ -810,16 +784,15 @@ extern "C" int tsfa_compact_mask(const unsigned char *mask, int64_t n, int32_t *
     if (n >= (1ll << 31)) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_compact_mask: more than 2^31 entries");
     int rc = rel_check_device(device, "tsfa_compact_mask");
     if (rc || n == 0) return rc;
-    long long *dcount = nullptr, got = 0;
-    REL_HIP(hipSetDevice(device));
-    REL_HIP(hipMalloc((void **)&dcount, sizeof(long long)));
-    k_compact_mask<<<1, REL_NT, 0, 0>>>(mask, n, indices, dcount);
-    REL_HIP(hipGetLastError());
-    REL_HIP(hipMemcpy(&got, dcount, sizeof(got), hipMemcpyDeviceToHost));
+    long long got = 0;
+    HIP_TRY(hipSetDevice(device));
+    DevPtr<long long> dcount;
+    HIP_TRY_MALLOC(dcount, sizeof(long long));
+    k_compact_mask<<<1, REL_NT, 0, 0>>>(mask, n, indices, dcount.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&got, dcount.get(), sizeof(got), hipMemcpyDeviceToHost));
     *count = (int64_t)got;
-done:
-    (void)hipFree(dcount);
-    return rc;
+    return TSFA_OK;
 }
 
 // k_gather_columns with the indices read from HBM, a leading dimension of the destination, and a flag for an index
@@ -842,17 +815,16 @@ extern "C" int tsfa_gather_columns_device(const double *X, int64_t n_rows, int64
         return tsfa_fail(TSFA_ERR_INVALID, "tsfa_gather_columns_device: null pointer or bad shape");
     int rc = rel_check_device(device, "tsfa_gather_columns_device");
     if (rc || n_rows == 0 || n_sel == 0) return rc;
-    int *dbad = nullptr, bad = 0;
-    REL_HIP(hipSetDevice(device));
-    REL_HIP(hipMalloc((void **)&dbad, sizeof(int)));
-    REL_HIP(hipMemset(dbad, 0, sizeof(int)));
-    k_gather_columns_device<<<2048, 256, 0, 0>>>(X, n_rows, ld, cols, n_sel, out, ld_out, dbad);
-    REL_HIP(hipGetLastError());
-    REL_HIP(hipMemcpy(&bad, dbad, sizeof(int), hipMemcpyDeviceToHost));
-    if (bad) rc = tsfa_fail(TSFA_ERR_INVALID, "tsfa_gather_columns_device: column index out of range");
-done:
-    (void)hipFree(dbad);
-    return rc;
+    int bad = 0;
+    HIP_TRY(hipSetDevice(device));
+    DevPtr<int> dbad;
+    HIP_TRY_MALLOC(dbad, sizeof(int));
+    HIP_TRY(hipMemset(dbad.get(), 0, sizeof(int)));
+    k_gather_columns_device<<<2048, 256, 0, 0>>>(X, n_rows, ld, cols, n_sel, out, ld_out, dbad.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&bad, dbad.get(), sizeof(int), hipMemcpyDeviceToHost));
+    if (bad) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_gather_columns_device: column index out of range");
+    return TSFA_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -928,55 +900,53 @@ extern "C" int tsfa_impute(double *X, int64_t n_rows, int64_t n_cols, int64_t ld
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
         return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_impute: no such HIP device (there is no CPU path)");
     if (n_cols == 0 || n_rows == 0) return TSFA_OK;
-    int rc = TSFA_OK;
     int64_t np2 = 2048;
     while (np2 < n_rows) np2 <<= 1;
     const int tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
     const int64_t batch = rel_batch_columns(np2, n_cols);
-    double *dX = nullptr, *dkeys = nullptr, *dstat = nullptr;
-    uint32_t *didx = nullptr;
-    int *dcnt = nullptr;
+    DevPtr<double> dX, dkeys, dstat;
+    DevPtr<uint32_t> didx;
+    DevPtr<int> dcnt;
     double *Xd = X;
     int64_t ldd = ld;   // leading dimension of the matrix the kernels work on
-    REL_HIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     // a host matrix may be a row-strided VIEW (ld > n_cols) that ends with its last row: only the n_cols-wide rows are
     // the caller's -- the device copy is dense (leading dimension n_cols) and the columns between the rows are never
     // read nor written back
     if (space == TSFA_HOST) {
         ldd = n_cols;
-        REL_HIP(hipMalloc((void **)&dX, (size_t)n_rows * n_cols * sizeof(double)));
-        REL_HIP(hipMemcpy2D(dX, (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
+        HIP_TRY_MALLOC(dX, (size_t)n_rows * n_cols * sizeof(double));
+        HIP_TRY(hipMemcpy2D(dX.get(), (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
                             (size_t)n_rows, hipMemcpyHostToDevice));
-        Xd = dX;
+        Xd = dX.get();
     }
-    REL_HIP(hipMalloc((void **)&dkeys, (size_t)batch * np2 * sizeof(double)));
-    REL_HIP(hipMalloc((void **)&didx, (size_t)batch * np2 * sizeof(uint32_t)));
-    REL_HIP(hipMalloc((void **)&dcnt, (size_t)n_cols * sizeof(int)));
-    REL_HIP(hipMalloc((void **)&dstat, (size_t)3 * n_cols * sizeof(double)));
+    HIP_TRY_MALLOC(dkeys, (size_t)batch * np2 * sizeof(double));
+    HIP_TRY_MALLOC(didx, (size_t)batch * np2 * sizeof(uint32_t));
+    HIP_TRY_MALLOC(dcnt, (size_t)n_cols * sizeof(int));
+    HIP_TRY_MALLOC(dstat, (size_t)3 * n_cols * sizeof(double));
     {
         const size_t lds = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
-        REL_HIP(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         for (int64_t c0 = 0; c0 < n_cols; c0 += batch) {
             const int64_t nb = (n_cols - c0 < batch) ? (n_cols - c0) : batch;
-            k_imp_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, dkeys, didx, np2, dcnt);
-            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(dkeys, didx, np2, tile);
-            k_imp_stats<<<dim3((unsigned)((nb + 63) / 64)), 64, 0, 0>>>(dkeys, np2, dcnt, c0, nb, dstat, dstat + n_cols, dstat + 2 * n_cols);
-            REL_HIP(hipGetLastError());
+            k_imp_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, dkeys.get(), didx.get(), np2, dcnt.get());
+            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(dkeys.get(), didx.get(), np2, tile);
+            k_imp_stats<<<dim3((unsigned)((nb + 63) / 64)), 64, 0, 0>>>(dkeys.get(), np2, dcnt.get(), c0, nb, dstat.get(), dstat.get() + n_cols,
+                                                                        dstat.get() + 2 * n_cols);
+            HIP_TRY(hipGetLastError());
         }
-        k_imp_apply<<<2048, 256, 0, 0>>>(Xd, n_rows, ldd, n_cols, dstat, dstat + n_cols, dstat + 2 * n_cols);
-        REL_HIP(hipGetLastError());
+        k_imp_apply<<<2048, 256, 0, 0>>>(Xd, n_rows, ldd, n_cols, dstat.get(), dstat.get() + n_cols, dstat.get() + 2 * n_cols);
+        HIP_TRY(hipGetLastError());
     }
-    if (col_max) REL_HIP(hipMemcpy(col_max, dstat, (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
-    if (col_min) REL_HIP(hipMemcpy(col_min, dstat + n_cols, (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
-    if (col_median) REL_HIP(hipMemcpy(col_median, dstat + 2 * n_cols, (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
-    if (finite_count) REL_HIP(hipMemcpy(finite_count, dcnt, (size_t)n_cols * sizeof(int), hipMemcpyDeviceToHost));
+    if (col_max) HIP_TRY(hipMemcpy(col_max, dstat.get(), (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
+    if (col_min) HIP_TRY(hipMemcpy(col_min, dstat.get() + n_cols, (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
+    if (col_median) HIP_TRY(hipMemcpy(col_median, dstat.get() + 2 * n_cols, (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
+    if (finite_count) HIP_TRY(hipMemcpy(finite_count, dcnt.get(), (size_t)n_cols * sizeof(int), hipMemcpyDeviceToHost));
     if (space == TSFA_HOST)
-        REL_HIP(hipMemcpy2D(X, (size_t)ld * sizeof(double), dX, (size_t)n_cols * sizeof(double), (size_t)n_cols * sizeof(double),
+        HIP_TRY(hipMemcpy2D(X, (size_t)ld * sizeof(double), dX.get(), (size_t)n_cols * sizeof(double), (size_t)n_cols * sizeof(double),
                             (size_t)n_rows, hipMemcpyDeviceToHost));
-    REL_HIP(hipDeviceSynchronize());
-done:
-    (void)hipFree(dX); (void)hipFree(dkeys); (void)hipFree(didx); (void)hipFree(dcnt); (void)hipFree(dstat);
-    return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return TSFA_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1015,30 +985,27 @@ extern "C" int tsfa_device_alloc(void **ptr, size_t bytes, int32_t device) {
     *ptr = nullptr;
     int rc = rel_check_device(device, "tsfa_device_alloc");
     if (rc) return rc;
-    REL_HIP(hipSetDevice(device));
-    REL_HIP(hipMalloc(ptr, bytes ? bytes : 1));
-done:
-    return rc;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMalloc(ptr, bytes ? bytes : 1));
+    return TSFA_OK;
 }
 
 extern "C" int tsfa_device_free(void *ptr, int32_t device) {
     if (!ptr) return TSFA_OK;
     int rc = rel_check_device(device, "tsfa_device_free");
     if (rc) return rc;
-    REL_HIP(hipSetDevice(device));
-    REL_HIP(hipFree(ptr));
-done:
-    return rc;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipFree(ptr));
+    return TSFA_OK;
 }
 
 extern "C" int tsfa_device_copy(void *dst, const void *src, size_t bytes, int32_t to_device, int32_t device) {
     if ((!dst || !src) && bytes) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_device_copy: null pointer");
     int rc = rel_check_device(device, "tsfa_device_copy");
     if (rc || !bytes) return rc;
-    REL_HIP(hipSetDevice(device));
-    REL_HIP(hipMemcpy(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
-done:
-    return rc;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMemcpy(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
+    return TSFA_OK;
 }
 
 extern "C" int tsfa_gather_columns(const double *X, int64_t n_rows, int64_t ld, const int32_t *cols, int64_t n_sel,
@@ -1049,18 +1016,16 @@ extern "C" int tsfa_gather_columns(const double *X, int64_t n_rows, int64_t ld, 
     if (rc || n_rows == 0 || n_sel == 0) return rc;
     for (int64_t c = 0; c < n_sel; ++c)
         if (cols[c] < 0 || cols[c] >= ld) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_gather_columns: column index out of range");
-    int32_t *dcols = nullptr;
-    double *dout = nullptr;
-    REL_HIP(hipSetDevice(device));
-    REL_HIP(hipMalloc((void **)&dcols, (size_t)n_sel * sizeof(int32_t)));
-    REL_HIP(hipMalloc((void **)&dout, (size_t)n_rows * n_sel * sizeof(double)));
-    REL_HIP(hipMemcpy(dcols, cols, (size_t)n_sel * sizeof(int32_t), hipMemcpyHostToDevice));
-    k_gather_columns<<<2048, 256, 0, 0>>>(X, n_rows, ld, dcols, n_sel, dout);
-    REL_HIP(hipGetLastError());
-    REL_HIP(hipMemcpy(out_host, dout, (size_t)n_rows * n_sel * sizeof(double), hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(dcols); (void)hipFree(dout);
-    return rc;
+    DevPtr<int32_t> dcols;
+    DevPtr<double> dout;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY_MALLOC(dcols, (size_t)n_sel * sizeof(int32_t));
+    HIP_TRY_MALLOC(dout, (size_t)n_rows * n_sel * sizeof(double));
+    HIP_TRY(hipMemcpy(dcols.get(), cols, (size_t)n_sel * sizeof(int32_t), hipMemcpyHostToDevice));
+    k_gather_columns<<<2048, 256, 0, 0>>>(X, n_rows, ld, dcols.get(), n_sel, dout.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out_host, dout.get(), (size_t)n_rows * n_sel * sizeof(double), hipMemcpyDeviceToHost));
+    return TSFA_OK;
 }
 
 extern "C" int tsfa_scatter_columns(double *dst, int64_t ld_dst, const int32_t *cols, const double *src, int64_t n_rows,
@@ -1071,16 +1036,14 @@ extern "C" int tsfa_scatter_columns(double *dst, int64_t ld_dst, const int32_t *
     if (rc || n_rows == 0 || n_src == 0) return rc;
     for (int64_t c = 0; c < n_src; ++c)
         if (cols[c] < 0 || cols[c] >= ld_dst) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_scatter_columns: column index out of range");
-    int32_t *dcols = nullptr;
-    REL_HIP(hipSetDevice(device));
-    REL_HIP(hipMalloc((void **)&dcols, (size_t)n_src * sizeof(int32_t)));
-    REL_HIP(hipMemcpy(dcols, cols, (size_t)n_src * sizeof(int32_t), hipMemcpyHostToDevice));
-    k_scatter_columns<<<2048, 256, 0, 0>>>(dst, ld_dst, dcols, src, n_rows, n_src);
-    REL_HIP(hipGetLastError());
-    REL_HIP(hipDeviceSynchronize());
-done:
-    (void)hipFree(dcols);
-    return rc;
+    DevPtr<int32_t> dcols;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY_MALLOC(dcols, (size_t)n_src * sizeof(int32_t));
+    HIP_TRY(hipMemcpy(dcols.get(), cols, (size_t)n_src * sizeof(int32_t), hipMemcpyHostToDevice));
+    k_scatter_columns<<<2048, 256, 0, 0>>>(dst, ld_dst, dcols.get(), src, n_rows, n_src);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return TSFA_OK;
 }
 
 // Pr(D >= h / lcm(m, n)) for the two-sided two-sample Kolmogorov-Smirnov statistic, m != n: the proportion of lattice
