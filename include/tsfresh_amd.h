@@ -365,6 +365,39 @@ int tsfa_pack_dense(const void *x, int32_t x_type, int64_t n_batch, int64_t n_ch
                     int64_t stride_channel, int64_t stride_time, const void *lengths, int32_t lengths_type, void *values_out,
                     int64_t channel_stride_out, int64_t *offsets_out, int32_t *flags_out, int32_t device, void *stream);
 
+/* Times packer: the per-sample `times` of tsfa_extract_timed / tsfa_extract_windows (float64 hours since the series' first
+ * stamp, what linear_trend_timewise regresses on) for a batch whose clock is an array in device memory, written in the
+ * ragged layout tsfa_pack_dense wrote for the samples of the same batch.  Replaces the host's pandas arithmetic on a
+ * DatetimeIndex (feature_extraction/data.py: _hours_since_first) for a batch that is an array.
+ *   t, t_type        logical (n_batch, n_time) stamps with non-negative element strides; stride_batch 0: one clock shared by
+ *                    every series.  TSFA_I64: integer ticks since any epoch, ticks_per_second of them per second (1, 10^3,
+ *                    10^6 or 10^9: numpy's datetime64[s|ms|us|ns] viewed as int64).  TSFA_F64: seconds, ticks_per_second is
+ *                    ignored.
+ *   offsets          the n_batch + 1 int64 tsfa_pack_dense wrote (a device pointer).  A series' length is the difference of
+ *                    its offsets (clamped into [0, n_time]); no stamp at or beyond a series' length is read.
+ *   hours_out        hours_out[offsets[b] + i], i < len(b); nothing outside [offsets[0], offsets[n_batch]) is written.
+ *                      ticks:   (double)(t[b,i] - t[b,0]) / (double)ticks_per_second / 3600.0
+ *                      seconds: (t[b,i] - t[b,0]) / 3600.0
+ *                    The subtraction is in int64, there is one correctly rounded int64 -> float64 conversion and two IEEE
+ *                    divisions, no reciprocal multiply: bit for bit pandas >= 2's
+ *                    `(index - index[0]).total_seconds() / 3600.0`, where total_seconds is `asi8 / periods_per_second`
+ *                    (pandas 1.x multiplied by 1e-9 and differs in the last bits).  Stamps need not ascend: the hours of an
+ *                    earlier stamp are negative.  A tick difference that overflows int64 wraps: stamps further apart than
+ *                    2^63 - 1 ticks are the caller's problem, as are infinite seconds.
+ *   flags_out        one int32 the call ORs into (the caller clears it; it may be the word tsfa_pack_dense used):
+ *                    TSFA_DENSE_BAD_TIME a NaT tick (INT64_MIN) or a NaN second inside a series' length; its hours are NaN,
+ *                    and every sample of a series whose FIRST stamp is missing has NaN hours.
+ *   stream           as in tsfa_pack_dense.  All pointers are device pointers on `device`; nothing is allocated.
+ * One kernel: PD_ROW_CHUNK stamps of one series per work item, consecutive lanes on consecutive stamps, no LDS, no barrier,
+ * one atomic OR per wavefront at most.
+ * TSFA_ERR_INVALID: a null pointer, another type, a ticks_per_second outside the four values, a negative stride, a
+ * dimension below 1 or an extent beyond 2^62 elements.  TSFA_ERR_TOO_LONG: n_time > 33 554 431.  TSFA_ERR_NO_DEVICE: no HIP
+ * device. */
+#define TSFA_DENSE_BAD_TIME 16
+int tsfa_pack_times(const void *t, int32_t t_type, int64_t ticks_per_second, int64_t n_batch, int64_t n_time,
+                    int64_t stride_batch, int64_t stride_time, const int64_t *offsets, double *hours_out, int32_t *flags_out,
+                    int32_t device, void *stream);
+
 /* Window builder: the rolled (forecasting) layout of one pack, built on the device from the pack's offsets.  Replaces, for a
  * frame packed by tsfa_pack_device / tsfa_pack_set_*, the host's enumeration of n_series x n_shifts window candidates
  * (tsfresh/utilities/dataframe_functions.py:340-358, _roll_out_time_series, for all shifts at once) and the upload of the

@@ -24,6 +24,7 @@ TSFA_I8, TSFA_I16, TSFA_U8, TSFA_U16, TSFA_U32, TSFA_U64, TSFA_BOOL = 4, 5, 6, 7
 TSFA_F16, TSFA_BF16 = 11, 12   # tsfa_pack_dense only
 TSFA_PACK_UNSORTED, TSFA_PACK_VALUE_NAN, TSFA_PACK_IN_ORDER = 1, 2, 4
 TSFA_DENSE_BAD_LENGTH = 8
+TSFA_DENSE_BAD_TIME = 16   # tsfa_pack_times
 TSFA_PACK_KEEP_SORT = 1
 TSFA_HOST, TSFA_DEVICE = 0, 1
 # enum tsfa_route: who evaluates the tail of a p-value cell (tsfa_relevance_tails_*)
@@ -64,6 +65,7 @@ EXPORTS = (
     "tsfa_pack_set_values",
     "tsfa_pack_set_destroy",
     "tsfa_pack_dense",
+    "tsfa_pack_times",
     "tsfa_roll_windows",
     "tsfa_windows_n_windows",
     "tsfa_windows_starts",
@@ -544,6 +546,31 @@ def pack_dense(x_ptr, x_type, shape, strides, values_ptr, channel_stride_out, of
         ctypes.c_void_p(stream) if stream else None))
 
 
+def _bind_pack_times_api(lib):
+    """The tsfa_pack_times prototype, bound on first use (a diagnostics library given through TSFA_LIB may predate it)."""
+    if getattr(lib, "_tsfa_pack_times_bound", False):
+        return
+    lib.tsfa_pack_times.argtypes = [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_int64] * 5 + [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+    lib.tsfa_pack_times.restype = ctypes.c_int
+    lib._tsfa_pack_times_bound = True
+
+
+def pack_times(t_ptr, t_type, ticks_per_second, shape, strides, offsets_ptr, hours_ptr, flags_ptr, device=0, stream=None):
+    """tsfa_pack_times on raw device pointers (ints): the stamps of logical `shape` (n_batch, n_time) and element `strides`
+    at t_ptr -- TSFA_I64 ticks, ticks_per_second of them per second, or TSFA_F64 seconds -- become float64 hours since each
+    series' first stamp at hours_ptr, in the ragged layout of the n_batch + 1 int64 offsets `pack_dense` wrote at
+    offsets_ptr.  flags_ptr: one int32 the call ORs TSFA_DENSE_BAD_TIME into (a NaT / NaN stamp inside a length).
+    stream: a hipStream_t as an int (the call only enqueues) or None (the call returns when the work is done)."""
+    lib = load()
+    _bind_pack_times_api(lib)
+    (n_batch, n_time), (sb, st) = shape, strides
+    _check(lib, lib.tsfa_pack_times(
+        ctypes.c_void_p(t_ptr), int(t_type), int(ticks_per_second), int(n_batch), int(n_time), int(sb), int(st),
+        ctypes.c_void_p(offsets_ptr), ctypes.c_void_p(hours_ptr), ctypes.c_void_p(flags_ptr), int(device),
+        ctypes.c_void_p(stream) if stream else None))
+
+
 class DensePack:
     """One channel of a tsfa_pack_dense result, as `Plan.extract_into(pack=...)` and `extract_parts_into(pack=...)` read a
     pack: the channel's stretch of the value buffer, the offsets every channel shares, the series count.  A view: the
@@ -914,30 +941,35 @@ class Plan:
             dm.free()
         return out
 
-    def extract_windows_into(self, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=0):
+    def extract_windows_into(self, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=0, times_ptr=None):
         """Device pointers (ints) in, columns [col0, col0 + n_cols) of the DeviceMatrix / BorrowedMatrix `matrix` out: window
         w is the view [starts[w], ends[w]) of the value buffer at values_ptr (TSFA_F32 / TSFA_F64), all of it on the matrix'
-        device -- one tsfa_extract_windows call with TSFA_DEVICE pointers, nothing is uploaded and the rows stay in HBM."""
+        device -- one tsfa_extract_windows call with TSFA_DEVICE pointers, nothing is uploaded and the rows stay in HBM.
+        times_ptr: float64 hours laid out like the value buffer (`pack_times`), for plans that hold linear_trend_timewise
+        columns; the kernel rebases them on each window's first stamp."""
         n_windows = int(n_windows)
         if matrix.device != self.device or matrix.shape[0] != n_windows or col0 < 0 or col0 + self.n_cols > matrix.shape[1]:
             raise ValueError("the device matrix does not hold [n_windows, col0 + n_cols] cells on the plan's device")
         if n_windows == 0 or self.n_cols == 0:
             return
         _check(self._lib, self._lib.tsfa_extract_windows(
-            self._h, ctypes.c_void_p(values_ptr), int(values_type), None, ctypes.c_void_p(starts_ptr), ctypes.c_void_p(ends_ptr),
-            n_windows, ctypes.c_void_p(matrix.ptr + 8 * col0), matrix.ld, TSFA_DEVICE, None))
+            self._h, ctypes.c_void_p(values_ptr), int(values_type), _ptr(times_ptr), ctypes.c_void_p(starts_ptr),
+            ctypes.c_void_p(ends_ptr), n_windows, ctypes.c_void_p(matrix.ptr + 8 * col0), matrix.ld, TSFA_DEVICE, None))
 
-    def extract_into(self, values, offsets, matrix, col0=0, times=None, pack=None):
+    def extract_into(self, values, offsets, matrix, col0=0, times=None, pack=None, times_ptr=None):
         """Host arrays in, columns [col0, col0 + n_cols) of the DeviceMatrix `matrix` out: the samples are copied to the
         device once and the feature rows stay there (tsfa_extract / tsfa_extract_timed with TSFA_DEVICE pointers).
-        pack: a DevicePack on the matrix' device instead of `values` / `offsets` -- nothing is uploaded."""
+        pack: a DevicePack on the matrix' device instead of `values` / `offsets` -- nothing is uploaded.
+        times_ptr (with pack): a device pointer (int) to float64 hours laid out like the pack's samples (`pack_times`)."""
+        if times_ptr is not None and pack is None:
+            raise ValueError("times_ptr goes with pack=: host arrays bring their times as `times`")
         if pack is not None:
             if pack.device != matrix.device or matrix.shape[0] != pack.n_series or col0 < 0 or col0 + self.n_cols > matrix.shape[1]:
                 raise ValueError("the device matrix does not hold [n_series, col0 + n_cols] cells on the pack's device")
             if pack.n_series == 0 or self.n_cols == 0:
                 return
             _check(self._lib, self._lib.tsfa_extract_timed(
-                self._h, ctypes.c_void_p(pack.values_ptr), pack.values_type, None, ctypes.c_void_p(pack.offsets_ptr),
+                self._h, ctypes.c_void_p(pack.values_ptr), pack.values_type, _ptr(times_ptr), ctypes.c_void_p(pack.offsets_ptr),
                 pack.n_series, ctypes.c_void_p(matrix.ptr + 8 * col0), matrix.ld, TSFA_DEVICE, None))
             return
         values = np.ascontiguousarray(values)
@@ -1029,14 +1061,17 @@ class DeviceMatrix:
         return out
 
 
-def extract_parts_into(parts, values, offsets, matrix, col0=0, times=None, pack=None):
+def extract_parts_into(parts, values, offsets, matrix, col0=0, times=None, pack=None, times_ptr=None):
     """Several native plans over ONE upload of the samples: parts = [(Plan, column indices in the caller's order)].  Every
     part's block is extracted into a transient device matrix and scattered (tsfa_scatter_columns) into columns
     col0 + cols of `matrix` (a DeviceMatrix): the composite plans of feature_extraction/extraction.py (several ADF lag
     selections, more than 128 CWT columns) without an upload per part, and with the matrix staying in HBM.
-    pack: a DevicePack on the matrix' device instead of `values` / `offsets` -- no upload at all."""
+    pack: a DevicePack on the matrix' device instead of `values` / `offsets` -- no upload at all; times_ptr: with it, a
+    device pointer (int) to float64 hours laid out like the pack's samples (`pack_times`), handed to every part."""
     lib = load()
     _bind_device_api(lib)
+    if times_ptr is not None and pack is None:
+        raise ValueError("times_ptr goes with pack=: host arrays bring their times as `times`")
     if pack is not None:
         if pack.device != matrix.device or pack.n_series != matrix.shape[0]:
             raise ValueError("the device matrix does not hold the pack's series on the pack's device")
@@ -1047,7 +1082,7 @@ def extract_parts_into(parts, values, offsets, matrix, col0=0, times=None, pack=
             for plan, cols in parts:
                 if plan.n_cols == 0:
                     continue
-                _check(lib, lib.tsfa_extract_timed(plan._h, ctypes.c_void_p(pack.values_ptr), pack.values_type, None,
+                _check(lib, lib.tsfa_extract_timed(plan._h, ctypes.c_void_p(pack.values_ptr), pack.values_type, _ptr(times_ptr),
                                                    ctypes.c_void_p(pack.offsets_ptr), pack.n_series, ctypes.c_void_p(tmp.ptr),
                                                    plan.n_cols, TSFA_DEVICE, None))
                 idx = np.ascontiguousarray(np.asarray(cols, dtype=np.int64) + int(col0), dtype=np.int32)
@@ -1094,10 +1129,11 @@ def extract_parts_into(parts, values, offsets, matrix, col0=0, times=None, pack=
             tmp.free()
 
 
-def extract_parts_windows_into(parts, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=0):
+def extract_parts_windows_into(parts, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=0, times_ptr=None):
     """The window twin of `extract_parts_into(pack=...)`: several native plans over the same device buffers.  Every part's
     block of the windows [starts[w], ends[w]) of the value buffer at values_ptr is extracted into a transient device matrix
-    and scattered (tsfa_scatter_columns) into columns col0 + cols of `matrix` (a DeviceMatrix or a BorrowedMatrix)."""
+    and scattered (tsfa_scatter_columns) into columns col0 + cols of `matrix` (a DeviceMatrix or a BorrowedMatrix).
+    times_ptr: as in `Plan.extract_windows_into`, handed to every part."""
     lib = load()
     _bind_device_api(lib)
     n_windows = int(n_windows)
@@ -1113,7 +1149,8 @@ def extract_parts_windows_into(parts, values_ptr, values_type, starts_ptr, ends_
             if plan.n_cols == 0:
                 continue
             plan.extract_windows_into(values_ptr, values_type, starts_ptr, ends_ptr, n_windows,
-                                      BorrowedMatrix(tmp.ptr, n_windows, plan.n_cols, matrix.device, owner=tmp))
+                                      BorrowedMatrix(tmp.ptr, n_windows, plan.n_cols, matrix.device, owner=tmp),
+                                      times_ptr=times_ptr)
             idx = np.ascontiguousarray(np.asarray(cols, dtype=np.int64) + int(col0), dtype=np.int32)
             _check(lib, lib.tsfa_scatter_columns(ctypes.c_void_p(matrix.ptr), matrix.ld, idx.ctypes.data_as(ctypes.c_void_p),
                                                  ctypes.c_void_p(tmp.ptr), n_windows, plan.n_cols, matrix.device))

@@ -1352,6 +1352,8 @@ TSFA_DEV void fam_basic_series(const BT &b0, XS xs, int n, const TsfaSpec *specs
                 const double t_first = (times != nullptr) ? times[0] : 0.0;
                 if (times != nullptr && n >= 2)
                     blk_linregress_xy(b, n, [=](int i) { return times[i] - t_first; }, [=](int i) { return xs[i]; }, ltt5);
+                else if (times != nullptr)
+                    ltt5[TSFA_ATTR_RVALUE] = 0.0;   // one sample: scipy's linregress returns r = 0 next to four NaN
                 have_ltt = true;
                 if (nloop < nspecs && b.tid == 0)
                     for (int k = 0; k < 5; ++k) ctx[TSFA_CTX_LTT + k] = ltt5[k];

@@ -169,16 +169,18 @@ class _CompositePlan:
             dm.free()
         return out
 
-    def extract_into(self, values, offsets, matrix, col0=0, times=None, pack=None):
+    def extract_into(self, values, offsets, matrix, col0=0, times=None, pack=None, times_ptr=None):
         """Columns [col0, col0 + n_cols) of the DeviceMatrix `matrix` (device_resident=True: the feature matrix never leaves
         HBM): every part extracts into a transient block that tsfa_scatter_columns puts in the caller's column order.
-        pack: a `_native.DevicePack` instead of host `values` / `offsets`."""
-        _native.extract_parts_into(self.parts, values, offsets, matrix, col0=col0, times=times, pack=pack)
+        pack: a `_native.DevicePack` instead of host `values` / `offsets`; times_ptr: with it, the device pointer to the
+        pack's hours (`_native.pack_times`), which every part gets."""
+        _native.extract_parts_into(self.parts, values, offsets, matrix, col0=col0, times=times, pack=pack, times_ptr=times_ptr)
 
-    def extract_windows_into(self, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=0):
+    def extract_windows_into(self, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=0, times_ptr=None):
         """Columns [col0, col0 + n_cols) of the device matrix `matrix` for windows held as device pointers
         (`Plan.extract_windows_into`): the parts' blocks are scattered into the caller's column order in HBM."""
-        _native.extract_parts_windows_into(self.parts, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=col0)
+        _native.extract_parts_windows_into(self.parts, values_ptr, values_type, starts_ptr, ends_ptr, n_windows, matrix, col0=col0,
+                                           times_ptr=times_ptr)
 
 
 def _split_native_specs(specs):

@@ -7,6 +7,8 @@ include/tsfresh_amd.h) and from there to the kernels `extract_features` runs, th
 same plan cache and the same composite plans (feature_extraction/extraction.py); the feature matrix stays on the device.
 The rolled entry adds the window builder between the two (`tsfa_roll_count` / `tsfa_roll_fill` on the packer's offsets) and
 hands the kernels `(start, end)` views instead of whole series (`tsfa_extract_windows` with device pointers).
+With `times=` the batch brings its clock as an array: `tsfa_pack_times` writes the hours since each series' first stamp next
+to the packed samples, and the plans hold the `linear_trend_timewise` columns a frame with a `DatetimeIndex` gets.
 """
 import numpy as np
 
@@ -49,6 +51,58 @@ def _dense_pack(torch, x3, lengths, device):
     packs = [_native.DensePack(values.data_ptr() + c * B * n * values.element_size(), vtype, offsets.data_ptr(), B, device,
                                owner=owner) for c in range(C)]
     return packs, flag
+
+
+# time_unit -> ticks per second (numpy's datetime64 units of the same names)
+_TIME_UNITS = {"s": 1, "ms": 10 ** 3, "us": 10 ** 6, "ns": 10 ** 9}
+
+
+def _times_argument(torch, times, time_unit, B, n):
+    """The checks on `times` -> (stamps: an int64 or float64 tensor of shape (n,) or (B, n), tsfa_dtype, ticks per second).
+    Nothing has moved to the device yet."""
+    tps = None
+    if isinstance(times, np.ndarray):
+        if times.dtype.kind == "M":
+            unit, count = np.datetime_data(times.dtype)
+            if unit not in _TIME_UNITS or count != 1:
+                raise TypeError("times must be datetime64[ns], [us], [ms] or [s], int64 ticks or float64 seconds, not {}".format(
+                    times.dtype))
+            tps = _TIME_UNITS[unit]   # the dtype names the unit: time_unit is not looked at
+            times = times.view(np.int64)
+        if times.dtype not in (np.int64, np.float64):
+            raise TypeError("times must be int64 ticks, datetime64 or float64 seconds, not {}".format(times.dtype))
+        if any(s < 0 for s in times.strides) or not times.dtype.isnative:
+            times = np.ascontiguousarray(times, dtype=times.dtype.newbyteorder("="))
+        times = torch.from_numpy(times)
+    if not isinstance(times, torch.Tensor):
+        raise TypeError("times must be a torch.Tensor or a numpy array, not {}".format(type(times).__name__))
+    if times.dtype not in (torch.int64, torch.float64):
+        raise TypeError("times must be int64 ticks, datetime64 or float64 seconds, not {}".format(times.dtype))
+    if times.dtype == torch.float64:
+        t_type, tps = _native.TSFA_F64, 1
+    else:
+        t_type = _native.TSFA_I64
+        if tps is None:
+            if time_unit not in _TIME_UNITS:
+                raise ValueError("time_unit must be one of 'ns', 'us', 'ms', 's': got {!r}".format(time_unit))
+            tps = _TIME_UNITS[time_unit]
+    if tuple(times.shape) not in ((n,), (B, n)):
+        raise ValueError("times must have shape ({n},) (one clock for the batch) or ({B}, {n}) (one per series): got {got}".format(
+            n=n, B=B, got=tuple(times.shape)))
+    return times, t_type, tps
+
+
+def _times_pack(torch, times, pack, flag, device):
+    """The hours of the batch's clock in the layout of `pack` (one channel of `_dense_pack`'s result; the channels share
+    their offsets) -> a float64 tensor the caller keeps alive while the kernels read it.  times: what `_times_argument`
+    returned, on `device` and of logical shape (B, n).  ORs TSFA_DENSE_BAD_TIME into the pack's flag word.  Runs after `_dense_pack`'s
+    synchronisation, on the library's stream, and returns when the hours are written."""
+    t, t_type, tps = times
+    B, n = t.shape
+    hours = torch.empty(B * n, dtype=torch.float64, device=t.device)   # [0, T) is written, T <= B * n
+    _native.pack_times(t.data_ptr(), t_type, tps, (B, n), t.stride(), pack.offsets_ptr, hours.data_ptr(), flag.data_ptr(),
+                       device=device)
+    return hours
 
 
 def _batch_arguments(torch, x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device):
@@ -104,10 +158,11 @@ def _batch_arguments(torch, x, lengths, kinds, channels_last, default_fc_paramet
     return x3, lengths, kinds, default_fc_parameters, int(device)
 
 
-def _kind_jobs(kinds, default_fc_parameters, kind_to_fc_parameters, device, pins, instead):
+def _kind_jobs(kinds, default_fc_parameters, kind_to_fc_parameters, device, pins, instead, timed=False):
     """The plans of the kinds that have columns -> ([(channel, kind, fplan, native plan, first column)], number of columns,
     column names).  A settings object the kernels do not serve, or a box without a device, fails here, before anything
-    moves.  instead: what the UnsupportedFeature of a callable calculator tells the caller to do."""
+    moves.  instead: what the UnsupportedFeature of a callable calculator tells the caller to do.  timed: the batch brings
+    its clock, so the plans keep linear_trend_timewise as those of a frame with a DatetimeIndex do."""
     from tsfresh_amd.feature_extraction import extraction
     from tsfresh_amd.feature_extraction.plan import compile_fc_parameters
     from tsfresh_amd.feature_extraction.registry import UnsupportedFeature
@@ -118,7 +173,7 @@ def _kind_jobs(kinds, default_fc_parameters, kind_to_fc_parameters, device, pins
             else default_fc_parameters
         key = id(fc_parameters)
         if key not in plan_cache:
-            fplan = compile_fc_parameters(fc_parameters, has_datetime_index=False)
+            fplan = compile_fc_parameters(fc_parameters, has_datetime_index=bool(timed))
             if fplan.host_calls:
                 raise UnsupportedFeature("custom (callable) calculators are evaluated per series on the host: " + instead)
             plan_cache[key] = (fplan, extraction._acquire_plan(fplan, device, pins) if fplan.names else None)
@@ -131,15 +186,22 @@ def _kind_jobs(kinds, default_fc_parameters, kind_to_fc_parameters, device, pins
     return jobs, n_cols, columns
 
 
-def _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=False):
-    """`_dense_pack` of the batch on `device` and its flag word's errors -> (x3 and lengths on the device, packs, steps).
-    steps (want_steps): the longest series, n without lengths -- with lengths their maximum, which comes back in the same
-    read as the flag word."""
+def _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=False, times=None):
+    """`_dense_pack` of the batch on `device` and its flag word's errors -> (x3 and lengths on the device, packs, steps,
+    hours).  steps (want_steps): the longest series, n without lengths -- with lengths their maximum, which comes back in
+    the same read as the flag word.  times: None or what `_times_argument` returned; hours: None or `_times_pack`'s tensor,
+    whose flag bit travels in the same word."""
     n = x3.shape[2]
     x3 = _to_device(x3, device)
     if lengths is not None:
         lengths = _to_device(lengths, device)
+    if times is not None:
+        t = _to_device(times[0], device)   # (before the pack: its synchronisation covers the copy)
+        if t.ndim == 1:
+            t = t.unsqueeze(0).expand(x3.shape[0], n)   # one clock for the batch: batch stride 0, n stamps on the device
+        times = (t,) + tuple(times[1:])
     packs, flag = _dense_pack(torch, x3, lengths, device)
+    hours = _times_pack(torch, times, packs[0], flag, device) if times is not None else None
     steps = n
     if lengths is not None or check_nan:
         if want_steps and lengths is not None:
@@ -151,11 +213,14 @@ def _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=False
             raise ValueError("lengths must lie in [1, {}] (the samples per series of x)".format(n))
         if check_nan and flags & _native.TSFA_PACK_VALUE_NAN:
             raise ValueError("Column must not contain NaN values: {}".format(_first_nan_kind(torch, x3, lengths, kinds)))
-    return x3, lengths, packs, int(steps)
+        if check_nan and flags & _native.TSFA_DENSE_BAD_TIME:
+            raise ValueError("times must not contain NaT / NaN")
+    return x3, lengths, packs, int(steps), hours
 
 
 def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, default_fc_parameters=None,
-                            kind_to_fc_parameters=None, device=None, check_nan=True, show_warnings=False):
+                            kind_to_fc_parameters=None, device=None, check_nan=True, show_warnings=False, times=None,
+                            time_unit="ns"):
     """Extract features from a batch of equally sampled series held as a tensor; the feature matrix stays on the GPU.
 
     :param x: `torch.Tensor` (on the GPU or on the CPU) or numpy array of dtype float64, float32, float16 or bfloat16 and
@@ -172,6 +237,19 @@ def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, de
         `extract_features` ($TSFRESH_AMD_DEVICE, else $LOCAL_RANK, else 0).
     :param check_nan: True (default): a NaN among the samples raises the reference's
         `ValueError("Column must not contain NaN values: <kind>")`; False skips the check and its read-back of one word.
+    :param times: optional time stamps of the samples, for an irregularly sampled batch: a `torch.Tensor` or numpy array of
+        shape `(n,)` (one clock for the batch) or `(B, n)` (one per series), any strides (expanded and stepped views are not
+        copied first); the kinds share the clock, as the value columns of a frame share its index.  dtype int64 (ticks,
+        counted in `time_unit`), numpy `datetime64[ns|us|ms|s]` (the unit comes from the dtype) or float64 seconds; anything
+        else raises `TypeError` (float32 seconds lack the precision).  A CPU tensor or an array is moved to `device` with
+        torch.  With `times` the plans are those of a frame with a `DatetimeIndex`: `linear_trend_timewise` is served (788
+        columns per kind under `ComprehensiveFCParameters` instead of 783), regressing on the hours since each series'
+        first stamp, which `tsfa_pack_times` writes on the device with pandas' arithmetic (bit-equal to `extract_features`
+        on the frame that carries the same stamps as its index).  Stamps beyond a series' length are never read.  With
+        `check_nan=True` a NaT (`INT64_MIN`) or NaN stamp inside a length raises
+        `ValueError("times must not contain NaT / NaN")` (the same read-back of one word); with `check_nan=False` the
+        hours of that sample -- of the whole series, when it is its first stamp -- are NaN.
+    :param time_unit: "ns" (default), "us", "ms" or "s": what one tick of an int64 `times` counts.
     :return: `(features, columns)`: a `torch.float64` tensor `[B, number of columns]` on the device and the list of column
         names ``"{kind}__{feature}"``, in exactly the order `extract_features` gives for the equivalent wide frame.
 
@@ -191,21 +269,24 @@ def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, de
     x3, lengths, kinds, default_fc_parameters, device = _batch_arguments(
         torch, x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device)
     B = x3.shape[0]
+    if times is not None:
+        times = _times_argument(torch, times, time_unit, B, x3.shape[2])
 
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("default" if show_warnings else "ignore")
         pins = set()
         jobs, n_cols, columns = _kind_jobs(kinds, default_fc_parameters, kind_to_fc_parameters, device, pins,
-                                           "build a DataFrame and call extract_features on it")
+                                           "build a DataFrame and call extract_features on it", timed=times is not None)
         x3 = _to_device(x3, device)
         features = torch.empty((B, n_cols), dtype=torch.float64, device=x3.device)
-        x3, lengths, packs, _ = _pack_checked(torch, x3, lengths, kinds, device, check_nan)
+        x3, lengths, packs, _, hours = _pack_checked(torch, x3, lengths, kinds, device, check_nan, times=times)
         if n_cols:
             matrix = _native.BorrowedMatrix(features.data_ptr(), B, n_cols, device, owner=features)
+            timed = {} if hours is None else {"times_ptr": hours.data_ptr()}
             for c, kind, fplan, nplan, col0 in jobs:
                 # (one native call per kind: the calls are synchronous, the plan's own stream runs the kernels)
-                nplan.extract_into(None, None, matrix, col0=col0, pack=packs[c])
+                nplan.extract_into(None, None, matrix, col0=col0, pack=packs[c], **timed)
         for pack in packs:
             pack.close()
         extraction._trim_cache(extraction._thread_cache())
@@ -238,7 +319,7 @@ def _roll_windows(torch, pack, series_len, rolling_direction, max_timeshift, min
 
 def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=False, rolling_direction=1, max_timeshift=None,
                                    min_timeshift=0, default_fc_parameters=None, kind_to_fc_parameters=None, device=None,
-                                   check_nan=True, show_warnings=False):
+                                   check_nan=True, show_warnings=False, times=None, time_unit="ns"):
     """`extract_rolled_features` for a batch that already is a tensor: sliding-window (forecasting) features of every series,
     without pandas; the windows are built in HBM and the feature matrix stays there.
 
@@ -247,6 +328,8 @@ def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=Fa
     :param rolling_direction, max_timeshift, min_timeshift: as in `roll_time_series` / `extract_rolled_features`; the
         reference's three `ValueError`s for them are raised before anything moves.  A window of w samples at every step is
         `max_timeshift=w - 1, min_timeshift=w - 1`.
+    :param times, time_unit: as in `extract_features_tensor`.  The hours are written once for the batch; the kernel rebases
+        them on each window's first stamp, as the reference does for the rolled frame.
     :return: `(features, columns, series, positions)`, all tensors on the device:
         `features` `torch.float64` `[n_windows, number of columns]`; `columns` the names ``"{kind}__{feature}"`` in exactly the
         order `extract_rolled_features` gives for the equivalent wide frame; `series` `torch.int64` `[n_windows]`, the batch
@@ -284,14 +367,18 @@ def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=Fa
     x3, lengths, kinds, default_fc_parameters, device = _batch_arguments(
         torch, x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device)
     n = x3.shape[2]
+    if times is not None:
+        times = _times_argument(torch, times, time_unit, x3.shape[0], n)
 
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("default" if show_warnings else "ignore")
         pins = set()
         jobs, n_cols, columns = _kind_jobs(kinds, default_fc_parameters, kind_to_fc_parameters, device, pins,
-                                           "build a DataFrame, roll it with roll_time_series and call extract_features on it")
-        x3, lengths, packs, steps = _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=True)
+                                           "build a DataFrame, roll it with roll_time_series and call extract_features on it",
+                                           timed=times is not None)
+        x3, lengths, packs, steps, hours = _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=True,
+                                                         times=times)
         # once for all kinds: the channels share their offsets, and starts / ends count from each channel's own base
         starts, ends, series, shifts = _roll_windows(torch, packs[0], n if lengths is None else None, int(rolling_direction),
                                                      max_timeshift, int(min_timeshift), steps)
@@ -300,9 +387,10 @@ def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=Fa
         if n_windows and n_cols:
             matrix = _native.BorrowedMatrix(features.data_ptr(), n_windows, n_cols, device, owner=features)
             _synchronize(torch, device)
+            timed = {} if hours is None else {"times_ptr": hours.data_ptr()}
             for c, kind, fplan, nplan, col0 in jobs:
                 nplan.extract_windows_into(packs[c].values_ptr, packs[c].values_type, starts.data_ptr(), ends.data_ptr(),
-                                           n_windows, matrix, col0=col0)
+                                           n_windows, matrix, col0=col0, **timed)
         positions = shifts - 1
         _synchronize(torch, device)
         for pack in packs:

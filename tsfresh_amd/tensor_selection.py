@@ -256,19 +256,22 @@ def select_features_tensor(X, y, columns=None, ml_task="auto", multiclass=False,
 def extract_relevant_features_tensor(x, y, lengths=None, kinds=None, channels_last=False, default_fc_parameters=None,
                                      kind_to_fc_parameters=None, ml_task="auto", multiclass=False, n_significant=1,
                                      test_for_binary_target_real_feature="mann", fdr_level=0.05, hypotheses_independent=False,
-                                     device=None, check_nan=True):
+                                     device=None, check_nan=True, times=None, time_unit="ns"):
     """`extract_relevant_features` for a batch held as a tensor: `extract_features_tensor`, `impute_tensor` and
     `select_features_tensor` on one matrix that never leaves the GPU.
 
     :param x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device, check_nan: as in
         `extract_features_tensor` (check_nan is about the samples; the imputed matrix holds no NaN).
     :param y: one target value per series, as in `calculate_relevance_tensor`; the selection options likewise.
+    :param times, time_unit: as in `extract_features_tensor`: the batch's clock, which adds the `linear_trend_timewise`
+        columns to the matrix the selection runs on.
     :return: `(features, columns)`: the relevant columns `[B, k]` on the device, in ascending column index of the extracted
         matrix, and their names."""
     from tsfresh_amd.tensor import extract_features_tensor
     features, columns = extract_features_tensor(x, lengths=lengths, kinds=kinds, channels_last=channels_last,
                                                 default_fc_parameters=default_fc_parameters,
-                                                kind_to_fc_parameters=kind_to_fc_parameters, device=device, check_nan=check_nan)
+                                                kind_to_fc_parameters=kind_to_fc_parameters, device=device, check_nan=check_nan,
+                                                times=times, time_unit=time_unit)
     impute_tensor(features)
     selected, names, _ = select_features_tensor(features, y, columns=columns, ml_task=ml_task, multiclass=multiclass,
                                                 n_significant=n_significant,
