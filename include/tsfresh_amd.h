@@ -398,6 +398,48 @@ int tsfa_pack_times(const void *t, int32_t t_type, int64_t ticks_per_second, int
                     int64_t stride_batch, int64_t stride_time, const int64_t *offsets, double *hours_out, int32_t *flags_out,
                     int32_t device, void *stream);
 
+/* Valid-step packer: tsfa_pack_dense for a batch with gaps -- what the wide frame of the same batch holds after `dropna()`.
+ * Step t of series b is dropped FOR EVERY CHANNEL when any channel's sample x[b, :, t] is NaN, and, with stamps, when its
+ * stamp is NaT (INT64_MIN ticks) or a NaN second; +-inf is a value and stays (dropna keeps it).  Steps at or beyond
+ * lengths[b] are never read.  The kept steps of a series keep their order.
+ *   x .. lengths_type   as in tsfa_pack_dense (the same element types, strides, conversions and clamping of the lengths)
+ *   t, t_type           NULL, or logical (n_batch, n_time) stamps with non-negative element strides t_stride_batch (0: one
+ *                       clock shared by every series) and t_stride_time; TSFA_I64 ticks or TSFA_F64 seconds, as
+ *                       tsfa_pack_times takes them
+ *   values_out          channel c occupies elements [c * channel_stride_out, c * channel_stride_out + T) of the output type,
+ *                       T = the kept steps of the batch, the series back to back; channel_stride_out >= n_batch * n_time
+ *   offsets_out         n_batch + 1 int64 shared by every channel: the exclusive scan of the kept counts (one workgroup, 64
+ *                       bits wide, a carry across its trips; no workgroup waits on another)
+ *   steps_out           int32[T <= n_batch * n_time]: steps_out[offsets[b] + k] = the original step index of the k-th kept
+ *                       step of series b
+ *   stamps_out          NULL without t; else (n_batch, n_time) elements of t's type, right-padded:
+ *                       stamps_out[b * n_time + k] = the stamp of the k-th kept step of series b; cells at or beyond a
+ *                       series' kept count are not written.  tsfa_pack_times(stamps_out, t_type, ticks_per_second, n_batch,
+ *                       n_time, n_time, 1, offsets_out, ...) gives the hours since each series' first KEPT stamp.
+ *   scratch             scratch_bytes >= 200 * n_batch * ceil(n_time / 1024) bytes of device memory, aligned to 8 (the kept
+ *                       counts, the keep masks and the per-round prefixes of the work items); the caller's, free to reuse
+ *                       when the call is done
+ *   flags_out           one int32 the call ORs into (the caller clears it): TSFA_DENSE_BAD_LENGTH as in tsfa_pack_dense;
+ *                       TSFA_DENSE_EMPTY_SERIES a series has no kept step (offsets_out[b + 1] == offsets_out[b]: the frame
+ *                       after dropna() has no row for it; the first such b is the caller's to find in offsets_out).
+ *                       TSFA_PACK_VALUE_NAN is never raised: no NaN is copied.
+ *   stream              as in tsfa_pack_dense.  All pointers are device pointers on `device`; nothing is allocated.
+ * Three launches over work items of 1024 steps of one series: a count pass (a 64-lane ballot per 64 steps is the keep mask,
+ * its population count the kept steps), the scan, and a compaction pass (a lane's cell is the work item's base + the kept
+ * steps of the work item's earlier rounds + the population count of its mask below the lane) that writes every channel,
+ * steps_out and stamps_out.  One route for every layout, the time stride a compile-time 1 when it is 1.  No atomic on a position: the
+ * result is deterministic.
+ * TSFA_ERR_INVALID: what tsfa_pack_dense refuses, a null steps_out or scratch, stamps of another type or without stamps_out,
+ * a negative stamp stride, a scratch that is too small or misaligned.  TSFA_ERR_TOO_LONG: n_time > 33 554 431.
+ * TSFA_ERR_NO_DEVICE: no HIP device. */
+#define TSFA_DENSE_EMPTY_SERIES 32
+int tsfa_pack_dense_valid(const void *x, int32_t x_type, int64_t n_batch, int64_t n_channels, int64_t n_time,
+                          int64_t stride_batch, int64_t stride_channel, int64_t stride_time, const void *lengths,
+                          int32_t lengths_type, const void *t, int32_t t_type, int64_t t_stride_batch, int64_t t_stride_time,
+                          void *values_out, int64_t channel_stride_out, int64_t *offsets_out, int32_t *steps_out,
+                          void *stamps_out, void *scratch, int64_t scratch_bytes, int32_t *flags_out, int32_t device,
+                          void *stream);
+
 /* Window builder: the rolled (forecasting) layout of one pack, built on the device from the pack's offsets.  Replaces, for a
  * frame packed by tsfa_pack_device / tsfa_pack_set_*, the host's enumeration of n_series x n_shifts window candidates
  * (tsfresh/utilities/dataframe_functions.py:340-358, _roll_out_time_series, for all shifts at once) and the upload of the

@@ -25,6 +25,7 @@ TSFA_F16, TSFA_BF16 = 11, 12   # tsfa_pack_dense only
 TSFA_PACK_UNSORTED, TSFA_PACK_VALUE_NAN, TSFA_PACK_IN_ORDER = 1, 2, 4
 TSFA_DENSE_BAD_LENGTH = 8
 TSFA_DENSE_BAD_TIME = 16   # tsfa_pack_times
+TSFA_DENSE_EMPTY_SERIES = 32   # tsfa_pack_dense_valid
 TSFA_PACK_KEEP_SORT = 1
 TSFA_HOST, TSFA_DEVICE = 0, 1
 # enum tsfa_route: who evaluates the tail of a p-value cell (tsfa_relevance_tails_*)
@@ -66,6 +67,7 @@ EXPORTS = (
     "tsfa_pack_set_destroy",
     "tsfa_pack_dense",
     "tsfa_pack_times",
+    "tsfa_pack_dense_valid",
     "tsfa_roll_windows",
     "tsfa_windows_n_windows",
     "tsfa_windows_starts",
@@ -569,6 +571,45 @@ def pack_times(t_ptr, t_type, ticks_per_second, shape, strides, offsets_ptr, hou
         ctypes.c_void_p(t_ptr), int(t_type), int(ticks_per_second), int(n_batch), int(n_time), int(sb), int(st),
         ctypes.c_void_p(offsets_ptr), ctypes.c_void_p(hours_ptr), ctypes.c_void_p(flags_ptr), int(device),
         ctypes.c_void_p(stream) if stream else None))
+
+
+def _bind_pack_dense_valid_api(lib):
+    """The tsfa_pack_dense_valid prototype, bound on first use (a diagnostics library given through TSFA_LIB may predate it)."""
+    if getattr(lib, "_tsfa_pack_dense_valid_bound", False):
+        return
+    lib.tsfa_pack_dense_valid.argtypes = (
+        [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_int64] * 6 + [ctypes.c_void_p, ctypes.c_int32]
+        + [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]
+        + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+           ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p])
+    lib.tsfa_pack_dense_valid.restype = ctypes.c_int
+    lib._tsfa_pack_dense_valid_bound = True
+
+
+def pack_dense_valid_scratch_bytes(n_batch, n_time):
+    """The scratch tsfa_pack_dense_valid asks for: 200 bytes per work item of 1024 steps of one series."""
+    return 200 * int(n_batch) * ((int(n_time) + 1023) // 1024)
+
+
+def pack_dense_valid(x_ptr, x_type, shape, strides, values_ptr, channel_stride_out, offsets_ptr, steps_ptr, scratch_ptr,
+                     scratch_bytes, flags_ptr, device=0, lengths_ptr=None, lengths_type=0, t_ptr=None, t_type=0,
+                     t_strides=(0, 0), stamps_ptr=None, stream=None):
+    """tsfa_pack_dense_valid on raw device pointers (ints): `pack_dense` without the steps a wide frame loses to dropna() -- a
+    step of a series goes, for every channel, when any channel's sample is NaN or (with t_ptr: int64 ticks or float64
+    seconds of logical shape (n_batch, n_time) and element strides t_strides) its stamp is NaT / NaN.  offsets_ptr receives
+    the exclusive scan of the kept counts, steps_ptr (int32, n_batch * n_time cells) the original step index of every kept
+    sample, stamps_ptr (with t_ptr: n_batch * n_time elements) the kept stamps as a right-padded (n_batch, n_time) array
+    for `pack_times`.  scratch_ptr: `pack_dense_valid_scratch_bytes` of device memory.  flags_ptr: one int32 the call ORs
+    TSFA_DENSE_BAD_LENGTH and TSFA_DENSE_EMPTY_SERIES into.  stream: a hipStream_t as an int (the call only enqueues) or
+    None (the call returns when the work is done)."""
+    lib = load()
+    _bind_pack_dense_valid_api(lib)
+    (n_batch, n_channels, n_time), (sb, sc, st), (tsb, tst) = shape, strides, t_strides
+    _check(lib, lib.tsfa_pack_dense_valid(
+        ctypes.c_void_p(x_ptr), int(x_type), int(n_batch), int(n_channels), int(n_time), int(sb), int(sc), int(st),
+        _ptr(lengths_ptr), int(lengths_type), _ptr(t_ptr), int(t_type), int(tsb), int(tst), ctypes.c_void_p(values_ptr),
+        int(channel_stride_out), ctypes.c_void_p(offsets_ptr), ctypes.c_void_p(steps_ptr), _ptr(stamps_ptr),
+        ctypes.c_void_p(scratch_ptr), int(scratch_bytes), ctypes.c_void_p(flags_ptr), int(device), _ptr(stream)))
 
 
 class DensePack:

@@ -218,9 +218,89 @@ def _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=False
     return x3, lengths, packs, int(steps), hours
 
 
+_NAN_POLICIES = ("raise", "drop")
+
+
+def _check_nan_policy(nan_policy):
+    if nan_policy not in _NAN_POLICIES:
+        raise ValueError("nan_policy must be one of 'raise', 'drop': got {!r}".format(nan_policy))
+    return nan_policy == "drop"
+
+
+def _valid_pack(torch, x3, lengths, times, device):
+    """(B, C, n) tensor on `device` without the steps a wide frame loses to `dropna()` (`tsfa_pack_dense_valid`: a step of a
+    series goes for every kind when any kind's sample is NaN, or its stamp NaT / NaN) -> ([one `_native.DensePack` per
+    channel], flag tensor of one int32, hours, steps, offsets).  times: None or what `_times_argument` returned, on
+    `device` and of logical shape (B, n).  hours: None, or `tsfa_pack_times`' float64 tensor for the kept stamps (hours since
+    each series' first kept stamp).  steps: int32 tensor over the packed layout, the original step index of every kept
+    sample.  offsets: the int64 tensor of B + 1 offsets the channels share.  The buffers are torch allocations the packs
+    keep alive."""
+    B, C, n = x3.shape
+    x_type = _X_TYPES[str(x3.dtype)]
+    out_dtype = torch.float64 if x_type == _native.TSFA_F64 else torch.float32
+    values = torch.empty((C, B * n), dtype=out_dtype, device=x3.device)
+    offsets = torch.empty(B + 1, dtype=torch.int64, device=x3.device)
+    steps = torch.empty(B * n, dtype=torch.int32, device=x3.device)   # [0, T) is written, T <= B * n
+    scratch_bytes = _native.pack_dense_valid_scratch_bytes(B, n)
+    scratch = torch.empty(scratch_bytes // 8, dtype=torch.int64, device=x3.device)
+    flag = torch.zeros(1, dtype=torch.int32, device=x3.device)
+    timed, stamps = {}, None
+    if times is not None:
+        t, t_type, tps = times
+        stamps = torch.empty((B, n), dtype=t.dtype, device=x3.device)
+        timed = dict(t_ptr=t.data_ptr(), t_type=t_type, t_strides=t.stride(), stamps_ptr=stamps.data_ptr())
+    _synchronize(torch, device)   # the producer of x, and the fill of the flag word, are done before another stream reads
+    lptr, ltype = None, 0
+    if lengths is not None:
+        lptr, ltype = lengths.data_ptr(), (_native.TSFA_I32 if lengths.dtype == torch.int32 else _native.TSFA_I64)
+    _native.pack_dense_valid(x3.data_ptr(), x_type, (B, C, n), x3.stride(), values.data_ptr(), B * n, offsets.data_ptr(),
+                             steps.data_ptr(), scratch.data_ptr(), scratch_bytes, flag.data_ptr(), device=device,
+                             lengths_ptr=lptr, lengths_type=ltype, **timed)
+    hours = None
+    if times is not None:
+        # the kept stamps are a right-padded (B, n) batch with the new offsets: the times packer's own arithmetic
+        hours = torch.empty(B * n, dtype=torch.float64, device=x3.device)
+        _native.pack_times(stamps.data_ptr(), t_type, tps, (B, n), (n, 1), offsets.data_ptr(), hours.data_ptr(), flag.data_ptr(),
+                           device=device)
+    owner = (values, offsets, flag, x3, lengths)
+    vtype = _native.TSFA_F64 if x_type == _native.TSFA_F64 else _native.TSFA_F32
+    packs = [_native.DensePack(values.data_ptr() + c * B * n * values.element_size(), vtype, offsets.data_ptr(), B, device,
+                               owner=owner) for c in range(C)]
+    return packs, flag, hours, steps, offsets
+
+
+def _pack_dropped(torch, x3, lengths, device, want_steps=False, times=None):
+    """`_valid_pack` of the batch on `device` and its flag word's errors -> (x3 on the device, packs, the longest kept length
+    (want_steps; it comes back in the same read as the flag word), hours, steps).  The flag word is always read: a length
+    outside [1, n] and a series without a kept step are errors whatever `check_nan` says."""
+    n = x3.shape[2]
+    x3 = _to_device(x3, device)
+    if lengths is not None:
+        lengths = _to_device(lengths, device)
+    if times is not None:
+        t = _to_device(times[0], device)
+        if t.ndim == 1:
+            t = t.unsqueeze(0).expand(x3.shape[0], n)
+        times = (t,) + tuple(times[1:])
+    packs, flag, hours, steps, offsets = _valid_pack(torch, x3, lengths, times, device)
+    longest = n
+    if want_steps:
+        # one read for both words, before any extraction kernel is launched
+        flags, longest = torch.stack([flag.reshape(()).to(torch.int64), (offsets[1:] - offsets[:-1]).max()]).tolist()
+    else:
+        flags = int(flag.item())
+    if flags & _native.TSFA_DENSE_BAD_LENGTH:
+        raise ValueError("lengths must lie in [1, {}] (the samples per series of x)".format(n))
+    if flags & _native.TSFA_DENSE_EMPTY_SERIES:
+        empty = int(torch.nonzero(offsets[1:] == offsets[:-1])[0].item())
+        raise ValueError("series {} has no step left after nan_policy='drop': every step holds a NaN sample{}".format(
+            empty, "" if times is None else " or a NaT / NaN stamp"))
+    return x3, packs, int(longest), hours, steps
+
+
 def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, default_fc_parameters=None,
-                            kind_to_fc_parameters=None, device=None, check_nan=True, show_warnings=False, times=None,
-                            time_unit="ns"):
+                            kind_to_fc_parameters=None, device=None, check_nan=True, show_warnings=False, nan_policy="raise",
+                            times=None, time_unit="ns"):
     """Extract features from a batch of equally sampled series held as a tensor; the feature matrix stays on the GPU.
 
     :param x: `torch.Tensor` (on the GPU or on the CPU) or numpy array of dtype float64, float32, float16 or bfloat16 and
@@ -237,6 +317,15 @@ def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, de
         `extract_features` ($TSFRESH_AMD_DEVICE, else $LOCAL_RANK, else 0).
     :param check_nan: True (default): a NaN among the samples raises the reference's
         `ValueError("Column must not contain NaN values: <kind>")`; False skips the check and its read-back of one word.
+    :param nan_policy: "raise" (default): the behaviour above, under either value of `check_nan`.  "drop": the result is
+        what the call returns for the equivalent wide frame after `dropna()`: step t of series b is dropped for every kind
+        when any kind's sample `x[b, :, t]` is NaN and, with `times`, when its stamp is NaT (`INT64_MIN`) or NaN
+        (`tsfa_pack_dense_valid` compacts the batch on the device; the hours count from each series' first kept stamp).
+        +-inf is a value and stays.  Steps at or beyond `lengths[b]` are never read.  `check_nan` is irrelevant: nothing that
+        is NaN reaches the kernels, and the one flag word is always read -- a series with no kept step has no row in that
+        frame and raises `ValueError` with its batch index.  Anything else raises `ValueError`.  Not offered: a
+        user-supplied validity mask, per-kind lengths (a kind dropping steps on its own), the frame entries (use
+        `frame.dropna()`), an enqueue-only mode.
     :param times: optional time stamps of the samples, for an irregularly sampled batch: a `torch.Tensor` or numpy array of
         shape `(n,)` (one clock for the batch) or `(B, n)` (one per series), any strides (expanded and stepped views are not
         copied first); the kinds share the clock, as the value columns of a frame share its index.  dtype int64 (ticks,
@@ -266,6 +355,7 @@ def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, de
 
     from tsfresh_amd.feature_extraction import extraction
 
+    drop = _check_nan_policy(nan_policy)
     x3, lengths, kinds, default_fc_parameters, device = _batch_arguments(
         torch, x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device)
     B = x3.shape[0]
@@ -280,7 +370,10 @@ def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, de
                                            "build a DataFrame and call extract_features on it", timed=times is not None)
         x3 = _to_device(x3, device)
         features = torch.empty((B, n_cols), dtype=torch.float64, device=x3.device)
-        x3, lengths, packs, _, hours = _pack_checked(torch, x3, lengths, kinds, device, check_nan, times=times)
+        if drop:
+            x3, packs, _, hours, _ = _pack_dropped(torch, x3, lengths, device, times=times)
+        else:
+            x3, lengths, packs, _, hours = _pack_checked(torch, x3, lengths, kinds, device, check_nan, times=times)
         if n_cols:
             matrix = _native.BorrowedMatrix(features.data_ptr(), B, n_cols, device, owner=features)
             timed = {} if hours is None else {"times_ptr": hours.data_ptr()}
@@ -319,7 +412,7 @@ def _roll_windows(torch, pack, series_len, rolling_direction, max_timeshift, min
 
 def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=False, rolling_direction=1, max_timeshift=None,
                                    min_timeshift=0, default_fc_parameters=None, kind_to_fc_parameters=None, device=None,
-                                   check_nan=True, show_warnings=False, times=None, time_unit="ns"):
+                                   check_nan=True, show_warnings=False, nan_policy="raise", times=None, time_unit="ns"):
     """`extract_rolled_features` for a batch that already is a tensor: sliding-window (forecasting) features of every series,
     without pandas; the windows are built in HBM and the feature matrix stays there.
 
@@ -330,6 +423,12 @@ def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=Fa
         `max_timeshift=w - 1, min_timeshift=w - 1`.
     :param times, time_unit: as in `extract_features_tensor`.  The hours are written once for the batch; the kernel rebases
         them on each window's first stamp, as the reference does for the rolled frame.
+    :param nan_policy: as in `extract_features_tensor`.  With "drop" the windows are rolled over the KEPT steps of every
+        series (the result of `extract_rolled_features` on the wide frame after `dropna()`, its sort column the step
+        index): they come from the ragged route (count, scan, fill on the compacted offsets; the longest kept length comes
+        back with the flag word), and `positions` holds ORIGINAL step indices -- of the window's last kept step for a
+        positive direction, of its first for a negative one -- gathered on the device from the packer's step array.  The
+        same things are not offered (a validity mask, per-kind lengths, the frame entries, an enqueue-only mode).
     :return: `(features, columns, series, positions)`, all tensors on the device:
         `features` `torch.float64` `[n_windows, number of columns]`; `columns` the names ``"{kind}__{feature}"`` in exactly the
         order `extract_rolled_features` gives for the equivalent wide frame; `series` `torch.int64` `[n_windows]`, the batch
@@ -364,6 +463,7 @@ def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=Fa
     from tsfresh_amd.utilities.dataframe_functions import check_roll_arguments
 
     check_roll_arguments(rolling_direction, max_timeshift, min_timeshift)
+    drop = _check_nan_policy(nan_policy)
     x3, lengths, kinds, default_fc_parameters, device = _batch_arguments(
         torch, x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device)
     n = x3.shape[2]
@@ -377,10 +477,17 @@ def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=Fa
         jobs, n_cols, columns = _kind_jobs(kinds, default_fc_parameters, kind_to_fc_parameters, device, pins,
                                            "build a DataFrame, roll it with roll_time_series and call extract_features on it",
                                            timed=times is not None)
-        x3, lengths, packs, steps, hours = _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=True,
-                                                         times=times)
+        kept_steps = None
+        if drop:
+            # the kept lengths are ragged whatever `lengths` is: the count / scan / fill route on the new offsets
+            x3, packs, steps, hours, kept_steps = _pack_dropped(torch, x3, lengths, device, want_steps=True, times=times)
+            series_len = None
+        else:
+            x3, lengths, packs, steps, hours = _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=True,
+                                                             times=times)
+            series_len = n if lengths is None else None
         # once for all kinds: the channels share their offsets, and starts / ends count from each channel's own base
-        starts, ends, series, shifts = _roll_windows(torch, packs[0], n if lengths is None else None, int(rolling_direction),
+        starts, ends, series, shifts = _roll_windows(torch, packs[0], series_len, int(rolling_direction),
                                                      max_timeshift, int(min_timeshift), steps)
         n_windows = int(series.shape[0])
         features = torch.empty((n_windows, n_cols), dtype=torch.float64, device=x3.device)
@@ -391,7 +498,12 @@ def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=Fa
             for c, kind, fplan, nplan, col0 in jobs:
                 nplan.extract_windows_into(packs[c].values_ptr, packs[c].values_type, starts.data_ptr(), ends.data_ptr(),
                                            n_windows, matrix, col0=col0, **timed)
-        positions = shifts - 1
+        if kept_steps is None:
+            positions = shifts - 1
+        else:
+            # the original step index of the sample that names the window: one gather on the device
+            named = ends - 1 if rolling_direction > 0 else starts
+            positions = kept_steps[named].to(torch.int64)
         _synchronize(torch, device)
         for pack in packs:
             pack.close()

@@ -256,7 +256,7 @@ def select_features_tensor(X, y, columns=None, ml_task="auto", multiclass=False,
 def extract_relevant_features_tensor(x, y, lengths=None, kinds=None, channels_last=False, default_fc_parameters=None,
                                      kind_to_fc_parameters=None, ml_task="auto", multiclass=False, n_significant=1,
                                      test_for_binary_target_real_feature="mann", fdr_level=0.05, hypotheses_independent=False,
-                                     device=None, check_nan=True, times=None, time_unit="ns"):
+                                     device=None, check_nan=True, nan_policy="raise", times=None, time_unit="ns"):
     """`extract_relevant_features` for a batch held as a tensor: `extract_features_tensor`, `impute_tensor` and
     `select_features_tensor` on one matrix that never leaves the GPU.
 
@@ -265,13 +265,16 @@ def extract_relevant_features_tensor(x, y, lengths=None, kinds=None, channels_la
     :param y: one target value per series, as in `calculate_relevance_tensor`; the selection options likewise.
     :param times, time_unit: as in `extract_features_tensor`: the batch's clock, which adds the `linear_trend_timewise`
         columns to the matrix the selection runs on.
+    :param nan_policy: as in `extract_features_tensor`: "drop" extracts from the steps the wide frame keeps after
+        `dropna()`; `y` stays one value per series.  Not offered here either: a validity mask, per-kind lengths, the frame
+        entries, an enqueue-only mode.
     :return: `(features, columns)`: the relevant columns `[B, k]` on the device, in ascending column index of the extracted
         matrix, and their names."""
     from tsfresh_amd.tensor import extract_features_tensor
     features, columns = extract_features_tensor(x, lengths=lengths, kinds=kinds, channels_last=channels_last,
                                                 default_fc_parameters=default_fc_parameters,
                                                 kind_to_fc_parameters=kind_to_fc_parameters, device=device, check_nan=check_nan,
-                                                times=times, time_unit=time_unit)
+                                                nan_policy=nan_policy, times=times, time_unit=time_unit)
     impute_tensor(features)
     selected, names, _ = select_features_tensor(features, y, columns=columns, ml_task=ml_task, multiclass=multiclass,
                                                 n_significant=n_significant,
