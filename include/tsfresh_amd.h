@@ -221,6 +221,12 @@ int32_t tsfa_plan_last_launches(const tsfa_plan *plan, tsfa_launch_info *out, in
  *   "sort_waves"     1|2   k_sort up to 2048 samples: one wavefront per series (1), or the two-wavefront form it replaced (2)
  *   "seq_rows"       -1|0|1 lempel_ziv_complexity's symbol rows in LDS (0), in HBM (1), or in HBM where that puts more series on a CU (-1, default)
  *   "host_chunks"    n     row chunks of the TSFA_HOST pipeline (0: by batch size)
+ *   "side_lane"      mask  two lanes: bit f = family f (enum tsfa_family) runs on a side stream beside the others, bit 9 = k_perm;
+ *                          0 = one lane.  Default: SEQ | TREND.  BASIC, SORT and ENTROPY are refused (they carry the shared
+ *                          statistics and the shared sample order).  Never while profiling, with TSFA_STREAMS > 1, beyond 4096 samples
+ *   "side_after"     f     the main lane's family behind which the side lane starts (default ENTROPY; at least the first launched)
+ *   "side_priority"  0|1   the side stream at the device's lowest priority (0, default) or at the main lane's (1)
+ *   "fail_after"     f     test hook: the batch returns an error after family f's launches (-1: off)
  *   "fill" v / "fill_off"  pre-fill the result matrix with v before the kernels run (audits: every cell is written anyway)
  * plan == NULL: library-wide options ("relevance_batch" n: columns per sort batch of tsfa_relevance_*).
  * Unknown names return TSFA_ERR_INVALID.  The reference has no counterpart (its knobs are n_jobs / chunksize).

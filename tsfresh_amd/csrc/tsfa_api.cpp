@@ -31,6 +31,16 @@ int tsfa_fail(int code, const char *msg) { return fail(code, std::string(msg ? m
 #define TSFA_MAX_AUX 3
 #define TSFA_MAX_CHUNKS 16
 #define TSFA_DEFAULT_STREAMS 1
+// The side lane's families (PlanOptions::side_lane).  BASIC, SORT and ENTROPY never go there: they carry the shared
+// per-series statistics and the shared sample order.  TSFA_SIDE_PERM: k_perm, which reads nothing but the samples.
+// The default is what profiles/r09_two_lanes.md measured best at 100 000 x 1024: k_seq, then k_trend, starting behind
+// k_entropy_bits -- beside k_ar and k_sort, which leave issue slots idle; k_entropy_bits itself (VALU busy 0.90) leaves few,
+// and neither k_perm on the side lane nor a side stream of the main lane's priority measured a gain.
+#define TSFA_SIDE_PERM (1u << TSFA_N_FAMILIES)
+#define TSFA_SIDE_ALLOWED ((TSFA_SIDE_PERM | (TSFA_SIDE_PERM - 1u)) & ~((1u << TSFA_FAM_BASIC) | (1u << TSFA_FAM_SORT) | (1u << TSFA_FAM_ENTROPY)))
+#define TSFA_SIDE_DEFAULT ((1u << TSFA_FAM_SEQ) | (1u << TSFA_FAM_TREND))
+#define TSFA_SIDE_PRIORITY_DEFAULT 0
+#define TSFA_SIDE_AFTER_DEFAULT TSFA_FAM_ENTROPY
 
 struct Timing {
     std::string name;
@@ -69,6 +79,10 @@ struct PlanOptions {
     bool trace = false;           // lab build: launch decisions to stderr
     bool row_form = true;         // BASIC / TREND: series of <= 256 samples four to a wavefront (k_basic_rows / k_trend_rows)
     int seq_rows = -1;            // lempel_ziv symbol rows: 0 in LDS, 1 in HBM, -1: in HBM where that puts more series on a CU
+    unsigned side_lane = TSFA_SIDE_DEFAULT;   // two lanes (tsfa_plan::side): bit f = family f on the side lane, TSFA_SIDE_PERM = k_perm; 0: one lane
+    int side_priority = TSFA_SIDE_PRIORITY_DEFAULT;   // the side stream's priority: 0 the device's lowest, 1 the main lane's
+    int side_after = TSFA_SIDE_AFTER_DEFAULT;   // the family of the main lane behind which the side lane starts
+    int fail_after = -1;          // test hook: run_batch returns an error after this family's launches (its exits after the fork)
 };
 
 #if defined(TSFA_LAB)
@@ -128,13 +142,18 @@ struct tsfa_plan {
     int *d_fill_cols = nullptr;
     int n_fill_cols = 0;
     int debug_skip_fam = -1;             // TSFA_DEBUG_SKIP_FAM=<family>: the audit's positive control
-    // Side lane (TSFA_PAIR=<families>, e.g. "seq" or "seq,spectral"): the named families run on a LOW-priority stream beside
-    // the others -- the dispatcher gives the main lane's workgroups every slot they can use and the side lane's the LDS /
+    // Two lanes (option "side_lane": a family bit mask, 0 = one lane; TSFA_PAIR=<families>, e.g. "seq" or "seq,spectral",
+    // overrides the default mask when the plan is built): the named families run on a second stream beside the others -- at
+    // LOW priority the dispatcher gives the main lane's workgroups every slot they can use and the side lane's the LDS /
     // register / wavefront slots they leave (k_entropy_bits holds 122 of 160 KB of LDS and 448 of 512 VGPRs per SIMD: two
-    // k_seq workgroups fit beside it), so a latency-bound kernel fills issue slots an issue-bound one leaves idle.
+    // k_seq workgroups fit beside it), at the main lane's priority (option "side_priority" 1) it mixes the workgroups of both
+    // -- so a latency-bound kernel fills issue slots an issue-bound one leaves idle.  The lane forks behind the main lane's
+    // family that option "side_after" names (at the earliest after the first of the order: k_basic and its statistics record)
+    // and joins before run_batch returns, on every exit path.  The stream and its events are made at the first batch that
+    // uses them (side_ready).
     hipStream_t side = nullptr;
-    hipEvent_t ev_side_fork = nullptr, ev_side_join = nullptr;
-    unsigned side_mask = 0;              // bit f: family f runs on the side lane
+    hipEvent_t ev_side_fork = nullptr, ev_side_join = nullptr, ev_side_long = nullptr;
+    int side_priority_made = -1;         // the option value `side` was created for
     double fill_value = __builtin_nan("");   // TSFA_DEBUG_FILL=<value>: a sentinel instead (profiles/fill_audit.py)
 
     // the body runs before the members' destructors: everything the plan owns is freed on its own device
@@ -148,7 +167,7 @@ struct tsfa_plan {
         for (hipEvent_t e : ev_in) drop_event(e);
         for (hipEvent_t e : ev_k) drop_event(e);
         for (hipEvent_t e : ev_join) drop_event(e);
-        for (hipEvent_t e : {ev_fork, ev_side_fork, ev_side_join}) drop_event(e);
+        for (hipEvent_t e : {ev_fork, ev_side_fork, ev_side_join, ev_side_long}) drop_event(e);
         for (hipStream_t s : aux) drop_stream(s);
         for (hipStream_t s : {s_in, s_out, side, stream}) drop_stream(s);
     }
@@ -296,15 +315,11 @@ int tsfa_plan_create_with_data(const tsfa_feature_spec *specs, int32_t n_specs, 
     }
     if (const char *e = getenv("TSFA_PAIR")) {
         static const char *nm[TSFA_N_FAMILIES] = {"basic", "sort", "spectral", "ar", "entropy", "cwt", "seq", "trend", "mprofile"};
+        // the named families instead of the default set ("perm": k_perm); a value that names none gives one lane
+        unsigned mask = strstr(e, "perm") ? TSFA_SIDE_PERM : 0u;
         for (int f = 0; f < TSFA_N_FAMILIES; ++f)
-            if (f != TSFA_FAM_BASIC && f != TSFA_FAM_SORT && f != TSFA_FAM_ENTROPY && strstr(e, nm[f])) plan->side_mask |= 1u << f;   // (SORT reads ENTROPY's sample order: both stay on the main lane)
-        if (plan->side_mask) {
-            int least = 0, greatest = 0;
-            (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-            ok = ok && hipStreamCreateWithPriority(&plan->side, hipStreamNonBlocking, least) == hipSuccess &&
-                 hipEventCreateWithFlags(&plan->ev_side_fork, hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&plan->ev_side_join, hipEventDisableTiming) == hipSuccess;
-        }
+            if (strstr(e, nm[f])) mask |= 1u << f;
+        plan->opt.side_lane = mask & TSFA_SIDE_ALLOWED;   // (SORT reads ENTROPY's sample order: both stay on the main lane)
     }
     if (const char *e = getenv("TSFA_HOST_CHUNKS")) plan->opt.host_chunks = std::max(atoi(e), 0);
     if (!ok) return fail(TSFA_ERR_HIP, "device allocation/upload failed while creating the plan");
@@ -327,6 +342,15 @@ int tsfa_plan_set_option(tsfa_plan *plan, const char *name, double value) {
     if (!name) return fail(TSFA_ERR_INVALID, "option name is NULL");
     const std::string n(name);
     const bool on = value != 0.0;
+    if (n == "side_lane") {   // (the mask is checked before the plan is looked at: the parser is testable without a device)
+        static const char *nm[TSFA_N_FAMILIES + 1] = {"BASIC", "SORT", "SPECTRAL", "AR", "ENTROPY", "CWT", "SEQ", "TREND", "MPROFILE", "k_perm"};
+        if (!(value >= 0.0 && value <= (double)(TSFA_SIDE_PERM | (TSFA_SIDE_PERM - 1u)) && value == (double)(unsigned)value))
+            return fail(TSFA_ERR_INVALID, "side_lane: 0 (one lane) or a bit mask of families (bit " + std::to_string(TSFA_N_FAMILIES) + ": k_perm)");
+        for (int f = 0; f <= TSFA_N_FAMILIES; ++f)
+            if ((((unsigned)value & ~TSFA_SIDE_ALLOWED) >> f) & 1u)
+                return fail(TSFA_ERR_INVALID, std::string("side_lane: ") + nm[f] + " stays on the main lane (BASIC, SORT and ENTROPY carry "
+                                              "the shared statistics and the shared sample order)");
+    }
     if (!plan) {   // library-wide
         if (n == "relevance_batch") { g_relevance_batch = value > 0.0 ? (int64_t)value : 0; return TSFA_OK; }
         return fail(TSFA_ERR_INVALID, "unknown library option '" + n + "'");
@@ -350,6 +374,10 @@ int tsfa_plan_set_option(tsfa_plan *plan, const char *name, double value) {
     else if (n == "perm_fused") { if (!on) plan->hints[TSFA_FAM_SORT].d = 0; }   // permutation_entropy stays in k_sort
     else if (n == "fill") { plan->fill_value = value; plan->fill_all = true; }   // pre-fill the matrix (NaN, or an audit's sentinel)
     else if (n == "fill_off") { plan->fill_all = false; }
+    else if (n == "side_lane") o.side_lane = (unsigned)value;   // (checked above)
+    else if (n == "side_priority") { if (value != 0.0 && value != 1.0) return fail(TSFA_ERR_INVALID, "side_priority: 0 (lowest) or 1 (the main lane's)"); o.side_priority = (int)value; }
+    else if (n == "side_after") { if (!(value >= 0.0 && value < (double)TSFA_N_FAMILIES && value == (double)(int)value)) return fail(TSFA_ERR_INVALID, "side_after: a family number"); o.side_after = (int)value; }
+    else if (n == "fail_after") o.fail_after = (value >= 0.0 && value < (double)TSFA_N_FAMILIES) ? (int)value : -1;
 #if defined(TSFA_LAB)
     else if (n == "skip_family") plan->debug_skip_fam = (int)value;
     else if (n == "trace") o.trace = on;
@@ -499,6 +527,45 @@ int tsfa_extract_chunks(const tsfa_plan *plan, int64_t n_series, int64_t *cuts, 
     return n_chunks;
 }
 
+// The side lane's stream and events, made when the first batch needs them (the options are set after the plan is built):
+// at the device's lowest priority, or at the priority of the main lane `st`.  A stream made for the other priority is
+// drained and replaced.
+static int side_ready(tsfa_plan *plan, hipStream_t st) {
+    if (plan->side && plan->side_priority_made == plan->opt.side_priority) return TSFA_OK;
+    if (plan->side) {
+        HIP_TRY(hipStreamSynchronize(plan->side));
+        HIP_TRY(hipStreamDestroy(plan->side));
+        plan->side = nullptr;
+    }
+    int least = 0, greatest = 0, prio = 0;
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    if (plan->opt.side_priority == 0) prio = least;
+    else HIP_TRY(hipStreamGetPriority(st, &prio));
+    HIP_TRY(hipStreamCreateWithPriority(&plan->side, hipStreamNonBlocking, prio));
+    plan->side_priority_made = plan->opt.side_priority;
+    for (hipEvent_t *e : {&plan->ev_side_fork, &plan->ev_side_join, &plan->ev_side_long})
+        if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    return TSFA_OK;
+}
+
+// Joins the side lane into the main one when run_batch leaves, by whichever return: the next batch of the plan (k_basic
+// writes the statistics record the side lane's kernels read) and the caller's copy-out both follow the main stream.
+struct SideJoin {
+    tsfa_plan *plan;
+    hipStream_t st;
+    bool used = false;
+    int join() {
+        if (!used) return TSFA_OK;
+        used = false;
+        HIP_TRY(hipEventRecord(plan->ev_side_join, plan->side));
+        HIP_TRY(hipStreamWaitEvent(st, plan->ev_side_join, 0));
+        return TSFA_OK;
+    }
+    ~SideJoin() {   // an error return: the error message of the call that failed stays
+        if (used && hipEventRecord(plan->ev_side_join, plan->side) == hipSuccess) (void)hipStreamWaitEvent(st, plan->ev_side_join, 0);
+    }
+};
+
 static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const double *d_times, const int64_t *d_starts,
                      const int64_t *d_ends, int64_t n_series, double *d_out, int64_t ld, const BatchShape &sh,
                      const int *d_sel, hipStream_t st, bool with_overlap) {
@@ -524,10 +591,47 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
         HIP_TRY(hipEventRecord(plan->ev_fork, st));
         for (int i = 0; i + 1 < plan->n_streams; ++i) HIP_TRY(hipStreamWaitEvent(plan->aux[i], plan->ev_fork, 0));
     }
-    // side lane: forked after the first family of the order (BASIC when it shares its statistics), joined at the end
-    bool pair = plan->side != nullptr && plan->side_mask != 0 && !overlap && !plan->profiling && with_overlap;
+    // Two lanes: the side lane forks after the first family of the order (BASIC when it shares its statistics) and joins
+    // before the kernels that follow the families -- on an error return too (SideJoin).  Not while profiling: the timing slots
+    // then bracket kernels that run one after another on one stream, so kernel_ms stays a serial per-kernel breakdown
+    // (the time a kernel takes alone, not the time it adds to a step it shares with another lane).
+    const unsigned side_mask = plan->opt.side_lane;
+    bool pair = side_mask != 0 && !overlap && !plan->profiling && with_overlap && !plan->opt.force_long;
     for (int g = 0; g < sh.n_groups; ++g) pair = pair && sh.g_maxn[g] <= 4096;   // (the HBM-scratch build shares one scratch region)
-    bool side_forked = false, side_used = false;
+    if (pair) {
+        const int rc = side_ready(plan, st);
+        if (rc) return rc;
+    }
+    // The main lane's families up to the one the side lane starts behind (option "side_after"; at least the first of the
+    // order), then the side lane's, k_seq at their head, then the rest of the main lane's: the side lane's first kernel starts
+    // when the main lane's next one does.  The order within each lane stays that of `order`.
+    int lane_order[TSFA_N_FAMILIES];
+    int fork_at = 1;
+    if (pair) {
+        const int after = plan->opt.side_after;
+        bool placed[TSFA_N_FAMILIES] = {false};
+        int k = 0;
+        lane_order[k++] = order[0];
+        placed[order[0]] = true;
+        if (after != order[0] && !((side_mask >> after) & 1u)) {
+            for (int fi = 1; fi < TSFA_N_FAMILIES; ++fi) {
+                if ((side_mask >> order[fi]) & 1u) continue;
+                lane_order[k++] = order[fi];
+                placed[order[fi]] = true;
+                if (order[fi] == after) break;
+            }
+            fork_at = k;
+        }
+        if ((side_mask >> TSFA_FAM_SEQ) & 1u) lane_order[k++] = TSFA_FAM_SEQ;
+        for (int fi = 1; fi < TSFA_N_FAMILIES; ++fi)
+            if (((side_mask >> order[fi]) & 1u) && order[fi] != TSFA_FAM_SEQ) lane_order[k++] = order[fi];
+        for (int fi = 1; fi < TSFA_N_FAMILIES; ++fi)
+            if (!((side_mask >> order[fi]) & 1u) && !placed[order[fi]]) lane_order[k++] = order[fi];
+        order = lane_order;
+    }
+    bool side_forked = false;
+    SideJoin side_join{plan, st};
+    hipStream_t long_lane = nullptr;     // the lane of the last launch from the HBM-scratch build (one scratch region for both)
     size_t slot = 0;
     int dealt = 0;
     // the sample order k_entropy_bits establishes is handed to k_sort through plan->perm_buf (2 bytes per sample): one
@@ -540,6 +644,13 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
     for (int g = 0; g <= TSFA_N_LEN_CLASSES; ++g) stream_done[g] = false;
     for (int fi = 0; fi < TSFA_N_FAMILIES; ++fi) {
         const int f = order[fi];
+        if (pair && !side_forked && fi == fork_at) {
+            // everything launched so far (the caller's work on `st`, the fill, k_basic and its statistics record where they
+            // are shared) precedes the side lane
+            HIP_TRY(hipEventRecord(plan->ev_side_fork, st));
+            HIP_TRY(hipStreamWaitEvent(plan->side, plan->ev_side_fork, 0));
+            side_forked = true;
+        }
         if (plan->fam_specs[f].empty()) continue;
         if (TSFA_LAB_ONLY(plan->debug_skip_fam == f)) continue;   // lab build (profiles/fill_audit.py): this family's cells keep the fill
         if (f == TSFA_FAM_BASIC && plan->stream_ok) {
@@ -552,14 +663,9 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
             const int k = dealt++ % plan->n_streams;
             if (k > 0) fst = plan->aux[k - 1];
         }
-        if (pair && fi > 0 && ((plan->side_mask >> f) & 1u)) {
-            if (!side_forked) {   // everything launched so far (k_basic and its statistics record) precedes the side lane
-                HIP_TRY(hipEventRecord(plan->ev_side_fork, st));
-                HIP_TRY(hipStreamWaitEvent(plan->side, plan->ev_side_fork, 0));
-                side_forked = true;
-            }
+        if (side_forked && ((side_mask >> f) & 1u)) {
             fst = plan->side;
-            side_used = true;
+            side_join.used = true;
         }
         const char *slot_name = (plan->stream_ok && (f == TSFA_FAM_SORT || (f == TSFA_FAM_BASIC && plan->fam_specs[TSFA_FAM_SORT].empty())))
                                     ? "k_stream" : fam_names[f];
@@ -838,6 +944,13 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                     return fail(TSFA_ERR_HIP, "hipMalloc failed for the long-series scratch");
                 a.long_scratch = (unsigned char *)plan->long_scratch.p;
                 a.long_bytes = (size_t)n_slots * slot_bytes;
+                if (pair) {   // one scratch region: a launch that uses it waits for the other lane's last one
+                    if (long_lane != nullptr && long_lane != fst) {
+                        HIP_TRY(hipEventRecord(plan->ev_side_long, long_lane));
+                        HIP_TRY(hipStreamWaitEvent(fst, plan->ev_side_long, 0));
+                    }
+                    long_lane = fst;
+                }
             }
             if (share_stats && g <= TSFA_N_LEN_CLASSES) {
                 if (f == TSFA_FAM_BASIC && !(plan->hints[f].c == 0 && a.nt <= 256)) {   // (k_basic_lite does not export)
@@ -949,14 +1062,23 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
         if (record(plan, fst, slot, slot_name, false)) return fail(TSFA_ERR_HIP, "event record failed");
         ++slot;
         if (!perm_launches.empty()) {
-            if (record(plan, fst, slot, "k_perm", true)) return fail(TSFA_ERR_HIP, "event record failed");
-            for (const auto &pa : perm_launches) {
+            // k_perm reads nothing but the samples: with two lanes it goes to the side one (in the SORT family's turn, so
+            // behind the side lane's own families)
+            hipStream_t pst = fst;
+            if (side_forked && (side_mask & TSFA_SIDE_PERM)) {
+                pst = plan->side;
+                side_join.used = true;
+            }
+            if (record(plan, pst, slot, "k_perm", true)) return fail(TSFA_ERR_HIP, "event record failed");
+            for (auto &pa : perm_launches) {
+                pa.stream = pst;
                 const int rc = tsfa_launch_perm(pa);
                 if (rc) return fail(TSFA_ERR_HIP, std::string("k_perm launch failed: ") + hipGetErrorString((hipError_t)rc));
             }
-            if (record(plan, fst, slot, "k_perm", false)) return fail(TSFA_ERR_HIP, "event record failed");
+            if (record(plan, pst, slot, "k_perm", false)) return fail(TSFA_ERR_HIP, "event record failed");
             ++slot;
         }
+        if (plan->opt.fail_after == f) return fail(TSFA_ERR_INVALID, std::string("fail_after: leaving after ") + fam_names[f]);
     }
     if (overlap) {
         for (int i = 0; i + 1 < plan->n_streams; ++i) {
@@ -964,9 +1086,9 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
             HIP_TRY(hipStreamWaitEvent(st, plan->ev_join[i], 0));
         }
     }
-    if (side_used) {
-        HIP_TRY(hipEventRecord(plan->ev_side_join, plan->side));
-        HIP_TRY(hipStreamWaitEvent(st, plan->ev_side_join, 0));
+    {
+        const int rc = side_join.join();
+        if (rc) return rc;
     }
     if (plan->bank.C > 0) {
         TsfaCwtLaunch c;

@@ -309,8 +309,15 @@ __global__ void __launch_bounds__(256) k_mprofile(const T *__restrict__ values, 
 }
 
 // BL: with the chirp-z transform of long non-power-of-two series (launched when the plan gave the group HBM scratch)
+// The LDS build without the transform is held to 96 VGPRs (five wavefronts per SIMD): SpectralLds is sized so that ten
+// two-wavefront workgroups fit a CU, and the allocator left to itself takes 97.
+#if defined(TSFA_LONG)
+#define TSFA_SPECTRAL_WPE(BL)
+#else
+#define TSFA_SPECTRAL_WPE(BL) __attribute__((amdgpu_waves_per_eu((BL) ? 1 : 5)))
+#endif
 template <typename T, bool BL>
-__global__ void __launch_bounds__(1024) k_spectral(const T *__restrict__ values, const int64_t *__restrict__ starts, const int64_t *__restrict__ ends, int64_t n_series, const int *__restrict__ sel,
+__global__ void __launch_bounds__(1024) TSFA_SPECTRAL_WPE(BL) k_spectral(const T *__restrict__ values, const int64_t *__restrict__ starts, const int64_t *__restrict__ ends, int64_t n_series, const int *__restrict__ sel,
                            const TsfaSpec *__restrict__ specs, int nspecs, double *__restrict__ out, int64_t ld,
                            int maxn, int dft_n, double *__restrict__ gscratch, int gscratch_n, int bl_min,
                            const double *__restrict__ twc, const double *__restrict__ tws, int hint_a, int hint_b,
