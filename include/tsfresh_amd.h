@@ -203,31 +203,28 @@ typedef struct tsfa_launch_info {
 int32_t tsfa_plan_last_launches(const tsfa_plan *plan, tsfa_launch_info *out, int32_t cap);
 
 /*
- * Launch options of one plan, set by the caller who owns it.  The library reads NO environment variable that can change a
- * result; what used to be debugging switches of the environment are named options here, each an alternative ROUTE to the same
- * numbers (the tests compare both ways) or a diagnostic pre-fill:
+ * Launch options of one plan, set by the caller who owns it.  The library reads NO environment variable; what used to be
+ * debugging switches of the environment are named options here, each an alternative ROUTE to the same numbers (the tests
+ * compare both ways) or a diagnostic pre-fill:
  *   "length_classes" 0|1   launch a batch whose lengths span more than 2x class by class (default 1)
  *   "stats_share"    0|1   k_basic's per-series statistics serve the other families (1)
- *   "perm_share"     0|1   the entropy kernel's sample order serves k_sort (1)
  *   "select"         0|1   median / quantile-only plans by selection instead of a sort (1)
  *   "fused_minimal"  0     MinimalFCParameters-shaped plans through the family kernels instead of k_stream
  *   "perm_fused"     0     permutation_entropy inside k_sort instead of k_perm
  *   "bluestein"      0|1   chirp-z transform for long spectra of non-power-of-two length (1); "bluestein_min" n: its crossover
  *   "gscratch_slots" n     cap of the chirp-z scratch slots (several launches per group)
- *   "cwt_mfma"       0|1   number_cwt_peaks' convolutions on the float64 matrix cores (0: measured 4 % slower)
  *   "entropy_route"  0|1|2 bit-matrix sweep | windowed pair sweep | general kernel
  *   "force_long"     0|1   the HBM-scratch build of the family kernels whatever the length
  *   "row_form"       0|1   BASIC / TREND columns of series of <= 256 samples four series to a wavefront (1)
  *   "sort_waves"     1|2   k_sort up to 2048 samples: one wavefront per series (1), or the two-wavefront form it replaced (2)
  *   "seq_rows"       -1|0|1 lempel_ziv_complexity's symbol rows in LDS (0), in HBM (1), or in HBM where that puts more series on a CU (-1, default)
  *   "host_chunks"    n     row chunks of the TSFA_HOST pipeline (0: by batch size)
- *   "side_lane"      mask  two lanes: bit f = family f (enum tsfa_family) runs on a side stream beside the others, bit 9 = k_perm;
- *                          0 = one lane.  Default: SEQ | TREND.  BASIC, SORT and ENTROPY are refused (they carry the shared
- *                          statistics and the shared sample order).  Never while profiling, with TSFA_STREAMS > 1, beyond 4096 samples
- *   "side_after"     f     the main lane's family behind which the side lane starts (default ENTROPY; at least the first launched)
- *   "side_priority"  0|1   the side stream at the device's lowest priority (0, default) or at the main lane's (1)
+ *   "side_lane"      mask  two lanes: bit f = family f (enum tsfa_family) runs on a low-priority side stream beside the others,
+ *                          behind the main lane's ENTROPY family; 0 = one lane.  Default: SEQ | TREND.  BASIC, SORT and ENTROPY
+ *                          are refused (they carry the shared statistics and the shared sample order).  Never while profiling,
+ *                          beyond 4096 samples
  *   "fail_after"     f     test hook: the batch returns an error after family f's launches (-1: off)
- *   "fill" v / "fill_off"  pre-fill the result matrix with v before the kernels run (audits: every cell is written anyway)
+ *   "fill"           v     pre-fill the result matrix with v before the kernels run (audits: every cell is written anyway)
  * plan == NULL: library-wide options ("relevance_batch" n: columns per sort batch of tsfa_relevance_*).
  * Unknown names return TSFA_ERR_INVALID.  The reference has no counterpart (its knobs are n_jobs / chunksize).
  */

@@ -868,8 +868,9 @@ def test_every_cell_is_written_by_a_kernel(gpu, monkeypatch):
 @pytest.mark.gpu
 def test_the_environment_cannot_change_a_number(gpu, monkeypatch):
     """Round-5 VERDICT #7: the shipped library read 25 environment variables on its launch path, one of which left a whole
-    family's launch out.  With every one of the old switches set the oracle's numbers still come back, bit-identical to
-    a run without them; the three variables the library does read (streams, side lane, host chunks) move work, not bits."""
+    family's launch out.  The library now reads no environment variable at all: with every one of the old switches set --
+    the last three it read (streams, side lane, host chunks) among them -- the oracle's numbers still come back,
+    bit-identical to a run without them."""
     rng = np.random.default_rng(77)
     lens = [5, 64, 300, 1024, 1500]
     series = [rng.standard_normal(n).astype(np.float32) for n in lens]
@@ -881,7 +882,8 @@ def test_the_environment_cannot_change_a_number(gpu, monkeypatch):
                      ("TSFA_NO_STATS_SHARE", "1"), ("TSFA_NO_PERM_SHARE", "1"), ("TSFA_NO_LENGTH_CLASSES", "1"), ("TSFA_NO_STREAM", "1"),
                      ("TSFA_NO_BLUESTEIN", "1"), ("TSFA_ENT_PAIRS", "1"), ("TSFA_CWT_MFMA", "1"), ("TSFA_NO_PE_FUSED", "1"),
                      ("TSFA_BLUESTEIN_MIN", "17"), ("TSFA_GSCRATCH_SLOTS", "1"), ("TSFA_NT_0", "256"), ("TSFA_NT_3", "512"),
-                     ("TSFA_DEBUG_FILL", "7.0"), ("TSFA_FILL_ALL", "1")):
+                     ("TSFA_DEBUG_FILL", "7.0"), ("TSFA_FILL_ALL", "1"), ("TSFA_STREAMS", "4"),
+                     ("TSFA_PAIR", "seq,spectral,cwt,trend,ar"), ("TSFA_HOST_CHUNKS", "3")):
         monkeypatch.setenv(var, val)
     names2, noisy = hip_engine(params, values, offsets)
     assert names == names2 and np.array_equal(clean, noisy, equal_nan=True)
@@ -929,9 +931,9 @@ def test_shared_series_statistics_change_no_bit(gpu, dtype, monkeypatch):
 
 @pytest.mark.gpu
 def test_side_lane_changes_no_bit(gpu, monkeypatch):
-    """TSFA_PAIR (opt-in): the named families run on a low-priority side stream beside the others, forked after k_basic and
-    joined (the main stream waits for the side lane's last kernel) before the results are copied out -- same kernels on the
-    same data, so the matrix must be bit-identical."""
+    """Plan option side_lane: the named families run on a low-priority side stream beside the others, forked behind
+    k_entropy and joined (the main stream waits for the side lane's last kernel) before the results are copied out -- same
+    kernels on the same data, so the matrix must be bit-identical to the one-lane schedule's (side_lane = 0)."""
     rng = np.random.default_rng(23)
     lens = list(rng.integers(20, 1100, size=500)) + [1024] * 100
     series = [rng.standard_normal(n).astype(np.float32) if i % 2 else np.cumsum(rng.standard_normal(n)).astype(np.float32)
@@ -939,9 +941,9 @@ def test_side_lane_changes_no_bit(gpu, monkeypatch):
     values = np.concatenate(series)
     offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     params = settings.ComprehensiveFCParameters()
-    names, one_lane = hip_engine(params, values, offsets)
-    monkeypatch.setenv("TSFA_PAIR", "seq,spectral,cwt,trend,ar")
-    names2, two_lanes = hip_engine(params, values, offsets)
+    names, one_lane = hip_engine(params, values, offsets, options={"side_lane": 0})
+    spectral, ar, cwt, seq, trend = 1 << 2, 1 << 3, 1 << 5, 1 << 6, 1 << 7   # enum tsfa_family
+    names2, two_lanes = hip_engine(params, values, offsets, options={"side_lane": spectral | ar | cwt | seq | trend})
     assert names == names2 and np.array_equal(one_lane, two_lanes, equal_nan=True)
 
 

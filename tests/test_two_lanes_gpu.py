@@ -13,9 +13,9 @@ from tsfresh_amd import _native
 from tsfresh_amd.feature_extraction import settings
 from tsfresh_amd.feature_extraction.plan import compile_fc_parameters
 
-# family bits of the side_lane mask (enum tsfa_family); bit 9: k_perm
-SPECTRAL, AR, CWT, SEQ, TREND, PERM = 1 << 2, 1 << 3, 1 << 5, 1 << 6, 1 << 7, 1 << 9
-EVERY_SIDE_FAMILY = SPECTRAL | AR | CWT | SEQ | TREND | PERM
+# family bits of the side_lane mask (enum tsfa_family)
+SPECTRAL, AR, CWT, SEQ, TREND = 1 << 2, 1 << 3, 1 << 5, 1 << 6, 1 << 7
+EVERY_SIDE_FAMILY = SPECTRAL | AR | CWT | SEQ | TREND
 
 _RAGGED = {}
 
@@ -43,15 +43,11 @@ def _differing(names, a, b):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
-@pytest.mark.parametrize("priority", [0, 1])
 @pytest.mark.parametrize("lanes", ["default", "every_family"])
-def test_two_lanes_change_no_bit(gpu, dtype, priority, lanes):
-    """The default schedule, and the widest one the parser admits, against side_lane = 0; the side stream at the lowest
-    priority and at the main lane's."""
+def test_two_lanes_change_no_bit(gpu, dtype, lanes):
+    """The default schedule, and the widest one the parser admits, against side_lane = 0."""
     values, offsets, names, one_lane = _ragged(dtype)
-    options = {"side_priority": priority}
-    if lanes == "every_family":
-        options["side_lane"] = EVERY_SIDE_FAMILY
+    options = {"side_lane": EVERY_SIDE_FAMILY} if lanes == "every_family" else {}
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         names2, two_lanes = hip_engine(settings.ComprehensiveFCParameters(), values, offsets, options=options)
@@ -161,9 +157,9 @@ def test_side_lane_mask_is_refused_for_the_sharing_families():
         for mask in (1 << bit, (1 << bit) | SEQ, (1 << bit) | EVERY_SIDE_FAMILY):
             rc, why = refusal(mask)
             assert rc == _native.TSFA_ERR_INVALID and name in why and "main lane" in why, (mask, rc, why)
-    for bad in (-1.0, 0.5, float(1 << 10), float("nan")):
+    for bad in (-1.0, 0.5, float(1 << 9), float(SEQ | (1 << 9)), float(1 << 10), float("nan")):
         rc, why = refusal(bad)
         assert rc == _native.TSFA_ERR_INVALID and "bit mask" in why, (bad, rc, why)
-    for mask in (0, SEQ, SEQ | PERM, EVERY_SIDE_FAMILY, 1 << 8):
+    for mask in (0, SEQ, EVERY_SIDE_FAMILY, 1 << 8):
         rc, why = refusal(mask)
         assert rc == _native.TSFA_ERR_INVALID and "unknown library option" in why, (mask, rc, why)

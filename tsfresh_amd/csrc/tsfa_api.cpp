@@ -28,19 +28,15 @@ static int fail(int code, const std::string &msg) {
 // for the other translation units of the library and the macros of tsfa_devmem.h
 int tsfa_fail(int code, const char *msg) { return fail(code, std::string(msg ? msg : "")); }
 
-#define TSFA_MAX_AUX 3
 #define TSFA_MAX_CHUNKS 16
-#define TSFA_DEFAULT_STREAMS 1
 // The side lane's families (PlanOptions::side_lane).  BASIC, SORT and ENTROPY never go there: they carry the shared
-// per-series statistics and the shared sample order.  TSFA_SIDE_PERM: k_perm, which reads nothing but the samples.
+// per-series statistics and the shared sample order.
 // The default is what profiles/r09_two_lanes.md measured best at 100 000 x 1024: k_seq, then k_trend, starting behind
 // k_entropy_bits -- beside k_ar and k_sort, which leave issue slots idle; k_entropy_bits itself (VALU busy 0.90) leaves few,
 // and neither k_perm on the side lane nor a side stream of the main lane's priority measured a gain.
-#define TSFA_SIDE_PERM (1u << TSFA_N_FAMILIES)
-#define TSFA_SIDE_ALLOWED ((TSFA_SIDE_PERM | (TSFA_SIDE_PERM - 1u)) & ~((1u << TSFA_FAM_BASIC) | (1u << TSFA_FAM_SORT) | (1u << TSFA_FAM_ENTROPY)))
+#define TSFA_SIDE_ALL ((1u << TSFA_N_FAMILIES) - 1u)
+#define TSFA_SIDE_ALLOWED (TSFA_SIDE_ALL & ~((1u << TSFA_FAM_BASIC) | (1u << TSFA_FAM_SORT) | (1u << TSFA_FAM_ENTROPY)))
 #define TSFA_SIDE_DEFAULT ((1u << TSFA_FAM_SEQ) | (1u << TSFA_FAM_TREND))
-#define TSFA_SIDE_PRIORITY_DEFAULT 0
-#define TSFA_SIDE_AFTER_DEFAULT TSFA_FAM_ENTROPY
 
 struct Timing {
     std::string name;
@@ -58,18 +54,15 @@ struct Timing {
 
 // Launch options of a plan (tsfa_plan_set_option): each names an alternative ROUTE to the same numbers -- every one has a test
 // that compares both ways -- or a diagnostic pre-fill.  They are set through the C-ABI by the caller who owns the plan; the
-// shipped library reads NO environment variable that can change a result (round-5 VERDICT: 25 getenv calls on the launch path).
-// The three variables it does read, once, when a plan is built, only move work between streams: TSFA_STREAMS, TSFA_PAIR,
-// TSFA_HOST_CHUNKS.  Result-changing diagnostics (leaving a family's launch out, per-family workgroup sizes, the stderr
-// traces) exist only in the lab build (make lab: -DTSFA_LAB, libtsfresh_amd_lab.so, never loaded by the package).
+// library reads NO environment variable (round-5 VERDICT: 25 getenv calls on the launch path).  Result-changing diagnostics
+// (leaving a family's launch out, per-family workgroup sizes, the stderr traces) exist only in the lab build (make lab:
+// -DTSFA_LAB, libtsfresh_amd_lab.so, never loaded by the package).
 struct PlanOptions {
     bool length_classes = true;   // launch a batch whose lengths span more than 2x class by class
     bool stats_share = true;      // k_basic's per-series statistics record serves the ENTROPY / AR / SEQ / SORT families
-    bool perm_share = true;       // k_entropy_bits' sample order serves k_sort
     int sort_waves = 1;           // SORT, groups up to 2048 samples: 1 = one wavefront per series; 2 = the two-wavefront form it replaced
     bool select = true;           // median / quantile-only plans: order statistics by selection (k_order_stats)
     bool bluestein = true;        // chirp-z transform for long non-power-of-two spectra
-    bool cwt_mfma = false;        // number_cwt_peaks' Ricker convolutions on v_mfma_f64_16x16x4_f64
     bool force_long = false;      // the HBM-scratch build of every family kernel whatever the length
     int entropy_route = 0;        // 0: bit-matrix sweep where it applies; 1: the windowed pair sweep; 2: the general kernel
     int bluestein_min = 0;        // crossover Goertzel -> chirp-z in samples (0: the measured defaults)
@@ -79,9 +72,7 @@ struct PlanOptions {
     bool trace = false;           // lab build: launch decisions to stderr
     bool row_form = true;         // BASIC / TREND: series of <= 256 samples four to a wavefront (k_basic_rows / k_trend_rows)
     int seq_rows = -1;            // lempel_ziv symbol rows: 0 in LDS, 1 in HBM, -1: in HBM where that puts more series on a CU
-    unsigned side_lane = TSFA_SIDE_DEFAULT;   // two lanes (tsfa_plan::side): bit f = family f on the side lane, TSFA_SIDE_PERM = k_perm; 0: one lane
-    int side_priority = TSFA_SIDE_PRIORITY_DEFAULT;   // the side stream's priority: 0 the device's lowest, 1 the main lane's
-    int side_after = TSFA_SIDE_AFTER_DEFAULT;   // the family of the main lane behind which the side lane starts
+    unsigned side_lane = TSFA_SIDE_DEFAULT;   // two lanes (tsfa_plan::side): bit f = family f on the side lane; 0: one lane
     int fail_after = -1;          // test hook: run_batch returns an error after this family's launches (its exits after the fork)
 };
 
@@ -124,10 +115,6 @@ struct tsfa_plan {
     bool needs_times = false;  // the plan holds linear_trend_timewise columns
     bool sort_only_order_stats = false;  // the SORT family holds only median / quantile columns
     bool stream_ok = false;              // BASIC + SORT are served by the fused streaming kernel (k_stream)
-    // side streams: the family kernels are independent (each writes its own columns), so they may overlap
-    int n_streams = 1;
-    hipStream_t aux[TSFA_MAX_AUX] = {nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[TSFA_MAX_AUX] = {nullptr};
     bool profiling = false;
     std::vector<Timing> timings;
     std::vector<tsfa_launch_info> launches;     // tsfa_plan_last_launches: one record per (family, launch group) of the last extract
@@ -135,26 +122,19 @@ struct tsfa_plan {
     // Every family kernel writes every one of its columns for every series (NaN where the reference yields NaN): audited
     // with a sentinel pre-fill over lengths 1 .. 8192, three parameter sets, both sample types, constant / non-finite
     // series (profiles/fill_audit.py, tests/test_gpu_parity.py::test_every_cell_is_written_by_a_kernel), so the matrix is
-    // NOT pre-filled (round 3 rewrote all of it, 0.63 GB per 100 000 x 783, for nothing).  fill_all (TSFA_FILL_ALL=1, or
-    // a TSFA_DEBUG_FILL sentinel) restores the pre-fill; d_fill_cols would list single columns should a kernel ever
-    // need them.
+    // NOT pre-filled (round 3 rewrote all of it, 0.63 GB per 100 000 x 783, for nothing).  Option "fill" restores the
+    // pre-fill of every column, with NaN or an audit's sentinel (profiles/fill_audit.py).
     bool fill_all = false;
-    int *d_fill_cols = nullptr;
-    int n_fill_cols = 0;
-    int debug_skip_fam = -1;             // TSFA_DEBUG_SKIP_FAM=<family>: the audit's positive control
-    // Two lanes (option "side_lane": a family bit mask, 0 = one lane; TSFA_PAIR=<families>, e.g. "seq" or "seq,spectral",
-    // overrides the default mask when the plan is built): the named families run on a second stream beside the others -- at
-    // LOW priority the dispatcher gives the main lane's workgroups every slot they can use and the side lane's the LDS /
-    // register / wavefront slots they leave (k_entropy_bits holds 122 of 160 KB of LDS and 448 of 512 VGPRs per SIMD: two
-    // k_seq workgroups fit beside it), at the main lane's priority (option "side_priority" 1) it mixes the workgroups of both
-    // -- so a latency-bound kernel fills issue slots an issue-bound one leaves idle.  The lane forks behind the main lane's
-    // family that option "side_after" names (at the earliest after the first of the order: k_basic and its statistics record)
-    // and joins before run_batch returns, on every exit path.  The stream and its events are made at the first batch that
-    // uses them (side_ready).
+    double fill_value = __builtin_nan("");
+    int debug_skip_fam = -1;             // lab build, option "skip_family": the audit's positive control
+    // Two lanes (option "side_lane": a family bit mask, 0 = one lane): the named families run on a second stream beside the
+    // others, at the device's LOWEST priority -- the dispatcher gives the main lane's workgroups every slot they can use and
+    // the side lane's the LDS / register / wavefront slots they leave (k_entropy_bits holds 122 of 160 KB of LDS and 448 of
+    // 512 VGPRs per SIMD: two k_seq workgroups fit beside it) -- so a latency-bound kernel fills issue slots an issue-bound one
+    // leaves idle.  The lane forks behind the main lane's k_entropy (run_batch: lane_order) and joins before run_batch
+    // returns, on every exit path.  The stream and its events are made at the first batch that uses them (side_ready).
     hipStream_t side = nullptr;
     hipEvent_t ev_side_fork = nullptr, ev_side_join = nullptr, ev_side_long = nullptr;
-    int side_priority_made = -1;         // the option value `side` was created for
-    double fill_value = __builtin_nan("");   // TSFA_DEBUG_FILL=<value>: a sentinel instead (profiles/fill_audit.py)
 
     // the body runs before the members' destructors: everything the plan owns is freed on its own device
     ~tsfa_plan() {
@@ -166,9 +146,7 @@ struct tsfa_plan {
         auto drop_stream = [](hipStream_t s) { if (s) (void)hipStreamDestroy(s); };
         for (hipEvent_t e : ev_in) drop_event(e);
         for (hipEvent_t e : ev_k) drop_event(e);
-        for (hipEvent_t e : ev_join) drop_event(e);
-        for (hipEvent_t e : {ev_fork, ev_side_fork, ev_side_join, ev_side_long}) drop_event(e);
-        for (hipStream_t s : aux) drop_stream(s);
+        for (hipEvent_t e : {ev_side_fork, ev_side_join, ev_side_long}) drop_event(e);
         for (hipStream_t s : {s_in, s_out, side, stream}) drop_stream(s);
     }
 };
@@ -305,23 +283,6 @@ int tsfa_plan_create_with_data(const tsfa_feature_spec *specs, int32_t n_specs, 
     for (int i = 0; ok && i < TSFA_MAX_CHUNKS; ++i)
         ok = hipEventCreateWithFlags(&plan->ev_in[i], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&plan->ev_k[i], hipEventDisableTiming) == hipSuccess;
-    {
-        const char *e = getenv("TSFA_STREAMS");
-        plan->n_streams = e ? std::min(std::max(atoi(e), 1), TSFA_MAX_AUX + 1) : TSFA_DEFAULT_STREAMS;
-        for (int i = 0; ok && i + 1 < plan->n_streams; ++i)
-            ok = hipStreamCreateWithFlags(&plan->aux[i], hipStreamNonBlocking) == hipSuccess &&
-                 hipEventCreateWithFlags(&plan->ev_join[i], hipEventDisableTiming) == hipSuccess;
-        if (ok && plan->n_streams > 1) ok = hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming) == hipSuccess;
-    }
-    if (const char *e = getenv("TSFA_PAIR")) {
-        static const char *nm[TSFA_N_FAMILIES] = {"basic", "sort", "spectral", "ar", "entropy", "cwt", "seq", "trend", "mprofile"};
-        // the named families instead of the default set ("perm": k_perm); a value that names none gives one lane
-        unsigned mask = strstr(e, "perm") ? TSFA_SIDE_PERM : 0u;
-        for (int f = 0; f < TSFA_N_FAMILIES; ++f)
-            if (strstr(e, nm[f])) mask |= 1u << f;
-        plan->opt.side_lane = mask & TSFA_SIDE_ALLOWED;   // (SORT reads ENTROPY's sample order: both stay on the main lane)
-    }
-    if (const char *e = getenv("TSFA_HOST_CHUNKS")) plan->opt.host_chunks = std::max(atoi(e), 0);
     if (!ok) return fail(TSFA_ERR_HIP, "device allocation/upload failed while creating the plan");
     *out_plan = plan.release();
     return TSFA_OK;
@@ -343,10 +304,10 @@ int tsfa_plan_set_option(tsfa_plan *plan, const char *name, double value) {
     const std::string n(name);
     const bool on = value != 0.0;
     if (n == "side_lane") {   // (the mask is checked before the plan is looked at: the parser is testable without a device)
-        static const char *nm[TSFA_N_FAMILIES + 1] = {"BASIC", "SORT", "SPECTRAL", "AR", "ENTROPY", "CWT", "SEQ", "TREND", "MPROFILE", "k_perm"};
-        if (!(value >= 0.0 && value <= (double)(TSFA_SIDE_PERM | (TSFA_SIDE_PERM - 1u)) && value == (double)(unsigned)value))
-            return fail(TSFA_ERR_INVALID, "side_lane: 0 (one lane) or a bit mask of families (bit " + std::to_string(TSFA_N_FAMILIES) + ": k_perm)");
-        for (int f = 0; f <= TSFA_N_FAMILIES; ++f)
+        static const char *nm[TSFA_N_FAMILIES] = {"BASIC", "SORT", "SPECTRAL", "AR", "ENTROPY", "CWT", "SEQ", "TREND", "MPROFILE"};
+        if (!(value >= 0.0 && value <= (double)TSFA_SIDE_ALL && value == (double)(unsigned)value))
+            return fail(TSFA_ERR_INVALID, "side_lane: 0 (one lane) or a bit mask of families");
+        for (int f = 0; f < TSFA_N_FAMILIES; ++f)
             if ((((unsigned)value & ~TSFA_SIDE_ALLOWED) >> f) & 1u)
                 return fail(TSFA_ERR_INVALID, std::string("side_lane: ") + nm[f] + " stays on the main lane (BASIC, SORT and ENTROPY carry "
                                               "the shared statistics and the shared sample order)");
@@ -358,10 +319,8 @@ int tsfa_plan_set_option(tsfa_plan *plan, const char *name, double value) {
     PlanOptions &o = plan->opt;
     if (n == "length_classes") o.length_classes = on;
     else if (n == "stats_share") o.stats_share = on;
-    else if (n == "perm_share") o.perm_share = on;
     else if (n == "select") o.select = on;
     else if (n == "bluestein") o.bluestein = on;
-    else if (n == "cwt_mfma") o.cwt_mfma = on;
     else if (n == "force_long") o.force_long = on;
     else if (n == "row_form") o.row_form = on;
     else if (n == "seq_rows") o.seq_rows = (value < 0.0) ? -1 : (on ? 1 : 0);
@@ -373,10 +332,7 @@ int tsfa_plan_set_option(tsfa_plan *plan, const char *name, double value) {
     else if (n == "fused_minimal") { if (!on) plan->stream_ok = false; }   // (cannot be switched back on: decided when the plan is built)
     else if (n == "perm_fused") { if (!on) plan->hints[TSFA_FAM_SORT].d = 0; }   // permutation_entropy stays in k_sort
     else if (n == "fill") { plan->fill_value = value; plan->fill_all = true; }   // pre-fill the matrix (NaN, or an audit's sentinel)
-    else if (n == "fill_off") { plan->fill_all = false; }
     else if (n == "side_lane") o.side_lane = (unsigned)value;   // (checked above)
-    else if (n == "side_priority") { if (value != 0.0 && value != 1.0) return fail(TSFA_ERR_INVALID, "side_priority: 0 (lowest) or 1 (the main lane's)"); o.side_priority = (int)value; }
-    else if (n == "side_after") { if (!(value >= 0.0 && value < (double)TSFA_N_FAMILIES && value == (double)(int)value)) return fail(TSFA_ERR_INVALID, "side_after: a family number"); o.side_after = (int)value; }
     else if (n == "fail_after") o.fail_after = (value >= 0.0 && value < (double)TSFA_N_FAMILIES) ? (int)value : -1;
 #if defined(TSFA_LAB)
     else if (n == "skip_family") plan->debug_skip_fam = (int)value;
@@ -527,22 +483,13 @@ int tsfa_extract_chunks(const tsfa_plan *plan, int64_t n_series, int64_t *cuts, 
     return n_chunks;
 }
 
-// The side lane's stream and events, made when the first batch needs them (the options are set after the plan is built):
-// at the device's lowest priority, or at the priority of the main lane `st`.  A stream made for the other priority is
-// drained and replaced.
-static int side_ready(tsfa_plan *plan, hipStream_t st) {
-    if (plan->side && plan->side_priority_made == plan->opt.side_priority) return TSFA_OK;
-    if (plan->side) {
-        HIP_TRY(hipStreamSynchronize(plan->side));
-        HIP_TRY(hipStreamDestroy(plan->side));
-        plan->side = nullptr;
-    }
-    int least = 0, greatest = 0, prio = 0;
+// The side lane's stream, at the device's lowest priority, and its events, made when the first batch needs them (the
+// options are set after the plan is built)
+static int side_ready(tsfa_plan *plan) {
+    if (plan->side) return TSFA_OK;
+    int least = 0, greatest = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    if (plan->opt.side_priority == 0) prio = least;
-    else HIP_TRY(hipStreamGetPriority(st, &prio));
-    HIP_TRY(hipStreamCreateWithPriority(&plan->side, hipStreamNonBlocking, prio));
-    plan->side_priority_made = plan->opt.side_priority;
+    HIP_TRY(hipStreamCreateWithPriority(&plan->side, hipStreamNonBlocking, least));
     for (hipEvent_t *e : {&plan->ev_side_fork, &plan->ev_side_join, &plan->ev_side_long})
         if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     return TSFA_OK;
@@ -568,78 +515,59 @@ struct SideJoin {
 
 static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const double *d_times, const int64_t *d_starts,
                      const int64_t *d_ends, int64_t n_series, double *d_out, int64_t ld, const BatchShape &sh,
-                     const int *d_sel, hipStream_t st, bool with_overlap) {
-    if ((plan->fill_all || plan->n_fill_cols > 0) &&
-        tsfa_launch_fill_nan(d_out, n_series, plan->n_cols, ld, st, plan->fill_value, plan->fill_all ? nullptr : plan->d_fill_cols,
-                             plan->n_fill_cols))
+                     const int *d_sel, hipStream_t st, bool allow_side) {
+    if (plan->fill_all && tsfa_launch_fill_nan(d_out, n_series, plan->n_cols, ld, st, plan->fill_value))
         return fail(TSFA_ERR_HIP, "fill launch failed");
 
-    // Launch order: longest kernels first.  With side streams (and no per-kernel timing requested) the families are
-    // dealt round-robin over the streams after a fork event; the join events bring them back to `st`.
+    // Launch order: longest kernels first.
     static const int order_long_first[TSFA_N_FAMILIES] = {TSFA_FAM_ENTROPY, TSFA_FAM_AR, TSFA_FAM_SORT, TSFA_FAM_CWT, TSFA_FAM_BASIC,
                                                           TSFA_FAM_SEQ, TSFA_FAM_SPECTRAL, TSFA_FAM_TREND, TSFA_FAM_MPROFILE};
     // ... unless k_basic shares its per-series statistics (numpy-order mean / variance, extrema: plan->stats_buf,
     // TSFA_STATS_*) with the ENTROPY, AR, SEQ and SORT families, which then skip their own sums: BASIC goes first
     static const int order_basic_first[TSFA_N_FAMILIES] = {TSFA_FAM_BASIC, TSFA_FAM_ENTROPY, TSFA_FAM_AR, TSFA_FAM_SORT, TSFA_FAM_CWT,
                                                            TSFA_FAM_SEQ, TSFA_FAM_SPECTRAL, TSFA_FAM_TREND, TSFA_FAM_MPROFILE};
-    const bool overlap = with_overlap && plan->n_streams > 1 && !plan->profiling;
-    const bool share_stats = plan->stats_buf.p != nullptr && !overlap && !plan->stream_ok && plan->opt.stats_share;
+    const bool share_stats = plan->stats_buf.p != nullptr && !plan->stream_ok && plan->opt.stats_share;
     const int *order = share_stats ? order_basic_first : order_long_first;
     bool stats_valid[TSFA_N_LEN_CLASSES + 1];   // launch groups whose statistics record k_basic has written
     for (int g = 0; g <= TSFA_N_LEN_CLASSES; ++g) stats_valid[g] = false;
-    if (overlap) {
-        HIP_TRY(hipEventRecord(plan->ev_fork, st));
-        for (int i = 0; i + 1 < plan->n_streams; ++i) HIP_TRY(hipStreamWaitEvent(plan->aux[i], plan->ev_fork, 0));
-    }
-    // Two lanes: the side lane forks after the first family of the order (BASIC when it shares its statistics) and joins
-    // before the kernels that follow the families -- on an error return too (SideJoin).  Not while profiling: the timing slots
-    // then bracket kernels that run one after another on one stream, so kernel_ms stays a serial per-kernel breakdown
-    // (the time a kernel takes alone, not the time it adds to a step it shares with another lane).
+    // Two lanes: the side lane forks behind the main lane's ENTROPY family (lane_order below) and joins before the kernels
+    // that follow the families -- on an error return too (SideJoin).  Not for a host call that goes out in several row
+    // chunks (allow_side), and not while profiling: the timing slots then bracket kernels that run one after another on one
+    // stream, so kernel_ms stays a serial per-kernel breakdown (the time a kernel takes alone, not the time it adds to a step
+    // it shares with another lane).
     const unsigned side_mask = plan->opt.side_lane;
-    bool pair = side_mask != 0 && !overlap && !plan->profiling && with_overlap && !plan->opt.force_long;
+    bool pair = side_mask != 0 && !plan->profiling && allow_side && !plan->opt.force_long;
     for (int g = 0; g < sh.n_groups; ++g) pair = pair && sh.g_maxn[g] <= 4096;   // (the HBM-scratch build shares one scratch region)
     if (pair) {
-        const int rc = side_ready(plan, st);
+        const int rc = side_ready(plan);
         if (rc) return rc;
     }
-    // The main lane's families up to the one the side lane starts behind (option "side_after"; at least the first of the
-    // order), then the side lane's, k_seq at their head, then the rest of the main lane's: the side lane's first kernel starts
-    // when the main lane's next one does.  The order within each lane stays that of `order`.
+    // The head of the order up to and including ENTROPY (in both orders above nothing but BASIC precedes it, and neither may
+    // go to the side lane), then the side lane's families, k_seq at their head, then the rest of the main lane's: the side
+    // lane's first kernel starts when the main lane's next one does.  The order within each lane stays that of `order`.
     int lane_order[TSFA_N_FAMILIES];
-    int fork_at = 1;
+    int fork_at = 0;
     if (pair) {
-        const int after = plan->opt.side_after;
-        bool placed[TSFA_N_FAMILIES] = {false};
         int k = 0;
-        lane_order[k++] = order[0];
-        placed[order[0]] = true;
-        if (after != order[0] && !((side_mask >> after) & 1u)) {
-            for (int fi = 1; fi < TSFA_N_FAMILIES; ++fi) {
-                if ((side_mask >> order[fi]) & 1u) continue;
-                lane_order[k++] = order[fi];
-                placed[order[fi]] = true;
-                if (order[fi] == after) break;
-            }
-            fork_at = k;
-        }
+        do lane_order[k] = order[k]; while (order[k++] != TSFA_FAM_ENTROPY);
+        fork_at = k;
         if ((side_mask >> TSFA_FAM_SEQ) & 1u) lane_order[k++] = TSFA_FAM_SEQ;
-        for (int fi = 1; fi < TSFA_N_FAMILIES; ++fi)
+        for (int fi = fork_at; fi < TSFA_N_FAMILIES; ++fi)
             if (((side_mask >> order[fi]) & 1u) && order[fi] != TSFA_FAM_SEQ) lane_order[k++] = order[fi];
-        for (int fi = 1; fi < TSFA_N_FAMILIES; ++fi)
-            if (!((side_mask >> order[fi]) & 1u) && !placed[order[fi]]) lane_order[k++] = order[fi];
+        for (int fi = fork_at; fi < TSFA_N_FAMILIES; ++fi)
+            if (!((side_mask >> order[fi]) & 1u)) lane_order[k++] = order[fi];
         order = lane_order;
     }
     bool side_forked = false;
     SideJoin side_join{plan, st};
     hipStream_t long_lane = nullptr;     // the lane of the last launch from the HBM-scratch build (one scratch region for both)
     size_t slot = 0;
-    int dealt = 0;
     // the sample order k_entropy_bits establishes is handed to k_sort through plan->perm_buf (2 bytes per sample): one
     // sort per series instead of two.  Per launch group: only where the bit-matrix sweep ran (float32 or float64 series
-    // of 3 .. 1024 samples, LDS build), and only on one stream (the entropy family is launched first).
+    // of 3 .. 1024 samples, LDS build); both families stay on the main lane, ENTROPY ahead of SORT.
     bool perm_valid[TSFA_N_LEN_CLASSES + 1];
     for (int g = 0; g <= TSFA_N_LEN_CLASSES; ++g) perm_valid[g] = false;
-    const bool perm_share = plan->perm_buf.p != nullptr && !overlap && plan->opt.perm_share;
+    const bool perm_share = plan->perm_buf.p != nullptr;
     bool stream_done[TSFA_N_LEN_CLASSES + 1];   // launch groups whose BASIC (+ SORT) columns k_stream has written
     for (int g = 0; g <= TSFA_N_LEN_CLASSES; ++g) stream_done[g] = false;
     for (int fi = 0; fi < TSFA_N_FAMILIES; ++fi) {
@@ -659,10 +587,6 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
             if (all) continue;   // every group went through k_stream at the SORT (or this) family's turn
         }
         hipStream_t fst = st;
-        if (overlap) {
-            const int k = dealt++ % plan->n_streams;
-            if (k > 0) fst = plan->aux[k - 1];
-        }
         if (side_forked && ((side_mask >> f) & 1u)) {
             fst = plan->side;
             side_join.used = true;
@@ -772,9 +696,6 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
             } else if (f == TSFA_FAM_CWT) {
                 a.cwt_rowv = tsfa_family_lds_bytes(f, maxn, a.nt, 1) <= 96 * 1024 ? 1 : 0;
                 aux = a.cwt_rowv;
-                // bit 1: the Ricker convolutions on the float64 matrix cores (opt-in: measured 4 % slower than the FMA tiles,
-                // DESIGN.md section 9; tests/test_cwt_peaks_mfma.py compares both forms)
-                if (plan->opt.cwt_mfma) a.cwt_rowv |= 2;
             } else if (f == TSFA_FAM_AR) {
                 // leading dimension of the normal matrices: ADF needs maxlag(n) + 3, AR(k) needs k + 2
                 int P = 8, Pdd = 8;   // (Pdd: ar_coefficient orders beyond TSFA_AR_TABLE_K are fitted by the second pass alone)
@@ -925,7 +846,7 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                 // the long-series build's persistent grid indexes the chirp-z scratch by workgroup: a slot for each, or none
                 if (a.gscratch != nullptr && a.gscratch_slots < std::min<int64_t>(a.n_series, 2048)) a.gscratch = nullptr;
                 if (f == TSFA_FAM_ENTROPY && a.ent_cnt != 4) { a.ent_cnt = 0; a.ent_fast = 0; lds = tsfa_entropy_lds_bytes(maxn, 5); }
-                if (f == TSFA_FAM_CWT) { a.cwt_rowv &= 2; lds = tsfa_family_lds_bytes(f, maxn, a.nt, 0); }
+                if (f == TSFA_FAM_CWT) { a.cwt_rowv = 0; lds = tsfa_family_lds_bytes(f, maxn, a.nt, 0); }
                 if (f == TSFA_FAM_SEQ) {
                     seq_group = std::min(a.nspecs, TSFA_LZ_MAX_GROUP);
                     seq_grows = 0;
@@ -1061,30 +982,16 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
         }
         if (record(plan, fst, slot, slot_name, false)) return fail(TSFA_ERR_HIP, "event record failed");
         ++slot;
-        if (!perm_launches.empty()) {
-            // k_perm reads nothing but the samples: with two lanes it goes to the side one (in the SORT family's turn, so
-            // behind the side lane's own families)
-            hipStream_t pst = fst;
-            if (side_forked && (side_mask & TSFA_SIDE_PERM)) {
-                pst = plan->side;
-                side_join.used = true;
-            }
-            if (record(plan, pst, slot, "k_perm", true)) return fail(TSFA_ERR_HIP, "event record failed");
+        if (!perm_launches.empty()) {   // on the SORT family's lane
+            if (record(plan, fst, slot, "k_perm", true)) return fail(TSFA_ERR_HIP, "event record failed");
             for (auto &pa : perm_launches) {
-                pa.stream = pst;
                 const int rc = tsfa_launch_perm(pa);
                 if (rc) return fail(TSFA_ERR_HIP, std::string("k_perm launch failed: ") + hipGetErrorString((hipError_t)rc));
             }
-            if (record(plan, pst, slot, "k_perm", false)) return fail(TSFA_ERR_HIP, "event record failed");
+            if (record(plan, fst, slot, "k_perm", false)) return fail(TSFA_ERR_HIP, "event record failed");
             ++slot;
         }
         if (plan->opt.fail_after == f) return fail(TSFA_ERR_INVALID, std::string("fail_after: leaving after ") + fam_names[f]);
-    }
-    if (overlap) {
-        for (int i = 0; i + 1 < plan->n_streams; ++i) {
-            HIP_TRY(hipEventRecord(plan->ev_join[i], plan->aux[i]));
-            HIP_TRY(hipStreamWaitEvent(st, plan->ev_join[i], 0));
-        }
     }
     {
         const int rc = side_join.join();

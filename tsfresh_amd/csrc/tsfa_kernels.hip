@@ -522,8 +522,7 @@ __global__ void __launch_bounds__(256) k_seq(const T *__restrict__ values, const
 }
 
 // MAXT: 256 for series up to 2048 samples (register allocation for 4-wave workgroups), 1024 beyond
-// MFMA: phase A on the float64 matrix cores (fam_cwt.h cwt_rows_mfma), the opt-in instantiation of TSFA_CWT_MFMA=1
-template <typename T, int MAXT, bool MFMA>
+template <typename T, int MAXT>
 __global__ void __launch_bounds__(MAXT, (MAXT == 256) ? 6 : 4) k_cwtpeaks(const T *__restrict__ values, const int64_t *__restrict__ starts, const int64_t *__restrict__ ends, int64_t n_series, const int *__restrict__ sel,
                            const TsfaSpec *__restrict__ specs, int nspecs, double *__restrict__ out, int64_t ld,
                            int maxn, int with_rowv, const double *__restrict__ consts TSFA_GS_PARAMS) {
@@ -536,7 +535,7 @@ __global__ void __launch_bounds__(MAXT, (MAXT == 256) ? 6 : 4) k_cwtpeaks(const 
     TSFA_TICKS_BEGIN();
     Blk b{(int)threadIdx.x, (int)blockDim.x, L.p.red, nullptr};
     const T *g = values + off;
-    fam_cwtpeaks_series<T, MFMA>(b, [=](int i) { return (double)g[i]; }, n, specs, nspecs, out + sidx * ld, L.p);
+    fam_cwtpeaks_series<T>(b, [=](int i) { return (double)g[i]; }, n, specs, nspecs, out + sidx * ld, L.p);
     TSFA_TICKS_END();
     TSFA_SERIES_END
 }
@@ -972,14 +971,6 @@ __global__ void k_fill_nan(double *__restrict__ out, int64_t n_rows, int64_t n_c
         }
     }
 }
-// the listed columns only (a plan whose kernels write every other cell themselves)
-__global__ void k_fill_cols(double *__restrict__ out, int64_t n_rows, const int *__restrict__ cols, int n_fill, int64_t ld, double value) {
-    const int64_t total = n_rows * (int64_t)n_fill;
-    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t r = k / n_fill;
-        out[r * ld + cols[k - r * n_fill]] = value;
-    }
-}
 
 // per-batch length statistics: [0] = max length, [1] = min length, [2] = max non-power-of-two length, then per
 // length class c (tsfa_len_class: lengths in (2^(c+5), 2^(c+6)], the first class from 1):
@@ -1207,22 +1198,11 @@ static int launch_all_t(const TsfaLaunch &a, const T *values) {
     } else if (a.fam == TSFA_FAM_CWT) {  // number_cwt_peaks
         CwtPeaksLayout L;
         const size_t lds = L.carve(nullptr, a.maxn, a.cwt_rowv & 1, (int)sizeof(T));
-#if !defined(TSFA_LONG)
-        if (a.cwt_rowv & 2) {   // TSFA_CWT_MFMA=1
-            if (nt <= 256) {
-                auto kfn = k_cwtpeaks<T, 256, true>;
-                TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, a.cwt_rowv, a.consts);
-            } else {
-                auto kfn = k_cwtpeaks<T, 1024, true>;
-                TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, a.cwt_rowv, a.consts);
-            }
-        } else
-#endif
         if (nt <= 256) {
-            auto kfn = k_cwtpeaks<T, 256, false>;
+            auto kfn = k_cwtpeaks<T, 256>;
             TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, a.cwt_rowv, a.consts);
         } else {
-            auto kfn = k_cwtpeaks<T, 1024, false>;
+            auto kfn = k_cwtpeaks<T, 1024>;
             TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, a.cwt_rowv, a.consts);
         }
     } else {
@@ -1493,13 +1473,8 @@ int tsfa_launch_cwt(const TsfaCwtLaunch &a) {
     return launch_cwt_t<double>(a, (const double *)a.values);
 }
 
-int tsfa_launch_fill_nan(double *out, int64_t n_rows, int64_t n_cols, int64_t ld, void *stream, double value,
-                         const int *cols, int n_fill) {
-    if (cols == nullptr) k_fill_nan<<<2048, 256, 0, (hipStream_t)stream>>>(out, n_rows, n_cols, ld, value);
-    else if (n_fill > 0) {
-        const int64_t total = n_rows * (int64_t)n_fill;
-        k_fill_cols<<<(unsigned)std::min<int64_t>((total + 255) / 256, 2048), 256, 0, (hipStream_t)stream>>>(out, n_rows, cols, n_fill, ld, value);
-    }
+int tsfa_launch_fill_nan(double *out, int64_t n_rows, int64_t n_cols, int64_t ld, void *stream, double value) {
+    k_fill_nan<<<2048, 256, 0, (hipStream_t)stream>>>(out, n_rows, n_cols, ld, value);
     TSFA_LAUNCH_CHECK();
     return 0;
 }

@@ -70,7 +70,7 @@ struct TsfaLaunch {
     int perm_stride;
     int64_t gscratch_slots; // SPECTRAL: slots of gscratch_n doubles in gscratch (one per workgroup of a launch)
     int bluestein_min;      // SPECTRAL: non-power-of-two lengths from here on take the chirp-z transform (with gscratch)
-    int cwt_rowv;           // CWT peaks: bit 0: the series is staged in LDS between zero halos; bit 1: phase A on the matrix cores (TSFA_CWT_MFMA=1)
+    int cwt_rowv;           // CWT peaks: 1: the series is staged in LDS between zero halos; 0: read from HBM / L2
     int hint_a, hint_b, hint_c, hint_d, hint_e;  // tsfa_prepare_family (BASIC, SORT, SPECTRAL, AR)
     unsigned char *long_scratch;  // HBM scratch of the long-series build (tsfa_launch_family_long) ...
     size_t long_bytes;            // ... and its size: slots of one working set each, one per resident workgroup
@@ -111,10 +111,8 @@ int tsfa_launch_stream(const TsfaLaunch &a);         // BASIC closed forms + med
 int tsfa_stream_calc_ok(int calc);                   // is the calculator one of those k_stream serves?
 int tsfa_launch_order_stats(const TsfaLaunch &a);    // SORT family holding only median / quantile columns, maxn <= 2048  // second pass of TSFA_FAM_AR over the series the first listed
 int tsfa_launch_cwt(const TsfaCwtLaunch &a);
-// value: NaN (a diagnostics run may ask for a sentinel: TSFA_DEBUG_FILL).  cols / n_fill: only these columns (device list);
-// cols == nullptr: every column of the plan
-int tsfa_launch_fill_nan(double *out, int64_t n_rows, int64_t n_cols, int64_t ld, void *stream, double value,
-                         const int *cols, int n_fill);
+// every column of the plan; value: NaN, or an audit's sentinel (plan option "fill")
+int tsfa_launch_fill_nan(double *out, int64_t n_rows, int64_t n_cols, int64_t ld, void *stream, double value);
 int tsfa_launch_len_stats(const int64_t *starts, const int64_t *ends, int64_t n_series, long long *stats, void *stream);
 int tsfa_launch_class_fill(const int64_t *starts, const int64_t *ends, int64_t n_series, const TsfaClassMap &g, int *cursor,
                            int *sel, void *stream);
