@@ -31,8 +31,14 @@
 // clears between series) starts out as NaN / a large finite value / a small negative one instead of zeros.  The outputs
 // must not depend on it (tests/test_oracle_golden.py): a kernel that reads scratch it has not written reads the PREVIOUS
 // series' values on the device.
-// non-power-of-two lengths from here on take the chirp-z transform on even series (TSFA_EMUL_BLUESTEIN_MIN: the tests
-// lower it to reach every tile / cross-pass shape on short series)
+// non-power-of-two lengths from here on take the chirp-z transform, like on the device (tsfa_api.cpp: scratch for every
+// series at or above its crossover).  TSFA_EMUL_BLUESTEIN_MIN: the tests lower it to reach every tile / cross-pass shape
+// on short series (the plan option "bluestein_min"); TSFA_EMUL_BLUESTEIN=0 withholds the scratch, so that every such
+// length takes the Goertzel sweep (the plan option "bluestein").
+static bool emul_bluestein_on() {
+    const char *e = getenv("TSFA_EMUL_BLUESTEIN");
+    return !e || atoi(e) != 0;
+}
 static int emul_bluestein_min() {
     const char *e = getenv("TSFA_EMUL_BLUESTEIN_MIN");
     return e ? std::max(atoi(e), 3) : TSFA_BLUESTEIN_MIN_EVEN;   // (the smaller of the two crossovers: scratch for both)
@@ -214,8 +220,8 @@ extern "C" int tsfa_emul_extract_timed(const tsfa_feature_spec *specs, int n_spe
             poison(chirp_tab);
             std::vector<int> iw(128);
             poison(Xr); poison(Xi); poison(tc); poison(ts); poison(win); poison(pxx); poison_int(iw);
-            // even series take the Bluestein route where it applies (HBM scratch on the device), odd ones the Goertzel sweep
-            std::vector<double> gsv((s % 2 == 0 && n >= emul_bluestein_min() && bluestein_m(n) <= TSFA_BLUESTEIN_MAXM)
+            // the Bluestein route where it applies (HBM scratch on the device), unless TSFA_EMUL_BLUESTEIN=0 withholds it
+            std::vector<double> gsv((emul_bluestein_on() && n >= emul_bluestein_min() && bluestein_m(n) <= TSFA_BLUESTEIN_MAXM)
                                         ? 4 * (size_t)bluestein_m(n) : 0);
             poison(gsv);
             fam_spectral_series(b, xs.data(), n, fam[TSFA_FAM_SPECTRAL].data(), (int)fam[TSFA_FAM_SPECTRAL].size(), row,

@@ -2,6 +2,10 @@
 
 TEST INFRASTRUCTURE ONLY.  The product (`tsfresh_amd`) never imports this; it exists because the build container
 has no GPU and GPU minutes are rationed, so kernel *logic* is first checked here against the oracle.
+
+Routes of the spectral family (tests/emul/emul.cpp reads them from the environment at every call): like the device, the
+emulation hands the chirp-z scratch to every series at or above its crossover.  TSFA_EMUL_BLUESTEIN=0 withholds it (the
+plan option "bluestein": 0), TSFA_EMUL_BLUESTEIN_MIN=<n> moves both crossovers to n (the plan option "bluestein_min").
 """
 import ctypes
 import os

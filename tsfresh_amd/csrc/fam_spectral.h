@@ -190,7 +190,11 @@ TSFA_DEV void blk_fft_pow2_batch(const Blk &b, double *re, double *im, int M, in
 //   other n  > 256   : Goertzel, lane = frequency bin, four bins per lane side by side: s_j = x_j + 2cos(th) s_{j-1}
 //                      - s_{j-2} with x_j an LDS broadcast read, X_k = s_{n-1} e^{i th} - s_{n-2}.  O(n^2) like the
 //                      direct DFT but register-resident (3 VALU per term, no twiddle table, no gather); its round-off
-//                      grows like n * eps / th: <= 1.3e-9 relative on 8191 samples, far inside the 1e-6 bar.
+//                      is held by tests/spectral_truth.py against the exact DFT in units of eps n^2 / (2 pi k')
+//                      max|x - mean|, k' = min(k, n/2 - k): 11 of them at 257 samples, 260 at 8197, 1100 at 32 766 (the
+//                      bins next to 0 and n/2 lose eps n / th^2, which that unit does not describe), 2100 on bin 0.
+// Every route but the radix-2 one transforms x - mean, and its error is bounded in sum|x - mean| at every level of the
+// series: direct (n + 8) eps, chirp-z 1e-13 (measured 2.2e-16), the radix-2 route 8 log2(n) eps sum|x|.
 template <class G>
 TSFA_DEV void blk_rfft(const Blk &b, int n, G g, double *Xr, double *Xi, double *tc, double *ts,
                        const double *twc, const double *tws) {
@@ -255,7 +259,8 @@ TSFA_DEV void blk_rfft(const Blk &b, int n, G g, double *Xr, double *Xi, double 
         //     cos(th) >= 0:  d_j = x_j - 4 sin^2(th/2) s_{j-1} + d_{j-1},  s_j = s_{j-1} + d_j
         //     cos(th) <  0:  d_j = x_j + 4 cos^2(th/2) s_{j-1} - d_{j-1},  s_j = d_j - s_{j-1}
         // nothing cancels, and X_k = s_{n-1} e^{i th} - s_{n-2} becomes s (cos th -+ 1) +- d.  One more addition per term than
-        // the plain form, which the lengths below keep (their error, eps n^2 / (2 pi k), is far inside the bar).
+        // the plain form, which the lengths below keep.  Measured against the exact DFT (tests/spectral_truth.py): 0.03 of
+        // eps n^2 / (2 pi k') max|x - mean| on 32 769 samples, where the plain form takes 1000 of them.
         blk_sync();
         for (int k0 = 4 * b.tid; k0 <= nh; k0 += 4 * b.nt) {
             double kap[4], sg[4], sn[4], cs[4], s1[4], d1[4];
@@ -546,7 +551,8 @@ TSFA_DEV bool bluestein_tiles_ok(int n) {
 //   * an even n is transformed as n / 2 complex points and split;
 //   * chirp values exp(i pi r / n), r < 2n <= 65536, are products of two table entries, r = 256 a + b: 2 x 256 sincospi
 //     per series (tab: 1024 doubles of LDS) instead of one per use; j^2 mod 2N in float64 (exact: j < 2^15).
-// Accuracy: 4e-16 sum|x| on 9 .. 32 767 samples (the Goertzel sweep: 6e-10).
+// Accuracy: 2.2e-16 sum|x - mean| on 257 .. 32 767 samples at every level up to 2^30, bin 0 2.2e-16 sum|x| (held to
+// 1e-13 by tests/test_spectral_routes_*.py; without the centring below 1.6e-7 sum|x - mean| at 2^30).
 // tab: cos / sin of pi 256 a / n (a < 256) and of pi b / n (b < 256): 4 x 256 doubles.
 template <class G>
 TSFA_DEV void blk_rfft_bluestein(const Blk &b, int n, G g, double *Xr, double *Xi, double *gs, double *tab,
@@ -559,6 +565,16 @@ TSFA_DEV void blk_rfft_bluestein(const Blk &b, int n, G g, double *Xr, double *X
     double *Are = gs, *Aim = gs + M, *Bre = gs + 2 * (size_t)M, *Bim = gs + 3 * (size_t)M;
     const double dn = (double)n, two_N = 2.0 * (double)N, inv_two_N = 1.0 / two_N;
     double *cA = tab, *sA = tab + 256, *cB = tab + 512, *sB = tab + 768;
+    // Like blk_rfft's O(n^2) routes the transform runs on x - x_first, the strided mean: a constant only feeds bin 0 (added
+    // back there), and the round-off of the three FFTs scales with what they carry -- with the spread of the series instead
+    // of its offset (1000 samples of N(0,1) + 2^30: 1e-5 absolute on bin 1 before, 1e-13 sum|x - mean| since).
+    double x_first;
+    {
+        double acc = 0.0;
+        for (int j = b.tid; j < n; j += b.nt) acc += g(j);
+        x_first = blk_sum(b, acc) / dn;
+        if (!(x_first == x_first) || isinf(x_first)) x_first = 0.0;
+    }
     blk_sync();
     for (int a = b.tid; a < 512; a += b.nt) {
         double sv, cv;
@@ -596,7 +612,7 @@ TSFA_DEV void blk_rfft_bluestein(const Blk &b, int n, G g, double *Xr, double *X
         if (j >= N) { *re = 0.0; *im = 0.0; return; }
         double c, s;
         chirp(j, &c, &s);
-        const double zr = half ? g(2 * j) : g(j), zi = half ? g(2 * j + 1) : 0.0;
+        const double zr = (half ? g(2 * j) : g(j)) - x_first, zi = half ? g(2 * j + 1) - x_first : 0.0;
         *re = zr * c + zi * s;   // (zr + i zi)(c - i s)
         *im = zi * c - zr * s;
     }, Are, Aim, M, Xr, Xi, T, twc, tws);
@@ -635,7 +651,7 @@ TSFA_DEV void blk_rfft_bluestein(const Blk &b, int n, G g, double *Xr, double *X
         for (int k = b.tid; k <= nh; k += b.nt) {
             double zr, zi;
             zbin(k, &zr, &zi);
-            Xr[k] = zr;
+            Xr[k] = (k == 0) ? zr + dn * x_first : zr;
             Xi[k] = (k == 0) ? 0.0 : zi;
         }
     } else {
@@ -645,7 +661,7 @@ TSFA_DEV void blk_rfft_bluestein(const Blk &b, int n, G g, double *Xr, double *X
             if (k == 0) {
                 double zr, zi;
                 zbin(0, &zr, &zi);
-                Xr[0] = zr + zi;
+                Xr[0] = (zr + zi) + dn * x_first;   // (the constant cancels in bin n / 2: n is even)
                 Xi[0] = 0.0;
                 Xr[N] = zr - zi;
                 Xi[N] = 0.0;

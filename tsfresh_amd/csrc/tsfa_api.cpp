@@ -671,9 +671,13 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                 // (A/B of the crossover, tests.  32 767: both crossovers travel packed in one int)
                 if (plan->opt.bluestein_min > 0) bl_odd = bl_even = std::min(std::max(plan->opt.bluestein_min, 17), 32767);
                 a.bluestein_min = TSFA_BLUESTEIN_PACK(bl_odd, bl_even);
-                if (max_np2 >= std::min(bl_odd, bl_even) && max_np2 <= 32768 && plan->opt.bluestein) {
+                // (a group whose longest non-power-of-two series lies beyond the transform's reach still gets the scratch, sized
+                //  for the longest length within it: its shorter series take the route they take in any other company; none
+                //  where even the shortest series of the shard lies beyond it)
+                if (max_np2 >= std::min(bl_odd, bl_even) && sh.min_len <= 32768 && plan->opt.bluestein) {
+                    const long long reach = std::min<long long>(max_np2, 32767);
                     long long M = 1;
-                    while (M < 2 * max_np2 - 1) M <<= 1;
+                    while (M < 2 * reach - 1) M <<= 1;
                     // one slot per workgroup of a launch; at most 1 GB (and at least the 2048 workgroups of the long-series
                     // build's persistent grid, 2 MB each at the longest length): a larger group goes out in several launches
                     const size_t slot_bytes = (size_t)(4 * M) * sizeof(double);
