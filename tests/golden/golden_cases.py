@@ -123,7 +123,47 @@ def long_series():
     return cases
 
 
-CASE_SETS = {"main": golden_series, "degenerate": degenerate_series, "offset": offset_series, "long": long_series}
+SHORT_LENGTHS = tuple(range(1, 71)) + (127, 128, 129)
+SHORT_FAMILIES = ("noise", "walk", "ints", "two", "const", "ramp", "prefix", "suffix")
+SHORT_WALK_LEN = 129
+
+
+def short_walk():
+    """The one float32 walk whose windows are the `prefix` / `suffix` families of short_series()."""
+    rng = np.random.default_rng(20261021)
+    return np.cumsum(rng.standard_normal(SHORT_WALK_LEN)).astype(np.float32).astype(np.float64)
+
+
+def short_series():
+    """Every length from 1 to 70, and 127 .. 129, of eight families: what extract_rolled_features with min_timeshift=0 and
+    ragged sensor batches send down the kernels -- lags, chunk lengths, segment counts, peak supports, CWT widths, Welch
+    segments, AR orders, ADF lags and embedding dimensions that are not smaller than the series, regressions without a
+    degree of freedom; fewer samples than a wavefront has lanes.  Every value is float32-representable: one fixture serves
+    float32 and float64 device input.  `prefix_n` = w[0:n] and `suffix_n` = w[129 - n:129] are the windows rolling cuts out
+    of one walk w (short_walk()), starting at every alignment.  `digits_9`, `digits_90` (and `ramp_10`, of the ramp
+    family) have uniformly spread leading digits: benford_correlation is 0/0 there in the reference."""
+    rng = np.random.default_rng(20261020)
+    f32 = lambda x: np.asarray(x, dtype=np.float32).astype(np.float64)   # noqa: E731
+    w = short_walk()
+    cases = []
+    for n in SHORT_LENGTHS:
+        cases.append(("noise_%d" % n, f32(rng.standard_normal(n))))
+        cases.append(("walk_%d" % n, f32(np.cumsum(rng.standard_normal(n)))))
+        cases.append(("ints_%d" % n, rng.integers(-2, 3, size=n).astype(np.float64)))
+        cases.append(("two_%d" % n, rng.integers(0, 2, size=n).astype(np.float64)))
+        cases.append(("const_%d" % n, np.full(n, np.float64(np.float32(0.1)))))
+        cases.append(("ramp_%d" % n, np.arange(n, dtype=np.float64)))
+        cases.append(("prefix_%d" % n, w[:n].copy()))
+        cases.append(("suffix_%d" % n, w[SHORT_WALK_LEN - n:].copy()))
+    digits = np.arange(1.0, 10.0)
+    cases.append(("digits_9", digits.copy()))
+    cases.append(("digits_90", np.tile(digits, 10)))
+    assert any(label == "ramp_10" for label, _ in cases)
+    return cases
+
+
+CASE_SETS = {"main": golden_series, "degenerate": degenerate_series, "offset": offset_series, "long": long_series,
+             "short": short_series}
 
 
 def pack(cases):

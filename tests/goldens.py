@@ -8,6 +8,7 @@ offsets, series, labels) tuples.
   degenerate_nosimd  ref_main_degenerate_nosimd.npz + ...         False
   offset / offset_nosimd   ref_main_offset*.npz + ref_conda_offset.npz   (|mean| >> spread: the rank cuts of np.polyfit / pinv)
   long            ref_main_long.npz + ref_conda_long.npz          True  (1025 .. 8192 samples, rolled windows of one walk)
+  short / short_nosimd   ref_main_short*.npz + ref_conda_short.npz       (EXTRA: every length 1 .. 70, 127 .. 129; eight families)
 """
 import os
 
@@ -44,6 +45,10 @@ EXTRA = {
     "degenerate_beyond": ("ref_main_degenerate_beyond.npz", "ref_conda_degenerate_beyond.npz", True),
     "offset_beyond": ("ref_main_offset_beyond.npz", "ref_conda_offset_beyond.npz", True),
     "long_beyond": ("ref_main_long_beyond.npz", "ref_conda_long_beyond.npz", True),
+    # golden_cases.short_series, ComprehensiveFCParameters: every length 1 .. 70 and 127 .. 129 of eight families, float32-
+    # representable values (tests/test_short_ladder.py)
+    "short": ("ref_main_short.npz", "ref_conda_short.npz", True),
+    "short_nosimd": ("ref_main_short_nosimd.npz", "ref_conda_short.npz", False),
 }
 
 

@@ -798,11 +798,20 @@ def _log_skips(names, n_series, skipped_cells):
         entry["skipped"][f] = entry["skipped"].get(f, 0) + 1
 
 
-def compare(names, got, want, series, rtol=RTOL, check_excluded=False, simd_golden=False, skipped=None, ar_sv=None):
+def series_facts(series):
+    """One _SeriesFacts per series, for compare(..., series_facts=): a test that compares several results on the SAME series
+    (two dtypes, two routes, two fixture pairs) evaluates the predicates' SVDs, fits and probes once.  They are functions of
+    the series alone, never of the values compared."""
+    return [_SeriesFacts(x) for x in series]
+
+
+def compare(names, got, want, series, rtol=RTOL, check_excluded=False, simd_golden=False, skipped=None, ar_sv=None,
+            series_facts=None):
     """names: list[str]; got, want: [n_series, n_cols]; series: list of 1-D arrays.  -> list[str] of mismatches.
     skipped: optional list that receives (series index, column) of every excluded cell.
     ar_sv: optional {k: [n_series, k + 1] singular values of the AR(k) designs as the reference's interpreter computed
-    them} (fixtures made with --params sweep; R4 is then also asked of THEM)."""
+    them} (fixtures made with --params sweep; R4 is then also asked of THEM).
+    series_facts: optional series_facts(series) of an earlier call on the same series (not together with ar_sv)."""
     bad = []
     got = np.asarray(got, dtype=np.float64)
     want = np.asarray(want, dtype=np.float64)
@@ -811,16 +820,17 @@ def compare(names, got, want, series, rtol=RTOL, check_excluded=False, simd_gold
         skipped = []
     n_before = len(skipped)
     try:
-        return _compare(names, got, want, series, rtol, check_excluded, simd_golden, skipped, bad, ar_sv)
+        assert series_facts is None or (ar_sv is None and len(series_facts) == len(series))
+        return _compare(names, got, want, series, rtol, check_excluded, simd_golden, skipped, bad, ar_sv, series_facts)
     finally:
         _log_skips(names, len(series), skipped[n_before:])
 
 
-def _compare(names, got, want, series, rtol, check_excluded, simd_golden, skipped, bad, ar_sv=None):
+def _compare(names, got, want, series, rtol, check_excluded, simd_golden, skipped, bad, ar_sv=None, series_facts=None):
     for i, x in enumerate(series):
         absum = float(np.abs(np.asarray(x, dtype=np.float64)).sum())
         spectrum = None
-        facts = _SeriesFacts(x)
+        facts = series_facts[i] if series_facts is not None else _SeriesFacts(x)
         rv = _rvalue_lookup(names, want[i])
         sv_i = {k: v[i] for k, v in ar_sv.items()} if ar_sv else None
         ax = np.abs(np.asarray(x, dtype=np.float64))

@@ -1224,14 +1224,14 @@ TSFA_DEV void fam_basic_series(const BT &b0, XS xs, int n, const TsfaSpec *specs
                 // np.log10(1 + 1 / d), d = 1 .. 9, as numpy returns them (fc.py:2356): nine float64 logarithms on one lane
                 // were ~1400 instructions per series in an issue-bound kernel
                 const double bd[9] = {0.3010299956639812, 0.17609125905568124, 0.12493873660829993, 0.09691001300805642, 0.07918124604762482, 0.06694678963061322, 0.05799194697768673, 0.05115252244738129, 0.04575749056067514};
-                double dd[9], mb = 0.0, md = 0.0;
-                for (int k = 0; k < 9; ++k) {
-                    dd[k] = (double)iw[k + 1] / dn;
-                    mb += bd[k];
-                    md += dd[k];
-                }
-                mb /= 9.0;
-                md /= 9.0;
+                double dd[9];
+                for (int k = 0; k < 9; ++k) dd[k] = (double)iw[k + 1] / dn;
+                // the two means in numpy's reduction order (np.cov -> np.average over the contiguous axis: eight partial sums
+                // combined pairwise, then the ninth term): nine shares of 0.1 -- 1 .. 9, arange(10), a counter -- sum to 0.9
+                // exactly this way, every deviation is 0 and the reference returns 0/0 = NaN; a serial sum is one ulp
+                // short and divides round-off by round-off
+                const double mb = ((((bd[0] + bd[1]) + (bd[2] + bd[3])) + ((bd[4] + bd[5]) + (bd[6] + bd[7]))) + bd[8]) / 9.0;
+                const double md = ((((dd[0] + dd[1]) + (dd[2] + dd[3])) + ((dd[4] + dd[5]) + (dd[6] + dd[7]))) + dd[8]) / 9.0;
                 double sbb = 0.0, sdd = 0.0, sbd = 0.0;
                 for (int k = 0; k < 9; ++k) {
                     sbb += (bd[k] - mb) * (bd[k] - mb);
