@@ -607,14 +607,16 @@ int tsfa_impute(double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t s
  * kendall_pvalue restated in float64; Fisher by one wavefront per cell, the closed forms by one lane per cell).  The two
  * HOST routes are left to the caller: the kernel writes NaN, counts the cell, and the caller overwrites p before
  * tsfa_relevance_fdr -- the exact Mann-Whitney distribution (a class or its complement with <= 8 rows, no ties) and every
- * Kolmogorov-Smirnov tail (with_ks, and two-valued columns under a real target). */
+ * Kolmogorov-Smirnov tail (with_ks, and two-valued columns under a real target) -- unless the *_ks variants below are asked
+ * to serve the exact Kolmogorov-Smirnov tail on the device (TSFA_ROUTE_KS_EXACT). */
 enum tsfa_route {
     TSFA_ROUTE_NONE = 0,           /* constant column: p = NaN */
     TSFA_ROUTE_MWU_NORMAL = 1,
     TSFA_ROUTE_FISHER = 2,
     TSFA_ROUTE_KENDALL = 3,
     TSFA_ROUTE_HOST_MWU_EXACT = 4,
-    TSFA_ROUTE_HOST_KS = 5
+    TSFA_ROUTE_HOST_KS = 5,
+    TSFA_ROUTE_KS_EXACT = 6        /* a Kolmogorov-Smirnov cell whose exact tail the device served (ks_tail, below) */
 };
 /* X, y_codes, n_classes as tsfa_relevance_classes; with_ks != 0 additionally runs the sweep of tsfa_relevance_classes_ks and
  * routes every real cell to TSFA_ROUTE_HOST_KS.  Device outputs: p[n_cols * n_classes], route[n_cols * n_classes],
@@ -632,6 +634,38 @@ int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_t n_cols, i
                               const int32_t *y_perm, const unsigned char *y_end, int64_t ytie, double y0, double y1,
                               int32_t device, double *p, unsigned char *route, unsigned char *type,
                               tsfa_relevance_real_col *cols, int64_t *n_host_cells);
+
+/* ---- the exact Kolmogorov-Smirnov tail on the device (csrc/rel_ks.h) ----
+ * significance_tests.py ks_2samp_pvalue(n1, n2, d) for max(n1, n2) <= 10 000, bit for bit: g = gcd, lcm = (n1 / g) * n2,
+ * h = rint(d * lcm); h == 0 gives 1.0; n1 == n2 the Horner form of the closed sum (a lane per cell); n1 != n2 the lattice
+ * walk of tsfa_ks_outer_prob by anti-diagonals (a wavefront per cell).  A cell is NOT served, and stays with the caller,
+ * when max(n1, n2) > 10 000 (scipy's kstwo.sf), when n1 < 1, n2 < 1 or d is not in [0, 1], and when the exact value is not
+ * inside [0, 1] (rounding can leave it an ulp above 1: the Python text then falls through to kstwo, and so must the caller).
+ *
+ * tsfa_ks_tails: n1[n_cells], n2[n_cells], d[n_cells] and the outputs p[n_cells], route[n_cells] are DEVICE arrays.  A served
+ * cell gets its p and TSFA_ROUTE_KS_EXACT, every other cell NaN and TSFA_ROUTE_HOST_KS.  Synchronous, on the null stream. */
+int tsfa_ks_tails(const int64_t *n1, const int64_t *n2, const double *d, int64_t n_cells, int32_t device, double *p,
+                  unsigned char *route);
+enum tsfa_ks_tail {
+    TSFA_KS_TAIL_HOST = 0,  /* every Kolmogorov-Smirnov cell is TSFA_ROUTE_HOST_KS: what tsfa_relevance_tails_* do */
+    TSFA_KS_TAIL_DEVICE = 1 /* the cells tsfa_ks_tails serves get their p and TSFA_ROUTE_KS_EXACT; the rest stay HOST_KS */
+};
+/* tsfa_relevance_tails_classes / tsfa_relevance_tails_real with the choice of ks_tail: with TSFA_KS_TAIL_DEVICE the
+ * Kolmogorov-Smirnov cells (with_ks: the real columns of every class table; real target: the two-valued columns) are
+ * evaluated from the statistics the sweep left in HBM, and n_host_cells counts what is left.  ks_d_device (class tables:
+ * [n_cols * n_classes], only with with_ks) and n_hi_device / ks_d_device (real target: [n_cols]) are optional caller-owned
+ * DEVICE arrays that receive the statistics of the Kolmogorov-Smirnov cells, so that a caller with a few cells left fetches
+ * those triples instead of the host copies (cols, ks_d).  Everything else as the functions above. */
+int tsfa_relevance_tails_classes_ks(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                    const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail, int32_t device,
+                                    double *p, unsigned char *route, unsigned char *type, tsfa_relevance_col *cols,
+                                    double *rank_sums, int64_t *hi_counts, double *ks_d, double *ks_d_device,
+                                    int64_t *n_host_cells);
+int tsfa_relevance_tails_real_ks(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
+                                 const int32_t *y_perm, const unsigned char *y_end, int64_t ytie, double y0, double y1,
+                                 int32_t ks_tail, int32_t device, double *p, unsigned char *route, unsigned char *type,
+                                 tsfa_relevance_real_col *cols, int64_t *n_hi_device, double *ks_d_device,
+                                 int64_t *n_host_cells);
 /* statsmodels' multipletests "fdr_bh" / "fdr_by" per table and relevance.py's combination of the tables.  All pointers are
  * device pointers.  p[n_cols * n_tables] (n_tables <= 256: the classes, or 1), type[n_cols].  Per table the columns whose type
  * is not 0 are tested (m of them); their p-values are sorted (NaN last, never rejected) and everything up to the largest

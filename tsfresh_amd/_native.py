@@ -30,7 +30,9 @@ TSFA_PACK_KEEP_SORT = 1
 TSFA_HOST, TSFA_DEVICE = 0, 1
 # enum tsfa_route: who evaluates the tail of a p-value cell (tsfa_relevance_tails_*)
 (TSFA_ROUTE_NONE, TSFA_ROUTE_MWU_NORMAL, TSFA_ROUTE_FISHER, TSFA_ROUTE_KENDALL, TSFA_ROUTE_HOST_MWU_EXACT,
- TSFA_ROUTE_HOST_KS) = range(6)
+ TSFA_ROUTE_HOST_KS, TSFA_ROUTE_KS_EXACT) = range(7)
+# enum tsfa_ks_tail: who evaluates the exact Kolmogorov-Smirnov tails (tsfa_relevance_tails_*_ks)
+TSFA_KS_TAIL_HOST, TSFA_KS_TAIL_DEVICE = 0, 1
 
 # every symbol include/tsfresh_amd.h declares
 EXPORTS = (
@@ -92,6 +94,9 @@ EXPORTS = (
     "tsfa_scatter_columns",
     "tsfa_relevance_tails_classes",
     "tsfa_relevance_tails_real",
+    "tsfa_ks_tails",
+    "tsfa_relevance_tails_classes_ks",
+    "tsfa_relevance_tails_real_ks",
     "tsfa_relevance_fdr",
     "tsfa_compact_mask",
     "tsfa_gather_columns_device",
@@ -1359,6 +1364,14 @@ def _bind_select_api(lib):
     lib.tsfa_relevance_tails_real.restype = i32
     lib.tsfa_relevance_tails_real.argtypes = [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i64, f64, f64, i32, ptr, ptr, ptr, ptr,
                                               ctypes.POINTER(i64)]
+    lib.tsfa_ks_tails.restype = i32
+    lib.tsfa_ks_tails.argtypes = [ptr, ptr, ptr, i64, i32, ptr, ptr]
+    lib.tsfa_relevance_tails_classes_ks.restype = i32
+    lib.tsfa_relevance_tails_classes_ks.argtypes = [ptr, i64, i64, i64, i32, ptr, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr,
+                                                    ptr, ctypes.POINTER(i64)]
+    lib.tsfa_relevance_tails_real_ks.restype = i32
+    lib.tsfa_relevance_tails_real_ks.argtypes = [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i64, f64, f64, i32, i32, ptr, ptr, ptr, ptr,
+                                                 ptr, ptr, ctypes.POINTER(i64)]
     lib.tsfa_relevance_fdr.restype = i32
     lib.tsfa_relevance_fdr.argtypes = [ptr, ptr, i64, i32, f64, f64, i32, i32, i32, ptr, ptr, ptr, ptr]
     lib.tsfa_compact_mask.restype = i32
@@ -1368,11 +1381,29 @@ def _bind_select_api(lib):
     lib._tsfa_select_api_bound = True
 
 
+def _ks_tail_code(ks_tail):
+    if ks_tail not in ("host", "device"):
+        raise ValueError("ks_tail must be 'host' or 'device', not {!r}".format(ks_tail))
+    return TSFA_KS_TAIL_DEVICE if ks_tail == "device" else TSFA_KS_TAIL_HOST
+
+
+def ks_tails(n1_ptr, n2_ptr, d_ptr, n_cells, p_ptr, route_ptr, device=0):
+    """tsfa_ks_tails: the exact Kolmogorov-Smirnov tails of n_cells triples (n1 int64, n2 int64, d float64: device arrays) into
+    the device arrays p [n_cells] float64 and route [n_cells] uint8 (TSFA_ROUTE_KS_EXACT, or NaN and TSFA_ROUTE_HOST_KS)."""
+    lib = load()
+    _bind_select_api(lib)
+    _check(lib, lib.tsfa_ks_tails(ctypes.c_void_p(n1_ptr), ctypes.c_void_p(n2_ptr), ctypes.c_void_p(d_ptr), int(n_cells), int(device),
+                                  ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr)))
+
+
 def relevance_tails_classes(x_ptr, n_rows, n_cols, ld, y_codes, n_classes, p_ptr, route_ptr, type_ptr, device=0, with_ks=False,
-                            want_stats=False):
+                            want_stats=False, ks_tail="host", ks_d_ptr=None):
     """The class tables of the device matrix at x_ptr, left on the device: p [m, C] float64, route [m, C] uint8, type [m]
     uint8 -> (host-route cells, statistics).  statistics (want_stats): what `relevance_classes` returns, for the caller's
-    host routes; None otherwise (nothing but the cell count is copied)."""
+    host routes; None otherwise (nothing but the cell count is copied).  ks_tail="device" (tsfa_relevance_tails_classes_ks)
+    serves the exact Kolmogorov-Smirnov tails on the device; ks_d_ptr: an optional device array [m, C] float64 that receives
+    the Kolmogorov-Smirnov distances (with_ks), and the statistics then come without them."""
+    ks_code = _ks_tail_code(ks_tail)
     lib = load()
     _bind_select_api(lib)
     y_codes = np.ascontiguousarray(y_codes, dtype=np.int32)
@@ -1384,12 +1415,19 @@ def relevance_tails_classes(x_ptr, n_rows, n_cols, ld, y_codes, n_classes, p_ptr
         cols = np.zeros(max(n_cols, 1), dtype=[("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("tie_term", "<f8")])
         rank_sums = np.zeros((n_cols, n_classes), dtype=np.float64)
         hi_counts = np.zeros((n_cols, n_classes), dtype=np.int64)
-        ks_d = np.zeros((n_cols, n_classes), dtype=np.float64) if with_ks else None
+        ks_d = np.zeros((n_cols, n_classes), dtype=np.float64) if (with_ks and ks_d_ptr is None) else None
     hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
-    _check(lib, lib.tsfa_relevance_tails_classes(
-        ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_codes.ctypes.data_as(ctypes.c_void_p),
-        int(n_classes), int(bool(with_ks)), int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr),
-        ctypes.c_void_p(type_ptr), hp(cols), hp(rank_sums), hp(hi_counts), hp(ks_d), ctypes.byref(n_host)))
+    if ks_code == TSFA_KS_TAIL_HOST and ks_d_ptr is None:
+        _check(lib, lib.tsfa_relevance_tails_classes(
+            ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_codes.ctypes.data_as(ctypes.c_void_p),
+            int(n_classes), int(bool(with_ks)), int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr),
+            ctypes.c_void_p(type_ptr), hp(cols), hp(rank_sums), hp(hi_counts), hp(ks_d), ctypes.byref(n_host)))
+    else:
+        _check(lib, lib.tsfa_relevance_tails_classes_ks(
+            ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_codes.ctypes.data_as(ctypes.c_void_p),
+            int(n_classes), int(bool(with_ks)), ks_code, int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr),
+            ctypes.c_void_p(type_ptr), hp(cols), hp(rank_sums), hp(hi_counts), hp(ks_d),
+            None if ks_d_ptr is None else ctypes.c_void_p(ks_d_ptr), ctypes.byref(n_host)))
     stats = None
     if want_stats:
         stats = (cols["n_unique"][:n_cols].copy(), cols["tie_term"][:n_cols].copy(), rank_sums, hi_counts, ks_d)
@@ -1410,10 +1448,14 @@ def target_order(y):
     return y_rank, y_perm, y_end
 
 
-def relevance_tails_real(x_ptr, n_rows, n_cols, ld, y, tie_statistics, p_ptr, route_ptr, type_ptr, device=0, want_stats=False):
+def relevance_tails_real(x_ptr, n_rows, n_cols, ld, y, tie_statistics, p_ptr, route_ptr, type_ptr, device=0, want_stats=False,
+                         ks_tail="host", n_hi_ptr=None, ks_d_ptr=None):
     """The table of a real target for the device matrix at x_ptr, left on the device: p [m], route [m], type [m] ->
     (host-route cells, records).  tie_statistics: callable dense ranks -> (ytie, y0, y1).  records (want_stats): the
-    structured array `relevance_real` returns."""
+    structured array `relevance_real` returns.  ks_tail="device" (tsfa_relevance_tails_real_ks) serves the exact
+    Kolmogorov-Smirnov tails on the device; n_hi_ptr / ks_d_ptr: optional device arrays [m] (int64 / float64) that receive
+    the two-valued columns' statistics."""
+    ks_code = _ks_tail_code(ks_tail)
     lib = load()
     _bind_select_api(lib)
     y = np.ascontiguousarray(y, dtype=np.float64)
@@ -1423,11 +1465,20 @@ def relevance_tails_real(x_ptr, n_rows, n_cols, ld, y, tie_statistics, p_ptr, ro
     ytie, y0, y1 = tie_statistics(y_rank)
     n_host = ctypes.c_int64(0)
     cols = np.zeros(max(n_cols, 1), dtype=_REAL_COL_DTYPE) if want_stats else None
-    _check(lib, lib.tsfa_relevance_tails_real(
-        ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_rank.ctypes.data_as(ctypes.c_void_p),
-        y_perm.ctypes.data_as(ctypes.c_void_p), y_end.ctypes.data_as(ctypes.c_void_p), int(ytie), float(y0), float(y1),
-        int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr), ctypes.c_void_p(type_ptr),
-        None if cols is None else cols.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_host)))
+    if ks_code == TSFA_KS_TAIL_HOST and n_hi_ptr is None and ks_d_ptr is None:
+        _check(lib, lib.tsfa_relevance_tails_real(
+            ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_rank.ctypes.data_as(ctypes.c_void_p),
+            y_perm.ctypes.data_as(ctypes.c_void_p), y_end.ctypes.data_as(ctypes.c_void_p), int(ytie), float(y0), float(y1),
+            int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr), ctypes.c_void_p(type_ptr),
+            None if cols is None else cols.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_host)))
+    else:
+        _check(lib, lib.tsfa_relevance_tails_real_ks(
+            ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_rank.ctypes.data_as(ctypes.c_void_p),
+            y_perm.ctypes.data_as(ctypes.c_void_p), y_end.ctypes.data_as(ctypes.c_void_p), int(ytie), float(y0), float(y1),
+            ks_code, int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr), ctypes.c_void_p(type_ptr),
+            None if cols is None else cols.ctypes.data_as(ctypes.c_void_p),
+            None if n_hi_ptr is None else ctypes.c_void_p(n_hi_ptr), None if ks_d_ptr is None else ctypes.c_void_p(ks_d_ptr),
+            ctypes.byref(n_host)))
     return int(n_host.value), (None if cols is None else cols[:n_cols])
 
 

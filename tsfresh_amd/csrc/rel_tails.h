@@ -12,7 +12,8 @@
 //   rt_compact_*    mask -> ascending indices
 // Every cell carries a route byte (enum below).  The two HOST routes are not served here: the exact Mann-Whitney
 // distribution is a big-integer recurrence and the Kolmogorov-Smirnov tail a lattice walk (tsfa_ks_outer_prob) or
-// scipy's kstwo; the kernel writes NaN there and the caller fills those cells in before the FDR step.
+// scipy's kstwo; the kernel writes NaN there and the caller fills those cells in before the FDR step.  (rel_ks.h serves the
+// lattice walk on the device where the caller asks for it: TSFA_ROUTE_KS_EXACT.)
 //
 // Compiled two ways like roll_device.h / pack_dense.h: by hipcc for gfx950 and by g++ -DTSFA_EMUL
 // (tests/emul/emul_rel_tails.cpp).  In the emulation one host thread is a workgroup and the lanes are looped: a per-lane
@@ -40,7 +41,7 @@
 
 #include "../../include/tsfresh_amd.h"  // enum tsfa_route
 
-#define RT_ROUTE_IS_HOST(r) ((r) >= TSFA_ROUTE_HOST_MWU_EXACT)
+#define RT_ROUTE_IS_HOST(r) ((r) == TSFA_ROUTE_HOST_MWU_EXACT || (r) == TSFA_ROUTE_HOST_KS)
 
 #define RT_NAN (__builtin_nan(""))
 #define RT_INF (__builtin_inf())

@@ -20,6 +20,7 @@
 
 #include "../../include/tsfresh_amd.h"
 #include "rel_tails.h"
+#include "rel_ks.h"
 #include "tsfa_devmem.h"
 
 static int rel_check_device(int32_t device, const char *who);
@@ -618,13 +619,107 @@ __global__ void __launch_bounds__(RT_THREADS) k_tails_real(const tsfa_relevance_
     if (rt_tails_real_cell(cols, n_rows, ytie, y0, y1, c, p, route, type)) atomicAdd(n_host, 1ull);
 }
 
-extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                            const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t device, double *p,
-                                            unsigned char *route, unsigned char *type, tsfa_relevance_col *cols, double *rank_sums,
-                                            int64_t *hi_counts, double *ks_d, int64_t *n_host_cells) {
+// ---- the exact Kolmogorov-Smirnov tail (rel_ks.h): the TSFA_ROUTE_HOST_KS cells of a table, where the device serves them ----
+// closed forms (h == 0, the Horner form of n1 == n2): thread = cell.  cnt[0]: cells served, cnt[1] / cnt[2]: lattice cells
+// whose ring fits the LDS slice / needs the scratch
+__global__ void __launch_bounds__(RT_THREADS) k_ks_closed(RkCells s, int64_t n_cells, double *__restrict__ p, unsigned char *__restrict__ route,
+                                                          unsigned long long *__restrict__ cnt) {
+    const int64_t cell = (int64_t)blockIdx.x * RT_THREADS + threadIdx.x;
+    if (cell >= n_cells) return;
+    const int r = rk_closed_cell(s, cell, p, route);
+    if (r != RK_CELL_NONE) atomicAdd(cnt + (r - 1), 1ull);
+}
+
+// lattice cells: wavefront = cell, in a grid-stride loop, so that the rings (LDS: 8 KB a wavefront; scratch: 128 KB a
+// wavefront, null when no cell needs it) are sized by the launch and not by the table.  The wavefronts of a workgroup never
+// meet: no barrier.
+__global__ void __launch_bounds__(RT_THREADS) k_ks_lattice(RkCells s, int64_t n_cells, double *__restrict__ scratch, double *__restrict__ p,
+                                                           unsigned char *__restrict__ route, unsigned long long *__restrict__ cnt) {
+    __shared__ double rings[(RT_THREADS / 64) * RK_LDS_CHUNKS * 64];
+    const int w = (int)(threadIdx.x >> 6);
+    const int64_t wave = (int64_t)blockIdx.x * (RT_THREADS / 64) + w, n_waves = (int64_t)gridDim.x * (RT_THREADS / 64);
+    double *lds = rings + w * (RK_LDS_CHUNKS * 64);
+    double *hbm = scratch ? scratch + wave * (RK_HBM_CHUNKS * 64) : nullptr;
+    for (int64_t cell = wave; cell < n_cells; cell += n_waves)
+        if (rk_lattice_cell(s, cell, lds, hbm, p, route) == RK_CELL_SERVED && (threadIdx.x & 63) == 0) atomicAdd(cnt, 1ull);
+}
+
+__global__ void __launch_bounds__(RT_THREADS) k_ks_init(int64_t n_cells, double *__restrict__ p, unsigned char *__restrict__ route) {
+    const int64_t cell = (int64_t)blockIdx.x * RT_THREADS + threadIdx.x;
+    if (cell >= n_cells) return;
+    p[cell] = RT_NAN;
+    route[cell] = TSFA_ROUTE_HOST_KS;
+}
+
+// the real table's n_hi and ks_d, out of the sweep's records into the caller's device arrays
+__global__ void __launch_bounds__(RT_THREADS) k_ks_handout_real(const tsfa_relevance_real_col *__restrict__ cols, int64_t n_cols,
+                                                                int64_t *__restrict__ n_hi, double *__restrict__ ks_d) {
+    const int64_t c = (int64_t)blockIdx.x * RT_THREADS + threadIdx.x;
+    if (c >= n_cols) return;
+    if (n_hi) n_hi[c] = cols[c].n_hi;
+    if (ks_d) ks_d[c] = cols[c].ks_d;
+}
+
+#define RK_MAX_WORKGROUPS 512   // of 4 wavefronts: at most 256 MB of scratch, and only when a cell needs it
+
+// The KS stage on the null stream of the current device: every TSFA_ROUTE_HOST_KS cell of route[n_cells] that rel_ks.h serves
+// gets its p and TSFA_ROUTE_KS_EXACT.  Synchronous; *served: how many.
+static int ks_tails_run(const RkCells &s, int64_t n_cells, double *p, unsigned char *route, int64_t *served) {
+    *served = 0;
+    if (n_cells == 0) return TSFA_OK;
+    unsigned long long cnt[3] = {0ull, 0ull, 0ull};
+    DevPtr<unsigned long long> dcnt;
+    DevPtr<double> dscratch;
+    HIP_TRY_MALLOC(dcnt, sizeof(cnt));
+    HIP_TRY(hipMemset(dcnt.get(), 0, sizeof(cnt)));
+    k_ks_closed<<<dim3((unsigned)((n_cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(s, n_cells, p, route, dcnt.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(cnt, dcnt.get(), sizeof(cnt), hipMemcpyDeviceToHost));
+    if (cnt[1] + cnt[2] > 0) {
+        int64_t nwg = (n_cells + RT_THREADS / 64 - 1) / (RT_THREADS / 64);
+        if (nwg > RK_MAX_WORKGROUPS) nwg = RK_MAX_WORKGROUPS;
+        if (cnt[2] > 0) HIP_TRY_MALLOC(dscratch, (size_t)nwg * (RT_THREADS / 64) * RK_HBM_CHUNKS * 64 * sizeof(double));
+        k_ks_lattice<<<dim3((unsigned)nwg), RT_THREADS, 0, 0>>>(s, n_cells, dscratch.get(), p, route, dcnt.get());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(cnt, dcnt.get(), sizeof(cnt[0]), hipMemcpyDeviceToHost));
+    }
+    *served = (int64_t)cnt[0];
+    return TSFA_OK;
+}
+
+extern "C" int tsfa_ks_tails(const int64_t *n1, const int64_t *n2, const double *d, int64_t n_cells, int32_t device, double *p,
+                             unsigned char *route) {
+    if (n_cells < 0 || (n_cells > 0 && (!n1 || !n2 || !d || !p || !route)))
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_ks_tails: null pointer or bad shape");
+    int rc = rel_check_device(device, "tsfa_ks_tails");
+    if (rc || n_cells == 0) return rc;
+    HIP_TRY(hipSetDevice(device));
+    k_ks_init<<<dim3((unsigned)((n_cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(n_cells, p, route);
+    HIP_TRY(hipGetLastError());
+    RkCells s = {};
+    s.n1 = n1;
+    s.n2 = n2;
+    s.d = d;
+    int64_t served = 0;
+    rc = ks_tails_run(s, n_cells, p, route, &served);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return TSFA_OK;
+}
+
+static int ks_tail_check(int32_t ks_tail, const char *who) {
+    if (ks_tail == TSFA_KS_TAIL_HOST || ks_tail == TSFA_KS_TAIL_DEVICE) return TSFA_OK;
+    return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": ks_tail must be TSFA_KS_TAIL_HOST or TSFA_KS_TAIL_DEVICE").c_str());
+}
+
+static int relevance_tails_classes_impl(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                        const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail, int32_t device,
+                                        double *p, unsigned char *route, unsigned char *type, tsfa_relevance_col *cols,
+                                        double *rank_sums, int64_t *hi_counts, double *ks_d, double *ks_d_device,
+                                        int64_t *n_host_cells) {
     if (n_host_cells) *n_host_cells = 0;
     if (n_cols > 0 && (!p || !route || !type)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: null output pointer");
-    if (ks_d && !with_ks) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: ks_d without with_ks");
+    if ((ks_d || ks_d_device) && !with_ks) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: ks_d without with_ks");
     RelClassesDev d;
     unsigned long long nh = 0ull;
     std::vector<int64_t> class_n;
@@ -638,8 +733,8 @@ extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int
     HIP_TRY_MALLOC(dnh, sizeof(unsigned long long));
     HIP_TRY(hipMemcpy(dcn.get(), class_n.data(), (size_t)n_classes * sizeof(int64_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(dnh.get(), 0, sizeof(unsigned long long)));
+    const int64_t cells = n_cols * n_classes;
     {
-        const int64_t cells = n_cols * n_classes;
         k_tails_classes<<<dim3((unsigned)((cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(
             d.dcols.get(), d.drs.get(), dcn.get(), n_rows, n_cols, n_classes, with_ks, p, route, type, dnh.get());
         HIP_TRY(hipGetLastError());
@@ -648,18 +743,49 @@ extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpy(&nh, dnh.get(), sizeof(nh), hipMemcpyDeviceToHost));
+    if (with_ks && ks_tail == TSFA_KS_TAIL_DEVICE && nh > 0) {
+        RkCells s = {};
+        s.d = d.dks.get();
+        s.class_n = dcn.get();
+        s.n_rows = n_rows;
+        s.n_classes = n_classes;
+        int64_t served = 0;
+        rc = ks_tails_run(s, cells, p, route, &served);
+        if (rc) return rc;
+        nh -= (unsigned long long)served;
+    }
     if (n_host_cells) *n_host_cells = (int64_t)nh;
     if (cols) HIP_TRY(hipMemcpy(cols, d.dcols.get(), (size_t)n_cols * sizeof(tsfa_relevance_col), hipMemcpyDeviceToHost));
     if (rank_sums) HIP_TRY(hipMemcpy(rank_sums, d.drs.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
     if (hi_counts) HIP_TRY(hipMemcpy(hi_counts, d.dhc.get(), (size_t)n_cols * n_classes * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (ks_d) HIP_TRY(hipMemcpy(ks_d, d.dks.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
+    if (ks_d_device) HIP_TRY(hipMemcpy(ks_d_device, d.dks.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToDevice));
     return TSFA_OK;
 }
 
-extern "C" int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                         const int32_t *y_rank, const int32_t *y_perm, const unsigned char *y_end, int64_t ytie,
-                                         double y0, double y1, int32_t device, double *p, unsigned char *route, unsigned char *type,
-                                         tsfa_relevance_real_col *cols, int64_t *n_host_cells) {
+extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                            const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t device, double *p,
+                                            unsigned char *route, unsigned char *type, tsfa_relevance_col *cols, double *rank_sums,
+                                            int64_t *hi_counts, double *ks_d, int64_t *n_host_cells) {
+    return relevance_tails_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, with_ks, TSFA_KS_TAIL_HOST, device, p, route,
+                                        type, cols, rank_sums, hi_counts, ks_d, nullptr, n_host_cells);
+}
+
+extern "C" int tsfa_relevance_tails_classes_ks(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                               const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail,
+                                               int32_t device, double *p, unsigned char *route, unsigned char *type,
+                                               tsfa_relevance_col *cols, double *rank_sums, int64_t *hi_counts, double *ks_d,
+                                               double *ks_d_device, int64_t *n_host_cells) {
+    if (n_host_cells) *n_host_cells = 0;
+    if (int rc = ks_tail_check(ks_tail, "tsfa_relevance_tails_classes_ks")) return rc;
+    return relevance_tails_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, with_ks, ks_tail, device, p, route, type, cols,
+                                        rank_sums, hi_counts, ks_d, ks_d_device, n_host_cells);
+}
+
+static int relevance_tails_real_impl(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
+                                     const int32_t *y_perm, const unsigned char *y_end, int64_t ytie, double y0, double y1,
+                                     int32_t ks_tail, int32_t device, double *p, unsigned char *route, unsigned char *type,
+                                     tsfa_relevance_real_col *cols, int64_t *n_hi_device, double *ks_d_device, int64_t *n_host_cells) {
     if (n_host_cells) *n_host_cells = 0;
     if (n_cols > 0 && (!p || !route || !type)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_real: null output pointer");
     RelRealDev d;
@@ -673,9 +799,43 @@ extern "C" int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_
                                                                                               route, type, dnh.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(&nh, dnh.get(), sizeof(nh), hipMemcpyDeviceToHost));
+    if (ks_tail == TSFA_KS_TAIL_DEVICE && nh > 0) {
+        RkCells s = {};
+        s.rcols = d.dcols.get();
+        s.n_rows = n_rows;
+        int64_t served = 0;
+        rc = ks_tails_run(s, n_cols, p, route, &served);
+        if (rc) return rc;
+        nh -= (unsigned long long)served;
+    }
     if (n_host_cells) *n_host_cells = (int64_t)nh;
     if (cols) HIP_TRY(hipMemcpy(cols, d.dcols.get(), (size_t)n_cols * sizeof(tsfa_relevance_real_col), hipMemcpyDeviceToHost));
+    if (n_hi_device || ks_d_device) {
+        k_ks_handout_real<<<dim3((unsigned)((n_cols + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(d.dcols.get(), n_cols, n_hi_device,
+                                                                                                       ks_d_device);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+    }
     return TSFA_OK;
+}
+
+extern "C" int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                         const int32_t *y_rank, const int32_t *y_perm, const unsigned char *y_end, int64_t ytie,
+                                         double y0, double y1, int32_t device, double *p, unsigned char *route, unsigned char *type,
+                                         tsfa_relevance_real_col *cols, int64_t *n_host_cells) {
+    return relevance_tails_real_impl(X, n_rows, n_cols, ld, space, y_rank, y_perm, y_end, ytie, y0, y1, TSFA_KS_TAIL_HOST, device, p, route,
+                                     type, cols, nullptr, nullptr, n_host_cells);
+}
+
+extern "C" int tsfa_relevance_tails_real_ks(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                            const int32_t *y_rank, const int32_t *y_perm, const unsigned char *y_end, int64_t ytie,
+                                            double y0, double y1, int32_t ks_tail, int32_t device, double *p, unsigned char *route,
+                                            unsigned char *type, tsfa_relevance_real_col *cols, int64_t *n_hi_device,
+                                            double *ks_d_device, int64_t *n_host_cells) {
+    if (n_host_cells) *n_host_cells = 0;
+    if (int rc = ks_tail_check(ks_tail, "tsfa_relevance_tails_real_ks")) return rc;
+    return relevance_tails_real_impl(X, n_rows, n_cols, ld, space, y_rank, y_perm, y_end, ytie, y0, y1, ks_tail, device, p, route, type, cols,
+                                     n_hi_device, ks_d_device, n_host_cells);
 }
 
 // masked sort keys of the p-value matrix (rt_fdr_key): what k_rel_stage / k_rel_sort then order, one key column per table

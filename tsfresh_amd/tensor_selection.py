@@ -8,11 +8,17 @@ Whitney's normal tail, Fisher's exact tail, Kendall's asymptotic tail), the FDR 
 `tsfa_gather_columns_device`).  What crosses PCIe is the target (n values in), one byte per column (the feature types, for the
 constant-features warning and the number of tested hypotheses), the count of selected columns and their indices.
 
-Two tails stay on the host in this version and are evaluated by the functions the frame entry points use: the exact Mann-Whitney
+Two tails stay on the host by default and are evaluated by the functions the frame entry points use: the exact Mann-Whitney
 distribution (a class or its complement with at most 8 rows, no ties) and every Kolmogorov-Smirnov tail
 (`test_for_binary_target_real_feature="smir"`, binary features under a real target).  The kernels flag those cells
 (`routes`), the statistics of the run come back only when such cells can occur, and the values are written into the device
 array before the FDR step.
+
+`ks_tail="device"` moves the exact Kolmogorov-Smirnov tail (samples of at most 10 000 rows) onto the GPU as well
+(`csrc/rel_ks.h`, route `TSFA_ROUTE_KS_EXACT`): the same float64 expressions as `ks_2samp_pvalue`, equal bit for bit.  What is
+left for the host then are the cells beyond 10 000 rows (scipy's `kstwo`), the rare exact value that rounding pushes outside
+[0, 1] (`ks_2samp_pvalue` falls through to `kstwo` there, and so does this), and the exact Mann-Whitney cells; only the
+triples of those cells are fetched.
 """
 import warnings
 
@@ -105,8 +111,11 @@ def impute_tensor(X):
 
 
 def _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant, test_for_binary_target_real_feature, fdr_level,
-               hypotheses_independent, check_nan):
+               hypotheses_independent, check_nan, ks_tail="host"):
     from tsfresh_amd.feature_selection.significance_tests import ks_2samp_pvalue, mannwhitney_pvalue, target_tie_statistics
+    if ks_tail not in ("host", "device"):
+        raise ValueError("ks_tail must be 'host' or 'device', not {!r}".format(ks_tail))
+    on_device = (ks_tail == "device")
     n, m = X.shape
     y = _target(torch, y, n)
     if columns is not None:
@@ -155,26 +164,52 @@ def _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant,
         class_n = np.bincount(codes, minlength=T)
         # the host routes can only occur under 'smir' or with a class (or its complement) of at most 8 rows: only then
         # are the statistics copied out
-        want_stats = smir or bool(((class_n <= 8) | (n - class_n <= 8)).any())
-        host_cells, stats_ = _native.relevance_tails_classes(X.data_ptr(), n, m, _ld(X), codes, T, p.data_ptr(), routes.data_ptr(),
-                                                             types.data_ptr(), device=device, with_ks=smir, want_stats=want_stats)
-        if host_cells:
-            _, tie_term, rank_sums, _, ks_d = stats_
-            r = routes.cpu().numpy()
-            cells = np.argwhere(r >= _native.TSFA_ROUTE_HOST_MWU_EXACT)
-            vals = [ks_2samp_pvalue(class_n[k], n - class_n[k], ks_d[j, k]) if r[j, k] == _native.TSFA_ROUTE_HOST_KS
-                    else mannwhitney_pvalue(rank_sums[j, k], class_n[k], n - class_n[k], tie_term[j]) for j, k in cells]
-            p.view(-1)[torch.as_tensor(cells[:, 0] * T + cells[:, 1], device=dev)] = torch.as_tensor(vals, dtype=torch.float64, device=dev)
+        if smir and on_device:
+            # every real cell is a Kolmogorov-Smirnov cell (no exact Mann-Whitney under 'smir'); the distances stay in HBM and
+            # of the cells left to the host only the triples are fetched
+            ks_dev = torch.empty((m, T), dtype=torch.float64, device=dev)
+            host_cells, _ = _native.relevance_tails_classes(X.data_ptr(), n, m, _ld(X), codes, T, p.data_ptr(), routes.data_ptr(),
+                                                            types.data_ptr(), device=device, with_ks=True, want_stats=False,
+                                                            ks_tail="device", ks_d_ptr=ks_dev.data_ptr())
+            if host_cells:
+                flat = torch.nonzero(routes.view(-1) == _native.TSFA_ROUTE_HOST_KS).view(-1)
+                k, dist = (flat % T).cpu().numpy(), ks_dev.view(-1)[flat].cpu().numpy()
+                vals = [ks_2samp_pvalue(class_n[k[q]], n - class_n[k[q]], dist[q]) for q in range(len(k))]
+                p.view(-1)[flat] = torch.as_tensor(vals, dtype=torch.float64, device=dev)
+        else:
+            want_stats = smir or bool(((class_n <= 8) | (n - class_n <= 8)).any())
+            host_cells, stats_ = _native.relevance_tails_classes(X.data_ptr(), n, m, _ld(X), codes, T, p.data_ptr(), routes.data_ptr(),
+                                                                 types.data_ptr(), device=device, with_ks=smir, want_stats=want_stats)
+            if host_cells:
+                _, tie_term, rank_sums, _, ks_d = stats_
+                r = routes.cpu().numpy()
+                cells = np.argwhere((r == _native.TSFA_ROUTE_HOST_MWU_EXACT) | (r == _native.TSFA_ROUTE_HOST_KS))
+                vals = [ks_2samp_pvalue(class_n[k], n - class_n[k], ks_d[j, k]) if r[j, k] == _native.TSFA_ROUTE_HOST_KS
+                        else mannwhitney_pvalue(rank_sums[j, k], class_n[k], n - class_n[k], tie_term[j]) for j, k in cells]
+                p.view(-1)[torch.as_tensor(cells[:, 0] * T + cells[:, 1], device=dev)] = torch.as_tensor(vals, dtype=torch.float64,
+                                                                                                       device=dev)
         labels = labels.tolist()
     else:
         yv = y.astype(np.float64)
-        host_cells, rec = _native.relevance_tails_real(X.data_ptr(), n, m, _ld(X), yv, target_tie_statistics, p.data_ptr(),
-                                                       routes.data_ptr(), types.data_ptr(), device=device, want_stats=True)
-        if host_cells:
-            r = routes.cpu().numpy()[:, 0]
-            cells = np.nonzero(r == _native.TSFA_ROUTE_HOST_KS)[0]
-            vals = [ks_2samp_pvalue(rec["n_hi"][j], n - rec["n_hi"][j], rec["ks_d"][j]) for j in cells]
-            p.view(-1)[torch.as_tensor(cells, device=dev)] = torch.as_tensor(vals, dtype=torch.float64, device=dev)
+        if on_device:
+            n_hi_dev = torch.empty(m, dtype=torch.int64, device=dev)
+            ks_dev = torch.empty(m, dtype=torch.float64, device=dev)
+            host_cells, _ = _native.relevance_tails_real(X.data_ptr(), n, m, _ld(X), yv, target_tie_statistics, p.data_ptr(),
+                                                         routes.data_ptr(), types.data_ptr(), device=device, want_stats=False,
+                                                         ks_tail="device", n_hi_ptr=n_hi_dev.data_ptr(), ks_d_ptr=ks_dev.data_ptr())
+            if host_cells:   # only the triples of the cells that are left
+                flat = torch.nonzero(routes.view(-1) == _native.TSFA_ROUTE_HOST_KS).view(-1)
+                n_hi, dist = n_hi_dev[flat].cpu().numpy(), ks_dev[flat].cpu().numpy()
+                vals = [ks_2samp_pvalue(n_hi[q], n - n_hi[q], dist[q]) for q in range(len(n_hi))]
+                p.view(-1)[flat] = torch.as_tensor(vals, dtype=torch.float64, device=dev)
+        else:
+            host_cells, rec = _native.relevance_tails_real(X.data_ptr(), n, m, _ld(X), yv, target_tie_statistics, p.data_ptr(),
+                                                           routes.data_ptr(), types.data_ptr(), device=device, want_stats=True)
+            if host_cells:
+                r = routes.cpu().numpy()[:, 0]
+                cells = np.nonzero(r == _native.TSFA_ROUTE_HOST_KS)[0]
+                vals = [ks_2samp_pvalue(rec["n_hi"][j], n - rec["n_hi"][j], rec["ks_d"][j]) for j in cells]
+                p.view(-1)[torch.as_tensor(cells, device=dev)] = torch.as_tensor(vals, dtype=torch.float64, device=dev)
 
     types_host = types.cpu().numpy()   # one byte per column: the constant columns' names and the number of hypotheses
     constant = np.nonzero(types_host == 0)[0]
@@ -199,7 +234,7 @@ def _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant,
 
 def calculate_relevance_tensor(X, y, columns=None, ml_task="auto", multiclass=False, n_significant=1,
                                test_for_binary_target_real_feature="mann", fdr_level=0.05, hypotheses_independent=False,
-                               device=None, check_nan=True):
+                               device=None, check_nan=True, ks_tail="host"):
     """`calculate_relevance_table` for a feature matrix held as a tensor; every result stays on the GPU.
 
     :param X: `torch.float64` tensor `[n, m]`.  A CPU tensor or a numpy array is moved to `device` with torch; another dtype, or a
@@ -215,18 +250,22 @@ def calculate_relevance_tensor(X, y, columns=None, ml_task="auto", multiclass=Fa
     :param device: HIP device ordinal.  Default: the device X lives on, else the rule of `extract_features`.
     :param check_nan: True (default): a NaN in X raises `ValueError("Feature <name> contains NaN values")` for the first such
         column; False skips the check and its read-back of one word.
+    :param ks_tail: who evaluates the exact Kolmogorov-Smirnov tails ("smir"; binary features under a real target).  "host"
+        (default): `ks_2samp_pvalue`, one cell at a time.  "device": the GPU, for samples of at most 10 000 rows, with equal
+        p-values (`routes` then shows `TSFA_ROUTE_KS_EXACT`, and `host_cells` counts what is left to the host).  Anything else
+        raises `ValueError`.
     :return: a `RelevanceTensors`.
 
     Synchronous, like `extract_features_tensor`: X is read after everything queued on torch's current stream has finished."""
     import torch
     X, device = _matrix(torch, X, device)
     return _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant, test_for_binary_target_real_feature,
-                      fdr_level, hypotheses_independent, check_nan)
+                      fdr_level, hypotheses_independent, check_nan, ks_tail)
 
 
 def select_features_tensor(X, y, columns=None, ml_task="auto", multiclass=False, n_significant=1,
                            test_for_binary_target_real_feature="mann", fdr_level=0.05, hypotheses_independent=False, device=None,
-                           check_nan=True):
+                           check_nan=True, ks_tail="host"):
     """`select_features` for a feature matrix held as a tensor: the relevant columns, gathered on the GPU.
 
     Parameters as in `calculate_relevance_tensor`.
@@ -239,7 +278,7 @@ def select_features_tensor(X, y, columns=None, ml_task="auto", multiclass=False,
     import torch
     X, device = _matrix(torch, X, device)
     res = _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant, test_for_binary_target_real_feature,
-                     fdr_level, hypotheses_independent, check_nan)
+                     fdr_level, hypotheses_independent, check_nan, ks_tail)
     n, m = X.shape
     indices = torch.empty(m, dtype=torch.int32, device=X.device)
     _synchronize(torch, device)
@@ -256,13 +295,14 @@ def select_features_tensor(X, y, columns=None, ml_task="auto", multiclass=False,
 def extract_relevant_features_tensor(x, y, lengths=None, kinds=None, channels_last=False, default_fc_parameters=None,
                                      kind_to_fc_parameters=None, ml_task="auto", multiclass=False, n_significant=1,
                                      test_for_binary_target_real_feature="mann", fdr_level=0.05, hypotheses_independent=False,
-                                     device=None, check_nan=True, nan_policy="raise", times=None, time_unit="ns"):
+                                     device=None, check_nan=True, ks_tail="host", nan_policy="raise", times=None, time_unit="ns"):
     """`extract_relevant_features` for a batch held as a tensor: `extract_features_tensor`, `impute_tensor` and
     `select_features_tensor` on one matrix that never leaves the GPU.
 
     :param x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device, check_nan: as in
         `extract_features_tensor` (check_nan is about the samples; the imputed matrix holds no NaN).
-    :param y: one target value per series, as in `calculate_relevance_tensor`; the selection options likewise.
+    :param y: one target value per series, as in `calculate_relevance_tensor`; the selection options (`ks_tail` among them)
+        likewise.
     :param times, time_unit: as in `extract_features_tensor`: the batch's clock, which adds the `linear_trend_timewise`
         columns to the matrix the selection runs on.
     :param nan_policy: as in `extract_features_tensor`: "drop" extracts from the steps the wide frame keeps after
@@ -271,6 +311,8 @@ def extract_relevant_features_tensor(x, y, lengths=None, kinds=None, channels_la
     :return: `(features, columns)`: the relevant columns `[B, k]` on the device, in ascending column index of the extracted
         matrix, and their names."""
     from tsfresh_amd.tensor import extract_features_tensor
+    if ks_tail not in ("host", "device"):   # before the extraction runs
+        raise ValueError("ks_tail must be 'host' or 'device', not {!r}".format(ks_tail))
     features, columns = extract_features_tensor(x, lengths=lengths, kinds=kinds, channels_last=channels_last,
                                                 default_fc_parameters=default_fc_parameters,
                                                 kind_to_fc_parameters=kind_to_fc_parameters, device=device, check_nan=check_nan,
@@ -280,5 +322,5 @@ def extract_relevant_features_tensor(x, y, lengths=None, kinds=None, channels_la
                                                 n_significant=n_significant,
                                                 test_for_binary_target_real_feature=test_for_binary_target_real_feature,
                                                 fdr_level=fdr_level, hypotheses_independent=hypotheses_independent,
-                                                device=features.device.index, check_nan=False)
+                                                device=features.device.index, check_nan=False, ks_tail=ks_tail)
     return selected, names
