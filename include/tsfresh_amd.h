@@ -288,6 +288,10 @@ int32_t tsfa_pack_device_flags(const tsfa_pack *pack);
 int32_t tsfa_pack_device_n_passes(const tsfa_pack *pack);
 int tsfa_pack_device_values(const tsfa_pack *pack, const void **values, int32_t *dtype);
 const int64_t *tsfa_pack_device_offsets(const tsfa_pack *pack);
+/* Device pointer of the pack's unique ids (n_groups elements of the id column's own type, ascending): what
+ * tsfa_pack_device_copy_ids copies, for a caller that keeps the ids in HBM.  Valid while the pack (or, for a view, any holder
+ * of the set's id buffer) lives. */
+const void *tsfa_pack_device_ids(const tsfa_pack *pack);
 int tsfa_pack_device_copy_ids(const tsfa_pack *pack, void *ids_host);
 int tsfa_pack_device_copy_offsets(const tsfa_pack *pack, int64_t *offsets_host);
 int tsfa_pack_device_copy_sort(const tsfa_pack *pack, void *sort_host);
@@ -333,6 +337,41 @@ int tsfa_pack_set_copy_kinds(const tsfa_pack_set *set, void *kinds_host);
 int32_t tsfa_pack_set_flags(const tsfa_pack_set *set);
 int32_t tsfa_pack_set_n_passes(const tsfa_pack_set *set);
 int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int32_t value_type, int32_t space, tsfa_pack **out_packs);
+/* Row packer: a value MATRIX through a set's permutation in one pass.  For a set made WITHOUT a kind column (a wide frame) whose
+ * n_cols value columns are one array in device memory of logical shape (n_rows, n_cols), row-aligned with the key columns,
+ * with any non-negative element strides stride_row / stride_col (row-major, column-major, sliced and expanded views).
+ * Replaces n_cols tsfa_pack_set_values calls, each of which re-reads the permutation and, on a row-major matrix, touches
+ * n_cols times the bytes it uses.
+ *   values, value_type   TSFA_DEVICE pointers only; the element types, conversions and NaN test of tsfa_pack_device
+ *   out_packs            n_cols handles; out_packs[c] is a view of column c: elements [c * n_rows, (c + 1) * n_rows) of ONE new
+ *                        buffer of n_cols * n_rows output elements, the set's offsets and ids, TSFA_PACK_VALUE_NAN raised per
+ *                        column; every tsfa_pack_device_* accessor and tsfa_extract* work on it, ownership as in
+ *                        tsfa_pack_set_values
+ * Two kernels, chosen from the strides: stride_col == 1 with several columns turns [position x column] tiles through LDS (the
+ * tile geometry of tsfa_pack_dense's channels-last route; the permutation is read once per row, the loads of a gathered row
+ * and the stores of a column are both unit-stride); anything else is a strided gather with one lane per (column, position).
+ * Grid-stride over the tiles, at most 2048 workgroups; no atomic but the OR into a column's flag.  Scratch: 4 bytes per column.
+ * Synchronous.  TSFA_ERR_INVALID: a null pointer, a set with a kind column, an unknown element type, n_cols outside
+ * [1, 2^31 - 1], a negative stride, an extent beyond 2^59 cells.  Otherwise the errors of tsfa_pack_set_values. */
+int tsfa_pack_set_rows(tsfa_pack_set *set, const void *values, int32_t value_type, int64_t n_cols, int64_t stride_row,
+                       int64_t stride_col, tsfa_pack **out_packs);
+/* Hours packer of a set: the per-sample `times` of tsfa_extract_timed for a frame whose stamps are a row-aligned array in
+ * device memory (the frame's DatetimeIndex), written in the set's packed order for ALL kinds at once:
+ *     hours_out[p] = hours between stamp t[perm[p] * stride] and the stamp of the first sorted row of p's (kind, id) group
+ * for every sorted position p in [0, n_rows); kind k's stretch starts at its first row, where tsfa_pack_set_values' views start.
+ *   t, t_type, ticks_per_second   TSFA_I64 ticks or TSFA_F64 seconds, exactly as tsfa_pack_times takes them, with its
+ *                        arithmetic (one int64 subtraction, one conversion, two IEEE divisions: pandas >= 2 bit for bit);
+ *                        stamps need not ascend
+ *   hours_out            n_rows float64 (a device pointer)
+ *   flags_out            one int32 the call ORs TSFA_DENSE_BAD_TIME into (the caller clears it): a NaT tick or NaN second; its
+ *                        hours are NaN, and so are those of a whole group whose FIRST stamp is missing
+ * One kernel over work items of 4096 sorted positions: one bisection of the set's offsets per work item, the offsets of the
+ * groups that start inside it staged in LDS, where the lanes bisect; at most 1024 workgroups, grid-stride.  Nothing is
+ * allocated.  Synchronous.  This is what a frame with a DatetimeIndex lacks to be packed on the device; the frame entries do
+ * not use it yet.
+ * TSFA_ERR_INVALID: a null pointer, another type, a ticks_per_second outside the four values, a negative stride. */
+int tsfa_pack_set_hours(const tsfa_pack_set *set, const void *t, int32_t t_type, int64_t ticks_per_second, int64_t stride,
+                        double *hours_out, int32_t *flags_out);
 void tsfa_pack_set_destroy(tsfa_pack_set *set);
 
 /* Dense packer: the ragged layout for a batch that already IS an array in device memory -- (n_batch, n_channels, n_time) with

@@ -12,6 +12,7 @@ from tsfresh_amd.feature_extraction.settings import (  # noqa: F401
 )
 
 from tsfresh_amd.tensor import extract_features_tensor, extract_rolled_features_tensor  # noqa: F401,E402
+from tsfresh_amd.tensor_long import extract_features_long_tensor  # noqa: F401,E402
 from tsfresh_amd.tensor_selection import (  # noqa: F401,E402
     calculate_relevance_tensor,
     extract_relevant_features_tensor,

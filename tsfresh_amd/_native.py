@@ -56,6 +56,7 @@ EXPORTS = (
     "tsfa_pack_device_n_passes",
     "tsfa_pack_device_values",
     "tsfa_pack_device_offsets",
+    "tsfa_pack_device_ids",
     "tsfa_pack_device_copy_ids",
     "tsfa_pack_device_copy_offsets",
     "tsfa_pack_device_copy_sort",
@@ -66,6 +67,8 @@ EXPORTS = (
     "tsfa_pack_set_flags",
     "tsfa_pack_set_n_passes",
     "tsfa_pack_set_values",
+    "tsfa_pack_set_rows",
+    "tsfa_pack_set_hours",
     "tsfa_pack_set_destroy",
     "tsfa_pack_dense",
     "tsfa_pack_times",
@@ -367,8 +370,9 @@ class DevicePack:
             TSFA_PACK_KEEP_SORT if (keep_sort and sort_a is not None) else 0, int(device), ctypes.byref(handle)))
         self._adopt(lib, handle, device, ids_a.dtype, None if sort_a is None or not keep_sort else sort_a.dtype)
 
-    def _adopt(self, lib, handle, device, ids_dtype, sort_dtype):
-        """Take over a `tsfa_pack*` (one made by tsfa_pack_device, or a view handed out by a DevicePackSet)."""
+    def _adopt(self, lib, handle, device, ids_dtype, sort_dtype, copy_ids=True):
+        """Take over a `tsfa_pack*` (one made by tsfa_pack_device, or a view handed out by a DevicePackSet).
+        copy_ids=False (the device-pointer path): `.ids` stays None, the ids stay in HBM at `.ids_ptr`."""
         self._lib, self._h, self.device = lib, handle, int(device)
         self.n_rows = int(lib.tsfa_pack_device_n_rows(handle))
         self.n_series = int(lib.tsfa_pack_device_n_groups(handle))
@@ -381,8 +385,17 @@ class DevicePack:
         self.offsets_ptr = lib.tsfa_pack_device_offsets(handle)
         self._sort_dtype = sort_dtype
         self._offsets = self._sort = None
-        self.ids = np.empty(self.n_series, dtype=ids_dtype)
-        _check(lib, lib.tsfa_pack_device_copy_ids(handle, self.ids.ctypes.data_as(ctypes.c_void_p)))
+        self.ids_dtype = np.dtype(ids_dtype)
+        self.ids = None
+        if copy_ids:
+            self.ids = np.empty(self.n_series, dtype=ids_dtype)
+            _check(lib, lib.tsfa_pack_device_copy_ids(handle, self.ids.ctypes.data_as(ctypes.c_void_p)))
+
+    @property
+    def ids_ptr(self):
+        """Device pointer (int) of the n_series unique ids, ascending, in the id column's own dtype (tsfa_pack_device_ids)."""
+        _bind_pack_set_api(self._lib)
+        return self._lib.tsfa_pack_device_ids(self._h)
 
     @property
     def value_nan(self):
@@ -445,6 +458,14 @@ def _bind_pack_set_api(lib):
     lib.tsfa_pack_set_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                          ctypes.POINTER(ctypes.c_void_p)]
     lib.tsfa_pack_set_values.restype = ctypes.c_int
+    lib.tsfa_pack_set_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                       ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]
+    lib.tsfa_pack_set_rows.restype = ctypes.c_int
+    lib.tsfa_pack_set_hours.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_void_p, ctypes.c_void_p]
+    lib.tsfa_pack_set_hours.restype = ctypes.c_int
+    lib.tsfa_pack_device_ids.argtypes = [ctypes.c_void_p]
+    lib.tsfa_pack_device_ids.restype = ctypes.c_void_p
     lib.tsfa_pack_set_destroy.argtypes = [ctypes.c_void_p]
     lib.tsfa_pack_set_destroy.restype = None
     lib._tsfa_pack_set_bound = True
@@ -456,12 +477,19 @@ class DevicePackSet:
     DevicePack per kind, in ascending order of the kind values (`.kinds`): views into one gathered buffer that share the
     set's offsets and ids.  The views and the set may be closed in any order; a buffer goes with its last holder.
     ids / sort / kinds: what `pack_column` returned; sort may be None, kinds may be None (one kind: a wide frame, one
-    `values` call per value column)."""
+    `values` call per value column, or one `rows` call for a value matrix).
+    space=TSFA_DEVICE (with n_rows): the columns are already in HBM on `device`, each given as (device pointer (int),
+    tsfa_dtype code, numpy dtype) of a contiguous column; they are used in place, nothing is staged, the views keep their
+    ids in HBM (`DevicePack.ids_ptr`, `.ids` is None) and `values` / `rows` / `hours` take device pointers."""
 
-    def __init__(self, ids, sort, kinds, device=0, keep_sort=False):
+    def __init__(self, ids, sort, kinds, device=0, keep_sort=False, space=TSFA_HOST, n_rows=None):
         lib = load()
         _bind_device_api(lib)
         _bind_pack_set_api(lib)
+        if space == TSFA_DEVICE:
+            self._init_device(lib, ids, sort, kinds, device, keep_sort, n_rows)
+            return
+        self.space = TSFA_HOST
         ids_a, ids_t = ids
         sort_a, sort_t = sort if sort is not None else (None, 0)
         kind_a, kind_t = kinds if kinds is not None else (None, 0)
@@ -485,26 +513,78 @@ class DevicePackSet:
             self.kinds = np.empty(self.n_kinds, dtype=kind_a.dtype)
             _check(lib, lib.tsfa_pack_set_copy_kinds(handle, self.kinds.ctypes.data_as(ctypes.c_void_p)))
 
+    def _init_device(self, lib, ids, sort, kinds, device, keep_sort, n_rows):
+        (ids_p, ids_t, ids_dtype) = ids
+        sort_p, sort_t, sort_dtype = sort if sort is not None else (None, 0, None)
+        kind_p, kind_t, kind_dtype = kinds if kinds is not None else (None, 0, None)
+        if n_rows is None:
+            raise ValueError("space=TSFA_DEVICE needs n_rows")
+        handle = ctypes.c_void_p()
+        _check(lib, lib.tsfa_pack_set_create(
+            ctypes.c_void_p(ids_p), int(ids_t), _ptr(sort_p), int(sort_t), _ptr(kind_p), int(kind_t), int(n_rows), TSFA_DEVICE,
+            TSFA_PACK_KEEP_SORT if (keep_sort and sort_p) else 0, int(device), ctypes.byref(handle)))
+        self.space = TSFA_DEVICE
+        self._lib, self._h, self.device = lib, handle, int(device)
+        self.n_rows = int(n_rows)
+        self.n_kinds = int(lib.tsfa_pack_set_n_kinds(handle))
+        self.flags = int(lib.tsfa_pack_set_flags(handle))
+        self.n_passes = int(lib.tsfa_pack_set_n_passes(handle))
+        self._ids_dtype = np.dtype(ids_dtype)
+        self._sort_dtype = None if not sort_p or not keep_sort else np.dtype(sort_dtype)
+        self.kinds = None
+        if kind_p:
+            self.kinds = np.empty(self.n_kinds, dtype=kind_dtype)   # (the library's host copy: nothing crosses the bus here)
+            _check(lib, lib.tsfa_pack_set_copy_kinds(handle, self.kinds.ctypes.data_as(ctypes.c_void_p)))
+
     @property
     def was_in_order(self):
         return bool(self.flags & TSFA_PACK_IN_ORDER)
 
-    def values(self, column):
-        """column: what `pack_column` returned for a value column of n_rows entries -> [DevicePack per kind]."""
-        val_a, val_t = column
-        if len(val_a) != self.n_rows:
-            raise ValueError("the value column must have one entry per row")
-        if not self._h:
-            raise ValueError("the pack set is closed")
-        handles = (ctypes.c_void_p * self.n_kinds)()
-        _check(self._lib, self._lib.tsfa_pack_set_values(self._h, val_a.ctypes.data_as(ctypes.c_void_p), val_t, TSFA_HOST,
-                                                         handles))
+    def _views(self, handles):
         packs = []
         for h in handles:
             pack = DevicePack.__new__(DevicePack)   # a view: no tsfa_pack_device call
             packs.append(pack)
-            pack._adopt(self._lib, ctypes.c_void_p(h), self.device, self._ids_dtype, self._sort_dtype)
+            pack._adopt(self._lib, ctypes.c_void_p(h), self.device, self._ids_dtype, self._sort_dtype,
+                        copy_ids=self.space == TSFA_HOST)
         return packs
+
+    def values(self, column):
+        """column: what `pack_column` returned for a value column of n_rows entries -- for a set made with
+        space=TSFA_DEVICE (device pointer (int), tsfa_dtype code) of a contiguous column -> [DevicePack per kind]."""
+        if not self._h:
+            raise ValueError("the pack set is closed")
+        handles = (ctypes.c_void_p * self.n_kinds)()
+        if self.space == TSFA_DEVICE:
+            val_p, val_t = column
+            _check(self._lib, self._lib.tsfa_pack_set_values(self._h, ctypes.c_void_p(val_p), int(val_t), TSFA_DEVICE, handles))
+            return self._views(handles)
+        val_a, val_t = column
+        if len(val_a) != self.n_rows:
+            raise ValueError("the value column must have one entry per row")
+        _check(self._lib, self._lib.tsfa_pack_set_values(self._h, val_a.ctypes.data_as(ctypes.c_void_p), val_t, TSFA_HOST,
+                                                         handles))
+        return self._views(handles)
+
+    def rows(self, values_ptr, value_type, n_cols, stride_row, stride_col):
+        """tsfa_pack_set_rows: the (n_rows, n_cols) value matrix at the device pointer `values_ptr` (element strides
+        stride_row / stride_col) through the permutation in one pass -> [DevicePack per column], views into one buffer
+        that share the set's offsets and ids.  Only for a set without a kind column."""
+        if not self._h:
+            raise ValueError("the pack set is closed")
+        handles = (ctypes.c_void_p * int(n_cols))()
+        _check(self._lib, self._lib.tsfa_pack_set_rows(self._h, ctypes.c_void_p(values_ptr), int(value_type), int(n_cols),
+                                                       int(stride_row), int(stride_col), handles))
+        return self._views(handles)
+
+    def hours(self, t_ptr, t_type, ticks_per_second, stride, hours_ptr, flags_ptr):
+        """tsfa_pack_set_hours on raw device pointers (ints): the n_rows row-aligned stamps at t_ptr (TSFA_I64 ticks or
+        TSFA_F64 seconds, element stride `stride`) -> float64 hours since the first stamp of each (kind, id) group at
+        hours_ptr, in the set's sorted order over all kinds; flags_ptr: one int32 the call ORs TSFA_DENSE_BAD_TIME into."""
+        if not self._h:
+            raise ValueError("the pack set is closed")
+        _check(self._lib, self._lib.tsfa_pack_set_hours(self._h, ctypes.c_void_p(t_ptr), int(t_type), int(ticks_per_second),
+                                                        int(stride), ctypes.c_void_p(hours_ptr), ctypes.c_void_p(flags_ptr)))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1,6 +1,7 @@
 // Device packer of the C-ABI (include/tsfresh_amd.h: tsfa_pack_device*): the kernels around the bodies of pack_device.h
 // and the host code that strings them together.  See pack_device.h for the scratch formula and the sort's design.
 // The window builder (tsfa_roll_windows, roll_device.h) lives here as well: it reads a pack's buffers and reuses k_pack_scan.
+// So does the row packer (tsfa_pack_set_rows, tsfa_pack_set_hours; pack_rows.h): it reads a set's permutation and offsets.
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "pack_device.h"
+#include "pack_rows.h"
 #include "roll_device.h"
 #include "tsfa_devmem.h"
 
@@ -162,6 +164,29 @@ __global__ void __launch_bounds__(PK_GRID_THREADS) k_pack_rebase(const int64_t *
     const PkBlk b{(int)threadIdx.x, (int)blockDim.x};
     pk_rebase_body(b, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, global, kind_rows, kind_groups, n_kinds, total,
                    out);
+}
+
+// ---- the row packer's kernels (pack_rows.h) ----
+template <int TYPE>
+__global__ void __launch_bounds__(PD_THREADS) k_pack_rows_tiles(PrArgs a) {
+    __shared__ uint32_t tile[(TYPE == TSFA_F32 ? 1 : 2) * PD_TILE_WORDS];
+    __shared__ uint32_t rows[PD_TILE_CELLS / 2];
+    const PkBlk b{(int)threadIdx.x, PD_THREADS};
+    pr_tiles_body<TYPE>(b, (int64_t)blockIdx.x, (int64_t)gridDim.x, a, tile, rows);
+}
+
+template <int TYPE>
+__global__ void __launch_bounds__(PK_GRID_THREADS) k_pack_rows_gather(PrArgs a) {
+    const PkBlk b{(int)threadIdx.x, (int)blockDim.x};
+    pr_gather_body<TYPE>(b, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, a);
+}
+
+template <int TYPE>
+__global__ void __launch_bounds__(PK_THREADS) k_pack_set_hours(PhArgs a) {
+    __shared__ uint32_t starts[PK_TILE];
+    __shared__ int64_t head;
+    const PkBlk b{(int)threadIdx.x, PK_THREADS};
+    ph_hours_body<TYPE>(b, (int64_t)blockIdx.x, (int64_t)gridDim.x, a, starts, &head);
 }
 
 // the function HIP_TRY and HIP_TRY_ALLOC name in their messages (redefined in front of every entry point below)
@@ -320,6 +345,7 @@ extern "C" int tsfa_pack_device_values(const tsfa_pack *pack, const void **value
 }
 
 extern "C" const int64_t *tsfa_pack_device_offsets(const tsfa_pack *pack) { return pack ? pack->offsets : nullptr; }
+extern "C" const void *tsfa_pack_device_ids(const tsfa_pack *pack) { return pack ? pack->uniq : nullptr; }
 
 static int pk_copy_out(const tsfa_pack *pack, void *dst, const void *src, size_t bytes, const char *who) {
     if (!pack || !dst) return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": null pointer").c_str());
@@ -581,6 +607,93 @@ extern "C" int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int3
         }
         out_packs[k] = pk;
     }
+    return TSFA_OK;
+}
+
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_pack_set_rows"
+extern "C" int tsfa_pack_set_rows(tsfa_pack_set *set, const void *values, int32_t value_type, int64_t n_cols, int64_t stride_row,
+                                  int64_t stride_col, tsfa_pack **out_packs) {
+    if (!set) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_rows: set is NULL");
+    if (set->has_kinds) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_rows: the set was made with a kind column (a value matrix is a wide frame)");
+    const char *why;
+    if (int rc = pr_check(values, value_type, set->n_rows, n_cols, stride_row, stride_col, out_packs, &why))
+        return tsfa_fail(rc, (std::string("tsfa_pack_set_rows: ") + why).c_str());
+    const int64_t n = set->n_rows;
+    const int out_type = pk_out_type(value_type), out_size = pk_itemsize(out_type);
+    for (int64_t c = 0; c < n_cols; ++c) out_packs[c] = nullptr;
+
+    HIP_TRY(hipSetDevice(set->device));
+    DevPtr<void> d_out_own;
+    DevPtr<unsigned int> d_flags;
+    HIP_TRY_ALLOC(d_flags, (size_t)n_cols * sizeof(unsigned int), "the columns' NaN flags");
+    HIP_TRY(hipMemset(d_flags.get(), 0, (size_t)n_cols * sizeof(unsigned int)));
+    HIP_TRY_ALLOC(d_out_own, (size_t)n_cols * (size_t)n * out_size, "the ragged sample buffers");
+    void *const d_out = d_out_own.get();
+    const std::shared_ptr<void> out = pk_share(d_out_own.release(), set->device);
+
+    PrArgs a;
+    a.values = values; a.perm = (const uint32_t *)set->perm.get(); a.n_rows = n; a.n_cols = n_cols;
+    a.sr = stride_row; a.sc = stride_col; a.out = d_out; a.nan_flags = d_flags.get();
+    const int route = pr_route(n_cols, stride_col);
+    pr_plan_work(&a, route);
+    if (route == PR_ROUTE_TILES) {
+        const unsigned grid = (unsigned)(a.n_work < PR_MAX_GRID ? a.n_work : PR_MAX_GRID);
+#define PR_LAUNCH(T) k_pack_rows_tiles<T><<<grid, PD_THREADS, 0, 0>>>(a)
+        PR_DISPATCH(value_type, PR_LAUNCH)
+#undef PR_LAUNCH
+    } else {
+        const int64_t blocks = (a.n_work + PK_GRID_THREADS - 1) / PK_GRID_THREADS;
+        const unsigned grid = (unsigned)(blocks < PR_MAX_GRID ? blocks : PR_MAX_GRID);
+#define PR_LAUNCH(T) k_pack_rows_gather<T><<<grid, PK_GRID_THREADS, 0, 0>>>(a)
+        PR_DISPATCH(value_type, PR_LAUNCH)
+#undef PR_LAUNCH
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<unsigned int> nan_flags((size_t)n_cols);
+    HIP_TRY(hipMemcpy(nan_flags.data(), d_flags.get(), (size_t)n_cols * sizeof(unsigned int), hipMemcpyDeviceToHost));  // (synchronises)
+    for (int64_t c = 0; c < n_cols; ++c) {
+        tsfa_pack *pk = new tsfa_pack();
+        pk->device = set->device;
+        pk->n_rows = n;
+        pk->n_groups = set->n_groups;
+        pk->flags = set->flags | (nan_flags[(size_t)c] ? TSFA_PACK_VALUE_NAN : 0);
+        pk->n_passes = set->n_passes;
+        pk->id_type = set->id_type; pk->sort_type = set->sort_type; pk->out_type = out_type;
+        pk->values = (char *)d_out + (size_t)c * (size_t)n * out_size;
+        pk->hold[0] = out;
+        pk->offsets = (int64_t *)set->offsets.get();
+        pk->hold[1] = set->offsets;
+        pk->uniq = set->uniq.get();
+        pk->hold[2] = set->uniq;
+        if (set->sort) {
+            pk->sort = set->sort.get();
+            pk->hold[3] = set->sort;
+        }
+        out_packs[c] = pk;
+    }
+    return TSFA_OK;
+}
+
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_pack_set_hours"
+extern "C" int tsfa_pack_set_hours(const tsfa_pack_set *set, const void *t, int32_t t_type, int64_t ticks_per_second, int64_t stride,
+                                   double *hours_out, int32_t *flags_out) {
+    if (!set) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_hours: set is NULL");
+    const char *why;
+    if (int rc = ph_check(t, t_type, ticks_per_second, set->n_rows, stride, hours_out, flags_out, &why))
+        return tsfa_fail(rc, (std::string("tsfa_pack_set_hours: ") + why).c_str());
+    PhArgs a;
+    a.t = t; a.stride = stride; a.tps = t_type == TSFA_I64 ? (double)ticks_per_second : 1.0;
+    a.perm = (const uint32_t *)set->perm.get(); a.offsets = (const int64_t *)set->offsets.get();
+    a.n_rows = set->n_rows; a.n_groups = set->n_groups; a.out = hours_out; a.flags = (unsigned int *)flags_out;
+    a.n_work = (set->n_rows + PK_TILE - 1) / PK_TILE;
+    const unsigned grid = (unsigned)(a.n_work < PH_MAX_GRID ? a.n_work : PH_MAX_GRID);
+    HIP_TRY(hipSetDevice(set->device));
+    if (t_type == TSFA_I64) k_pack_set_hours<TSFA_I64><<<grid, PK_THREADS, 0, 0>>>(a);
+    else k_pack_set_hours<TSFA_F64><<<grid, PK_THREADS, 0, 0>>>(a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(0));
     return TSFA_OK;
 }
 
