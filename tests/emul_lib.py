@@ -9,34 +9,22 @@ plan option "bluestein": 0), TSFA_EMUL_BLUESTEIN_MIN=<n> moves both crossovers t
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
+
+import emul_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "emul", "emul.cpp")
 LIB = os.path.join(HERE, "emul", "libtsfa_emul.so")
-CSRC = os.path.join(HERE, "..", "tsfresh_amd", "csrc")
 
 
 class _Spec(ctypes.Structure):
     _fields_ = [("calc", ctypes.c_int32), ("reserved", ctypes.c_int32), ("p", ctypes.c_double * 4)]
 
 
-def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
 def load():
-    if _stale():
-        tmp = "%s.%d.tmp" % (LIB, os.getpid())  # atomic: several processes (the gloo test's ranks) may build at once
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-DTSFA_EMUL",
-                               SRC, "-o", tmp])
-        os.replace(tmp, LIB)
+    emul_build.build(SRC, LIB)
     lib = ctypes.CDLL(LIB)
     lib.tsfa_emul_calc_id.argtypes = [ctypes.c_char_p]
     lib.tsfa_emul_calc_id.restype = ctypes.c_int

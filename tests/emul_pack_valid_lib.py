@@ -5,10 +5,10 @@ TEST INFRASTRUCTURE ONLY.  The product never imports this.
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+import emul_build
 import emul_pack_dense_lib as epd
 import emul_pack_times_lib as ept
 from tsfresh_amd import _native
@@ -16,7 +16,6 @@ from tsfresh_amd import _native
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "emul", "emul_pack_valid.cpp")
 LIB = os.path.join(HERE, "emul", "libtsfa_emul_pack_valid.so")
-CSRC = os.path.join(HERE, "..", "tsfresh_amd", "csrc")
 _lib = None
 
 GUARD = 64                 # sentinel cells on either side of every output
@@ -26,24 +25,11 @@ STAMP_SENTINEL = -5555555555
 OFFSET_SENTINEL = -12345
 
 
-def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC, os.path.join(HERE, "..", "include", "tsfresh_amd.h")]
-    deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
 def load():
     global _lib
     if _lib is not None:
         return _lib
-    if _stale():
-        tmp = "%s.%d.tmp" % (LIB, os.getpid())  # atomic: several processes may build at once
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-DTSFA_EMUL",
-                               SRC, "-o", tmp])
-        os.replace(tmp, LIB)
+    emul_build.build(SRC, LIB)
     lib = ctypes.CDLL(LIB)
     lib.tsfa_emul_pack_valid_const.argtypes, lib.tsfa_emul_pack_valid_const.restype = [ctypes.c_int], ctypes.c_int
     lib.tsfa_emul_pack_valid.argtypes = (

@@ -5,40 +5,26 @@ TEST INFRASTRUCTURE ONLY.  The product never imports this.
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
+
+import emul_build
+from tsfresh_amd._native import _REAL_COL_DTYPE as REAL_COL_DTYPE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "emul", "emul_rel_ks.cpp")
 LIB = os.path.join(HERE, "emul", "libtsfa_emul_rel_ks.so")
-CSRC = os.path.join(HERE, "..", "tsfresh_amd", "csrc")
 _lib = None
 
 HOST_KS, KS_EXACT = 5, 6
-REAL_COL_DTYPE = [("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("dis", "<i8"), ("xtie", "<i8"), ("ntie", "<i8"),
-                  ("x0", "<f8"), ("x1", "<f8"), ("n_hi", "<i8"), ("ks_d", "<f8")]
 ANY, LDS, SCRATCH = 0, 1, 2   # the ring of tsfa_emul_ks_lattice: the driver's choice, the LDS slice, the scratch slice
-
-
-def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC, os.path.join(HERE, "..", "include", "tsfresh_amd.h"), os.path.join(CSRC, "rel_tails.h"),
-            os.path.join(CSRC, "rel_ks.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
 
 
 def load():
     global _lib
     if _lib is not None:
         return _lib
-    if _stale():
-        tmp = "%s.%d.tmp" % (LIB, os.getpid())  # atomic: several processes may build at once
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-DTSFA_EMUL",
-                               SRC, "-o", tmp])
-        os.replace(tmp, LIB)
+    emul_build.build(SRC, LIB)
     lib = ctypes.CDLL(LIB)
     i64, f64, i32, ptr = ctypes.c_int64, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p
     lib.tsfa_emul_ks_ring_chunks.argtypes, lib.tsfa_emul_ks_ring_chunks.restype = [i64] * 4, i64

@@ -5,41 +5,27 @@ TEST INFRASTRUCTURE ONLY.  The product never imports this.
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
+
+import emul_build
+from tsfresh_amd._native import _CLASS_COL_DTYPE as COL_DTYPE, _REAL_COL_DTYPE as REAL_COL_DTYPE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "emul", "emul_rel_tails.cpp")
 LIB = os.path.join(HERE, "emul", "libtsfa_emul_rel_tails.so")
-CSRC = os.path.join(HERE, "..", "tsfresh_amd", "csrc")
 _lib = None
 
 NONE, MWU_NORMAL, FISHER, KENDALL, HOST_MWU_EXACT, HOST_KS = range(6)
-COL_DTYPE = [("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("tie_term", "<f8")]
-REAL_COL_DTYPE = [("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("dis", "<i8"), ("xtie", "<i8"), ("ntie", "<i8"),
-                  ("x0", "<f8"), ("x1", "<f8"), ("n_hi", "<i8"), ("ks_d", "<f8")]
 SENTINEL = -7
 GUARD = 16          # sentinel cells after the last index
-
-
-def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC, os.path.join(HERE, "..", "include", "tsfresh_amd.h"), os.path.join(CSRC, "rel_tails.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
 
 
 def load():
     global _lib
     if _lib is not None:
         return _lib
-    if _stale():
-        tmp = "%s.%d.tmp" % (LIB, os.getpid())  # atomic: several processes may build at once
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-DTSFA_EMUL",
-                               SRC, "-o", tmp])
-        os.replace(tmp, LIB)
+    emul_build.build(SRC, LIB)
     lib = ctypes.CDLL(LIB)
     i64, f64, i32, ptr = ctypes.c_int64, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p
     lib.tsfa_emul_mwu_normal.argtypes, lib.tsfa_emul_mwu_normal.restype = [f64, i64, i64, f64], f64

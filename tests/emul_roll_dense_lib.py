@@ -5,38 +5,25 @@ TEST INFRASTRUCTURE ONLY.  The product never imports this.
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
+
+import emul_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "emul", "emul_roll_dense.cpp")
 LIB = os.path.join(HERE, "emul", "libtsfa_emul_roll_dense.so")
-CSRC = os.path.join(HERE, "..", "tsfresh_amd", "csrc")
 _lib = None
 
 SENTINEL = -7
 GUARD = 16          # sentinel cells after the last window of every output array
 
 
-def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC, os.path.join(HERE, "..", "include", "tsfresh_amd.h")]
-    deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
 def load():
     global _lib
     if _lib is not None:
         return _lib
-    if _stale():
-        tmp = "%s.%d.tmp" % (LIB, os.getpid())  # atomic: several processes may build at once
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-DTSFA_EMUL",
-                               SRC, "-o", tmp])
-        os.replace(tmp, LIB)
+    emul_build.build(SRC, LIB)
     lib = ctypes.CDLL(LIB)
     lib.tsfa_emul_roll_count.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),

@@ -439,9 +439,6 @@ def _device_relevance_real(lib, xptr, n, m, ld, y):
     y_end = np.ones(n, dtype=np.uint8)
     y_end[:-1] = ys[1:] != ys[:-1]
     cols = np.zeros(m, dtype=_native._REAL_COL_DTYPE)
-    lib.tsfa_relevance_real.restype = ctypes.c_int32
-    lib.tsfa_relevance_real.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     _native._check(lib, lib.tsfa_relevance_real(xptr, n, m, ld, _native.TSFA_DEVICE, _ptr(y_rank), _ptr(y_perm), _ptr(y_end),
                                                 0, _ptr(cols)))
     return cols
@@ -449,12 +446,8 @@ def _device_relevance_real(lib, xptr, n, m, ld, y):
 
 def _device_relevance_classes_ks(lib, xptr, n, m, ld, codes, C):
     from tsfresh_amd import _native
-    rec = np.zeros(m, dtype=[("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("tie_term", "<f8")])
+    rec = np.zeros(m, dtype=_native._CLASS_COL_DTYPE)
     rs, hc, ks = np.zeros((m, C)), np.zeros((m, C), dtype=np.int64), np.zeros((m, C))
-    lib.tsfa_relevance_classes_ks.restype = ctypes.c_int32
-    lib.tsfa_relevance_classes_ks.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                              ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     _native._check(lib, lib.tsfa_relevance_classes_ks(xptr, n, m, ld, _native.TSFA_DEVICE, _ptr(codes), C, 0, _ptr(rec),
                                                       _ptr(rs), _ptr(hc), _ptr(ks)))
     return rec["n_unique"], rec["v_lo"], rec["v_hi"], rec["tie_term"], rs, hc, ks
@@ -463,9 +456,6 @@ def _device_relevance_classes_ks(lib, xptr, n, m, ld, codes, C):
 def _device_impute(lib, xptr, n, m, ld):
     from tsfresh_amd import _native
     mx, mn, med, cnt = np.zeros(m), np.zeros(m), np.zeros(m), np.zeros(m, dtype=np.int32)
-    lib.tsfa_impute.restype = ctypes.c_int32
-    lib.tsfa_impute.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     _native._check(lib, lib.tsfa_impute(xptr, n, m, ld, _native.TSFA_DEVICE, 0, _ptr(mx), _ptr(mn), _ptr(med), _ptr(cnt)))
     return mx, mn, med, cnt
 
@@ -479,7 +469,6 @@ def test_gpu_device_space_column_block_inside_a_wider_matrix(gpu):
     the NaN cells of the block are uploaded before the impute call."""
     from tsfresh_amd import _native
     lib = _native.load()
-    _native._bind_device_api(lib)
     rng = np.random.default_rng(13)
     n, ld, c0, m = 4097, 13, 3, 7
     y = np.round(rng.standard_normal(n), 1)

@@ -107,7 +107,6 @@ def test_host_and_small_auto_never_touch_the_device(monkeypatch, numpy_plan):
 
 def test_roll_windows_without_a_device_is_an_error_not_a_cpu_route():
     lib = _native.load()
-    _native._bind_roll_api(lib)
     handle = ctypes.c_void_p()
     rc = lib.tsfa_roll_windows(None, 1, 0, 0, 5, ctypes.byref(handle))
     assert not handle.value

@@ -51,8 +51,6 @@ def _one_chunk(params, n_windows):
     """The host form extracts n_windows windows of these settings as ONE chunk (on every native plan behind them)."""
     nplan = extraction._acquire_plan(compile_fc_parameters(params, has_datetime_index=False), 0)
     lib = _native.load()
-    lib.tsfa_extract_chunks.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32]
-    lib.tsfa_extract_chunks.restype = ctypes.c_int
     edges = (ctypes.c_int64 * 17)()
     plans = [pl for pl, _ in nplan.parts] if isinstance(nplan, extraction._CompositePlan) else [nplan]
     return all(lib.tsfa_extract_chunks(pl._h, n_windows, edges, 17) == 1 for pl in plans)

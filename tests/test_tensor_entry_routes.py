@@ -186,8 +186,7 @@ def test_callable_calculators_are_refused(emulated):
 
 
 def test_without_a_device_the_real_call_is_an_error_not_a_cpu_route():
-    lib = _native.load()
-    _native._bind_pack_dense_api(lib)
+    _native.load()
     buf = np.zeros(64, dtype=np.float64)
     p = buf.ctypes.data
     if _native.device_count() > 0:

@@ -34,76 +34,6 @@ TSFA_HOST, TSFA_DEVICE = 0, 1
 # enum tsfa_ks_tail: who evaluates the exact Kolmogorov-Smirnov tails (tsfa_relevance_tails_*_ks)
 TSFA_KS_TAIL_HOST, TSFA_KS_TAIL_DEVICE = 0, 1
 
-# every symbol include/tsfresh_amd.h declares
-EXPORTS = (
-    "tsfa_version", "tsfa_device_count", "tsfa_last_error", "tsfa_calc_id", "tsfa_calc_name", "tsfa_calc_count",
-    "tsfa_plan_create", "tsfa_plan_create_with_data", "tsfa_plan_n_cols", "tsfa_plan_destroy", "tsfa_extract", "tsfa_extract_timed",
-    "tsfa_extract_windows",
-    "tsfa_extract_chunks",
-    "tsfa_plan_set_profiling",
-    "tsfa_plan_set_option",
-    "tsfa_plan_last_timings",
-    "tsfa_plan_last_launches",
-    "tsfa_plan_set_length_hint",
-    "tsfa_host_alloc",
-    "tsfa_host_free",
-    "tsfa_pack_scan",
-    "tsfa_pack_offsets",
-    "tsfa_pack_device",
-    "tsfa_pack_device_n_rows",
-    "tsfa_pack_device_n_groups",
-    "tsfa_pack_device_flags",
-    "tsfa_pack_device_n_passes",
-    "tsfa_pack_device_values",
-    "tsfa_pack_device_offsets",
-    "tsfa_pack_device_ids",
-    "tsfa_pack_device_copy_ids",
-    "tsfa_pack_device_copy_offsets",
-    "tsfa_pack_device_copy_sort",
-    "tsfa_pack_device_destroy",
-    "tsfa_pack_set_create",
-    "tsfa_pack_set_n_kinds",
-    "tsfa_pack_set_copy_kinds",
-    "tsfa_pack_set_flags",
-    "tsfa_pack_set_n_passes",
-    "tsfa_pack_set_values",
-    "tsfa_pack_set_rows",
-    "tsfa_pack_set_hours",
-    "tsfa_pack_set_destroy",
-    "tsfa_pack_dense",
-    "tsfa_pack_times",
-    "tsfa_pack_dense_valid",
-    "tsfa_roll_windows",
-    "tsfa_windows_n_windows",
-    "tsfa_windows_starts",
-    "tsfa_windows_ends",
-    "tsfa_windows_copy_series",
-    "tsfa_windows_copy_timeshifts",
-    "tsfa_windows_copy_starts",
-    "tsfa_windows_copy_ends",
-    "tsfa_roll_shift_values",
-    "tsfa_windows_destroy",
-    "tsfa_roll_count",
-    "tsfa_roll_fill",
-    "tsfa_impute",
-    "tsfa_relevance_classes",
-    "tsfa_relevance_classes_ks",
-    "tsfa_relevance_real",
-    "tsfa_ks_outer_prob",
-    "tsfa_device_alloc",
-    "tsfa_device_free",
-    "tsfa_device_copy",
-    "tsfa_gather_columns",
-    "tsfa_scatter_columns",
-    "tsfa_relevance_tails_classes",
-    "tsfa_relevance_tails_real",
-    "tsfa_ks_tails",
-    "tsfa_relevance_tails_classes_ks",
-    "tsfa_relevance_tails_real_ks",
-    "tsfa_relevance_fdr",
-    "tsfa_compact_mask",
-    "tsfa_gather_columns_device",
-)
 
 
 class FeatureSpec(ctypes.Structure):
@@ -115,6 +45,12 @@ class RelevanceCol(ctypes.Structure):
                 ("tie_term", ctypes.c_double)]
 
 
+# the records of tsfa_relevance_col (above) and tsfa_relevance_real_col as numpy reads and writes them
+_CLASS_COL_DTYPE = [("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("tie_term", "<f8")]
+_REAL_COL_DTYPE = [("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("dis", "<i8"), ("xtie", "<i8"), ("ntie", "<i8"),
+                   ("x0", "<f8"), ("x1", "<f8"), ("n_hi", "<i8"), ("ks_d", "<f8")]
+
+
 class LaunchInfo(ctypes.Structure):
     """tsfa_launch_info: what one (kernel family, launch group) of the last extract launched (Plan.last_launches)."""
     _fields_ = [("family", ctypes.c_int32), ("length_class", ctypes.c_int32), ("max_len", ctypes.c_int32),
@@ -124,6 +60,98 @@ class LaunchInfo(ctypes.Structure):
 
 # enum tsfa_family (csrc/tsfa_specs.h), by number
 FAMILY_NAMES = ("BASIC", "SORT", "SPECTRAL", "AR", "ENTROPY", "CWT", "SEQ", "TREND", "MPROFILE")
+
+
+i32, i64, f64, ptr, size_t, char_p, P = (ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t,
+                                         ctypes.c_char_p, ctypes.POINTER)
+
+# name -> (return type, argument types) of every function include/tsfresh_amd.h declares, in the header's order: the ONE place a
+# prototype is written (load() binds them all; tests/test_native_abi.py holds the table to the header).  Handles and buffers
+# are `ptr` (they take a Python int, None or a ctypes object), out-parameters passed with byref are P(...).
+PROTOTYPES = {
+    "tsfa_version": (i32, []),
+    "tsfa_device_count": (i32, []),
+    "tsfa_last_error": (char_p, []),
+    "tsfa_calc_id": (i32, [char_p]),
+    "tsfa_calc_name": (char_p, [i32]),
+    "tsfa_calc_count": (i32, []),
+    "tsfa_plan_create": (i32, [P(FeatureSpec), i32, i32, P(ptr)]),
+    "tsfa_plan_create_with_data": (i32, [P(FeatureSpec), i32, ptr, i64, i32, P(ptr)]),
+    "tsfa_plan_n_cols": (i32, [ptr]),
+    "tsfa_plan_destroy": (None, [ptr]),
+    "tsfa_extract": (i32, [ptr, ptr, i32, ptr, i64, ptr, i64, i32, ptr]),
+    "tsfa_extract_timed": (i32, [ptr, ptr, i32, ptr, ptr, i64, ptr, i64, i32, ptr]),
+    "tsfa_extract_windows": (i32, [ptr, ptr, i32, ptr, ptr, ptr, i64, ptr, i64, i32, ptr]),
+    "tsfa_extract_chunks": (i32, [ptr, i64, ptr, i32]),
+    "tsfa_plan_set_profiling": (i32, [ptr, i32]),
+    "tsfa_plan_last_timings": (i32, [ptr, P(char_p), P(ctypes.c_float), i32]),
+    "tsfa_plan_last_launches": (i32, [ptr, P(LaunchInfo), i32]),
+    "tsfa_plan_set_option": (i32, [ptr, char_p, f64]),
+    "tsfa_plan_set_length_hint": (i32, [ptr, i64, i64]),
+    "tsfa_pack_scan": (i32, [ptr, i32, ptr, i32, ptr, i32, i64, P(i32), P(i64)]),
+    "tsfa_pack_offsets": (i32, [ptr, i64, i64]),
+    "tsfa_pack_device": (i32, [ptr, i32, ptr, i32, ptr, i32, i64, i32, i32, i32, P(ptr)]),
+    "tsfa_pack_device_n_rows": (i64, [ptr]),
+    "tsfa_pack_device_n_groups": (i64, [ptr]),
+    "tsfa_pack_device_flags": (i32, [ptr]),
+    "tsfa_pack_device_n_passes": (i32, [ptr]),
+    "tsfa_pack_device_values": (i32, [ptr, P(ptr), P(i32)]),
+    "tsfa_pack_device_offsets": (ptr, [ptr]),
+    "tsfa_pack_device_ids": (ptr, [ptr]),
+    "tsfa_pack_device_copy_ids": (i32, [ptr, ptr]),
+    "tsfa_pack_device_copy_offsets": (i32, [ptr, ptr]),
+    "tsfa_pack_device_copy_sort": (i32, [ptr, ptr]),
+    "tsfa_pack_device_destroy": (None, [ptr]),
+    "tsfa_pack_set_create": (i32, [ptr, i32, ptr, i32, ptr, i32, i64, i32, i32, i32, P(ptr)]),
+    "tsfa_pack_set_n_kinds": (i32, [ptr]),
+    "tsfa_pack_set_copy_kinds": (i32, [ptr, ptr]),
+    "tsfa_pack_set_flags": (i32, [ptr]),
+    "tsfa_pack_set_n_passes": (i32, [ptr]),
+    "tsfa_pack_set_values": (i32, [ptr, ptr, i32, i32, P(ptr)]),
+    "tsfa_pack_set_rows": (i32, [ptr, ptr, i32, i64, i64, i64, P(ptr)]),
+    "tsfa_pack_set_hours": (i32, [ptr, ptr, i32, i64, i64, ptr, ptr]),
+    "tsfa_pack_set_destroy": (None, [ptr]),
+    "tsfa_pack_dense": (i32, [ptr, i32, i64, i64, i64, i64, i64, i64, ptr, i32, ptr, i64, ptr, ptr, i32, ptr]),
+    "tsfa_pack_times": (i32, [ptr, i32, i64, i64, i64, i64, i64, ptr, ptr, ptr, i32, ptr]),
+    "tsfa_pack_dense_valid": (i32, [ptr, i32, i64, i64, i64, i64, i64, i64, ptr, i32, ptr, i32, i64, i64, ptr, i64, ptr, ptr, ptr,
+                                    ptr, i64, ptr, i32, ptr]),
+    "tsfa_roll_windows": (i32, [ptr, i32, i64, i64, i64, P(ptr)]),
+    "tsfa_windows_n_windows": (i64, [ptr]),
+    "tsfa_windows_starts": (ptr, [ptr]),
+    "tsfa_windows_ends": (ptr, [ptr]),
+    "tsfa_windows_copy_series": (i32, [ptr, ptr]),
+    "tsfa_windows_copy_timeshifts": (i32, [ptr, ptr]),
+    "tsfa_windows_copy_starts": (i32, [ptr, ptr]),
+    "tsfa_windows_copy_ends": (i32, [ptr, ptr]),
+    "tsfa_roll_shift_values": (i32, [ptr, ptr, ptr]),
+    "tsfa_windows_destroy": (None, [ptr]),
+    "tsfa_roll_count": (i32, [ptr, i64, i64, i32, i64, i64, i64, ptr, P(i64), i32, ptr]),
+    "tsfa_roll_fill": (i32, [ptr, i64, ptr, i64, i64, i32, i64, i64, i64, ptr, ptr, ptr, ptr, i32, ptr]),
+    "tsfa_host_alloc": (i32, [P(ptr), size_t]),
+    "tsfa_host_free": (i32, [ptr]),
+    "tsfa_device_alloc": (i32, [P(ptr), size_t, i32]),
+    "tsfa_device_free": (i32, [ptr, i32]),
+    "tsfa_device_copy": (i32, [ptr, ptr, size_t, i32, i32]),
+    "tsfa_gather_columns": (i32, [ptr, i64, i64, ptr, i64, ptr, i32]),
+    "tsfa_scatter_columns": (i32, [ptr, i64, ptr, ptr, i64, i64, i32]),
+    "tsfa_relevance_classes": (i32, [ptr, i64, i64, i64, i32, ptr, i32, i32, ptr, ptr, ptr]),
+    "tsfa_relevance_classes_ks": (i32, [ptr, i64, i64, i64, i32, ptr, i32, i32, ptr, ptr, ptr, ptr]),
+    "tsfa_relevance_real": (i32, [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i32, ptr]),
+    "tsfa_ks_outer_prob": (f64, [i64, i64, i64, i64]),
+    "tsfa_impute": (i32, [ptr, i64, i64, i64, i32, i32, ptr, ptr, ptr, ptr]),
+    "tsfa_relevance_tails_classes": (i32, [ptr, i64, i64, i64, i32, ptr, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, P(i64)]),
+    "tsfa_relevance_tails_real": (i32, [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i64, f64, f64, i32, ptr, ptr, ptr, ptr, P(i64)]),
+    "tsfa_ks_tails": (i32, [ptr, ptr, ptr, i64, i32, ptr, ptr]),
+    "tsfa_relevance_tails_classes_ks": (i32, [ptr, i64, i64, i64, i32, ptr, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr,
+                                              ptr, P(i64)]),
+    "tsfa_relevance_tails_real_ks": (i32, [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i64, f64, f64, i32, i32, ptr, ptr, ptr, ptr,
+                                           ptr, ptr, P(i64)]),
+    "tsfa_relevance_fdr": (i32, [ptr, ptr, i64, i32, f64, f64, i32, i32, i32, ptr, ptr, ptr, ptr]),
+    "tsfa_compact_mask": (i32, [ptr, i64, ptr, P(i64), i32]),
+    "tsfa_gather_columns_device": (i32, [ptr, i64, i64, ptr, i64, ptr, i64, i32]),
+}
+# every symbol include/tsfresh_amd.h declares
+EXPORTS = tuple(PROTOTYPES)
 
 
 class NativeError(RuntimeError):
@@ -145,67 +173,12 @@ def load():
             "{} is missing: build it with `make -C tsfresh_amd/csrc` (hipcc --offload-arch=gfx950). "
             "tsfresh_amd has no CPU fallback.".format(LIB_PATH))
     lib = ctypes.CDLL(LIB_PATH)
-    lib.tsfa_version.restype = ctypes.c_int
-    lib.tsfa_device_count.restype = ctypes.c_int
-    lib.tsfa_last_error.restype = ctypes.c_char_p
-    lib.tsfa_calc_id.argtypes = [ctypes.c_char_p]
-    lib.tsfa_calc_id.restype = ctypes.c_int
-    lib.tsfa_calc_name.argtypes = [ctypes.c_int]
-    lib.tsfa_calc_name.restype = ctypes.c_char_p
-    lib.tsfa_calc_count.restype = ctypes.c_int
-    lib.tsfa_plan_create.argtypes = [ctypes.POINTER(FeatureSpec), ctypes.c_int32, ctypes.c_int32,
-                                     ctypes.POINTER(ctypes.c_void_p)]
-    lib.tsfa_plan_create.restype = ctypes.c_int
-    lib.tsfa_plan_create_with_data.argtypes = [ctypes.POINTER(FeatureSpec), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
-                                               ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
-    lib.tsfa_plan_create_with_data.restype = ctypes.c_int
-    lib.tsfa_plan_n_cols.argtypes = [ctypes.c_void_p]
-    lib.tsfa_plan_n_cols.restype = ctypes.c_int32
-    lib.tsfa_plan_destroy.argtypes = [ctypes.c_void_p]
-    lib.tsfa_plan_destroy.restype = None
-    lib.tsfa_extract.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
-                                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]
-    lib.tsfa_extract.restype = ctypes.c_int
-    lib.tsfa_extract_timed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                       ctypes.c_void_p]
-    lib.tsfa_extract_timed.restype = ctypes.c_int
-    lib.tsfa_extract_windows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                         ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]
-    lib.tsfa_extract_windows.restype = ctypes.c_int
-    lib.tsfa_plan_set_profiling.argtypes = [ctypes.c_void_p, ctypes.c_int32]
-    lib.tsfa_plan_set_profiling.restype = ctypes.c_int
-    lib.tsfa_plan_last_timings.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p),
-                                           ctypes.POINTER(ctypes.c_float), ctypes.c_int32]
-    lib.tsfa_plan_last_timings.restype = ctypes.c_int32
-    lib.tsfa_pack_scan.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                   ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
-                                   ctypes.POINTER(ctypes.c_int64)]
-    lib.tsfa_pack_scan.restype = ctypes.c_int
-    lib.tsfa_pack_offsets.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
-    lib.tsfa_pack_offsets.restype = ctypes.c_int
-    lib.tsfa_pack_device.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                     ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                     ctypes.POINTER(ctypes.c_void_p)]
-    lib.tsfa_pack_device.restype = ctypes.c_int
-    for name, res in (("n_rows", ctypes.c_int64), ("n_groups", ctypes.c_int64), ("flags", ctypes.c_int32),
-                      ("n_passes", ctypes.c_int32), ("offsets", ctypes.c_void_p)):
-        fn = getattr(lib, "tsfa_pack_device_" + name)
-        fn.argtypes, fn.restype = [ctypes.c_void_p], res
-    lib.tsfa_pack_device_values.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32)]
-    lib.tsfa_pack_device_values.restype = ctypes.c_int
-    for name in ("copy_ids", "copy_offsets", "copy_sort"):
-        fn = getattr(lib, "tsfa_pack_device_" + name)
-        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
-    lib.tsfa_pack_device_destroy.argtypes = [ctypes.c_void_p]
-    lib.tsfa_pack_device_destroy.restype = None
-    lib.tsfa_host_alloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-    lib.tsfa_host_alloc.restype = ctypes.c_int
-    lib.tsfa_host_free.argtypes = [ctypes.c_void_p]
-    lib.tsfa_host_free.restype = ctypes.c_int
-    lib.tsfa_plan_set_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_double]
-    lib.tsfa_plan_set_option.restype = ctypes.c_int
+    # A symbol the library lacks is skipped: an older build given through TSFA_LIB may predate it, and using it then raises
+    # AttributeError with the symbol's name.  (The in-tree library is held to every symbol by tests/test_native_abi.py.)
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -213,6 +186,31 @@ def load():
 def _check(lib, rc):
     if rc != TSFA_OK:
         raise NativeError(rc, lib.tsfa_last_error().decode("utf-8", "replace"))
+
+
+class _Owner:
+    """Owns the library handle `_h` (made through `_lib`) until `close()`, which hands it to the function named `_destroy`."""
+
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        # at interpreter exit the HIP runtime may already be gone: leak rather than call into it
+        try:
+            if not sys.is_finalizing():
+                self.close()
+        except Exception:
+            pass
 
 
 def set_library_option(name, value):
@@ -268,7 +266,7 @@ class _PinnedBlock:
                     _PIN_POOL.setdefault(self.size, []).append(ptr)
                     _PIN_POOL_BYTES[0] += self.size
                     return
-            self._lib.tsfa_host_free(ctypes.c_void_p(ptr))
+            self._lib.tsfa_host_free(ptr)
         except Exception:  # interpreter shutdown
             pass
 
@@ -279,7 +277,7 @@ def release_pinned_pool():
     with _PIN_LOCK:
         for size, ptrs in _PIN_POOL.items():
             for ptr in ptrs:
-                lib.tsfa_host_free(ctypes.c_void_p(ptr))
+                lib.tsfa_host_free(ptr)
         _PIN_POOL.clear()
         _PIN_POOL_BYTES[0] = 0
 
@@ -313,7 +311,7 @@ def pack_scan(ids, sort_values, values):
             a = a.view(np.int64)  # datetime64 / timedelta64 sort keys compare like their integer ticks (no NaT: checked)
         if not isinstance(a, np.ndarray) or a.ndim != 1 or not a.flags.c_contiguous or a.dtype not in _PACK_TYPES:
             return None
-        cols.append((a.ctypes.data_as(ctypes.c_void_p), _PACK_TYPES[a.dtype]))
+        cols.append((a.ctypes.data, _PACK_TYPES[a.dtype]))   # (a view shares the caller's memory)
     lib = load()
     flags, groups = ctypes.c_int32(0), ctypes.c_int64(0)
     n = len(ids)
@@ -322,7 +320,7 @@ def pack_scan(ids, sort_values, values):
     if flags.value & TSFA_PACK_UNSORTED:
         return flags.value, None
     offsets = np.empty(groups.value + 1, dtype=np.int64)
-    _check(lib, lib.tsfa_pack_offsets(offsets.ctypes.data_as(ctypes.c_void_p), groups.value, n))
+    _check(lib, lib.tsfa_pack_offsets(offsets.ctypes.data, groups.value, n))
     return flags.value, offsets
 
 
@@ -349,25 +347,25 @@ def pack_column(a):
     return np.ascontiguousarray(a), code
 
 
-class DevicePack:
+class DevicePack(_Owner):
     """Owns a `tsfa_pack*`: one kind of a frame in ANY row order, grouped by id and ordered by the sort column on the device
     (tsfa_pack_device).  The ragged sample buffer and the offsets stay in HBM and go to `Plan.extract_pack` / the
     `pack=` form of `extract_into` as device pointers; only the unique ids (`.ids`) come back at once, `.offsets`, `.sort`
     and `.values_host()` when asked for.  ids / sort / values: what `pack_column` returned (sort may be None)."""
 
+    _destroy = "tsfa_pack_device_destroy"
+
     def __init__(self, ids, sort, values, device=0, keep_sort=False):
         lib = load()
-        _bind_device_api(lib)
         (ids_a, ids_t), (val_a, val_t) = ids, values
         sort_a, sort_t = sort if sort is not None else (None, 0)
         if len(val_a) != len(ids_a) or (sort_a is not None and len(sort_a) != len(ids_a)):
             raise ValueError("the id, sort and value columns must have one entry per row")
         handle = ctypes.c_void_p()
         _check(lib, lib.tsfa_pack_device(
-            ids_a.ctypes.data_as(ctypes.c_void_p), ids_t,
-            None if sort_a is None else sort_a.ctypes.data_as(ctypes.c_void_p), sort_t,
-            val_a.ctypes.data_as(ctypes.c_void_p), val_t, len(ids_a), TSFA_HOST,
-            TSFA_PACK_KEEP_SORT if (keep_sort and sort_a is not None) else 0, int(device), ctypes.byref(handle)))
+            ids_a.ctypes.data, ids_t, None if sort_a is None else sort_a.ctypes.data, sort_t, val_a.ctypes.data, val_t,
+            len(ids_a), TSFA_HOST, TSFA_PACK_KEEP_SORT if (keep_sort and sort_a is not None) else 0, int(device),
+            ctypes.byref(handle)))
         self._adopt(lib, handle, device, ids_a.dtype, None if sort_a is None or not keep_sort else sort_a.dtype)
 
     def _adopt(self, lib, handle, device, ids_dtype, sort_dtype, copy_ids=True):
@@ -389,12 +387,11 @@ class DevicePack:
         self.ids = None
         if copy_ids:
             self.ids = np.empty(self.n_series, dtype=ids_dtype)
-            _check(lib, lib.tsfa_pack_device_copy_ids(handle, self.ids.ctypes.data_as(ctypes.c_void_p)))
+            _check(lib, lib.tsfa_pack_device_copy_ids(handle, self.ids.ctypes.data))
 
     @property
     def ids_ptr(self):
         """Device pointer (int) of the n_series unique ids, ascending, in the id column's own dtype (tsfa_pack_device_ids)."""
-        _bind_pack_set_api(self._lib)
         return self._lib.tsfa_pack_device_ids(self._h)
 
     @property
@@ -409,7 +406,7 @@ class DevicePack:
     def offsets(self):
         if self._offsets is None:
             out = np.empty(self.n_series + 1, dtype=np.int64)
-            _check(self._lib, self._lib.tsfa_pack_device_copy_offsets(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+            _check(self._lib, self._lib.tsfa_pack_device_copy_offsets(self._h, out.ctypes.data))
             self._offsets = out
         return self._offsets
 
@@ -418,60 +415,18 @@ class DevicePack:
         """The sort column in packed order (None unless the pack was made with keep_sort=True)."""
         if self._sort is None and self._sort_dtype is not None:
             out = np.empty(self.n_rows, dtype=self._sort_dtype)
-            _check(self._lib, self._lib.tsfa_pack_device_copy_sort(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+            _check(self._lib, self._lib.tsfa_pack_device_copy_sort(self._h, out.ctypes.data))
             self._sort = out
         return self._sort
 
     def values_host(self):
         """A host copy of the ragged sample buffer (tsfa_device_copy)."""
         out = np.empty(self.n_rows, dtype=self.values_dtype)
-        _check(self._lib, self._lib.tsfa_device_copy(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(self.values_ptr),
-                                                     out.nbytes, 0, self.device))
+        _check(self._lib, self._lib.tsfa_device_copy(out.ctypes.data, self.values_ptr, out.nbytes, 0, self.device))
         return out
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tsfa_pack_device_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            if not sys.is_finalizing():
-                self.close()
-        except Exception:
-            pass
-
-
-def _bind_pack_set_api(lib):
-    """The tsfa_pack_set_* prototypes, bound on first use (a diagnostics library given through TSFA_LIB may predate them)."""
-    if getattr(lib, "_tsfa_pack_set_bound", False):
-        return
-    lib.tsfa_pack_set_create.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                         ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                         ctypes.POINTER(ctypes.c_void_p)]
-    lib.tsfa_pack_set_create.restype = ctypes.c_int
-    for name in ("n_kinds", "flags", "n_passes"):
-        fn = getattr(lib, "tsfa_pack_set_" + name)
-        fn.argtypes, fn.restype = [ctypes.c_void_p], ctypes.c_int32
-    lib.tsfa_pack_set_copy_kinds.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.tsfa_pack_set_copy_kinds.restype = ctypes.c_int
-    lib.tsfa_pack_set_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                         ctypes.POINTER(ctypes.c_void_p)]
-    lib.tsfa_pack_set_values.restype = ctypes.c_int
-    lib.tsfa_pack_set_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
-                                       ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]
-    lib.tsfa_pack_set_rows.restype = ctypes.c_int
-    lib.tsfa_pack_set_hours.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
-                                        ctypes.c_void_p, ctypes.c_void_p]
-    lib.tsfa_pack_set_hours.restype = ctypes.c_int
-    lib.tsfa_pack_device_ids.argtypes = [ctypes.c_void_p]
-    lib.tsfa_pack_device_ids.restype = ctypes.c_void_p
-    lib.tsfa_pack_set_destroy.argtypes = [ctypes.c_void_p]
-    lib.tsfa_pack_set_destroy.restype = None
-    lib._tsfa_pack_set_bound = True
-
-
-class DevicePackSet:
+class DevicePackSet(_Owner):
     """Owns a `tsfa_pack_set*`: a frame of several kinds in ANY row order, sorted ONCE by (kind, id, sort) on the device
     (tsfa_pack_set_create).  `values(column)` gathers one value column through the stored permutation and returns one
     DevicePack per kind, in ascending order of the kind values (`.kinds`): views into one gathered buffer that share the
@@ -482,59 +437,37 @@ class DevicePackSet:
     tsfa_dtype code, numpy dtype) of a contiguous column; they are used in place, nothing is staged, the views keep their
     ids in HBM (`DevicePack.ids_ptr`, `.ids` is None) and `values` / `rows` / `hours` take device pointers."""
 
+    _destroy = "tsfa_pack_set_destroy"
+
     def __init__(self, ids, sort, kinds, device=0, keep_sort=False, space=TSFA_HOST, n_rows=None):
         lib = load()
-        _bind_device_api(lib)
-        _bind_pack_set_api(lib)
+        # either form of the three key columns -> (pointer or None, tsfa_dtype code, numpy dtype) each
         if space == TSFA_DEVICE:
-            self._init_device(lib, ids, sort, kinds, device, keep_sort, n_rows)
-            return
-        self.space = TSFA_HOST
-        ids_a, ids_t = ids
-        sort_a, sort_t = sort if sort is not None else (None, 0)
-        kind_a, kind_t = kinds if kinds is not None else (None, 0)
-        if any(c is not None and len(c) != len(ids_a) for c in (sort_a, kind_a)):
-            raise ValueError("the id, sort and kind columns must have one entry per row")
+            cols = [c if c is not None and c[0] else (None, 0, None) for c in (ids, sort, kinds)]
+            if n_rows is None:
+                raise ValueError("space=TSFA_DEVICE needs n_rows")
+        else:
+            cols = [(None, 0, None) if c is None else (c[0].ctypes.data, c[1], c[0].dtype) for c in (ids, sort, kinds)]
+            space, n_rows = TSFA_HOST, len(ids[0])
+            if any(c is not None and len(c[0]) != n_rows for c in (sort, kinds)):
+                raise ValueError("the id, sort and kind columns must have one entry per row")
+        (ids_p, ids_t, ids_dtype), (sort_p, sort_t, sort_dtype), (kind_p, kind_t, kind_dtype) = cols
+        keep_sort = bool(keep_sort) and sort_p is not None
         handle = ctypes.c_void_p()
-        _check(lib, lib.tsfa_pack_set_create(
-            ids_a.ctypes.data_as(ctypes.c_void_p), ids_t,
-            None if sort_a is None else sort_a.ctypes.data_as(ctypes.c_void_p), sort_t,
-            None if kind_a is None else kind_a.ctypes.data_as(ctypes.c_void_p), kind_t, len(ids_a), TSFA_HOST,
-            TSFA_PACK_KEEP_SORT if (keep_sort and sort_a is not None) else 0, int(device), ctypes.byref(handle)))
-        self._lib, self._h, self.device = lib, handle, int(device)
-        self.n_rows = len(ids_a)
-        self.n_kinds = int(lib.tsfa_pack_set_n_kinds(handle))
-        self.flags = int(lib.tsfa_pack_set_flags(handle))
-        self.n_passes = int(lib.tsfa_pack_set_n_passes(handle))
-        self._ids_dtype = ids_a.dtype
-        self._sort_dtype = None if sort_a is None or not keep_sort else sort_a.dtype
-        self.kinds = None
-        if kind_a is not None:
-            self.kinds = np.empty(self.n_kinds, dtype=kind_a.dtype)
-            _check(lib, lib.tsfa_pack_set_copy_kinds(handle, self.kinds.ctypes.data_as(ctypes.c_void_p)))
-
-    def _init_device(self, lib, ids, sort, kinds, device, keep_sort, n_rows):
-        (ids_p, ids_t, ids_dtype) = ids
-        sort_p, sort_t, sort_dtype = sort if sort is not None else (None, 0, None)
-        kind_p, kind_t, kind_dtype = kinds if kinds is not None else (None, 0, None)
-        if n_rows is None:
-            raise ValueError("space=TSFA_DEVICE needs n_rows")
-        handle = ctypes.c_void_p()
-        _check(lib, lib.tsfa_pack_set_create(
-            ctypes.c_void_p(ids_p), int(ids_t), _ptr(sort_p), int(sort_t), _ptr(kind_p), int(kind_t), int(n_rows), TSFA_DEVICE,
-            TSFA_PACK_KEEP_SORT if (keep_sort and sort_p) else 0, int(device), ctypes.byref(handle)))
-        self.space = TSFA_DEVICE
+        _check(lib, lib.tsfa_pack_set_create(ids_p, int(ids_t), sort_p, int(sort_t), kind_p, int(kind_t), int(n_rows), int(space),
+                                             TSFA_PACK_KEEP_SORT if keep_sort else 0, int(device), ctypes.byref(handle)))
+        self.space = int(space)
         self._lib, self._h, self.device = lib, handle, int(device)
         self.n_rows = int(n_rows)
         self.n_kinds = int(lib.tsfa_pack_set_n_kinds(handle))
         self.flags = int(lib.tsfa_pack_set_flags(handle))
         self.n_passes = int(lib.tsfa_pack_set_n_passes(handle))
         self._ids_dtype = np.dtype(ids_dtype)
-        self._sort_dtype = None if not sort_p or not keep_sort else np.dtype(sort_dtype)
+        self._sort_dtype = np.dtype(sort_dtype) if keep_sort else None
         self.kinds = None
-        if kind_p:
+        if kind_p is not None:
             self.kinds = np.empty(self.n_kinds, dtype=kind_dtype)   # (the library's host copy: nothing crosses the bus here)
-            _check(lib, lib.tsfa_pack_set_copy_kinds(handle, self.kinds.ctypes.data_as(ctypes.c_void_p)))
+            _check(lib, lib.tsfa_pack_set_copy_kinds(handle, self.kinds.ctypes.data))
 
     @property
     def was_in_order(self):
@@ -545,8 +478,7 @@ class DevicePackSet:
         for h in handles:
             pack = DevicePack.__new__(DevicePack)   # a view: no tsfa_pack_device call
             packs.append(pack)
-            pack._adopt(self._lib, ctypes.c_void_p(h), self.device, self._ids_dtype, self._sort_dtype,
-                        copy_ids=self.space == TSFA_HOST)
+            pack._adopt(self._lib, h, self.device, self._ids_dtype, self._sort_dtype, copy_ids=self.space == TSFA_HOST)
         return packs
 
     def values(self, column):
@@ -557,13 +489,12 @@ class DevicePackSet:
         handles = (ctypes.c_void_p * self.n_kinds)()
         if self.space == TSFA_DEVICE:
             val_p, val_t = column
-            _check(self._lib, self._lib.tsfa_pack_set_values(self._h, ctypes.c_void_p(val_p), int(val_t), TSFA_DEVICE, handles))
+            _check(self._lib, self._lib.tsfa_pack_set_values(self._h, val_p, int(val_t), TSFA_DEVICE, handles))
             return self._views(handles)
         val_a, val_t = column
         if len(val_a) != self.n_rows:
             raise ValueError("the value column must have one entry per row")
-        _check(self._lib, self._lib.tsfa_pack_set_values(self._h, val_a.ctypes.data_as(ctypes.c_void_p), val_t, TSFA_HOST,
-                                                         handles))
+        _check(self._lib, self._lib.tsfa_pack_set_values(self._h, val_a.ctypes.data, val_t, TSFA_HOST, handles))
         return self._views(handles)
 
     def rows(self, values_ptr, value_type, n_cols, stride_row, stride_col):
@@ -573,8 +504,8 @@ class DevicePackSet:
         if not self._h:
             raise ValueError("the pack set is closed")
         handles = (ctypes.c_void_p * int(n_cols))()
-        _check(self._lib, self._lib.tsfa_pack_set_rows(self._h, ctypes.c_void_p(values_ptr), int(value_type), int(n_cols),
-                                                       int(stride_row), int(stride_col), handles))
+        _check(self._lib, self._lib.tsfa_pack_set_rows(self._h, values_ptr, int(value_type), int(n_cols), int(stride_row),
+                                                       int(stride_col), handles))
         return self._views(handles)
 
     def hours(self, t_ptr, t_type, ticks_per_second, stride, hours_ptr, flags_ptr):
@@ -583,37 +514,8 @@ class DevicePackSet:
         hours_ptr, in the set's sorted order over all kinds; flags_ptr: one int32 the call ORs TSFA_DENSE_BAD_TIME into."""
         if not self._h:
             raise ValueError("the pack set is closed")
-        _check(self._lib, self._lib.tsfa_pack_set_hours(self._h, ctypes.c_void_p(t_ptr), int(t_type), int(ticks_per_second),
-                                                        int(stride), ctypes.c_void_p(hours_ptr), ctypes.c_void_p(flags_ptr)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tsfa_pack_set_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            if not sys.is_finalizing():
-                self.close()
-        except Exception:
-            pass
-
-
-def _bind_pack_dense_api(lib):
-    """The tsfa_pack_dense prototype, bound on first use (a diagnostics library given through TSFA_LIB may predate it)."""
-    if getattr(lib, "_tsfa_pack_dense_bound", False):
-        return
-    lib.tsfa_pack_dense.argtypes = [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_int64] * 6 + [
-        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-        ctypes.c_void_p]
-    lib.tsfa_pack_dense.restype = ctypes.c_int
-    lib._tsfa_pack_dense_bound = True
+        _check(self._lib, self._lib.tsfa_pack_set_hours(self._h, t_ptr, int(t_type), int(ticks_per_second), int(stride),
+                                                        hours_ptr, flags_ptr))
 
 
 def pack_dense(x_ptr, x_type, shape, strides, values_ptr, channel_stride_out, offsets_ptr, flags_ptr, device=0,
@@ -624,23 +526,10 @@ def pack_dense(x_ptr, x_type, shape, strides, values_ptr, channel_stride_out, of
     flag word the call ORs into.  lengths_ptr: n_batch int32 / int64 (lengths_type TSFA_I32 / TSFA_I64) or None.
     stream: a hipStream_t as an int (the call only enqueues) or None (the call returns when the work is done)."""
     lib = load()
-    _bind_pack_dense_api(lib)
     (n_batch, n_channels, n_time), (sb, sc, st) = shape, strides
     _check(lib, lib.tsfa_pack_dense(
-        ctypes.c_void_p(x_ptr), int(x_type), int(n_batch), int(n_channels), int(n_time), int(sb), int(sc), int(st),
-        ctypes.c_void_p(lengths_ptr) if lengths_ptr else None, int(lengths_type), ctypes.c_void_p(values_ptr),
-        int(channel_stride_out), ctypes.c_void_p(offsets_ptr), ctypes.c_void_p(flags_ptr), int(device),
-        ctypes.c_void_p(stream) if stream else None))
-
-
-def _bind_pack_times_api(lib):
-    """The tsfa_pack_times prototype, bound on first use (a diagnostics library given through TSFA_LIB may predate it)."""
-    if getattr(lib, "_tsfa_pack_times_bound", False):
-        return
-    lib.tsfa_pack_times.argtypes = [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_int64] * 5 + [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
-    lib.tsfa_pack_times.restype = ctypes.c_int
-    lib._tsfa_pack_times_bound = True
+        x_ptr, int(x_type), int(n_batch), int(n_channels), int(n_time), int(sb), int(sc), int(st), lengths_ptr or None,
+        int(lengths_type), values_ptr, int(channel_stride_out), offsets_ptr, flags_ptr, int(device), stream or None))
 
 
 def pack_times(t_ptr, t_type, ticks_per_second, shape, strides, offsets_ptr, hours_ptr, flags_ptr, device=0, stream=None):
@@ -650,25 +539,9 @@ def pack_times(t_ptr, t_type, ticks_per_second, shape, strides, offsets_ptr, hou
     offsets_ptr.  flags_ptr: one int32 the call ORs TSFA_DENSE_BAD_TIME into (a NaT / NaN stamp inside a length).
     stream: a hipStream_t as an int (the call only enqueues) or None (the call returns when the work is done)."""
     lib = load()
-    _bind_pack_times_api(lib)
     (n_batch, n_time), (sb, st) = shape, strides
-    _check(lib, lib.tsfa_pack_times(
-        ctypes.c_void_p(t_ptr), int(t_type), int(ticks_per_second), int(n_batch), int(n_time), int(sb), int(st),
-        ctypes.c_void_p(offsets_ptr), ctypes.c_void_p(hours_ptr), ctypes.c_void_p(flags_ptr), int(device),
-        ctypes.c_void_p(stream) if stream else None))
-
-
-def _bind_pack_dense_valid_api(lib):
-    """The tsfa_pack_dense_valid prototype, bound on first use (a diagnostics library given through TSFA_LIB may predate it)."""
-    if getattr(lib, "_tsfa_pack_dense_valid_bound", False):
-        return
-    lib.tsfa_pack_dense_valid.argtypes = (
-        [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_int64] * 6 + [ctypes.c_void_p, ctypes.c_int32]
-        + [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]
-        + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-           ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p])
-    lib.tsfa_pack_dense_valid.restype = ctypes.c_int
-    lib._tsfa_pack_dense_valid_bound = True
+    _check(lib, lib.tsfa_pack_times(t_ptr, int(t_type), int(ticks_per_second), int(n_batch), int(n_time), int(sb), int(st),
+                                    offsets_ptr, hours_ptr, flags_ptr, int(device), stream or None))
 
 
 def pack_dense_valid_scratch_bytes(n_batch, n_time):
@@ -688,13 +561,11 @@ def pack_dense_valid(x_ptr, x_type, shape, strides, values_ptr, channel_stride_o
     TSFA_DENSE_BAD_LENGTH and TSFA_DENSE_EMPTY_SERIES into.  stream: a hipStream_t as an int (the call only enqueues) or
     None (the call returns when the work is done)."""
     lib = load()
-    _bind_pack_dense_valid_api(lib)
     (n_batch, n_channels, n_time), (sb, sc, st), (tsb, tst) = shape, strides, t_strides
     _check(lib, lib.tsfa_pack_dense_valid(
-        ctypes.c_void_p(x_ptr), int(x_type), int(n_batch), int(n_channels), int(n_time), int(sb), int(sc), int(st),
-        _ptr(lengths_ptr), int(lengths_type), _ptr(t_ptr), int(t_type), int(tsb), int(tst), ctypes.c_void_p(values_ptr),
-        int(channel_stride_out), ctypes.c_void_p(offsets_ptr), ctypes.c_void_p(steps_ptr), _ptr(stamps_ptr),
-        ctypes.c_void_p(scratch_ptr), int(scratch_bytes), ctypes.c_void_p(flags_ptr), int(device), _ptr(stream)))
+        x_ptr, int(x_type), int(n_batch), int(n_channels), int(n_time), int(sb), int(sc), int(st), lengths_ptr or None,
+        int(lengths_type), t_ptr or None, int(t_type), int(tsb), int(tst), values_ptr, int(channel_stride_out), offsets_ptr,
+        steps_ptr, stamps_ptr or None, scratch_ptr, int(scratch_bytes), flags_ptr, int(device), stream or None))
 
 
 class DensePack:
@@ -725,40 +596,6 @@ class BorrowedMatrix:
         self.owner = owner
 
 
-def _bind_roll_api(lib):
-    """The tsfa_roll_* / tsfa_windows_* prototypes, bound on first use (a diagnostics library given through TSFA_LIB may
-    predate them)."""
-    if getattr(lib, "_tsfa_roll_bound", False):
-        return
-    lib.tsfa_roll_windows.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                      ctypes.POINTER(ctypes.c_void_p)]
-    lib.tsfa_roll_windows.restype = ctypes.c_int
-    lib.tsfa_windows_n_windows.argtypes, lib.tsfa_windows_n_windows.restype = [ctypes.c_void_p], ctypes.c_int64
-    for name in ("starts", "ends"):
-        fn = getattr(lib, "tsfa_windows_" + name)
-        fn.argtypes, fn.restype = [ctypes.c_void_p], ctypes.c_void_p
-    for name in ("copy_series", "copy_timeshifts", "copy_starts", "copy_ends"):
-        fn = getattr(lib, "tsfa_windows_" + name)
-        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
-    lib.tsfa_roll_shift_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.tsfa_roll_shift_values.restype = ctypes.c_int
-    lib.tsfa_windows_destroy.argtypes = [ctypes.c_void_p]
-    lib.tsfa_windows_destroy.restype = None
-    lib.tsfa_roll_count.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
-                                    ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32,
-                                    ctypes.c_void_p]
-    lib.tsfa_roll_count.restype = ctypes.c_int
-    lib.tsfa_roll_fill.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [ctypes.c_int32,
-                                                                                                         ctypes.c_void_p]
-    lib.tsfa_roll_fill.restype = ctypes.c_int
-    lib._tsfa_roll_bound = True
-
-
-def _ptr(p):
-    return ctypes.c_void_p(p) if p else None
-
-
 def roll_count(offsets_ptr, n_series, rolling_direction=1, max_timeshift=None, min_timeshift=0, steps=1, scanned_ptr=None,
                series_len=0, device=0, stream=None):
     """tsfa_roll_count on raw device pointers (ints) -> the number of windows of the batch whose n_series + 1 int64 offsets
@@ -766,11 +603,10 @@ def roll_count(offsets_ptr, n_series, rolling_direction=1, max_timeshift=None, m
     per-series counts, which `roll_fill` reads; the call waits for its stream), or None for a uniform batch of series_len
     samples per series (the closed form: nothing is launched or read back, offsets_ptr may be None)."""
     lib = load()
-    _bind_roll_api(lib)
     total = ctypes.c_int64(0)
-    _check(lib, lib.tsfa_roll_count(_ptr(offsets_ptr), int(n_series), int(series_len), int(rolling_direction),
-                                    int(max_timeshift or 0), int(min_timeshift), int(steps), _ptr(scanned_ptr),
-                                    ctypes.byref(total), int(device), _ptr(stream)))
+    _check(lib, lib.tsfa_roll_count(offsets_ptr or None, int(n_series), int(series_len), int(rolling_direction),
+                                    int(max_timeshift or 0), int(min_timeshift), int(steps), scanned_ptr or None,
+                                    ctypes.byref(total), int(device), stream or None))
     return int(total.value)
 
 
@@ -781,14 +617,13 @@ def roll_fill(offsets_ptr, n_series, n_windows, starts_ptr, ends_ptr, series_ptr
     (series, ascending timeshift) order.  stream: a hipStream_t as an int (the call only enqueues) or None (the call
     returns when the work is done)."""
     lib = load()
-    _bind_roll_api(lib)
-    _check(lib, lib.tsfa_roll_fill(_ptr(offsets_ptr), int(n_series), _ptr(scanned_ptr), int(series_len), int(n_windows),
+    _check(lib, lib.tsfa_roll_fill(offsets_ptr or None, int(n_series), scanned_ptr or None, int(series_len), int(n_windows),
                                    int(rolling_direction), int(max_timeshift or 0), int(min_timeshift), int(steps),
-                                   _ptr(starts_ptr), _ptr(ends_ptr), _ptr(series_ptr), _ptr(timeshifts_ptr), int(device),
-                                   _ptr(stream)))
+                                   starts_ptr or None, ends_ptr or None, series_ptr or None, timeshifts_ptr or None, int(device),
+                                   stream or None))
 
 
-class DeviceWindows:
+class DeviceWindows(_Owner):
     """Owns a `tsfa_windows*`: the rolled windows of one DevicePack, built on the device from the pack's offsets
     (tsfa_roll_windows).  The starts and ends stay in HBM and go to `Plan.extract_windows_pack` as device pointers; the host
     gets the series index and the timeshift of every window (`.series`, `.timeshifts`: what the window ids are built from),
@@ -796,10 +631,10 @@ class DeviceWindows:
     steps: the reference's prediction_steps -- the longest series of the whole frame, which another kind may own.
     The pack must stay open for as long as the windows are used."""
 
+    _destroy = "tsfa_windows_destroy"
+
     def __init__(self, pack, rolling_direction=1, max_timeshift=None, min_timeshift=0, steps=None):
         lib = load()
-        _bind_device_api(lib)
-        _bind_roll_api(lib)
         if steps is None:
             steps = int(np.diff(pack.offsets).max()) if pack.n_series else 1
         handle = ctypes.c_void_p()
@@ -816,7 +651,7 @@ class DeviceWindows:
         if what not in self._host:
             out = np.empty(self.n_windows, dtype=np.int64)
             fn = getattr(self._lib, "tsfa_windows_copy_" + what)
-            _check(self._lib, fn(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+            _check(self._lib, fn(self._h, out.ctypes.data))
             self._host[what] = out
         return self._host[what]
 
@@ -842,26 +677,8 @@ class DeviceWindows:
         if self._pack._sort_dtype is None:
             raise ValueError("the pack was made without keep_sort=True: it holds no sort column")
         out = np.empty(self.n_windows, dtype=self._pack._sort_dtype)
-        _check(self._lib, self._lib.tsfa_roll_shift_values(self._h, self._pack._h, out.ctypes.data_as(ctypes.c_void_p)))
+        _check(self._lib, self._lib.tsfa_roll_shift_values(self._h, self._pack._h, out.ctypes.data))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tsfa_windows_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            if not sys.is_finalizing():
-                self.close()
-        except Exception:
-            pass
 
 
 def _result_matrix(n_rows, n_cols):
@@ -871,8 +688,19 @@ def _result_matrix(n_rows, n_cols):
     return np.empty((n_rows, n_cols), dtype=np.float64)
 
 
-class Plan:
+def _samples(values):
+    """The samples as tsfa_extract* read them: -> (C-contiguous ndarray, float32 as it is and anything else as float64; its
+    TSFA_F32 / TSFA_F64 code)."""
+    values = np.ascontiguousarray(values)
+    if values.dtype == np.float32:
+        return values, TSFA_F32
+    return np.ascontiguousarray(values, dtype=np.float64), TSFA_F64
+
+
+class Plan(_Owner):
     """Owns a `tsfa_plan*`: the compiled list of output columns of one kind on one device."""
+
+    _destroy = "tsfa_plan_destroy"
 
     def __init__(self, specs, device=0):
         """specs: iterable of (calc_id, (p0, p1, p2, p3)).  A parameter tuple longer than four carries an ARRAY-valued
@@ -902,19 +730,6 @@ class Plan:
         self.n_cols = len(specs)
         self.device = int(device)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tsfa_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        # at interpreter exit the HIP runtime may already be gone: leak rather than call into it
-        try:
-            if not sys.is_finalizing():
-                self.close()
-        except Exception:
-            pass
-
     def set_option(self, name, value=1.0):
         """A launch option of this plan (include/tsfresh_amd.h: tsfa_plan_set_option): an alternative route to the same
         numbers, or a diagnostic pre-fill.  Environment variables do not reach the kernels."""
@@ -925,8 +740,6 @@ class Plan:
 
     def set_length_hint(self, min_len, max_len):
         """Promise the length range of every following batch (skips the per-call length scan and its host sync)."""
-        self._lib.tsfa_plan_set_length_hint.restype = ctypes.c_int32
-        self._lib.tsfa_plan_set_length_hint.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
         _check(self._lib, self._lib.tsfa_plan_set_length_hint(self._h, int(min_len), int(max_len)))
 
     def last_timings(self):
@@ -941,7 +754,6 @@ class Plan:
         FAMILY_NAMES), length_class, max_len, n_series, threads, lds_bytes, long_build, variant (include/tsfresh_amd.h:
         tsfa_plan_last_launches).  Read-only."""
         fn = self._lib.tsfa_plan_last_launches
-        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.POINTER(LaunchInfo), ctypes.c_int32], ctypes.c_int32
         n = fn(self._h, None, 0)
         arr = (LaunchInfo * max(n, 1))()
         n = min(n, fn(self._h, arr, n))
@@ -953,12 +765,7 @@ class Plan:
         times: float64 ndarray laid out like `values` (hours since each series' first timestamp) for plans that
         hold linear_trend_timewise columns.  out: optional C-contiguous-row float64 [n_series, >= n_cols] target (a row
         slice of a larger matrix); default: a new page-locked matrix."""
-        values = np.ascontiguousarray(values)
-        if values.dtype == np.float32:
-            dt = TSFA_F32
-        else:
-            values = np.ascontiguousarray(values, dtype=np.float64)
-            dt = TSFA_F64
+        values, dt = _samples(values)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n_series = offsets.shape[0] - 1
         if out is None:
@@ -976,21 +783,15 @@ class Plan:
             times = np.ascontiguousarray(times, dtype=np.float64)
             if times.shape != values.shape:
                 raise ValueError("times must have one entry per sample")
-            tptr = times.ctypes.data_as(ctypes.c_void_p)
-        _check(self._lib, self._lib.tsfa_extract_timed(
-            self._h, values.ctypes.data_as(ctypes.c_void_p), dt, tptr, offsets.ctypes.data_as(ctypes.c_void_p),
-            n_series, out.ctypes.data_as(ctypes.c_void_p), ld, TSFA_HOST, None))
+            tptr = times.ctypes.data
+        _check(self._lib, self._lib.tsfa_extract_timed(self._h, values.ctypes.data, dt, tptr, offsets.ctypes.data, n_series,
+                                                       out.ctypes.data, ld, TSFA_HOST, None))
         return out
 
     def extract_windows_host(self, values, starts, ends, times=None):
         """Window views of one shared buffer: series s = values[starts[s]:ends[s]] (views may overlap) ->
         float64 [n_windows, n_cols].  The rolled (forecasting) layout without materialising the windows."""
-        values = np.ascontiguousarray(values)
-        if values.dtype == np.float32:
-            dt = TSFA_F32
-        else:
-            values = np.ascontiguousarray(values, dtype=np.float64)
-            dt = TSFA_F64
+        values, dt = _samples(values)
         starts = np.ascontiguousarray(starts, dtype=np.int64)
         ends = np.ascontiguousarray(ends, dtype=np.int64)
         if starts.shape != ends.shape or starts.ndim != 1:
@@ -1004,10 +805,9 @@ class Plan:
         tptr = None
         if times is not None:
             times = np.ascontiguousarray(times, dtype=np.float64)
-            tptr = times.ctypes.data_as(ctypes.c_void_p)
-        _check(self._lib, self._lib.tsfa_extract_windows(
-            self._h, values.ctypes.data_as(ctypes.c_void_p), dt, tptr, starts.ctypes.data_as(ctypes.c_void_p),
-            ends.ctypes.data_as(ctypes.c_void_p), n, out.ctypes.data_as(ctypes.c_void_p), self.n_cols, TSFA_HOST, None))
+            tptr = times.ctypes.data
+        _check(self._lib, self._lib.tsfa_extract_windows(self._h, values.ctypes.data, dt, tptr, starts.ctypes.data, ends.ctypes.data,
+                                                         n, out.ctypes.data, self.n_cols, TSFA_HOST, None))
         return out
 
     def extract_pack(self, pack, out=None):
@@ -1043,8 +843,6 @@ class Plan:
         if chunk_rows is None:
             # the cuts of the TSFA_HOST pipeline, from the library: the same launches as extract_windows_host, bit-equal features
             edges = (ctypes.c_int64 * 17)()
-            self._lib.tsfa_extract_chunks.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32]
-            self._lib.tsfa_extract_chunks.restype = ctypes.c_int
             n_chunks = self._lib.tsfa_extract_chunks(self._h, n, edges, 17)
             if n_chunks < 0:
                 _check(self._lib, n_chunks)
@@ -1057,12 +855,10 @@ class Plan:
             for r0, r1 in cuts:
                 rows = r1 - r0
                 _check(self._lib, self._lib.tsfa_extract_windows(
-                    self._h, ctypes.c_void_p(pack.values_ptr), pack.values_type, None,
-                    ctypes.c_void_p(windows.starts_ptr + 8 * r0), ctypes.c_void_p(windows.ends_ptr + 8 * r0), rows,
-                    ctypes.c_void_p(dm.ptr), dm.ld, TSFA_DEVICE, None))
+                    self._h, pack.values_ptr, pack.values_type, None, windows.starts_ptr + 8 * r0, windows.ends_ptr + 8 * r0,
+                    rows, dm.ptr, dm.ld, TSFA_DEVICE, None))
                 part = out[r0:r0 + rows]
-                _check(self._lib, self._lib.tsfa_device_copy(part.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(dm.ptr),
-                                                             part.nbytes, 0, self.device))
+                _check(self._lib, self._lib.tsfa_device_copy(part.ctypes.data, dm.ptr, part.nbytes, 0, self.device))
         finally:
             dm.free()
         return out
@@ -1078,9 +874,8 @@ class Plan:
             raise ValueError("the device matrix does not hold [n_windows, col0 + n_cols] cells on the plan's device")
         if n_windows == 0 or self.n_cols == 0:
             return
-        _check(self._lib, self._lib.tsfa_extract_windows(
-            self._h, ctypes.c_void_p(values_ptr), int(values_type), _ptr(times_ptr), ctypes.c_void_p(starts_ptr),
-            ctypes.c_void_p(ends_ptr), n_windows, ctypes.c_void_p(matrix.ptr + 8 * col0), matrix.ld, TSFA_DEVICE, None))
+        _check(self._lib, self._lib.tsfa_extract_windows(self._h, values_ptr, int(values_type), times_ptr or None, starts_ptr, ends_ptr,
+                                                         n_windows, matrix.ptr + 8 * col0, matrix.ld, TSFA_DEVICE, None))
 
     def extract_into(self, values, offsets, matrix, col0=0, times=None, pack=None, times_ptr=None):
         """Host arrays in, columns [col0, col0 + n_cols) of the DeviceMatrix `matrix` out: the samples are copied to the
@@ -1095,15 +890,10 @@ class Plan:
             if pack.n_series == 0 or self.n_cols == 0:
                 return
             _check(self._lib, self._lib.tsfa_extract_timed(
-                self._h, ctypes.c_void_p(pack.values_ptr), pack.values_type, _ptr(times_ptr), ctypes.c_void_p(pack.offsets_ptr),
-                pack.n_series, ctypes.c_void_p(matrix.ptr + 8 * col0), matrix.ld, TSFA_DEVICE, None))
+                self._h, pack.values_ptr, pack.values_type, times_ptr or None, pack.offsets_ptr, pack.n_series,
+                matrix.ptr + 8 * col0, matrix.ld, TSFA_DEVICE, None))
             return
-        values = np.ascontiguousarray(values)
-        if values.dtype == np.float32:
-            dt = TSFA_F32
-        else:
-            values = np.ascontiguousarray(values, dtype=np.float64)
-            dt = TSFA_F64
+        values, dt = _samples(values)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n_series = offsets.shape[0] - 1
         if matrix.shape[0] != n_series or col0 < 0 or col0 + self.n_cols > matrix.shape[1]:
@@ -1120,19 +910,17 @@ class Plan:
                 if times.shape != values.shape:
                     raise ValueError("times must have one entry per sample")
                 bufs.append(_DeviceBuffer(self._lib, times, matrix.device))
-                tptr = ctypes.c_void_p(bufs[2].ptr)
-            _check(self._lib, self._lib.tsfa_extract_timed(
-                self._h, ctypes.c_void_p(bufs[0].ptr), dt, tptr, ctypes.c_void_p(bufs[1].ptr), n_series,
-                ctypes.c_void_p(matrix.ptr + 8 * col0), matrix.ld, TSFA_DEVICE, None))
+                tptr = bufs[2].ptr
+            _check(self._lib, self._lib.tsfa_extract_timed(self._h, bufs[0].ptr, dt, tptr, bufs[1].ptr, n_series,
+                                                           matrix.ptr + 8 * col0, matrix.ld, TSFA_DEVICE, None))
         finally:
             for bf in bufs:
                 bf.free()
 
     def extract_device(self, values_ptr, dtype, offsets_ptr, n_series, out_ptr, ld_out, stream=None):
         """Raw device-pointer entry (ints): used with torch tensors (`.data_ptr()`) by bench.py / the sharded path."""
-        _check(self._lib, self._lib.tsfa_extract(
-            self._h, ctypes.c_void_p(values_ptr), int(dtype), ctypes.c_void_p(offsets_ptr), int(n_series),
-            ctypes.c_void_p(out_ptr), int(ld_out), TSFA_DEVICE, ctypes.c_void_p(stream) if stream else None))
+        _check(self._lib, self._lib.tsfa_extract(self._h, values_ptr, int(dtype), offsets_ptr, int(n_series), out_ptr, int(ld_out),
+                                                 TSFA_DEVICE, stream or None))
 
 
 class DeviceMatrix:
@@ -1145,7 +933,6 @@ class DeviceMatrix:
         self.shape = (int(n_rows), int(n_cols))
         self.device = int(device)
         self._ptr = ctypes.c_void_p()
-        _bind_device_api(self._lib)
         _check(self._lib, self._lib.tsfa_device_alloc(ctypes.byref(self._ptr), max(1, 8 * self.shape[0] * self.shape[1]),
                                                       self.device))
 
@@ -1177,13 +964,12 @@ class DeviceMatrix:
                 out = np.empty((n, m), dtype=np.float64)
             elif out.dtype != np.float64 or out.shape != (n, m) or not out.flags.c_contiguous:
                 raise ValueError("out must be a C-contiguous float64 matrix of the device matrix' shape")
-            _check(self._lib, self._lib.tsfa_device_copy(out.ctypes.data_as(ctypes.c_void_p), self._ptr, out.nbytes, 0,
-                                                         self.device))
+            _check(self._lib, self._lib.tsfa_device_copy(out.ctypes.data, self._ptr, out.nbytes, 0, self.device))
             return out
         cols = np.ascontiguousarray(cols, dtype=np.int32)
         out = np.empty((n, cols.shape[0]), dtype=np.float64)
-        _check(self._lib, self._lib.tsfa_gather_columns(self._ptr, n, m, cols.ctypes.data_as(ctypes.c_void_p),
-                                                        cols.shape[0], out.ctypes.data_as(ctypes.c_void_p), self.device))
+        _check(self._lib, self._lib.tsfa_gather_columns(self._ptr, n, m, cols.ctypes.data, cols.shape[0], out.ctypes.data,
+                                                        self.device))
         return out
 
 
@@ -1195,59 +981,37 @@ def extract_parts_into(parts, values, offsets, matrix, col0=0, times=None, pack=
     pack: a DevicePack on the matrix' device instead of `values` / `offsets` -- no upload at all; times_ptr: with it, a
     device pointer (int) to float64 hours laid out like the pack's samples (`pack_times`), handed to every part."""
     lib = load()
-    _bind_device_api(lib)
+    device = matrix.device
     if times_ptr is not None and pack is None:
         raise ValueError("times_ptr goes with pack=: host arrays bring their times as `times`")
     if pack is not None:
-        if pack.device != matrix.device or pack.n_series != matrix.shape[0]:
+        if pack.device != device or pack.n_series != matrix.shape[0]:
             raise ValueError("the device matrix does not hold the pack's series on the pack's device")
-        if pack.n_series == 0:
-            return
-        tmp = DeviceMatrix(pack.n_series, max(plan.n_cols for plan, _ in parts), matrix.device)
-        try:
-            for plan, cols in parts:
-                if plan.n_cols == 0:
-                    continue
-                _check(lib, lib.tsfa_extract_timed(plan._h, ctypes.c_void_p(pack.values_ptr), pack.values_type, _ptr(times_ptr),
-                                                   ctypes.c_void_p(pack.offsets_ptr), pack.n_series, ctypes.c_void_p(tmp.ptr),
-                                                   plan.n_cols, TSFA_DEVICE, None))
-                idx = np.ascontiguousarray(np.asarray(cols, dtype=np.int64) + int(col0), dtype=np.int32)
-                _check(lib, lib.tsfa_scatter_columns(ctypes.c_void_p(matrix.ptr), matrix.ld, idx.ctypes.data_as(ctypes.c_void_p),
-                                                     ctypes.c_void_p(tmp.ptr), pack.n_series, plan.n_cols, matrix.device))
-        finally:
-            tmp.free()
-        return
-    values = np.ascontiguousarray(values)
-    if values.dtype == np.float32:
-        dt = TSFA_F32
+        n_series = pack.n_series
     else:
-        values = np.ascontiguousarray(values, dtype=np.float64)
-        dt = TSFA_F64
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    n_series = offsets.shape[0] - 1
+        values, dt = _samples(values)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n_series = offsets.shape[0] - 1
     if n_series == 0:
         return
-    if values.size == 0:
+    if pack is None and values.size == 0:
         raise ValueError("every series must hold at least one sample")
-    device = matrix.device
-    bufs = [_DeviceBuffer(lib, values, device), _DeviceBuffer(lib, offsets, device)]
-    tmp = None
+    bufs, tmp = [], None
     try:
-        tptr = None
-        if times is not None:
-            times = np.ascontiguousarray(times, dtype=np.float64)
-            bufs.append(_DeviceBuffer(lib, times, device))
-            tptr = ctypes.c_void_p(bufs[2].ptr)
-        width = max(plan.n_cols for plan, _ in parts)
-        tmp = DeviceMatrix(n_series, width, device)
+        if pack is not None:
+            vptr, dt, optr, tptr = pack.values_ptr, pack.values_type, pack.offsets_ptr, times_ptr or None
+        else:   # one upload of the samples, the offsets and the times for all parts
+            host = [values, offsets] + ([] if times is None else [np.ascontiguousarray(times, dtype=np.float64)])
+            for a in host:
+                bufs.append(_DeviceBuffer(lib, a, device))
+            vptr, optr, tptr = bufs[0].ptr, bufs[1].ptr, (None if times is None else bufs[2].ptr)
+        tmp = DeviceMatrix(n_series, max(plan.n_cols for plan, _ in parts), device)
         for plan, cols in parts:
             if plan.n_cols == 0:
                 continue
-            _check(lib, lib.tsfa_extract_timed(plan._h, ctypes.c_void_p(bufs[0].ptr), dt, tptr, ctypes.c_void_p(bufs[1].ptr),
-                                               n_series, ctypes.c_void_p(tmp.ptr), plan.n_cols, TSFA_DEVICE, None))
+            _check(lib, lib.tsfa_extract_timed(plan._h, vptr, dt, tptr, optr, n_series, tmp.ptr, plan.n_cols, TSFA_DEVICE, None))
             idx = np.ascontiguousarray(np.asarray(cols, dtype=np.int64) + int(col0), dtype=np.int32)
-            _check(lib, lib.tsfa_scatter_columns(ctypes.c_void_p(matrix.ptr), matrix.ld, idx.ctypes.data_as(ctypes.c_void_p),
-                                                 ctypes.c_void_p(tmp.ptr), n_series, plan.n_cols, device))
+            _check(lib, lib.tsfa_scatter_columns(matrix.ptr, matrix.ld, idx.ctypes.data, tmp.ptr, n_series, plan.n_cols, device))
     finally:
         for bf in bufs:
             bf.free()
@@ -1261,7 +1025,6 @@ def extract_parts_windows_into(parts, values_ptr, values_type, starts_ptr, ends_
     and scattered (tsfa_scatter_columns) into columns col0 + cols of `matrix` (a DeviceMatrix or a BorrowedMatrix).
     times_ptr: as in `Plan.extract_windows_into`, handed to every part."""
     lib = load()
-    _bind_device_api(lib)
     n_windows = int(n_windows)
     if matrix.shape[0] != n_windows:
         raise ValueError("the device matrix does not hold one row per window")
@@ -1278,28 +1041,10 @@ def extract_parts_windows_into(parts, values_ptr, values_type, starts_ptr, ends_
                                       BorrowedMatrix(tmp.ptr, n_windows, plan.n_cols, matrix.device, owner=tmp),
                                       times_ptr=times_ptr)
             idx = np.ascontiguousarray(np.asarray(cols, dtype=np.int64) + int(col0), dtype=np.int32)
-            _check(lib, lib.tsfa_scatter_columns(ctypes.c_void_p(matrix.ptr), matrix.ld, idx.ctypes.data_as(ctypes.c_void_p),
-                                                 ctypes.c_void_p(tmp.ptr), n_windows, plan.n_cols, matrix.device))
+            _check(lib, lib.tsfa_scatter_columns(matrix.ptr, matrix.ld, idx.ctypes.data, tmp.ptr, n_windows, plan.n_cols,
+                                                 matrix.device))
     finally:
         tmp.free()
-
-
-def _bind_device_api(lib):
-    if getattr(lib, "_tsfa_device_api_bound", False):
-        return
-    lib.tsfa_device_alloc.restype = ctypes.c_int32
-    lib.tsfa_device_alloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_int32]
-    lib.tsfa_device_free.restype = ctypes.c_int32
-    lib.tsfa_device_free.argtypes = [ctypes.c_void_p, ctypes.c_int32]
-    lib.tsfa_device_copy.restype = ctypes.c_int32
-    lib.tsfa_device_copy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int32]
-    lib.tsfa_gather_columns.restype = ctypes.c_int32
-    lib.tsfa_gather_columns.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                                        ctypes.c_void_p, ctypes.c_int32]
-    lib.tsfa_scatter_columns.restype = ctypes.c_int32
-    lib.tsfa_scatter_columns.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                         ctypes.c_int64, ctypes.c_int32]
-    lib._tsfa_device_api_bound = True
 
 
 class _DeviceBuffer:
@@ -1308,9 +1053,8 @@ class _DeviceBuffer:
     def __init__(self, lib, array, device):
         self._lib, self.device = lib, device
         self._ptr = ctypes.c_void_p()
-        _bind_device_api(lib)
         _check(lib, lib.tsfa_device_alloc(ctypes.byref(self._ptr), max(1, array.nbytes), device))
-        _check(lib, lib.tsfa_device_copy(self._ptr, array.ctypes.data_as(ctypes.c_void_p), array.nbytes, 1, device))
+        _check(lib, lib.tsfa_device_copy(self._ptr, array.ctypes.data, array.nbytes, 1, device))
 
     @property
     def ptr(self):
@@ -1325,11 +1069,11 @@ class _DeviceBuffer:
 def _matrix_args(X):
     """(pointer, n_rows, n_cols, ld, space, keepalive) of a host ndarray or a DeviceMatrix."""
     if isinstance(X, DeviceMatrix):
-        return ctypes.c_void_p(X.ptr), X.shape[0], X.shape[1], X.ld, TSFA_DEVICE, X
+        return X.ptr, X.shape[0], X.shape[1], X.ld, TSFA_DEVICE, X
     X = np.ascontiguousarray(X, dtype=np.float64)
     if X.ndim != 2:
         raise ValueError("X must be two-dimensional")
-    return X.ctypes.data_as(ctypes.c_void_p), X.shape[0], X.shape[1], X.shape[1], TSFA_HOST, X
+    return X.ctypes.data, X.shape[0], X.shape[1], X.shape[1], TSFA_HOST, X
 
 
 def relevance_classes(X, y_codes, n_classes, device=0, with_ks=False):
@@ -1340,33 +1084,19 @@ def relevance_classes(X, y_codes, n_classes, device=0, with_ks=False):
     y_codes = np.ascontiguousarray(y_codes, dtype=np.int32)
     if y_codes.shape != (n,):
         raise ValueError("one class code per row")
-    cols = (RelevanceCol * max(m, 1))()
+    cols = np.zeros(max(m, 1), dtype=_CLASS_COL_DTYPE)
     rank_sums = np.zeros((m, n_classes), dtype=np.float64)
     hi_counts = np.zeros((m, n_classes), dtype=np.int64)
-    lib.tsfa_relevance_classes.restype = ctypes.c_int32
-    lib.tsfa_relevance_classes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                           ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_void_p]
+    args = (xptr, n, m, ld, space, y_codes.ctypes.data, int(n_classes), int(device), cols.ctypes.data, rank_sums.ctypes.data,
+            hi_counts.ctypes.data)
     if with_ks:
         ks_d = np.zeros((m, n_classes), dtype=np.float64)
-        lib.tsfa_relevance_classes_ks.restype = ctypes.c_int32
-        lib.tsfa_relevance_classes_ks.argtypes = lib.tsfa_relevance_classes.argtypes + [ctypes.c_void_p]
-        _check(lib, lib.tsfa_relevance_classes_ks(xptr, n, m, ld, space,
-                                                  y_codes.ctypes.data_as(ctypes.c_void_p), int(n_classes), int(device),
-                                                  ctypes.cast(cols, ctypes.c_void_p), rank_sums.ctypes.data_as(ctypes.c_void_p),
-                                                  hi_counts.ctypes.data_as(ctypes.c_void_p), ks_d.ctypes.data_as(ctypes.c_void_p)))
+        _check(lib, lib.tsfa_relevance_classes_ks(*args, ks_d.ctypes.data))
     else:
-        _check(lib, lib.tsfa_relevance_classes(xptr, n, m, ld, space,
-                                               y_codes.ctypes.data_as(ctypes.c_void_p), int(n_classes), int(device),
-                                               ctypes.cast(cols, ctypes.c_void_p), rank_sums.ctypes.data_as(ctypes.c_void_p),
-                                               hi_counts.ctypes.data_as(ctypes.c_void_p)))
-    rec = np.frombuffer(cols, dtype=[("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("tie_term", "<f8")], count=m)
+        _check(lib, lib.tsfa_relevance_classes(*args))
+    rec = cols[:m]
     res = (rec["n_unique"].copy(), rec["v_lo"].copy(), rec["v_hi"].copy(), rec["tie_term"].copy(), rank_sums, hi_counts)
     return res + (ks_d,) if with_ks else res
-
-
-_REAL_COL_DTYPE = [("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("dis", "<i8"), ("xtie", "<i8"), ("ntie", "<i8"),
-                   ("x0", "<f8"), ("x1", "<f8"), ("n_hi", "<i8"), ("ks_d", "<f8")]
 
 
 def relevance_real(X, y, device=0):
@@ -1380,13 +1110,8 @@ def relevance_real(X, y, device=0):
     # the target is one vector: its dense ranks / sorted order are prepared here once for all columns
     y_rank, y_perm, y_end = target_order(y)
     cols = np.zeros(max(m, 1), dtype=_REAL_COL_DTYPE)
-    lib.tsfa_relevance_real.restype = ctypes.c_int32
-    lib.tsfa_relevance_real.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
-    _check(lib, lib.tsfa_relevance_real(xptr, n, m, ld, space,
-                                        y_rank.ctypes.data_as(ctypes.c_void_p), y_perm.ctypes.data_as(ctypes.c_void_p),
-                                        y_end.ctypes.data_as(ctypes.c_void_p), int(device),
-                                        cols.ctypes.data_as(ctypes.c_void_p)))
+    _check(lib, lib.tsfa_relevance_real(xptr, n, m, ld, space, y_rank.ctypes.data, y_perm.ctypes.data, y_end.ctypes.data,
+                                        int(device), cols.ctypes.data))
     return cols[:m], y_rank
 
 
@@ -1395,71 +1120,33 @@ def impute_matrix(X, device=0):
     -> (col_max, col_min, col_median of the finite values, number of finite cells per column)."""
     lib = load()
     if isinstance(X, DeviceMatrix):
-        xptr, (n, m), ld, space = ctypes.c_void_p(X.ptr), X.shape, X.ld, TSFA_DEVICE
+        xptr, (n, m), ld, space = X.ptr, X.shape, X.ld, TSFA_DEVICE
         device = X.device
     else:
         if not (isinstance(X, np.ndarray) and X.dtype == np.float64 and X.ndim == 2 and X.flags.writeable
                 and (X.shape[1] == 0 or X.strides[1] == 8) and X.strides[0] % 8 == 0 and X.strides[0] >= 8 * X.shape[1]):
             raise ValueError("impute_matrix needs a writeable float64 matrix with contiguous rows")
         n, m = X.shape
-        xptr, ld, space = X.ctypes.data_as(ctypes.c_void_p), (X.strides[0] // 8 if n else m), TSFA_HOST
+        xptr, ld, space = X.ctypes.data, (X.strides[0] // 8 if n else m), TSFA_HOST
     cmax, cmin, cmed = (np.zeros(m) for _ in range(3))
     cnt = np.zeros(m, dtype=np.int32)
-    lib.tsfa_impute.restype = ctypes.c_int32
-    lib.tsfa_impute.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    _check(lib, lib.tsfa_impute(xptr, n, m, ld, space, int(device),
-                                cmax.ctypes.data_as(ctypes.c_void_p), cmin.ctypes.data_as(ctypes.c_void_p),
-                                cmed.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
+    _check(lib, lib.tsfa_impute(xptr, n, m, ld, space, int(device), cmax.ctypes.data, cmin.ctypes.data, cmed.ctypes.data,
+                                cnt.ctypes.data))
     return cmax, cmin, cmed, cnt
 
 
 def impute_ptr(x_ptr, n_rows, n_cols, ld, space, device=0):
     """tsfa_impute in place on the float64 matrix at x_ptr (host or device memory by `space`), leading dimension ld."""
     lib = load()
-    lib.tsfa_impute.restype = ctypes.c_int32
-    lib.tsfa_impute.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    _check(lib, lib.tsfa_impute(ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), int(space), int(device), None, None,
-                                None, None))
+    _check(lib, lib.tsfa_impute(x_ptr, int(n_rows), int(n_cols), int(ld), int(space), int(device), None, None, None, None))
 
 
 def ks_outer_prob(m, n, g, h):
-    lib = load()
-    lib.tsfa_ks_outer_prob.restype = ctypes.c_double
-    lib.tsfa_ks_outer_prob.argtypes = [ctypes.c_int64] * 4
-    return float(lib.tsfa_ks_outer_prob(int(m), int(n), int(g), int(h)))
+    return float(load().tsfa_ks_outer_prob(int(m), int(n), int(g), int(h)))
 
 
 # ---- selection on the device (tsfa_relevance_tails_* / tsfa_relevance_fdr / tsfa_compact_mask / tsfa_gather_columns_device):
 # the matrix and every output are device pointers (ints, e.g. torch's `.data_ptr()`) owned by the caller ----
-
-def _bind_select_api(lib):
-    if getattr(lib, "_tsfa_select_api_bound", False):
-        return
-    i64, i32, f64, ptr = ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p
-    lib.tsfa_relevance_tails_classes.restype = i32
-    lib.tsfa_relevance_tails_classes.argtypes = [ptr, i64, i64, i64, i32, ptr, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr,
-                                                 ctypes.POINTER(i64)]
-    lib.tsfa_relevance_tails_real.restype = i32
-    lib.tsfa_relevance_tails_real.argtypes = [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i64, f64, f64, i32, ptr, ptr, ptr, ptr,
-                                              ctypes.POINTER(i64)]
-    lib.tsfa_ks_tails.restype = i32
-    lib.tsfa_ks_tails.argtypes = [ptr, ptr, ptr, i64, i32, ptr, ptr]
-    lib.tsfa_relevance_tails_classes_ks.restype = i32
-    lib.tsfa_relevance_tails_classes_ks.argtypes = [ptr, i64, i64, i64, i32, ptr, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr,
-                                                    ptr, ctypes.POINTER(i64)]
-    lib.tsfa_relevance_tails_real_ks.restype = i32
-    lib.tsfa_relevance_tails_real_ks.argtypes = [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i64, f64, f64, i32, i32, ptr, ptr, ptr, ptr,
-                                                 ptr, ptr, ctypes.POINTER(i64)]
-    lib.tsfa_relevance_fdr.restype = i32
-    lib.tsfa_relevance_fdr.argtypes = [ptr, ptr, i64, i32, f64, f64, i32, i32, i32, ptr, ptr, ptr, ptr]
-    lib.tsfa_compact_mask.restype = i32
-    lib.tsfa_compact_mask.argtypes = [ptr, i64, ptr, ctypes.POINTER(i64), i32]
-    lib.tsfa_gather_columns_device.restype = i32
-    lib.tsfa_gather_columns_device.argtypes = [ptr, i64, i64, ptr, i64, ptr, i64, i32]
-    lib._tsfa_select_api_bound = True
-
 
 def _ks_tail_code(ks_tail):
     if ks_tail not in ("host", "device"):
@@ -1471,9 +1158,7 @@ def ks_tails(n1_ptr, n2_ptr, d_ptr, n_cells, p_ptr, route_ptr, device=0):
     """tsfa_ks_tails: the exact Kolmogorov-Smirnov tails of n_cells triples (n1 int64, n2 int64, d float64: device arrays) into
     the device arrays p [n_cells] float64 and route [n_cells] uint8 (TSFA_ROUTE_KS_EXACT, or NaN and TSFA_ROUTE_HOST_KS)."""
     lib = load()
-    _bind_select_api(lib)
-    _check(lib, lib.tsfa_ks_tails(ctypes.c_void_p(n1_ptr), ctypes.c_void_p(n2_ptr), ctypes.c_void_p(d_ptr), int(n_cells), int(device),
-                                  ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr)))
+    _check(lib, lib.tsfa_ks_tails(n1_ptr, n2_ptr, d_ptr, int(n_cells), int(device), p_ptr, route_ptr))
 
 
 def relevance_tails_classes(x_ptr, n_rows, n_cols, ld, y_codes, n_classes, p_ptr, route_ptr, type_ptr, device=0, with_ks=False,
@@ -1485,29 +1170,24 @@ def relevance_tails_classes(x_ptr, n_rows, n_cols, ld, y_codes, n_classes, p_ptr
     the Kolmogorov-Smirnov distances (with_ks), and the statistics then come without them."""
     ks_code = _ks_tail_code(ks_tail)
     lib = load()
-    _bind_select_api(lib)
     y_codes = np.ascontiguousarray(y_codes, dtype=np.int32)
     if y_codes.shape != (n_rows,):
         raise ValueError("one class code per row")
     n_host = ctypes.c_int64(0)
     cols = rank_sums = hi_counts = ks_d = None
     if want_stats:
-        cols = np.zeros(max(n_cols, 1), dtype=[("n_unique", "<i8"), ("v_lo", "<f8"), ("v_hi", "<f8"), ("tie_term", "<f8")])
+        cols = np.zeros(max(n_cols, 1), dtype=_CLASS_COL_DTYPE)
         rank_sums = np.zeros((n_cols, n_classes), dtype=np.float64)
         hi_counts = np.zeros((n_cols, n_classes), dtype=np.int64)
         ks_d = np.zeros((n_cols, n_classes), dtype=np.float64) if (with_ks and ks_d_ptr is None) else None
-    hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    stats_ptrs = [None if a is None else a.ctypes.data for a in (cols, rank_sums, hi_counts, ks_d)]
+    head = (x_ptr, int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_codes.ctypes.data, int(n_classes), int(bool(with_ks)))
     if ks_code == TSFA_KS_TAIL_HOST and ks_d_ptr is None:
-        _check(lib, lib.tsfa_relevance_tails_classes(
-            ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_codes.ctypes.data_as(ctypes.c_void_p),
-            int(n_classes), int(bool(with_ks)), int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr),
-            ctypes.c_void_p(type_ptr), hp(cols), hp(rank_sums), hp(hi_counts), hp(ks_d), ctypes.byref(n_host)))
+        _check(lib, lib.tsfa_relevance_tails_classes(*head, int(device), p_ptr, route_ptr, type_ptr, *stats_ptrs,
+                                                     ctypes.byref(n_host)))
     else:
-        _check(lib, lib.tsfa_relevance_tails_classes_ks(
-            ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_codes.ctypes.data_as(ctypes.c_void_p),
-            int(n_classes), int(bool(with_ks)), ks_code, int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr),
-            ctypes.c_void_p(type_ptr), hp(cols), hp(rank_sums), hp(hi_counts), hp(ks_d),
-            None if ks_d_ptr is None else ctypes.c_void_p(ks_d_ptr), ctypes.byref(n_host)))
+        _check(lib, lib.tsfa_relevance_tails_classes_ks(*head, ks_code, int(device), p_ptr, route_ptr, type_ptr, *stats_ptrs,
+                                                        ks_d_ptr, ctypes.byref(n_host)))
     stats = None
     if want_stats:
         stats = (cols["n_unique"][:n_cols].copy(), cols["tie_term"][:n_cols].copy(), rank_sums, hi_counts, ks_d)
@@ -1537,7 +1217,6 @@ def relevance_tails_real(x_ptr, n_rows, n_cols, ld, y, tie_statistics, p_ptr, ro
     the two-valued columns' statistics."""
     ks_code = _ks_tail_code(ks_tail)
     lib = load()
-    _bind_select_api(lib)
     y = np.ascontiguousarray(y, dtype=np.float64)
     if y.shape != (n_rows,):
         raise ValueError("one target value per row")
@@ -1545,20 +1224,14 @@ def relevance_tails_real(x_ptr, n_rows, n_cols, ld, y, tie_statistics, p_ptr, ro
     ytie, y0, y1 = tie_statistics(y_rank)
     n_host = ctypes.c_int64(0)
     cols = np.zeros(max(n_cols, 1), dtype=_REAL_COL_DTYPE) if want_stats else None
+    cols_ptr = None if cols is None else cols.ctypes.data
+    head = (x_ptr, int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_rank.ctypes.data, y_perm.ctypes.data, y_end.ctypes.data,
+            int(ytie), float(y0), float(y1))
     if ks_code == TSFA_KS_TAIL_HOST and n_hi_ptr is None and ks_d_ptr is None:
-        _check(lib, lib.tsfa_relevance_tails_real(
-            ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_rank.ctypes.data_as(ctypes.c_void_p),
-            y_perm.ctypes.data_as(ctypes.c_void_p), y_end.ctypes.data_as(ctypes.c_void_p), int(ytie), float(y0), float(y1),
-            int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr), ctypes.c_void_p(type_ptr),
-            None if cols is None else cols.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_host)))
+        _check(lib, lib.tsfa_relevance_tails_real(*head, int(device), p_ptr, route_ptr, type_ptr, cols_ptr, ctypes.byref(n_host)))
     else:
-        _check(lib, lib.tsfa_relevance_tails_real_ks(
-            ctypes.c_void_p(x_ptr), int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_rank.ctypes.data_as(ctypes.c_void_p),
-            y_perm.ctypes.data_as(ctypes.c_void_p), y_end.ctypes.data_as(ctypes.c_void_p), int(ytie), float(y0), float(y1),
-            ks_code, int(device), ctypes.c_void_p(p_ptr), ctypes.c_void_p(route_ptr), ctypes.c_void_p(type_ptr),
-            None if cols is None else cols.ctypes.data_as(ctypes.c_void_p),
-            None if n_hi_ptr is None else ctypes.c_void_p(n_hi_ptr), None if ks_d_ptr is None else ctypes.c_void_p(ks_d_ptr),
-            ctypes.byref(n_host)))
+        _check(lib, lib.tsfa_relevance_tails_real_ks(*head, ks_code, int(device), p_ptr, route_ptr, type_ptr, cols_ptr, n_hi_ptr,
+                                                     ks_d_ptr, ctypes.byref(n_host)))
     return int(n_host.value), (None if cols is None else cols[:n_cols])
 
 
@@ -1566,26 +1239,20 @@ def relevance_fdr(p_ptr, type_ptr, n_cols, n_tables, alpha, c_m, n_significant, 
                   n_significant_ptr, p_min_ptr, device=0):
     """tsfa_relevance_fdr: the step-up per table and the combination of the tables, device arrays in and out."""
     lib = load()
-    _bind_select_api(lib)
-    _check(lib, lib.tsfa_relevance_fdr(ctypes.c_void_p(p_ptr), ctypes.c_void_p(type_ptr), int(n_cols), int(n_tables), float(alpha),
-                                       float(c_m), int(n_significant), int(bool(multiclass)), int(device),
-                                       ctypes.c_void_p(rel_table_ptr), ctypes.c_void_p(relevant_ptr),
-                                       ctypes.c_void_p(n_significant_ptr), ctypes.c_void_p(p_min_ptr)))
+    _check(lib, lib.tsfa_relevance_fdr(p_ptr, type_ptr, int(n_cols), int(n_tables), float(alpha), float(c_m), int(n_significant),
+                                       int(bool(multiclass)), int(device), rel_table_ptr, relevant_ptr, n_significant_ptr,
+                                       p_min_ptr))
 
 
 def compact_mask(mask_ptr, n, indices_ptr, device=0):
     """tsfa_compact_mask: ascending int32 indices of the non-zero bytes of the device mask -> their count."""
     lib = load()
-    _bind_select_api(lib)
     count = ctypes.c_int64(0)
-    _check(lib, lib.tsfa_compact_mask(ctypes.c_void_p(mask_ptr), int(n), ctypes.c_void_p(indices_ptr), ctypes.byref(count),
-                                      int(device)))
+    _check(lib, lib.tsfa_compact_mask(mask_ptr, int(n), indices_ptr, ctypes.byref(count), int(device)))
     return int(count.value)
 
 
 def gather_columns_device(x_ptr, n_rows, ld, cols_ptr, n_sel, out_ptr, ld_out, device=0):
     """tsfa_gather_columns_device: out[r, c] = X[r, cols[c]] within HBM."""
     lib = load()
-    _bind_select_api(lib)
-    _check(lib, lib.tsfa_gather_columns_device(ctypes.c_void_p(x_ptr), int(n_rows), int(ld), ctypes.c_void_p(cols_ptr), int(n_sel),
-                                               ctypes.c_void_p(out_ptr), int(ld_out), int(device)))
+    _check(lib, lib.tsfa_gather_columns_device(x_ptr, int(n_rows), int(ld), cols_ptr, int(n_sel), out_ptr, int(ld_out), int(device)))
