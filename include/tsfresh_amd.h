@@ -218,6 +218,7 @@ int32_t tsfa_plan_last_launches(const tsfa_plan *plan, tsfa_launch_info *out, in
  *   "row_form"       0|1   BASIC / TREND columns of series of <= 256 samples four series to a wavefront (1)
  *   "sort_waves"     1|2   k_sort up to 2048 samples: one wavefront per series (1), or the two-wavefront form it replaced (2)
  *   "seq_rows"       -1|0|1 lempel_ziv_complexity's symbol rows in LDS (0), in HBM (1), or in HBM where that puts more series on a CU (-1, default)
+ *   "cwt_links"      0|1   number_cwt_peaks with n <= 5: ridge lines linked column by column (1), or by the general linker of the wider plans (0)
  *   "host_chunks"    n     row chunks of the TSFA_HOST pipeline (0: by batch size)
  *   "side_lane"      mask  two lanes: bit f = family f (enum tsfa_family) runs on a low-priority side stream beside the others,
  *                          behind the main lane's ENTROPY family; 0 = one lane.  Default: SEQ | TREND.  BASIC, SORT and ENTROPY

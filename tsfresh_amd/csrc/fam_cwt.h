@@ -3,7 +3,9 @@
 // restated from scipy/signal/_peak_finding.py (find_peaks_cwt, _identify_ridge_lines, _filter_ridge_lines,
 // _boolrelextrema), scipy/signal/_wavelets.py (_cwt) and fc.py:1307 (_ricker).
 //   phase A : CWT rows by direct convolution with the Ricker taps (one column per lane), relative-maximum bit mask
-//   phase B : ridge-line linking, one row at a time, every step parallel over columns / lines:
+//   phase B : ridge-line linking.  Widths up to 5 (cwt_link_columns): column by column from the mask alone, no barrier
+//               between rows -- a maximum can only join a line of its own column or, on one row, of a neighbouring one.
+//               Any width (cwt_link_general): one row at a time, every step parallel over columns / lines:
 //               snapshot of the live lines' last columns (column -> line map), each maximum looks up its nearest
 //               line in the snapshot, new lines get indices in ascending column order (ballot prefix), then every
 //               line collects the maxima that chose it.  The reference's algorithm is sequential and O(lines^2).
@@ -68,6 +70,7 @@ struct CwtPeaksLds {
     double *red; double *row0; double *rowv; double *taps; void *xpad; unsigned short *mask; cwt_idx_t *lcol;
     cwt_idx_t *linf; cwt_idx_t *colmap; cwt_idx_t *mline; int *misc;
     const double *rk = nullptr;   // the plan's Ricker tap table (tsfa_build_consts + TSFA_CONSTS_RICKER; global memory), or null
+    int links = 1;                // phase B: 1: the column linker where W <= 5; 0: the general linker everywhere (plan option cwt_links)
 };
 
 // linf packing: length (6 bits, saturating), gap (2 bits), retired flag, last row (4 bits)
@@ -417,44 +420,41 @@ TSFA_DEV double cwt_filter_counts(const Blk &b, X xv, int n, const CwtPeaksLds &
     return kept;
 }
 
-// ST: element type of the padded LDS copy of the series (the input precision: float32 samples stay float32)
-// derive_w1 / kept_w1: also return number_cwt_peaks(n = 1) of the same series (phase C), W <= 14
-template <class ST, class X>
-TSFA_DEV double number_cwt_peaks_one(const Blk &b, X xv, int n, int W, const CwtPeaksLds &L, bool derive_w1 = false,
-                                     double *kept_w1 = nullptr) {
-    const int cap = n;  // line capacity
-    TSFA_TICKER(tk, 0);
-    blk_sync();
-    for (int c = b.tid; c < n; c += b.nt) { L.mask[c] = 0; L.colmap[c] = 0; L.mline[c] = 0; }
-    blk_sync();
-    // ---- phase A: the series goes to LDS between two zero halos (xpad[TSFA_CWTP_HALO + i] = x[i]) when it fits ----
-    if (L.xpad != nullptr) {
-        blk_sync();
-        ST *xpad = (ST *)L.xpad;
-        for (int i = b.tid; i < n + 2 * TSFA_CWTP_HALO + 8; i += b.nt) {
-            const int j = i - TSFA_CWTP_HALO;
-            xpad[i] = (j >= 0 && j < n) ? (ST)xv(j) : (ST)0;
-        }
-        const ST *xp0 = xpad + TSFA_CWTP_HALO;
-        cwt_rows_tiled(b, [=](int i) { return (double)xp0[i]; }, n, W, L);
-    } else {  // no room for the padded copy (very long series): the same tiles, samples straight from HBM / L2
-        cwt_rows_tiled(b, [=](int i) { return (i >= 0 && i < n) ? xv(i) : 0.0; }, n, W, L);
-    }
-    blk_sync();
-    TSFA_TICK(tk, b, 151);
-    // ---- phase B ----
-    // A thread owns CT consecutive columns: the maxima of a row that start new lines get their indices from ONE
-    // workgroup scan of per-thread counts (ascending column order = the reference's order of creation).
+// ---- phase B: the two linkers ----
+// A thread owns CT consecutive columns: what its columns start or end gets indices from ONE workgroup scan of per-thread
+// counts (ascending column order = the reference's order of creation).
+struct CwtOwnCols { int ctbits, cbeg, cend; };
+TSFA_DEV CwtOwnCols cwt_own_columns(const Blk &b, int n) {
     const int CT = (n + b.nt - 1) / b.nt;
-    int ctbits = 1;
-    while ((1 << ctbits) <= CT) ++ctbits;
-    const int cbeg = CT * b.tid, cend = (cbeg + CT < n) ? cbeg + CT : n;
+    CwtOwnCols o;
+    o.ctbits = 1;
+    while ((1 << o.ctbits) <= CT) ++o.ctbits;
+    o.cbeg = CT * b.tid;
+    o.cend = (o.cbeg + CT < n) ? o.cbeg + CT : n;
+    return o;
+}
+// the highest row with a maximum (-1: none): where the reference starts its lines
+TSFA_DEV int cwt_start_row(const Blk &b, int W, const CwtPeaksLds &L, const CwtOwnCols &o) {
     unsigned anyrow = 0;
-    for (int c = cbeg; c < cend; ++c) anyrow |= L.mask[c];
+    for (int c = o.cbeg; c < o.cend; ++c) anyrow |= L.mask[c];
     anyrow = blk_or16(b, anyrow) & ((1u << W) - 1u);
     int start_row = -1;
     for (int r = 0; r < W; ++r)
         if ((anyrow >> r) & 1u) start_row = r;
+    return start_row;
+}
+
+// Both linkers read the relative-maximum mask (complete, behind a barrier) and leave the END POINTS of the ridge lines of at
+// least min_length = ceil(W / 4) maxima at the front of (lcol, linf) -- entry k = (column lcol[k], row linf[k]), the form
+// phase C reads -- and return their number.  cap: entries / lines the arrays hold; more than that sets *overflow (the
+// caller answers NaN) and nothing is written past them.  derive_w1: a qualifying line that ends on row 0 is not listed but
+// marked, bit W + 1 of mask[column] (number_cwt_peaks_one, phase C).
+//
+// The GENERAL linker, any width: scipy's _identify_ridge_lines one row at a time, every step parallel over columns / lines
+// (the head of this file).  It wants colmap cleared over the series; (mline, colmap) hold cap entries while it compacts.
+TSFA_DEV int cwt_link_general(const Blk &b, int n, int W, int start_row, const CwtPeaksLds &L, const CwtOwnCols &o, int cap,
+                              bool derive_w1, int *overflow_out) {
+    const int ctbits = o.ctbits, cbeg = o.cbeg, cend = o.cend;
     int nlines = 0, overflow = 0;
     if (start_row >= 0) {
         const unsigned sbit = 1u << start_row;
@@ -493,8 +493,8 @@ TSFA_DEV double number_cwt_peaks_one(const Blk &b, X xv, int n, int W, const Cwt
                     int best = 0;
                     if (c - d >= 0 && L.colmap[c - d]) best = L.colmap[c - d];
                     if (d > 0 && c + d < n && L.colmap[c + d]) {
-                        const int o = L.colmap[c + d];
-                        if (best == 0 || o < best) best = o;
+                        const int o2 = L.colmap[c + d];
+                        if (best == 0 || o2 < best) best = o2;
                     }
                     line = best;
                 }
@@ -537,33 +537,8 @@ TSFA_DEV double number_cwt_peaks_one(const Blk &b, X xv, int n, int W, const Cwt
             }
         }
     }
-    blk_sync();
-    TSFA_TICK(tk, b, 152);
-    // ---- phase C ----
+    // The qualifying lines are compacted to the front of (lcol, linf), so every lane of the filter has work.
     const int min_length = (W + 3) / 4;             // ceil(rows / 4)
-    const int window = (n + 19) / 20;               // ceil(num_points / 20)
-    const int hf = window / 2, odd = window % 2;
-    // cwt[row, col] of a line that ended above row 0 is re-evaluated here; its Ricker taps (exp / pow / sqrt each) are
-    // tabulated once per width instead of once per tap per line:  taps[5 (w-2)(w+1) + k] = reversed tap k of width w
-    const bool taps_cached = (W >= 2) && (10 * W < n) && (5 * (W - 1) * (W + 2) <= TSFA_CWTP_MAXTAPS + 16);
-    if (taps_cached) {
-        blk_sync();
-        for (int w = 2; w <= W; ++w) {
-            const int nw = 10 * w;
-            double *tw = L.taps + 5 * (w - 2) * (w + 1);
-            for (int k = b.tid; k < nw; k += b.nt) tw[k] = ricker_tap_t(L.rk, nw, w, nw - 1 - k);
-        }
-        blk_sync();
-    }
-    // Long series: the noise window holds hundreds of samples and its 10th percentile is no longer among the eight
-    // smallest: every entry is decided by counting its window against thresholds at +-|signal| (cwt_filter_counts).
-    const bool long_windows = ((int)(0.1 * (double)(window - 1)) + 1 >= 8);
-    // The filter needs (column, row) of a line's end point.  The qualifying lines are compacted to the front of
-    // (lcol, linf) -- entry k = (lcol[k], row in linf[k]) -- so every lane of the evaluation below has work.
-    // derive_w1 (the plan also asks for n = 1, whose ridge lines are exactly the maxima of row 0, each of length 1): the
-    // lines of THIS width that end on row 0 are not evaluated here but marked (bit W + 1 of mask[col]); the second list --
-    // all maxima of row 0 -- then yields the n = 1 count and, through the marks, this width's row-0 lines: one noise
-    // percentile per row-0 maximum for both columns of the plan, one argsort, one CWT.
     const unsigned short bit_a = (unsigned short)(1u << (W + 1));
     int cnt_a = 0;
     blk_sync();
@@ -600,6 +575,161 @@ TSFA_DEV double number_cwt_peaks_one(const Blk &b, X xv, int n, int W, const Cwt
         }
         blk_sync();
     }
+    *overflow_out = overflow;
+    return cnt_a;
+}
+
+// The COLUMN linker, W <= 5.  The link distance (row + 1) / 4 is 0 on rows 0 .. 2 and 1 on row 3, so a maximum joins a line
+// of its own column, or -- on row 3 only -- of a neighbouring one; and row 3 links only under a start row 4, when every live
+// line is a maximum of row 4, one link long, born in ascending column order ("the earliest line wins a distance tie" = the
+// smaller column wins).  What a column holds after any row is then a function of the mask alone -- of five neighbouring columns
+// on row 3, of the column itself on every other row -- and a thread walks its columns down the rows without a barrier, a
+// snapshot or a line index.  With Lb(x) / M(x) = column x is a maximum of row 4 / row 3 (neither ever holds two neighbours):
+//   a maximum at c chooses the line at c, else the one at c - 1, else the one at c + 1, else it starts a line;
+//   a line at p is continued by the maxima that chose it -- p itself, or p - 1 and / or p + 1 -- grows by their number and
+//   moves to the largest of them; a line nobody chose stays where it is with a gap of one.
+// After row 3 column c therefore holds
+//   M(c),  Lb(c)                       : the line of c, 2 links
+//   M(c),  Lb(c-1)                     : the line of c - 1, moved here, 2 links (3 if c - 2 chose it too; min_length <= 2
+//                                        is all a length is ever compared with, so the third is not counted)
+//   M(c),  Lb(c+1), neither of those   : the line of c + 1, moved here, 2 links -- unless M(c+2), which takes it further:
+//                                        then c is only counted (by c + 2, the case above) and holds nothing
+//   M(c),  no line within reach        : a new line
+//   !M(c), Lb(c)                       : its line with a gap, unless M(c+1), or M(c-1) without Lb(c-2), carried it off
+// Below row 3 a live line gains a link from a maximum of its column, a maximum without a line starts one, and a line retires
+// on its second gap in a row, keeping its length and end point.  Five rows hold at most one retired and one live line per
+// column (a second retirement needs a sixth row); both are entries if they qualify.
+#define TSFA_CWT_COLUMN_LINKS_MAXW 5
+TSFA_DEV int cwt_link_columns(const Blk &b, int n, int W, int start_row, const CwtPeaksLds &L, const CwtOwnCols &o, int cap,
+                              bool derive_w1, int *overflow_out) {
+    const int min_length = (W + 3) / 4;             // ceil(rows / 4)
+    const unsigned short bit_a = (unsigned short)(1u << (W + 1));
+    cwt_idx_t *live = L.colmap, *done = L.mline;    // per column: the live and the retired line, TSFA_LI_PACK or 0 (none)
+    int mine = 0;
+    if (start_row >= 0) {
+        const bool near3 = (start_row == 4);   // row 3 links across columns
+        const int cb = o.cbeg;
+        // the mask of columns c - 2 .. c + 2, sliding: one read per column; outside the series: no maxima
+        unsigned m2 = (cb >= 2 && cb - 2 < n) ? L.mask[cb - 2] : 0u;
+        unsigned m1 = (cb >= 1 && cb - 1 < n) ? L.mask[cb - 1] : 0u, m0 = (cb < n) ? L.mask[cb] : 0u;
+        unsigned p1 = (cb + 1 < n) ? L.mask[cb + 1] : 0u;
+        for (int c = o.cbeg; c < o.cend; ++c) {
+            const unsigned p2 = (c + 2 < n) ? L.mask[c + 2] : 0u;
+            int v = ((m0 >> start_row) & 1u) ? (int)TSFA_LI_PACK(1, 0, 0, start_row) : 0, r = 0;
+            int row = start_row - 1;
+            if (near3) {
+                const bool Mc = (m0 >> 3) & 1u, Lc = (m0 >> 4) & 1u;
+                if (Mc) {
+                    if (Lc) v = TSFA_LI_PACK(2, 0, 0, 3);
+                    else if ((m1 >> 4) & 1u) v = TSFA_LI_PACK(2, 0, 0, 3);
+                    else if ((p1 >> 4) & 1u) v = ((p2 >> 3) & 1u) ? 0 : (int)TSFA_LI_PACK(2, 0, 0, 3);
+                    else v = TSFA_LI_PACK(1, 0, 0, 3);
+                } else if (Lc) {
+                    const bool gone = ((p1 >> 3) & 1u) || (((m1 >> 3) & 1u) && !((m2 >> 4) & 1u));
+                    v = gone ? 0 : (int)TSFA_LI_PACK(1, 1, 0, 4);
+                }
+                row = 2;
+            }
+            for (; row >= 0; --row) {
+                if ((m0 >> row) & 1u) {
+                    v = TSFA_LI_PACK(v ? TSFA_LI_LEN(v) + 1 : 1, 0, 0, row);
+                } else if (v) {
+                    if (TSFA_LI_GAP(v) >= 1) { r = v; v = 0; }   // the second gap (gap_thresh = ceil(widths[0]) = 1)
+                    else v = TSFA_LI_PACK(TSFA_LI_LEN(v), 1, 0, TSFA_LI_ROW(v));
+                }
+            }
+            if (TSFA_LI_LEN(v) < min_length) v = 0;
+            if (TSFA_LI_LEN(r) < min_length) r = 0;
+            live[c] = (cwt_idx_t)v;
+            done[c] = (cwt_idx_t)r;
+            // (a retired line ends on row 2 or above: only the live one can end on row 0)
+            mine += (r ? 1 : 0) + ((v && !(derive_w1 && TSFA_LI_ROW(v) == 0)) ? 1 : 0);
+            m2 = m1; m1 = m0; m0 = p1; p1 = p2;
+        }
+    }
+    // two entries per column at the most: one more bit than the count of columns
+    int cnt = 0;
+    int idx = blk_excl_sum_small(b, mine, o.ctbits + 1, &cnt);
+    blk_sync();   // every thread has read its neighbours' maxima: the marks may go into the mask
+    if (start_row >= 0) {
+        for (int c = o.cbeg; c < o.cend; ++c) {
+            const int r = done[c], v = live[c];
+            if (r) {
+                if (idx < cap) { L.lcol[idx] = (cwt_idx_t)c; L.linf[idx] = (cwt_idx_t)TSFA_LI_ROW(r); }
+                ++idx;
+            }
+            if (v) {
+                if (derive_w1 && TSFA_LI_ROW(v) == 0) {
+                    L.mask[c] |= bit_a;
+                } else {
+                    if (idx < cap) { L.lcol[idx] = (cwt_idx_t)c; L.linf[idx] = (cwt_idx_t)TSFA_LI_ROW(v); }
+                    ++idx;
+                }
+            }
+        }
+    }
+    blk_sync();
+    *overflow_out = (cnt > cap) ? 1 : 0;
+    return (cnt > cap) ? cap : cnt;
+}
+
+// ST: element type of the padded LDS copy of the series (the input precision: float32 samples stay float32)
+// derive_w1 / kept_w1: also return number_cwt_peaks(n = 1) of the same series (phase C), W <= 14
+template <class ST, class X>
+TSFA_DEV double number_cwt_peaks_one(const Blk &b, X xv, int n, int W, const CwtPeaksLds &L, bool derive_w1 = false,
+                                     double *kept_w1 = nullptr) {
+    const int cap = n;  // line capacity
+    TSFA_TICKER(tk, 0);
+    blk_sync();
+    for (int c = b.tid; c < n; c += b.nt) { L.mask[c] = 0; L.colmap[c] = 0; L.mline[c] = 0; }
+    blk_sync();
+    // ---- phase A: the series goes to LDS between two zero halos (xpad[TSFA_CWTP_HALO + i] = x[i]) when it fits ----
+    if (L.xpad != nullptr) {
+        blk_sync();
+        ST *xpad = (ST *)L.xpad;
+        for (int i = b.tid; i < n + 2 * TSFA_CWTP_HALO + 8; i += b.nt) {
+            const int j = i - TSFA_CWTP_HALO;
+            xpad[i] = (j >= 0 && j < n) ? (ST)xv(j) : (ST)0;
+        }
+        const ST *xp0 = xpad + TSFA_CWTP_HALO;
+        cwt_rows_tiled(b, [=](int i) { return (double)xp0[i]; }, n, W, L);
+    } else {  // no room for the padded copy (very long series): the same tiles, samples straight from HBM / L2
+        cwt_rows_tiled(b, [=](int i) { return (i >= 0 && i < n) ? xv(i) : 0.0; }, n, W, L);
+    }
+    blk_sync();
+    TSFA_TICK(tk, b, 151);
+    // ---- phase B: the ridge lines' end points to the front of (lcol, linf) ----
+    const CwtOwnCols own = cwt_own_columns(b, n);
+    const int ctbits = own.ctbits, cbeg = own.cbeg, cend = own.cend;
+    const int start_row = cwt_start_row(b, W, L, own);
+    // derive_w1 (the plan also asks for n = 1, whose ridge lines are exactly the maxima of row 0, each of length 1): the
+    // lines of THIS width that end on row 0 are not evaluated in the first list but marked (bit W + 1 of mask[col]); the second
+    // list -- all maxima of row 0 -- then yields the n = 1 count and, through the marks, this width's row-0 lines: one noise
+    // percentile per row-0 maximum for both columns of the plan, one argsort, one CWT.
+    const unsigned short bit_a = (unsigned short)(1u << (W + 1));
+    int overflow = 0;
+    const int cnt_a = (L.links != 0 && W <= TSFA_CWT_COLUMN_LINKS_MAXW)
+                          ? cwt_link_columns(b, n, W, start_row, L, own, cap, derive_w1, &overflow)
+                          : cwt_link_general(b, n, W, start_row, L, own, cap, derive_w1, &overflow);
+    TSFA_TICK(tk, b, 152);
+    // ---- phase C ----
+    const int window = (n + 19) / 20;               // ceil(num_points / 20)
+    const int hf = window / 2, odd = window % 2;
+    // cwt[row, col] of a line that ended above row 0 is re-evaluated here; its Ricker taps (exp / pow / sqrt each) are
+    // tabulated once per width instead of once per tap per line:  taps[5 (w-2)(w+1) + k] = reversed tap k of width w
+    const bool taps_cached = (W >= 2) && (10 * W < n) && (5 * (W - 1) * (W + 2) <= TSFA_CWTP_MAXTAPS + 16);
+    if (taps_cached) {
+        blk_sync();
+        for (int w = 2; w <= W; ++w) {
+            const int nw = 10 * w;
+            double *tw = L.taps + 5 * (w - 2) * (w + 1);
+            for (int k = b.tid; k < nw; k += b.nt) tw[k] = ricker_tap_t(L.rk, nw, w, nw - 1 - k);
+        }
+        blk_sync();
+    }
+    // Long series: the noise window holds hundreds of samples and its 10th percentile is no longer among the eight
+    // smallest: every entry is decided by counting its window against thresholds at +-|signal| (cwt_filter_counts).
+    const bool long_windows = ((int)(0.1 * (double)(window - 1)) + 1 >= 8);
     double unused = 0.0;
     double kept;
     const ST *xp0 = (L.xpad != nullptr) ? (const ST *)L.xpad + TSFA_CWTP_HALO : nullptr;

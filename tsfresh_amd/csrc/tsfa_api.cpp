@@ -73,6 +73,7 @@ struct PlanOptions {
     bool row_form = true;         // BASIC / TREND: series of <= 256 samples four to a wavefront (k_basic_rows / k_trend_rows)
     int seq_rows = -1;            // lempel_ziv symbol rows: 0 in LDS, 1 in HBM, -1: in HBM where that puts more series on a CU
     unsigned side_lane = TSFA_SIDE_DEFAULT;   // two lanes (tsfa_plan::side): bit f = family f on the side lane; 0: one lane
+    int cwt_links = 1;            // number_cwt_peaks, widths <= 5: 1 = ridge lines linked column by column; 0 = the general linker it replaced there
     int fail_after = -1;          // test hook: run_batch returns an error after this family's launches (its exits after the fork)
 };
 
@@ -326,6 +327,7 @@ int tsfa_plan_set_option(tsfa_plan *plan, const char *name, double value) {
     else if (n == "seq_rows") o.seq_rows = (value < 0.0) ? -1 : (on ? 1 : 0);
     else if (n == "entropy_route") { if (value != 0.0 && value != 1.0 && value != 2.0) return fail(TSFA_ERR_INVALID, "entropy_route: 0, 1 or 2"); o.entropy_route = (int)value; }
     else if (n == "sort_waves") { if (value != 1.0 && value != 2.0) return fail(TSFA_ERR_INVALID, "sort_waves: 1 or 2"); o.sort_waves = (int)value; }
+    else if (n == "cwt_links") { if (value != 0.0 && value != 1.0) return fail(TSFA_ERR_INVALID, "cwt_links: 0 or 1"); o.cwt_links = (int)value; }
     else if (n == "bluestein_min") o.bluestein_min = value > 0.0 ? (int)std::min(value, 32767.0) : 0;
     else if (n == "gscratch_slots") o.gscratch_slots = value > 0.0 ? (int)std::min(value, 2147483647.0) : 0;
     else if (n == "host_chunks") o.host_chunks = value > 0.0 ? (int)std::min(value, (double)TSFA_MAX_CHUNKS) : 0;
@@ -699,6 +701,7 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                 }
             } else if (f == TSFA_FAM_CWT) {
                 a.cwt_rowv = tsfa_family_lds_bytes(f, maxn, a.nt, 1) <= 96 * 1024 ? 1 : 0;
+                a.cwt_links = plan->opt.cwt_links;
                 aux = a.cwt_rowv;
             } else if (f == TSFA_FAM_AR) {
                 // leading dimension of the normal matrices: ADF needs maxlag(n) + 3, AR(k) needs k + 2

@@ -532,6 +532,7 @@ __global__ void __launch_bounds__(MAXT, (MAXT == 256) ? 6 : 4) k_cwtpeaks(const 
     CwtPeaksLayout L;
     L.carve(tsfa_base, maxn, with_rowv & 1, (int)sizeof(T));
     L.p.rk = consts ? consts + TSFA_CONSTS_RICKER : nullptr;
+    L.p.links = (with_rowv & 2) ? 0 : 1;   // bit 1: the general linker for every width (plan option cwt_links = 0)
     TSFA_TICKS_BEGIN();
     Blk b{(int)threadIdx.x, (int)blockDim.x, L.p.red, nullptr};
     const T *g = values + off;
@@ -1198,12 +1199,13 @@ static int launch_all_t(const TsfaLaunch &a, const T *values) {
     } else if (a.fam == TSFA_FAM_CWT) {  // number_cwt_peaks
         CwtPeaksLayout L;
         const size_t lds = L.carve(nullptr, a.maxn, a.cwt_rowv & 1, (int)sizeof(T));
+        const int with_rowv = (a.cwt_rowv & 1) | (a.cwt_links ? 0 : 2);   // bit 0: the staged series, bit 1: the general linker only
         if (nt <= 256) {
             auto kfn = k_cwtpeaks<T, 256>;
-            TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, a.cwt_rowv, a.consts);
+            TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, with_rowv, a.consts);
         } else {
             auto kfn = k_cwtpeaks<T, 1024>;
-            TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, a.cwt_rowv, a.consts);
+            TSFA_KLAUNCH(kfn, lds, values, a.starts, a.ends, a.n_series, a.sel, a.specs, a.nspecs, a.out, a.ld, a.maxn, with_rowv, a.consts);
         }
     } else {
         return -1;

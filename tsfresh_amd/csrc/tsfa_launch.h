@@ -71,6 +71,7 @@ struct TsfaLaunch {
     int64_t gscratch_slots; // SPECTRAL: slots of gscratch_n doubles in gscratch (one per workgroup of a launch)
     int bluestein_min;      // SPECTRAL: non-power-of-two lengths from here on take the chirp-z transform (with gscratch)
     int cwt_rowv;           // CWT peaks: 1: the series is staged in LDS between zero halos; 0: read from HBM / L2
+    int cwt_links;          // CWT peaks: 1: ridge lines of widths <= 5 linked column by column; 0: the general linker for every width
     int hint_a, hint_b, hint_c, hint_d, hint_e;  // tsfa_prepare_family (BASIC, SORT, SPECTRAL, AR)
     unsigned char *long_scratch;  // HBM scratch of the long-series build (tsfa_launch_family_long) ...
     size_t long_bytes;            // ... and its size: slots of one working set each, one per resident workgroup
