@@ -349,6 +349,22 @@ def test_gpu_impute_statistics_and_patch_at_the_tile_boundaries(gpu, n):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [2049, 4097])
+def test_gpu_impute_in_column_batches(gpu, n):
+    """The batch loop of `tsfa_impute`: the 11 columns in batches of 3 (a last batch of 2), with one LDS tile a column
+    (2049 rows: 4096 padded) and with the merge levels in HBM (4097 rows: 8192 padded); statistics, finite counts and the
+    patched matrix against the same references as the single batch, exactly."""
+    from tsfresh_amd import _native
+    data = _impute_matrix(n, np.random.default_rng([n, 4]))
+    assert data.shape[1] % 3 != 0
+    _native.set_library_option("relevance_batch", 3)
+    try:
+        _check_impute(data)
+    finally:
+        _native.set_library_option("relevance_batch", 0)
+
+
+@pytest.mark.gpu
 def test_gpu_impute_patch_wraps_the_grid_stride(gpu):
     """Gap 5: 3000 x 200 = 600 000 cells, more than the 2048 x 256 = 524 288 threads of `k_imp_apply`."""
     rng = np.random.default_rng(200)

@@ -165,6 +165,31 @@ def test_multiclass_counts_the_tables(gpu, n, classes, n_significant):
     assert res.n_significant.cpu().numpy().tolist() == [int(table.loc[f, "n_significant"]) for f in NAMES]
 
 
+def test_fdr_in_table_batches(gpu):
+    """The batch loop of `tsfa_relevance_fdr`: the three tables of a 3-class target in batches of 2 (a batch of 2 and a batch
+    of 1; the sweep in front of it then runs in column batches of 2 as well) against the oracle's masks and p-values, and
+    against the single batch."""
+    from tsfresh_amd import _native as N
+    n, classes, n_significant = 300, 3, 2
+    masks, distance = _reference_masks(n, classes, False)
+    types, p = _reference(n, classes)
+    assert masks.shape[1] == 3 and distance > 1e-6
+    whole = _device(n, classes, multiclass=True, n_significant=n_significant)
+    N.set_library_option("relevance_batch", 2)
+    try:
+        res = _device(n, classes, multiclass=True, n_significant=n_significant)
+    finally:
+        N.set_library_option("relevance_batch", 0)
+    assert np.array_equal(res.relevant_per_table.cpu().numpy(), masks)
+    assert np.array_equal(res.relevant.cpu().numpy(), masks.sum(axis=1) >= n_significant)
+    assert np.array_equal(res.n_significant.cpu().numpy(), masks.sum(axis=1).astype(np.int32))
+    live, p_min = types != 0, res.p_value.cpu().numpy()
+    assert np.isnan(p_min[~live]).all() and p_min[live] == pytest.approx(p[live].min(axis=1), **P_TOL)
+    assert np.array_equal(p_min[live], res.p_values.cpu().numpy()[live].min(axis=1))
+    for name in ("p_values", "p_value", "relevant_per_table", "relevant", "n_significant"):   # NaN: the constant column
+        assert np.array_equal(getattr(res, name).cpu().numpy(), getattr(whole, name).cpu().numpy(), equal_nan=True), name
+
+
 @pytest.mark.parametrize("n,classes", [(300, 3), (2049, 0), (4097, 2)])
 def test_selected_matrix_is_the_named_columns(gpu, n, classes):
     from tsfresh_amd import select_features, select_features_tensor

@@ -23,8 +23,6 @@
 #include "rel_ks.h"
 #include "tsfa_devmem.h"
 
-static int rel_check_device(int32_t device, const char *who);
-
 #define REL_NT 1024
 #define REL_TILE 4096
 #define REL_MAXC 256
@@ -157,50 +155,65 @@ __global__ void __launch_bounds__(REL_NT) k_rel_stats(const double *__restrict__
     }
 }
 
+// The two-sample Kolmogorov-Smirnov walk of both KS kernels below, by one workgroup over positions 0 .. n - 1 of an
+// ordered sample: hit(p) says whether position p belongs to the first sample, end(p) whether a tie group ends at p.
+// Per-thread chunk counts, their exclusive scan (thread 0, serially), then k1 / n1 - (p + 1 - k1) / n0 at every group
+// end -- searchsorted(side="right") / n, as scipy -- and the min / max reduction (thread 0, serially).  The order of
+// these operations is the result's bits: do not reorder.  Every thread of the workgroup calls it (the leading barrier lets
+// a caller loop over it).  Returns the hit total in *total -- the word it is broadcast through, in LDS or in the column's
+// record -- and, on thread 0, the distance.
+template <class Hit, class End>
+__device__ __forceinline__ double rel_ks_walk(int64_t n, Hit hit, End end, long long *s_cnt, double *s_max, double *s_min,
+                                              int64_t *total) {
+    const int64_t chunk = (n + REL_NT - 1) / REL_NT;
+    const int64_t p0 = (int64_t)threadIdx.x * chunk, p1 = (p0 + chunk < n) ? p0 + chunk : n;
+    long long c = 0;
+    for (int64_t p = p0; p < p1; ++p) c += hit(p) ? 1 : 0;
+    __syncthreads();
+    s_cnt[threadIdx.x] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long acc = 0;
+        for (int t = 0; t < REL_NT; ++t) { const long long v = s_cnt[t]; s_cnt[t] = acc; acc += v; }
+        *total = acc;
+    }
+    __syncthreads();
+    const double n1 = (double)*total, n0 = (double)(n - *total);
+    long long k1 = s_cnt[threadIdx.x];
+    double mx = -__builtin_inf(), mn = __builtin_inf();
+    for (int64_t p = p0; p < p1; ++p) {
+        k1 += hit(p) ? 1 : 0;
+        if (end(p)) {
+            const double d = (double)k1 / n1 - (double)(p + 1 - k1) / n0;
+            mx = fmax(mx, d);
+            mn = fmin(mn, d);
+        }
+    }
+    s_max[threadIdx.x] = mx; s_min[threadIdx.x] = mn;
+    __syncthreads();
+    if (threadIdx.x != 0) return 0.0;
+    for (int t = 1; t < REL_NT; ++t) { mx = fmax(mx, s_max[t]); mn = fmin(mn, s_min[t]); }
+    double mins = -mn;
+    mins = (mins < 0.0) ? 0.0 : ((mins > 1.0) ? 1.0 : mins);
+    return (mins > mx) ? mins : mx;
+}
+
 // 'smir' option (significance_tests.py:121: scipy.stats.ks_2samp(x[y == label], x[y != label])): the Kolmogorov-Smirnov
-// distance of the column split by each class label, walked along the sorted column (prefix counts by a block scan,
-// evaluated where a tie group of the column ends).
+// distance of the column split by each class label, walked along the sorted column (evaluated where a tie group of the
+// column ends).
 __global__ void __launch_bounds__(REL_NT) k_rel_ks_classes(const double *__restrict__ keys, const uint32_t *__restrict__ idx, int64_t np2, int64_t n,
                                                             const int32_t *__restrict__ y, int n_classes, int64_t c0,
                                                             double *__restrict__ ks_d) {
     __shared__ long long s_cnt[REL_NT];
     __shared__ double s_max[REL_NT], s_min[REL_NT];
-    __shared__ long long s_total;
+    __shared__ int64_t s_total;
     const double *K = keys + (int64_t)blockIdx.x * np2;
     const uint32_t *I = idx + (int64_t)blockIdx.x * np2;
-    const int64_t chunk = (n + REL_NT - 1) / REL_NT;
-    const int64_t p0 = (int64_t)threadIdx.x * chunk, p1 = (p0 + chunk < n) ? p0 + chunk : n;
     for (int k = 0; k < n_classes; ++k) {
-        long long c = 0;
-        for (int64_t p = p0; p < p1; ++p) c += (y[I[p]] == k) ? 1 : 0;
-        __syncthreads();
-        s_cnt[threadIdx.x] = c;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            long long acc = 0;
-            for (int t = 0; t < REL_NT; ++t) { const long long v = s_cnt[t]; s_cnt[t] = acc; acc += v; }
-            s_total = acc;
-        }
-        __syncthreads();
-        const double n1 = (double)s_total, n0 = (double)(n - s_total);
-        long long k1 = s_cnt[threadIdx.x];
-        double mx = -__builtin_inf(), mn = __builtin_inf();
-        for (int64_t p = p0; p < p1; ++p) {
-            k1 += (y[I[p]] == k) ? 1 : 0;
-            if (p == n - 1 || K[p + 1] != K[p]) {
-                const double d = (double)k1 / n1 - (double)(p + 1 - k1) / n0;
-                mx = fmax(mx, d);
-                mn = fmin(mn, d);
-            }
-        }
-        s_max[threadIdx.x] = mx; s_min[threadIdx.x] = mn;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int t = 1; t < REL_NT; ++t) { mx = fmax(mx, s_max[t]); mn = fmin(mn, s_min[t]); }
-            double mins = -mn;
-            mins = (mins < 0.0) ? 0.0 : ((mins > 1.0) ? 1.0 : mins);
-            ks_d[(c0 + blockIdx.x) * n_classes + k] = (mins > mx) ? mins : mx;
-        }
+        const double d = rel_ks_walk(
+            n, [&](int64_t p) { return y[I[p]] == k; }, [&](int64_t p) { return p == n - 1 || K[p + 1] != K[p]; }, s_cnt, s_max, s_min,
+            &s_total);
+        if (threadIdx.x == 0) ks_d[(c0 + blockIdx.x) * n_classes + k] = d;
     }
 }
 
@@ -357,79 +370,149 @@ __global__ void __launch_bounds__(REL_NT) k_rel_ks(const double *__restrict__ X,
     if (o.n_unique != 2) return;
     const double vhi = o.v_hi;
     const double *col = X + blockIdx.x;
-    const int64_t chunk = (n + REL_NT - 1) / REL_NT;
-    const int64_t p0 = (int64_t)threadIdx.x * chunk, p1 = (p0 + chunk < n) ? p0 + chunk : n;
-    long long c = 0;
-    for (int64_t p = p0; p < p1; ++p) c += (col[(int64_t)yperm[p] * ld] == vhi) ? 1 : 0;
-    s_cnt[threadIdx.x] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long acc = 0;
-        for (int t = 0; t < REL_NT; ++t) { const long long v = s_cnt[t]; s_cnt[t] = acc; acc += v; }
-        o.n_hi = acc;
-    }
-    __syncthreads();
-    const double n1 = (double)o.n_hi, n0 = (double)(n - o.n_hi);
-    long long k1 = s_cnt[threadIdx.x];
-    double mx = -__builtin_inf(), mn = __builtin_inf();
-    for (int64_t p = p0; p < p1; ++p) {
-        k1 += (col[(int64_t)yperm[p] * ld] == vhi) ? 1 : 0;
-        if (yend[p]) {
-            const double d = (double)k1 / n1 - (double)(p + 1 - k1) / n0;  // searchsorted(side="right") / n, as scipy
-            mx = fmax(mx, d);
-            mn = fmin(mn, d);
-        }
-    }
-    s_max[threadIdx.x] = mx; s_min[threadIdx.x] = mn;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int t = 1; t < REL_NT; ++t) { mx = fmax(mx, s_max[t]); mn = fmin(mn, s_min[t]); }
-        double mins = -mn;
-        mins = (mins < 0.0) ? 0.0 : ((mins > 1.0) ? 1.0 : mins);
-        o.ks_d = (mins > mx) ? mins : mx;
-    }
+    const double d = rel_ks_walk(
+        n, [&](int64_t p) { return col[(int64_t)yperm[p] * ld] == vhi; }, [&](int64_t p) { return yend[p] != 0; }, s_cnt, s_max, s_min,
+        &o.n_hi);
+    if (threadIdx.x == 0) o.ks_d = d;
 }
 
-// columns per batch: bound the sort scratch (12 B per padded row and column) to ~4 GB; tsfa_plan_set_option(NULL,
-// "relevance_batch", n) overrides (tests)
+// ---------------------------------------------------------------------------------------------------------------------
+// What every host driver below starts with: the device check, the staged input matrix, the column sorter.
+// ---------------------------------------------------------------------------------------------------------------------
+#define REL_NO_CPU_PATH " (there is no CPU path)"   // the note of the entry points that compute on the device
+
+static int rel_check_device(int32_t device, const char *who, const char *note = "") {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
+        return tsfa_fail(TSFA_ERR_NO_DEVICE, (std::string(who) + ": no such HIP device" + note).c_str());
+    return TSFA_OK;
+}
+
+// The n_rows x n_cols input matrix as the kernels read it: the caller's pointer and leading dimension (TSFA_DEVICE), or
+// a device copy that this object owns (TSFA_HOST).  A host matrix may be a row-strided VIEW (ld > n_cols) that ends with
+// its last row: only the n_cols-wide rows are the caller's -- the device copy is dense (leading dimension n_cols) and
+// the columns between the rows are never read nor written back.
+struct RelMatrix {
+    const double *X = nullptr;
+    int64_t ld = 0;
+    DevPtr<double> own;
+
+    int stage(const double *Xc, int64_t n_rows, int64_t n_cols, int64_t ldc, int32_t space) {
+        X = Xc;
+        ld = ldc;
+        if (space != TSFA_HOST) return TSFA_OK;
+        HIP_TRY_MALLOC(own, (size_t)n_rows * n_cols * sizeof(double));
+        HIP_TRY(hipMemcpy2D(own.get(), (size_t)n_cols * sizeof(double), Xc, (size_t)ldc * sizeof(double), (size_t)n_cols * sizeof(double),
+                            (size_t)n_rows, hipMemcpyHostToDevice));
+        X = own.get();
+        ld = n_cols;
+        return TSFA_OK;
+    }
+    // the owned copy back into the host matrix it was staged from (tsfa_impute); nothing to do for a device matrix
+    int write_back(double *Xc, int64_t n_rows, int64_t n_cols, int64_t ldc) const {
+        if (!own) return TSFA_OK;
+        HIP_TRY(hipMemcpy2D(Xc, (size_t)ldc * sizeof(double), own.get(), (size_t)n_cols * sizeof(double), (size_t)n_cols * sizeof(double),
+                            (size_t)n_rows, hipMemcpyDeviceToHost));
+        return TSFA_OK;
+    }
+};
+
 int64_t tsfa_relevance_batch_override();
-static int64_t rel_batch_columns(int64_t np2, int64_t n_cols) {
-    int64_t batch = (int64_t)(4.0e9 / (12.0 * (double)np2));
-    if (tsfa_relevance_batch_override() > 0) batch = tsfa_relevance_batch_override();
-    if (batch < 1) batch = 1;
-    if (batch > n_cols) batch = n_cols;
-    return batch;
-}
 
-static int relevance_classes_impl(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                  const int32_t *y_codes, int32_t n_classes, int32_t device, tsfa_relevance_col *cols,
-                                  double *rank_sums, int64_t *hi_counts, double *ks_d);
+// The staged HBM sort of n_columns key columns of n_keys keys each, in batches of columns: the geometry k_rel_sort and the
+// kernels behind it are launched with, and the (key, payload) scratch of one batch.
+struct RelSorter {
+    int64_t np2 = 0, batch = 0;
+    int tile = 0;
+    size_t lds = 0;   // dynamic LDS of k_rel_sort: one tile of keys and payloads
+    DevPtr<double> keys;
+    DevPtr<uint32_t> idx;
 
-extern "C" int tsfa_relevance_classes(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                      const int32_t *y_codes, int32_t n_classes, int32_t device, tsfa_relevance_col *cols,
-                                      double *rank_sums, int64_t *hi_counts) {
-    return relevance_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, device, cols, rank_sums, hi_counts, nullptr);
-}
+    // n_keys < 2^31 (every caller has refused more): the payload is 32 bits wide
+    int init(int64_t n_keys, int64_t n_columns) {
+        // np2: a power of two >= 2048 = 2 * REL_NT, so that k_rel_inversions' seg = np2 / REL_NT is >= 2
+        static_assert(2048 >= 2 * REL_NT && (REL_TILE & (REL_TILE - 1)) == 0 && REL_TILE >= 2048, "sort geometry");
+        np2 = 2048;
+        while (np2 < n_keys) np2 <<= 1;
+        // tile: a power of two that divides np2 (both are powers of two, tile <= np2), as k_rel_sort's phases need
+        tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
+        // columns per batch: bound the scratch (12 B per padded key and column) to ~4 GB; tsfa_plan_set_option(NULL,
+        // "relevance_batch", n) overrides (tests)
+        batch = (int64_t)(4.0e9 / (12.0 * (double)np2));
+        if (tsfa_relevance_batch_override() > 0) batch = tsfa_relevance_batch_override();
+        if (batch < 1) batch = 1;
+        if (batch > n_columns) batch = n_columns;
+        lds = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
+        HIP_TRY_MALLOC(keys, (size_t)batch * np2 * sizeof(double));
+        HIP_TRY_MALLOC(idx, (size_t)batch * np2 * sizeof(uint32_t));
+        HIP_TRY(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        return TSFA_OK;
+    }
 
-extern "C" int tsfa_relevance_classes_ks(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                         const int32_t *y_codes, int32_t n_classes, int32_t device, tsfa_relevance_col *cols,
-                                         double *rank_sums, int64_t *hi_counts, double *ks_d) {
-    if (!ks_d) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_classes_ks: null ks_d");
-    return relevance_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, device, cols, rank_sums, hi_counts, ks_d);
-}
+    // per batch of nb columns from c0 on, on the null stream: stage(c0, nb) fills keys / idx (np2 entries per column),
+    // k_rel_sort orders them, consume(c0, nb) reads the sorted columns.  The staging kernels stay apart on purpose
+    // (k_rel_stage pads the payload with the row, k_rel_stage_real with 0xFFFFFFFF, k_imp_stage also counts the finite
+    // cells): the tie-break of rel_lds_stages depends on those pads.
+    template <class Stage, class Consume>
+    int run(int64_t n_columns, Stage stage, Consume consume) const {
+        for (int64_t c0 = 0; c0 < n_columns; c0 += batch) {
+            const int64_t nb = (n_columns - c0 < batch) ? (n_columns - c0) : batch;
+            stage(c0, nb);
+            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(keys.get(), idx.get(), np2, tile);
+            consume(c0, nb);
+            HIP_TRY(hipGetLastError());
+        }
+        return TSFA_OK;
+    }
+};
 
 // The device side of one statistics sweep: what the sweep allocates, and what it leaves in HBM for the caller -- the
 // host copies of tsfa_relevance_classes*, or the tails kernels of tsfa_relevance_tails_classes.
 struct RelClassesDev {
-    DevPtr<double> dX, dkeys, drs, dks;
-    DevPtr<uint32_t> didx;
+    RelMatrix dX;
+    RelSorter sort;
+    DevPtr<double> drs, dks;
     DevPtr<int32_t> dy;
     DevPtr<int64_t> dhc;
     DevPtr<tsfa_relevance_col> dcols;
 };
 
+// validates, allocates and runs the sweep on the null stream; on return (any status) the caller owns `d`, and what the
+// sweep allocated goes with it.  With TSFA_OK and n_cols > 0 the kernels are queued (not waited for) and d.dcols / d.drs /
+// d.dhc (/ d.dks) will hold the statistics.
 static int rel_classes_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_codes,
-                             int32_t n_classes, int32_t device, bool with_ks, RelClassesDev &d);
+                             int32_t n_classes, int32_t device, bool with_ks, RelClassesDev &d) {
+    if (!X || !y_codes || n_rows < 1 || n_cols < 0 || ld < n_cols)
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_classes: null pointer or bad shape");
+    if (n_classes < 1 || n_classes > REL_MAXC) return tsfa_fail(TSFA_ERR_UNSUPPORTED, "tsfa_relevance_classes: 1 .. 256 classes");
+    if (n_rows >= (1ll << 31)) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_relevance_classes: more than 2^31 rows");
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (y_codes[r] < 0 || y_codes[r] >= n_classes) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_classes: class code out of range");
+    int rc = rel_check_device(device, "tsfa_relevance_classes", REL_NO_CPU_PATH);
+    if (rc || n_cols == 0) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if ((rc = d.dX.stage(X, n_rows, n_cols, ld, space))) return rc;
+    if ((rc = d.sort.init(n_rows, n_cols))) return rc;
+    HIP_TRY_MALLOC(d.dy, (size_t)n_rows * sizeof(int32_t));
+    HIP_TRY_MALLOC(d.drs, (size_t)n_cols * n_classes * sizeof(double));
+    HIP_TRY_MALLOC(d.dhc, (size_t)n_cols * n_classes * sizeof(int64_t));
+    HIP_TRY_MALLOC(d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_col));
+    if (with_ks) HIP_TRY_MALLOC(d.dks, (size_t)n_cols * n_classes * sizeof(double));
+    HIP_TRY(hipMemcpy(d.dy.get(), y_codes, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    const RelSorter &s = d.sort;
+    return s.run(
+        n_cols,
+        [&](int64_t c0, int64_t nb) {
+            k_rel_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dX.X, n_rows, d.dX.ld, c0, s.keys.get(), s.idx.get(), s.np2);
+        },
+        [&](int64_t c0, int64_t nb) {
+            k_rel_stats<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(s.keys.get(), s.idx.get(), s.np2, n_rows, d.dy.get(), n_classes, c0,
+                                                              d.dcols.get(), d.drs.get(), d.dhc.get());
+            if (with_ks)
+                k_rel_ks_classes<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(s.keys.get(), s.idx.get(), s.np2, n_rows, d.dy.get(), n_classes, c0,
+                                                                       d.dks.get());
+        });
+}
 
 static int relevance_classes_impl(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
                                   const int32_t *y_codes, int32_t n_classes, int32_t device, tsfa_relevance_col *cols,
@@ -445,75 +528,64 @@ static int relevance_classes_impl(const double *X, int64_t n_rows, int64_t n_col
     return TSFA_OK;
 }
 
-// validates, allocates and runs the sweep on the null stream; on return (any status) the caller owns `d`, and what the
-// sweep allocated goes with it.  With TSFA_OK and n_cols > 0 the kernels are queued (not waited for) and d.dcols / d.drs /
-// d.dhc (/ d.dks) will hold the statistics.
-static int rel_classes_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_codes,
-                             int32_t n_classes, int32_t device, bool with_ks, RelClassesDev &d) {
-    if (!X || !y_codes || n_rows < 1 || n_cols < 0 || ld < n_cols)
-        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_classes: null pointer or bad shape");
-    if (n_classes < 1 || n_classes > REL_MAXC) return tsfa_fail(TSFA_ERR_UNSUPPORTED, "tsfa_relevance_classes: 1 .. 256 classes");
-    if (n_rows >= (1ll << 31)) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_relevance_classes: more than 2^31 rows");
-    for (int64_t r = 0; r < n_rows; ++r)
-        if (y_codes[r] < 0 || y_codes[r] >= n_classes) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_classes: class code out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
-        return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_relevance_classes: no such HIP device (there is no CPU path)");
-    if (n_cols == 0) return TSFA_OK;
-    int64_t np2 = 2048;
-    while (np2 < n_rows) np2 <<= 1;
-    const int tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
-    int64_t batch = rel_batch_columns(np2, n_cols);
-    const double *Xd = X;
-    int64_t ldd = ld;   // leading dimension of the matrix the kernels work on (a host matrix is staged dense)
-    HIP_TRY(hipSetDevice(device));
-    // a host matrix may be a row-strided VIEW (ld > n_cols) that ends with its last row: only the n_cols-wide rows are
-    // the caller's -- the device copy is dense (leading dimension n_cols) and the columns between the rows are never
-    // read nor written back
-    if (space == TSFA_HOST) {
-        ldd = n_cols;
-        HIP_TRY_MALLOC(d.dX, (size_t)n_rows * n_cols * sizeof(double));
-        HIP_TRY(hipMemcpy2D(d.dX.get(), (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
-                            (size_t)n_rows, hipMemcpyHostToDevice));
-        Xd = d.dX.get();
-    }
-    HIP_TRY_MALLOC(d.dkeys, (size_t)batch * np2 * sizeof(double));
-    HIP_TRY_MALLOC(d.didx, (size_t)batch * np2 * sizeof(uint32_t));
-    HIP_TRY_MALLOC(d.dy, (size_t)n_rows * sizeof(int32_t));
-    HIP_TRY_MALLOC(d.drs, (size_t)n_cols * n_classes * sizeof(double));
-    HIP_TRY_MALLOC(d.dhc, (size_t)n_cols * n_classes * sizeof(int64_t));
-    HIP_TRY_MALLOC(d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_col));
-    if (with_ks) HIP_TRY_MALLOC(d.dks, (size_t)n_cols * n_classes * sizeof(double));
-    HIP_TRY(hipMemcpy(d.dy.get(), y_codes, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
-    {
-        const size_t lds = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
-        HIP_TRY(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        for (int64_t c0 = 0; c0 < n_cols; c0 += batch) {
-            const int64_t nb = (n_cols - c0 < batch) ? (n_cols - c0) : batch;
-            k_rel_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, d.dkeys.get(), d.didx.get(), np2);
-            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(d.dkeys.get(), d.didx.get(), np2, tile);
-            k_rel_stats<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys.get(), d.didx.get(), np2, n_rows, d.dy.get(), n_classes, c0,
-                                                              d.dcols.get(), d.drs.get(), d.dhc.get());
-            if (with_ks)
-                k_rel_ks_classes<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys.get(), d.didx.get(), np2, n_rows, d.dy.get(), n_classes, c0,
-                                                                       d.dks.get());
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return TSFA_OK;
+extern "C" int tsfa_relevance_classes(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                      const int32_t *y_codes, int32_t n_classes, int32_t device, tsfa_relevance_col *cols,
+                                      double *rank_sums, int64_t *hi_counts) {
+    return relevance_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, device, cols, rank_sums, hi_counts, nullptr);
+}
+
+extern "C" int tsfa_relevance_classes_ks(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                         const int32_t *y_codes, int32_t n_classes, int32_t device, tsfa_relevance_col *cols,
+                                         double *rank_sums, int64_t *hi_counts, double *ks_d) {
+    if (!ks_d) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_classes_ks: null ks_d");
+    return relevance_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, device, cols, rank_sums, hi_counts, ks_d);
 }
 
 // The device side of tsfa_relevance_real's sweep, as RelClassesDev
 struct RelRealDev {
-    DevPtr<double> dX, dkeys;
-    DevPtr<uint32_t> didx;
+    RelMatrix dX;
+    RelSorter sort;
     DevPtr<int32_t> dyr, dyp;
     DevPtr<unsigned char> dye;
     DevPtr<tsfa_relevance_real_col> dcols;
 };
 
 static int rel_real_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
-                          const int32_t *y_perm, const unsigned char *y_end, int32_t device, RelRealDev &d);
+                          const int32_t *y_perm, const unsigned char *y_end, int32_t device, RelRealDev &d) {
+    if (!X || !y_rank || !y_perm || !y_end || n_rows < 1 || n_cols < 0 || ld < n_cols)
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_real: null pointer or bad shape");
+    if (n_rows >= (1ll << 31)) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_relevance_real: more than 2^31 rows");
+    int rc = rel_check_device(device, "tsfa_relevance_real", REL_NO_CPU_PATH);
+    if (rc || n_cols == 0) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if ((rc = d.dX.stage(X, n_rows, n_cols, ld, space))) return rc;
+    if ((rc = d.sort.init(n_rows, n_cols))) return rc;
+    HIP_TRY_MALLOC(d.dyr, (size_t)n_rows * sizeof(int32_t));
+    HIP_TRY_MALLOC(d.dyp, (size_t)n_rows * sizeof(int32_t));
+    HIP_TRY_MALLOC(d.dye, (size_t)n_rows);
+    HIP_TRY_MALLOC(d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_real_col));
+    HIP_TRY(hipMemcpy(d.dyr.get(), y_rank, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.dyp.get(), y_perm, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.dye.get(), y_end, (size_t)n_rows, hipMemcpyHostToDevice));
+    const RelSorter &s = d.sort;
+    const size_t lds_inv = (size_t)s.tile * 2 * sizeof(uint32_t);
+    HIP_TRY(hipFuncSetAttribute((const void *)k_rel_inversions, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
+    rc = s.run(
+        n_cols,
+        [&](int64_t c0, int64_t nb) {
+            k_rel_stage_real<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dX.X, n_rows, d.dX.ld, c0, d.dyr.get(), s.keys.get(), s.idx.get(), s.np2);
+        },
+        [&](int64_t c0, int64_t nb) {
+            k_rel_xties<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(s.keys.get(), s.idx.get(), s.np2, n_rows, c0, d.dcols.get());
+            // the sorted values are dead now: their storage is the second buffer of the merge sort (np2 words per column
+            // out of the np2 doubles)
+            k_rel_inversions<<<dim3((unsigned)nb), REL_NT, lds_inv, 0>>>(s.idx.get(), (uint32_t *)s.keys.get(), s.np2, s.tile, c0, d.dcols.get());
+        });
+    if (rc) return rc;
+    k_rel_ks<<<dim3((unsigned)n_cols), REL_NT, 0, 0>>>(d.dX.X, n_rows, d.dX.ld, d.dyp.get(), d.dye.get(), d.dcols.get());
+    HIP_TRY(hipGetLastError());
+    return TSFA_OK;
+}
 
 extern "C" int tsfa_relevance_real(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
                                    const int32_t *y_rank, const int32_t *y_perm, const unsigned char *y_end, int32_t device,
@@ -523,62 +595,6 @@ extern "C" int tsfa_relevance_real(const double *X, int64_t n_rows, int64_t n_co
     int rc = rel_real_sweep(X, n_rows, n_cols, ld, space, y_rank, y_perm, y_end, device, d);
     if (rc != TSFA_OK || n_cols == 0) return rc;
     HIP_TRY(hipMemcpy(cols, d.dcols.get(), (size_t)n_cols * sizeof(tsfa_relevance_real_col), hipMemcpyDeviceToHost));
-    return TSFA_OK;
-}
-
-static int rel_real_sweep(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
-                          const int32_t *y_perm, const unsigned char *y_end, int32_t device, RelRealDev &d) {
-    if (!X || !y_rank || !y_perm || !y_end || n_rows < 1 || n_cols < 0 || ld < n_cols)
-        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_real: null pointer or bad shape");
-    if (n_rows >= (1ll << 31)) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_relevance_real: more than 2^31 rows");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
-        return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_relevance_real: no such HIP device (there is no CPU path)");
-    if (n_cols == 0) return TSFA_OK;
-    int64_t np2 = 2048;
-    while (np2 < n_rows) np2 <<= 1;
-    const int tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
-    int64_t batch = rel_batch_columns(np2, n_cols);
-    const double *Xd = X;
-    int64_t ldd = ld;   // leading dimension of the matrix the kernels work on (a host matrix is staged dense)
-    HIP_TRY(hipSetDevice(device));
-    // a host matrix may be a row-strided VIEW (ld > n_cols) that ends with its last row: only the n_cols-wide rows are
-    // the caller's -- the device copy is dense (leading dimension n_cols) and the columns between the rows are never
-    // read nor written back
-    if (space == TSFA_HOST) {
-        ldd = n_cols;
-        HIP_TRY_MALLOC(d.dX, (size_t)n_rows * n_cols * sizeof(double));
-        HIP_TRY(hipMemcpy2D(d.dX.get(), (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
-                            (size_t)n_rows, hipMemcpyHostToDevice));
-        Xd = d.dX.get();
-    }
-    HIP_TRY_MALLOC(d.dkeys, (size_t)batch * np2 * sizeof(double));
-    HIP_TRY_MALLOC(d.didx, (size_t)batch * np2 * sizeof(uint32_t));
-    HIP_TRY_MALLOC(d.dyr, (size_t)n_rows * sizeof(int32_t));
-    HIP_TRY_MALLOC(d.dyp, (size_t)n_rows * sizeof(int32_t));
-    HIP_TRY_MALLOC(d.dye, (size_t)n_rows);
-    HIP_TRY_MALLOC(d.dcols, (size_t)n_cols * sizeof(tsfa_relevance_real_col));
-    HIP_TRY(hipMemcpy(d.dyr.get(), y_rank, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.dyp.get(), y_perm, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.dye.get(), y_end, (size_t)n_rows, hipMemcpyHostToDevice));
-    {
-        const size_t lds_sort = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
-        const size_t lds_inv = (size_t)tile * 2 * sizeof(uint32_t);
-        HIP_TRY(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort));
-        HIP_TRY(hipFuncSetAttribute((const void *)k_rel_inversions, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_inv));
-        for (int64_t c0 = 0; c0 < n_cols; c0 += batch) {
-            const int64_t nb = (n_cols - c0 < batch) ? (n_cols - c0) : batch;
-            k_rel_stage_real<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, d.dyr.get(), d.dkeys.get(), d.didx.get(), np2);
-            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds_sort, 0>>>(d.dkeys.get(), d.didx.get(), np2, tile);
-            k_rel_xties<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(d.dkeys.get(), d.didx.get(), np2, n_rows, c0, d.dcols.get());
-            // the sorted values are dead now: their storage is the second buffer of the merge sort (np2 words per column
-            // out of the np2 doubles)
-            k_rel_inversions<<<dim3((unsigned)nb), REL_NT, lds_inv, 0>>>(d.didx.get(), (uint32_t *)d.dkeys.get(), np2, tile, c0, d.dcols.get());
-            HIP_TRY(hipGetLastError());
-        }
-        k_rel_ks<<<dim3((unsigned)n_cols), REL_NT, 0, 0>>>(Xd, n_rows, ldd, d.dyp.get(), d.dye.get(), d.dcols.get());
-        HIP_TRY(hipGetLastError());
-    }
     return TSFA_OK;
 }
 
@@ -890,35 +906,28 @@ extern "C" int tsfa_relevance_fdr(const double *p, const unsigned char *type, in
     if (n_cols >= (1ll << 31)) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_relevance_fdr: more than 2^31 columns");
     int rc = rel_check_device(device, "tsfa_relevance_fdr");
     if (rc || n_cols == 0) return rc;
-    int64_t np2 = 2048;
-    while (np2 < n_cols) np2 <<= 1;
-    const int tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
-    const int64_t batch = rel_batch_columns(np2, n_tables);
     const int64_t cells = n_cols * n_tables;
     HIP_TRY(hipSetDevice(device));
-    DevPtr<double> dmask, dkeys;
-    DevPtr<uint32_t> didx;
+    DevPtr<double> dmask;
+    RelSorter s;
     HIP_TRY_MALLOC(dmask, (size_t)cells * sizeof(double));
-    HIP_TRY_MALLOC(dkeys, (size_t)batch * np2 * sizeof(double));
-    HIP_TRY_MALLOC(didx, (size_t)batch * np2 * sizeof(uint32_t));
-    {
-        const size_t lds = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
-        HIP_TRY(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_fdr_keys<<<dim3((unsigned)((cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(p, type, n_cols, n_tables, dmask.get());
-        HIP_TRY(hipGetLastError());
-        for (int64_t t0 = 0; t0 < n_tables; t0 += batch) {
-            const int64_t nb = (n_tables - t0 < batch) ? (n_tables - t0) : batch;
-            // the key matrix is [n_cols, n_tables]: a table is a column of it, its rows are the feature columns
-            k_rel_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dmask.get(), n_cols, n_tables, t0, dkeys.get(), didx.get(), np2);
-            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(dkeys.get(), didx.get(), np2, tile);
-            k_fdr_stepup<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dkeys.get(), didx.get(), np2, type, n_cols, n_tables, (int)t0, alpha, c_m,
+    if ((rc = s.init(n_cols, n_tables))) return rc;
+    k_fdr_keys<<<dim3((unsigned)((cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(p, type, n_cols, n_tables, dmask.get());
+    HIP_TRY(hipGetLastError());
+    // the key matrix is [n_cols, n_tables]: a table is a column of it, its rows are the feature columns
+    rc = s.run(
+        n_tables,
+        [&](int64_t t0, int64_t nb) {
+            k_rel_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(dmask.get(), n_cols, n_tables, t0, s.keys.get(), s.idx.get(), s.np2);
+        },
+        [&](int64_t t0, int64_t nb) {
+            k_fdr_stepup<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(s.keys.get(), s.idx.get(), s.np2, type, n_cols, n_tables, (int)t0, alpha, c_m,
                                                               relevant_per_table);
-            HIP_TRY(hipGetLastError());
-        }
-        k_fdr_combine<<<dim3((unsigned)((n_cols + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(
-            p, relevant_per_table, type, n_cols, n_tables, multiclass, n_significant, relevant, n_significant_out, p_min);
-        HIP_TRY(hipGetLastError());
-    }
+        });
+    if (rc) return rc;
+    k_fdr_combine<<<dim3((unsigned)((n_cols + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(
+        p, relevant_per_table, type, n_cols, n_tables, multiclass, n_significant, relevant, n_significant_out, p_min);
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return TSFA_OK;
 }
@@ -1056,55 +1065,35 @@ extern "C" int tsfa_impute(double *X, int64_t n_rows, int64_t n_cols, int64_t ld
                            double *col_max, double *col_min, double *col_median, int32_t *finite_count) {
     if (!X || n_rows < 0 || n_cols < 0 || ld < n_cols) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_impute: null pointer or bad shape");
     if (n_rows >= (1ll << 31)) return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_impute: more than 2^31 rows");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
-        return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_impute: no such HIP device (there is no CPU path)");
-    if (n_cols == 0 || n_rows == 0) return TSFA_OK;
-    int64_t np2 = 2048;
-    while (np2 < n_rows) np2 <<= 1;
-    const int tile = (int)((np2 < REL_TILE) ? np2 : REL_TILE);
-    const int64_t batch = rel_batch_columns(np2, n_cols);
-    DevPtr<double> dX, dkeys, dstat;
-    DevPtr<uint32_t> didx;
+    int rc = rel_check_device(device, "tsfa_impute", REL_NO_CPU_PATH);
+    if (rc || n_cols == 0 || n_rows == 0) return rc;
+    RelMatrix m;
+    RelSorter s;
+    DevPtr<double> dstat;
     DevPtr<int> dcnt;
-    double *Xd = X;
-    int64_t ldd = ld;   // leading dimension of the matrix the kernels work on
     HIP_TRY(hipSetDevice(device));
-    // a host matrix may be a row-strided VIEW (ld > n_cols) that ends with its last row: only the n_cols-wide rows are
-    // the caller's -- the device copy is dense (leading dimension n_cols) and the columns between the rows are never
-    // read nor written back
-    if (space == TSFA_HOST) {
-        ldd = n_cols;
-        HIP_TRY_MALLOC(dX, (size_t)n_rows * n_cols * sizeof(double));
-        HIP_TRY(hipMemcpy2D(dX.get(), (size_t)n_cols * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)n_cols * sizeof(double),
-                            (size_t)n_rows, hipMemcpyHostToDevice));
-        Xd = dX.get();
-    }
-    HIP_TRY_MALLOC(dkeys, (size_t)batch * np2 * sizeof(double));
-    HIP_TRY_MALLOC(didx, (size_t)batch * np2 * sizeof(uint32_t));
+    if ((rc = m.stage(X, n_rows, n_cols, ld, space))) return rc;
+    if ((rc = s.init(n_rows, n_cols))) return rc;
     HIP_TRY_MALLOC(dcnt, (size_t)n_cols * sizeof(int));
     HIP_TRY_MALLOC(dstat, (size_t)3 * n_cols * sizeof(double));
-    {
-        const size_t lds = (size_t)tile * (sizeof(double) + sizeof(uint32_t));
-        HIP_TRY(hipFuncSetAttribute((const void *)k_rel_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        for (int64_t c0 = 0; c0 < n_cols; c0 += batch) {
-            const int64_t nb = (n_cols - c0 < batch) ? (n_cols - c0) : batch;
-            k_imp_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(Xd, n_rows, ldd, c0, dkeys.get(), didx.get(), np2, dcnt.get());
-            k_rel_sort<<<dim3((unsigned)nb), REL_NT, lds, 0>>>(dkeys.get(), didx.get(), np2, tile);
-            k_imp_stats<<<dim3((unsigned)((nb + 63) / 64)), 64, 0, 0>>>(dkeys.get(), np2, dcnt.get(), c0, nb, dstat.get(), dstat.get() + n_cols,
-                                                                        dstat.get() + 2 * n_cols);
-            HIP_TRY(hipGetLastError());
-        }
-        k_imp_apply<<<2048, 256, 0, 0>>>(Xd, n_rows, ldd, n_cols, dstat.get(), dstat.get() + n_cols, dstat.get() + 2 * n_cols);
-        HIP_TRY(hipGetLastError());
-    }
-    if (col_max) HIP_TRY(hipMemcpy(col_max, dstat.get(), (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
-    if (col_min) HIP_TRY(hipMemcpy(col_min, dstat.get() + n_cols, (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
-    if (col_median) HIP_TRY(hipMemcpy(col_median, dstat.get() + 2 * n_cols, (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
+    double *cmax = dstat.get(), *cmin = cmax + n_cols, *cmed = cmin + n_cols;
+    rc = s.run(
+        n_cols,
+        [&](int64_t c0, int64_t nb) {
+            k_imp_stage<<<dim3((unsigned)nb), REL_NT, 0, 0>>>(m.X, n_rows, m.ld, c0, s.keys.get(), s.idx.get(), s.np2, dcnt.get());
+        },
+        [&](int64_t c0, int64_t nb) {
+            k_imp_stats<<<dim3((unsigned)((nb + 63) / 64)), 64, 0, 0>>>(s.keys.get(), s.np2, dcnt.get(), c0, nb, cmax, cmin, cmed);
+        });
+    if (rc) return rc;
+    // the matrix that is patched: the staged copy of a host matrix (written back below), or the caller's device matrix
+    k_imp_apply<<<2048, 256, 0, 0>>>(m.own ? m.own.get() : X, n_rows, m.ld, n_cols, cmax, cmin, cmed);
+    HIP_TRY(hipGetLastError());
+    if (col_max) HIP_TRY(hipMemcpy(col_max, cmax, (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
+    if (col_min) HIP_TRY(hipMemcpy(col_min, cmin, (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
+    if (col_median) HIP_TRY(hipMemcpy(col_median, cmed, (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost));
     if (finite_count) HIP_TRY(hipMemcpy(finite_count, dcnt.get(), (size_t)n_cols * sizeof(int), hipMemcpyDeviceToHost));
-    if (space == TSFA_HOST)
-        HIP_TRY(hipMemcpy2D(X, (size_t)ld * sizeof(double), dX.get(), (size_t)n_cols * sizeof(double), (size_t)n_cols * sizeof(double),
-                            (size_t)n_rows, hipMemcpyDeviceToHost));
+    if ((rc = m.write_back(X, n_rows, n_cols, ld))) return rc;
     HIP_TRY(hipDeviceSynchronize());
     return TSFA_OK;
 }
@@ -1131,13 +1120,6 @@ __global__ void __launch_bounds__(256) k_scatter_columns(double *__restrict__ ds
         const int64_t r = i / n_src, c = i - r * n_src;
         dst[r * ld_dst + cols[c]] = src[i];
     }
-}
-
-static int rel_check_device(int32_t device, const char *who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
-        return tsfa_fail(TSFA_ERR_NO_DEVICE, (std::string(who) + ": no such HIP device").c_str());
-    return TSFA_OK;
 }
 
 extern "C" int tsfa_device_alloc(void **ptr, size_t bytes, int32_t device) {
