@@ -1,14 +1,15 @@
 // TEST INFRASTRUCTURE ONLY: the pack set's kernel bodies (tsfresh_amd/csrc/pack_device.h) compiled by g++ -DTSFA_EMUL and driven
-// tile by tile with ONE thread per workgroup, in the order tsfa_pack_set_create / tsfa_pack_set_values launch them on the GPU.
-// The product never loads this; it lets tests/test_pack_set_emul.py compare the set with data._pack's host route, kind by
-// kind, on a box without a GPU.  The host steps between the launches (pass planning) are the shared pk_plan_passes and
-// pk_plan_kind_passes of the header.
+// tile by tile with ONE thread per workgroup.  The product never loads this; it lets tests/test_pack_set_emul.py compare the
+// set with data._pack's host route, kind by kind, on a box without a GPU.  Steps 1-3 (the sort, kind digits included) are
+// EmulPkSorter of emul_pack_sort.h, the one emulated twin of the device's PkSorter; this file adds the set's own step 4 on and
+// tsfa_pack_set_values.  That the order is the GPU's is held by that one header and by the GPU tests that compare device and
+// emulation case by case.
 #include <stdint.h>
 #include <string.h>
 
 #include <vector>
 
-#include "../../tsfresh_amd/csrc/pack_device.h"
+#include "emul_pack_sort.h"
 
 struct EmulPackSet {
     int64_t n = 0, n_groups = 0, n_kinds = 0;
@@ -26,84 +27,43 @@ extern "C" EmulPackSet *tsfa_emul_pack_set_create(const void *ids, int32_t id_ty
     if (!ids || n < 1 || n > 0xffffffffll || !pk_is_key_type(id_type, false)) return nullptr;
     if (sort && !pk_is_key_type(sort_type, true)) return nullptr;
     if (kinds && !pk_is_key_type(kind_type, false)) return nullptr;
-    const PkBlk b{0, 1};
-    const int64_t n_tiles = (n + PK_TILE - 1) / PK_TILE;
     const int id_size = pk_itemsize(id_type), sort_size = sort ? pk_itemsize(sort_type) : 0, kind_size = kinds ? pk_itemsize(kind_type) : 0;
-    PkStats st;
-    PkSetStats ks;
-    pk_stats_init(&st);
-    pk_set_stats_init(&ks);
-    pk_u64 red[5];
-    std::vector<unsigned int> lds(16 * PK_RADIX);
+    EmulPkSorter s;
+    s.run(ids, id_type, sort, sort_type, kinds, kind_type, n);
+    const PkBlk b = s.b;
+    const int64_t n_tiles = s.n_tiles;
+    const pk_u64 *hi = s.hi[s.cur].data();
+    const uint32_t *idx = s.idx[s.cur].data();
+    unsigned int *lds = s.lds.data();
     EmulPackSet *set = new EmulPackSet();
     set->n = n; set->id_type = id_type; set->sort_type = sort ? sort_type : 0; set->kind_type = kinds ? kind_type : 0;
+    set->flags = s.in_order ? TSFA_PACK_IN_ORDER : 0;
+    set->n_passes = s.n_passes;
 
-    pk_minmax_body(b, 0, 1, ids, id_type, sort, sort_type, n, red, &st);
-    if (kinds) pk_kind_minmax_body(b, 0, 1, kinds, kind_type, ids, id_type, sort, sort_type, n, red, &ks);
-    const bool inner_in_order = st.descents == 0;
-    const bool in_order = kinds ? ks.descents == 0 : inner_in_order;
-    if (in_order) set->flags |= TSFA_PACK_IN_ORDER;
-    std::vector<pk_u64> hi[2], lo[2];
-    std::vector<uint32_t> idx[2];
-    for (int k = 0; k < (in_order ? 1 : 2); ++k) {
-        hi[k].resize((size_t)n); lo[k].resize((size_t)n); idx[k].resize((size_t)n);
-    }
-    std::vector<uint32_t> counts((size_t)n_tiles * PK_RADIX);
-    const int inner_passes = (in_order || inner_in_order) ? 0 : 1;
-    pk_keys_body(b, 0, 1, ids, id_type, sort, sort_type, n, st.kmin[0], sort ? st.kmin[1] : 0ull, pk_sig_bytes(st.kmax[0] - st.kmin[0]),
-                 sort ? pk_sig_bytes(st.kmax[1] - st.kmin[1]) : 0, inner_passes, hi[0].data(), lo[0].data(), idx[0].data(),
-                 lds.data(), &st);
-    if (kinds && !in_order) pk_kind_hist_body(b, 0, 1, kinds, kind_type, n, ks.kmin, pk_sig_bytes(ks.kmax - ks.kmin), lds.data(), &ks);
-    int cur = 0;
-    if (!in_order) {
-        int pass_word[16], pass_byte[16], kind_byte[8];
-        const int np = inner_passes ? pk_plan_passes(&st, n, sort != nullptr, pass_word, pass_byte) : 0;
-        for (int p = 0; p < np; ++p) {
-            const pk_u64 *key = pass_word[p] ? lo[cur].data() : hi[cur].data();
-            const int shift = 8 * pass_byte[p];
-            for (int64_t t = 0; t < n_tiles; ++t) pk_hist_body(b, t, n_tiles, key, shift, n, lds.data(), counts.data());
-            pk_scan_body(b, counts.data(), (size_t)n_tiles * PK_RADIX, lds.data(), nullptr);
-            for (int64_t t = 0; t < n_tiles; ++t)
-                pk_scatter_body(b, t, n_tiles, key, shift, n, counts.data(), hi[cur].data(), lo[cur].data(), idx[cur].data(),
-                                hi[cur ^ 1].data(), lo[cur ^ 1].data(), idx[cur ^ 1].data(), lds.data());
-            cur ^= 1;
-        }
-        const int nkp = kinds ? pk_plan_kind_passes(&ks, n, kind_byte) : 0;
-        for (int p = 0; p < nkp; ++p) {
-            const PkKindDigit dg{kinds, kind_type, ks.kmin, idx[cur].data(), 8 * kind_byte[p]};
-            for (int64_t t = 0; t < n_tiles; ++t) pk_hist_impl(b, t, n_tiles, dg, n, lds.data(), counts.data());
-            pk_scan_body(b, counts.data(), (size_t)n_tiles * PK_RADIX, lds.data(), nullptr);
-            for (int64_t t = 0; t < n_tiles; ++t)
-                pk_scatter_impl(b, t, n_tiles, dg, n, counts.data(), hi[cur].data(), lo[cur].data(), idx[cur].data(),
-                                hi[cur ^ 1].data(), lo[cur ^ 1].data(), idx[cur ^ 1].data(), lds.data());
-            cur ^= 1;
-        }
-        set->n_passes = np + nkp;
-    }
-    uint32_t *heads = counts.data(), *kheads = counts.data() + n_tiles;
+    uint32_t *heads = s.counts.data(), *kheads = s.counts.data() + n_tiles;
     for (int64_t t = 0; t < n_tiles; ++t)
-        pk_set_heads_count_body(b, t, hi[cur].data(), idx[cur].data(), kinds, kind_type, n, lds.data(), heads, kheads);
-    pk_scan_body(b, heads, (size_t)n_tiles, lds.data(), &st.n_groups);
-    pk_scan_body(b, kheads, (size_t)n_tiles, lds.data(), &ks.n_kinds);
-    const int64_t ng = set->n_groups = (int64_t)st.n_groups, nk = set->n_kinds = (int64_t)ks.n_kinds;
+        pk_set_heads_count_body(b, t, hi, idx, kinds, kind_type, n, lds, heads, kheads);
+    pk_scan_body(b, heads, (size_t)n_tiles, lds, &s.st.n_groups);
+    pk_scan_body(b, kheads, (size_t)n_tiles, lds, &s.ks.n_kinds);
+    const int64_t ng = set->n_groups = (int64_t)s.st.n_groups, nk = set->n_kinds = (int64_t)s.ks.n_kinds;
     set->offsets.resize((size_t)ng + 1);
     set->uniq.resize((size_t)ng * id_size);
     set->kind_rows.resize((size_t)nk + 1);
     set->kind_groups.resize((size_t)nk + 1);
     set->kind_vals.resize((size_t)nk * kind_size + 1);
     for (int64_t t = 0; t < n_tiles; ++t)
-        pk_set_groups_body(b, t, hi[cur].data(), idx[cur].data(), kinds, kind_type, n, heads, kheads, ng, nk, ids, id_size,
+        pk_set_groups_body(b, t, hi, idx, kinds, kind_type, n, heads, kheads, ng, nk, ids, id_size,
                            set->offsets.data(), set->uniq.data(), set->kind_rows.data(), set->kind_groups.data(),
-                           set->kind_vals.data(), lds.data());
+                           set->kind_vals.data(), lds);
     if (nk > 1) {
         set->rebased.resize((size_t)(ng + nk));
         pk_rebase_body(b, 0, 1, set->offsets.data(), set->kind_rows.data(), set->kind_groups.data(), nk, ng + nk, set->rebased.data());
     }
     if (keep_sort && sort) {
         set->sort.resize((size_t)n * sort_size);
-        pk_gather_raw_body(b, 0, 1, sort, sort_size, idx[cur].data(), n, set->sort.data());
+        pk_gather_raw_body(b, 0, 1, sort, sort_size, idx, n, set->sort.data());
     }
-    set->perm.swap(idx[cur]);
+    set->perm.swap(s.idx[s.cur]);
     return set;
 }
 

@@ -17,8 +17,10 @@ LIBS = ("emul_lib", "emul_pack_lib", "emul_pack_set_lib", "emul_pack_rows_lib", 
 
 
 def build(src, lib):
-    """Compile `src` into the shared library `lib` unless `lib` is newer than `src`, the C header and every kernel header."""
-    deps = [src, os.path.join(ROOT, "include", "tsfresh_amd.h")] + glob.glob(os.path.join(ROOT, "tsfresh_amd", "csrc", "*.h"))
+    """Compile `src` into the shared library `lib` unless `lib` is newer than `src`, the C header, every kernel header and
+    every header the drivers share (tests/emul/*.h)."""
+    deps = [src, os.path.join(ROOT, "include", "tsfresh_amd.h")] + glob.glob(os.path.join(ROOT, "tsfresh_amd", "csrc", "*.h")) \
+        + glob.glob(os.path.join(HERE, "emul", "*.h"))
     if os.path.exists(lib) and all(os.path.getmtime(d) <= os.path.getmtime(lib) for d in deps):
         return
     tmp = "%s.%d.tmp" % (lib, os.getpid())  # atomic: several processes (the gloo test's ranks) may build at once

@@ -1,5 +1,7 @@
-// Ownership of device memory in the host layer (tsfa_api.cpp, tsfa_pack_device.hip, tsfa_relevance.hip), and the one
-// family of error macros these files check their HIP calls with.  Host-only; needs nothing but the HIP runtime.
+// Ownership of device memory in the host layer (tsfa_api.cpp, tsfa_relevance.hip, tsfa_pack_device.hip and the three small
+// packers tsfa_pack_dense.hip, tsfa_pack_valid.hip, tsfa_pack_times.hip), the one family of error macros these files check
+// their HIP calls with, and the one device check of their entry points (tsfa_check_device).  Host-only; needs nothing but
+// the HIP runtime.
 //
 // Whoever allocates device memory holds it in a DevPtr or a DevBuf, as a local variable or as a member of an object on the
 // heap, and the destructor frees it: a function returns from wherever it fails, and a new member of a plan, a pack or a
@@ -87,8 +89,21 @@ inline int tsfa_fail_hip(const char *who, const std::string &what, hipError_t e)
     return tsfa_fail(TSFA_ERR_HIP, ((*who ? std::string(who) + ": " : std::string()) + what + ": " + hipGetErrorString(e)).c_str());
 }
 
+// "<who>: no HIP device visible: tsfresh_amd has no CPU fallback" on a box without a device, "<who>: no such HIP device" for
+// an ordinal it does not have.  With a note (tsfa_relevance.hip; it may be empty) both cases read
+// "<who>: no such HIP device<note>".
+inline int tsfa_check_device(const char *who, int32_t device, const char *note = nullptr) {
+    int ndev = 0;
+    const bool none = hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1;
+    if (none && !note) return tsfa_fail(TSFA_ERR_NO_DEVICE, (std::string(who) + ": no HIP device visible: tsfresh_amd has no CPU fallback").c_str());
+    if (none || device < 0 || device >= ndev)
+        return tsfa_fail(TSFA_ERR_NO_DEVICE, (std::string(who) + ": no such HIP device" + (note ? note : "")).c_str());
+    return TSFA_OK;
+}
+
 // The function the messages name: a string literal, redefined in front of each entry point that wants its name in them
-// (tsfa_pack_device.hip); empty elsewhere.
+// (the packer files), or `who` in front of helpers that several entry points share and that take the name as an argument
+// or hold it as a member (tsfa_pack_device.hip); empty elsewhere.
 #ifndef TSFA_WHO
 #define TSFA_WHO ""
 #endif

@@ -5,8 +5,10 @@
 #include <string>
 
 #include "pack_dense.h"
+#include "tsfa_devmem.h"
 
-int tsfa_fail(int code, const char *msg);
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_pack_dense"
 
 namespace {
 
@@ -44,26 +46,14 @@ void pd_launch(int route, const PdArgs &a, unsigned grid, hipStream_t st) {
     else k_dense_rows<TYPE, false><<<grid, PD_THREADS, 0, st>>>(a);
 }
 
-int pd_fail_hip(const char *what, hipError_t e) {
-    return tsfa_fail(TSFA_ERR_HIP, (std::string("tsfa_pack_dense: ") + what + ": " + hipGetErrorString(e)).c_str());
-}
-
-#define PD_HIP(expr)                                       \
-    do {                                                   \
-        hipError_t e_ = (expr);                            \
-        if (e_ != hipSuccess) return pd_fail_hip(#expr, e_); \
-    } while (0)
-
 }  // namespace
 
 extern "C" int tsfa_pack_dense(const void *x, int32_t x_type, int64_t n_batch, int64_t n_channels, int64_t n_time,
                                int64_t stride_batch, int64_t stride_channel, int64_t stride_time, const void *lengths,
                                int32_t lengths_type, void *values_out, int64_t channel_stride_out, int64_t *offsets_out,
                                int32_t *flags_out, int32_t device, void *stream) {
-    int ndev = 0;  // before the arguments are looked at: without a device no device pointer can exist
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_pack_dense: no HIP device visible: tsfresh_amd has no CPU fallback");
-    if (device < 0 || device >= ndev) return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_pack_dense: no such HIP device");
+    // before the arguments are looked at: without a device no device pointer can exist
+    if (int rc = tsfa_check_device(TSFA_WHO, device)) return rc;
     const char *why;
     if (int rc = pd_check(x, x_type, n_batch, n_channels, n_time, stride_batch, stride_channel, stride_time, lengths, lengths_type,
                           values_out, channel_stride_out, offsets_out, flags_out, &why))
@@ -79,21 +69,21 @@ extern "C" int tsfa_pack_dense(const void *x, int32_t x_type, int64_t n_batch, i
     const unsigned grid = (unsigned)(a.n_work < PD_MAX_GRID ? a.n_work : PD_MAX_GRID);
     hipStream_t st = (hipStream_t)stream;   // NULL: the null stream
 
-    PD_HIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     if (lengths) {
         k_dense_scan<<<1, PD_SCAN_THREADS, 0, st>>>(lengths, lengths_type, n_batch, n_time, offsets_out, (unsigned int *)flags_out);
     } else {
         const int64_t blocks = (n_batch + 1 + PD_GRID_THREADS - 1) / PD_GRID_THREADS;
         k_dense_offsets<<<(unsigned)(blocks > 2048 ? 2048 : blocks), PD_GRID_THREADS, 0, st>>>(n_batch, n_time, offsets_out);
     }
-    PD_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     switch (x_type) {
     case TSFA_F64: pd_launch<TSFA_F64>(route, a, grid, st); break;
     case TSFA_F32: pd_launch<TSFA_F32>(route, a, grid, st); break;
     case TSFA_F16: pd_launch<TSFA_F16>(route, a, grid, st); break;
     default: pd_launch<TSFA_BF16>(route, a, grid, st); break;
     }
-    PD_HIP(hipGetLastError());
-    if (!stream) PD_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    if (!stream) HIP_TRY(hipStreamSynchronize(st));
     return TSFA_OK;
 }

@@ -1,11 +1,16 @@
 // Device packer of the C-ABI (include/tsfresh_amd.h: tsfa_pack_device*): the kernels around the bodies of pack_device.h
 // and the host code that strings them together.  See pack_device.h for the scratch formula and the sort's design.
+// tsfa_pack_device and tsfa_pack_set_create share their steps 1-3 -- min / max, keys, the planned radix passes between two
+// buffer sets -- as PkSorter, which states the invariants the kernels rely on (n_tiles, the size and reuse of counts, one
+// buffer set when in order); each entry goes on with its own boundary and gather kernels.  tests/emul/emul_pack_sort.h is the
+// sorter's twin on looped kernel bodies.  Staging, argument checks, view filling and copy-out are one helper each.
 // The window builder (tsfa_roll_windows, roll_device.h) lives here as well: it reads a pack's buffers and reuses k_pack_scan.
 // So does the row packer (tsfa_pack_set_rows, tsfa_pack_set_hours; pack_rows.h): it reads a set's permutation and offsets.
 #include <hip/hip_runtime.h>
 
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "pack_device.h"
@@ -189,10 +194,6 @@ __global__ void __launch_bounds__(PK_THREADS) k_pack_set_hours(PhArgs a) {
     ph_hours_body<TYPE>(b, (int64_t)blockIdx.x, (int64_t)gridDim.x, a, starts, &head);
 }
 
-// the function HIP_TRY and HIP_TRY_ALLOC name in their messages (redefined in front of every entry point below)
-#undef TSFA_WHO
-#define TSFA_WHO "tsfa_pack_device"
-
 // a device buffer as several holders keep it: freed on its device when the last of them goes
 std::shared_ptr<void> pk_share(void *p, int32_t device) {
     return std::shared_ptr<void>(p, [device](void *q) {
@@ -201,107 +202,182 @@ std::shared_ptr<void> pk_share(void *p, int32_t device) {
     });
 }
 
-int pk_check_device(int32_t device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_pack_device: no HIP device visible: tsfresh_amd has no CPU fallback");
-    if (device < 0 || device >= ndev) return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_pack_device: no such HIP device");
-    return TSFA_OK;
-}
-
 int pk_grid(int64_t n) {
     const int64_t blocks = (n + PK_GRID_THREADS - 1) / PK_GRID_THREADS;
     return (int)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks));
 }
 
+// A pack that looks into the buffers of `set` and into `out`, the ragged samples of one call: what the views of
+// tsfa_pack_set_values and tsfa_pack_set_rows have in common.  The caller sets rows, groups and the four pointers.
+tsfa_pack *pk_view(const tsfa_pack_set *set, int out_type, unsigned int nan_flag, const std::shared_ptr<void> &out) {
+    tsfa_pack *pk = new tsfa_pack();
+    pk->device = set->device;
+    pk->flags = set->flags | (nan_flag ? TSFA_PACK_VALUE_NAN : 0);
+    pk->n_passes = set->n_passes;
+    pk->id_type = set->id_type; pk->sort_type = set->sort_type; pk->out_type = out_type;
+    pk->hold[0] = out;
+    pk->hold[1] = set->rebased ? set->rebased : set->offsets;  // (several kinds : one)
+    pk->hold[2] = set->uniq;
+    pk->hold[3] = set->sort;
+    return pk;
+}
+
+// ---- what several entry points share.  Each helper takes its entry's name as `who` (an argument or a member), and that is
+// ---- the function HIP_TRY and HIP_TRY_ALLOC name in the messages here.
+#undef TSFA_WHO
+#define TSFA_WHO who
+
+// A host column (TSFA_HOST) is staged: `own` takes the device copy and *col is repointed at it.  A device column
+// (TSFA_DEVICE) and an absent one (NULL) stay as they are.  what: the column's noun in the out-of-memory message.
+int pk_stage(const char *who, int32_t space, DevPtr<void> &own, const void **col, size_t bytes, const char *what) {
+    if (space != TSFA_HOST || !*col) return TSFA_OK;
+    HIP_TRY_ALLOC(own, bytes, what);
+    HIP_TRY(hipMemcpy(own.get(), *col, bytes, hipMemcpyHostToDevice));
+    *col = own.get();
+    return TSFA_OK;
+}
+
+// The argument checks of tsfa_pack_device and tsfa_pack_set_create, in the order both make them.  own: NULL, or what the
+// entry refuses its own column with (values / kinds); it is reported where both report it, after the key columns' types.
+// dev_who: the name in front of the device check's messages.
+int pk_check_frame(const char *who, const void *ids, int32_t id_type, const void *sort, int32_t sort_type, int64_t n_rows,
+                   int32_t space, int32_t options, const char *own, const char *dev_who, int32_t device) {
+    const auto refuse = [who](int code, const char *why) { return tsfa_fail(code, (std::string(who) + ": " + why).c_str()); };
+    if (!ids || n_rows < 1 || (space != TSFA_HOST && space != TSFA_DEVICE) || (options & ~TSFA_PACK_KEEP_SORT))
+        return refuse(TSFA_ERR_INVALID, "bad arguments");
+    if (!pk_is_key_type(id_type, false)) return refuse(TSFA_ERR_INVALID, "the id column must be of an integer type");
+    if (sort && !pk_is_key_type(sort_type, true))
+        return refuse(TSFA_ERR_INVALID, "the sort column must be of an integer type, float32 or float64");
+    if (own) return refuse(TSFA_ERR_INVALID, own);
+    if ((options & TSFA_PACK_KEEP_SORT) && !sort) return refuse(TSFA_ERR_INVALID, "TSFA_PACK_KEEP_SORT without a sort column");
+    if (int rc = tsfa_check_device(dev_who, device)) return rc;
+    if (n_rows > 0xffffffffll) return refuse(TSFA_ERR_TOO_LONG, "more than 4 294 967 295 rows (the row indices are 32 bits wide)");
+    return TSFA_OK;
+}
+
+// Steps 1-3 of tsfa_pack_device and tsfa_pack_set_create: the rows' indices sorted by (id, sort) or, with a kind column, by
+// (kind, id, sort), on the null stream.  After run() the entry reads hi[cur] / idx[cur] (the sorted id keys and the
+// permutation), counts, d_st and st, in_order and n_passes, and goes on with its own step 4; what it does not release()
+// goes with the sorter.  tests/emul/emul_pack_sort.h is the same sequence on looped kernel bodies.
+struct PkSorter {
+    const char *who;                 // the entry point the messages name
+    PkStats st;                      // host copy of *d_st, as last read back
+    PkSetStats ks;                   // host copy of *d_ks, the caller's kind counters (read back here only with a kind column)
+    DevPtr<PkStats> d_st;
+    DevPtr<pk_u64> hi[2], lo[2];     // id and sort keys of the rows in the order of idx
+    DevPtr<uint32_t> idx[2], counts;
+    int64_t n_tiles = 0;
+    int cur = 0, n_passes = 0;       // the live set of hi / lo / idx; the passes that ran
+    bool in_order = false;
+
+    explicit PkSorter(const char *w) : who(w) { pk_set_stats_init(&ks); }
+
+    // kinds (optional) with d_ks, its initialised counters on the device: without a kind column nothing is launched,
+    // allocated or copied on its behalf.  n <= 2^32 - 1 (pk_check_frame).
+    int run(const void *ids, int id_type, const void *sort, int sort_type, int64_t n, const void *kinds = nullptr, int kind_type = 0,
+            PkSetStats *d_ks = nullptr) {
+        // INVARIANT n_tiles = ceil(n / PK_TILE) is the grid of every tile kernel (k_pack_hist*, k_pack_scatter*, the entries'
+        // heads and groups kernels): block t owns rows [t * PK_TILE, (t + 1) * PK_TILE) and row t * PK_RADIX .. of counts.
+        n_tiles = (n + PK_TILE - 1) / PK_TILE;
+        HIP_TRY_ALLOC(d_st, sizeof(PkStats), "the packer's counters");
+        pk_stats_init(&st);
+        HIP_TRY(hipMemcpy(d_st.get(), &st, sizeof(st), hipMemcpyHostToDevice));
+
+        // 1. min / max of the keys, descents of (id, sort) and of (kind, id, sort)
+        k_pack_minmax<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, d_st.get());
+        if (kinds) k_pack_kind_minmax<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(kinds, kind_type, ids, id_type, sort, sort_type, n, d_ks);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(&st, d_st.get(), sizeof(st), hipMemcpyDeviceToHost));
+        if (kinds) HIP_TRY(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
+        const bool inner_in_order = st.descents == 0;              // (id, sort): only the kind passes are left
+        in_order = kinds ? ks.descents == 0 : inner_in_order;      // (kind, id, sort): nothing is sorted
+
+        // 2. id and sort keys, identity permutation, byte histograms.
+        // INVARIANT one set of buffers when in order: no pass runs, cur stays 0 and set 1 is never touched (20 of the 40
+        // scratch bytes per row).  INVARIANT counts holds n_tiles x PK_RADIX words, a pass's (digit, tile) matrix; step 4
+        // of either entry reuses its front for per-tile head counts, n_tiles words (2 n_tiles in the set) <= that size.
+        for (int k = 0; k < (in_order ? 1 : 2); ++k) {
+            HIP_TRY_ALLOC(hi[k], (size_t)n * 8, "the id keys (sort scratch: 40 bytes per row in all)");
+            HIP_TRY_ALLOC(lo[k], (size_t)n * 8, "the sort keys (sort scratch: 40 bytes per row in all)");
+            HIP_TRY_ALLOC(idx[k], (size_t)n * 4, "the row indices (sort scratch: 40 bytes per row in all)");
+        }
+        HIP_TRY_ALLOC(counts, (size_t)n_tiles * PK_RADIX * 4, "the per-tile digit counts");
+        const int inner_passes = (in_order || inner_in_order) ? 0 : 1;
+        k_pack_keys<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, st.kmin[0], sort ? st.kmin[1] : 0ull,
+                                                             pk_sig_bytes(st.kmax[0] - st.kmin[0]),
+                                                             sort ? pk_sig_bytes(st.kmax[1] - st.kmin[1]) : 0, inner_passes,
+                                                             hi[0].get(), lo[0].get(), idx[0].get(), d_st.get());
+        if (kinds && !in_order)
+            k_pack_kind_hist<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(kinds, kind_type, n, ks.kmin, pk_sig_bytes(ks.kmax - ks.kmin), d_ks);
+        HIP_TRY(hipGetLastError());
+        if (in_order) return TSFA_OK;
+
+        // 3. the radix passes, least significant digit first: sort bytes, id bytes, kind bytes; constant digits are skipped.
+        // A pass sorts set cur into set cur ^ 1.  The plain digit (a key word and a shift) and the kind digit (read
+        // through the row index: PkKindDigit) differ only in the two launches around the scan.
+        int pass_word[16], pass_byte[16], kind_byte[8];
+        HIP_TRY(hipMemcpy(&st, d_st.get(), sizeof(st), hipMemcpyDeviceToHost));
+        if (kinds) HIP_TRY(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
+        const int np = inner_passes ? pk_plan_passes(&st, n, sort != nullptr, pass_word, pass_byte) : 0;
+        const int nkp = kinds ? pk_plan_kind_passes(&ks, n, kind_byte) : 0;
+        for (int p = 0; p < np + nkp; ++p) {
+            const bool plain = p < np;
+            pk_u64 *const h0 = hi[cur].get(), *const l0 = lo[cur].get(), *const h1 = hi[cur ^ 1].get(), *const l1 = lo[cur ^ 1].get();
+            uint32_t *const i0 = idx[cur].get(), *const i1 = idx[cur ^ 1].get(), *const cnt = counts.get();
+            const pk_u64 *key = (plain && pass_word[p]) ? l0 : h0;
+            const int shift = 8 * (plain ? pass_byte[p] : kind_byte[p - np]);
+            const PkKindDigit dg{kinds, kind_type, ks.kmin, i0, shift};
+            if (plain) k_pack_hist<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, cnt);
+            else k_pack_hist_kind<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, dg, n, cnt);
+            k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(cnt, (size_t)n_tiles * PK_RADIX, nullptr);
+            if (plain) k_pack_scatter<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, cnt, h0, l0, i0, h1, l1, i1);
+            else k_pack_scatter_kind<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, dg, n, cnt, h0, l0, i0, h1, l1, i1);
+            HIP_TRY(hipGetLastError());
+            cur ^= 1;
+        }
+        n_passes = np + nkp;
+        return TSFA_OK;
+    }
+};
+
 }  // namespace
 
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_pack_device"
 extern "C" int tsfa_pack_device(const void *ids, int32_t id_type, const void *sort, int32_t sort_type, const void *values,
                                 int32_t value_type, int64_t n_rows, int32_t space, int32_t options, int32_t device,
                                 tsfa_pack **out_pack) {
     if (!out_pack) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_device: out_pack is NULL");
     *out_pack = nullptr;
-    if (!ids || !values || n_rows < 1 || (space != TSFA_HOST && space != TSFA_DEVICE) || (options & ~TSFA_PACK_KEEP_SORT))
-        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_device: bad arguments");
-    if (!pk_is_key_type(id_type, false)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_device: the id column must be of an integer type");
-    if (sort && !pk_is_key_type(sort_type, true))
-        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_device: the sort column must be of an integer type, float32 or float64");
-    if (pk_itemsize(value_type) == 0) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_device: unknown element type of the value column");
-    if ((options & TSFA_PACK_KEEP_SORT) && !sort)
-        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_device: TSFA_PACK_KEEP_SORT without a sort column");
-    int rc = pk_check_device(device);
+    if (!values) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_device: bad arguments");
+    int rc = pk_check_frame(TSFA_WHO, ids, id_type, sort, sort_type, n_rows, space, options,
+                            pk_itemsize(value_type) == 0 ? "unknown element type of the value column" : nullptr, TSFA_WHO, device);
     if (rc) return rc;
-    if (n_rows > 0xffffffffll)
-        return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_pack_device: more than 4 294 967 295 rows (the row indices are 32 bits wide)");
 
-    const int64_t n = n_rows, n_tiles = (n + PK_TILE - 1) / PK_TILE;
+    const int64_t n = n_rows;
     const int id_size = pk_itemsize(id_type), sort_size = sort ? pk_itemsize(sort_type) : 0, val_size = pk_itemsize(value_type);
     const int out_type = pk_out_type(value_type);
-    PkStats st;
     std::unique_ptr<tsfa_pack, void (*)(tsfa_pack *)> pk(new tsfa_pack(), tsfa_pack_device_destroy);
-    int cur = 0;
     pk->device = device; pk->n_rows = n; pk->id_type = id_type; pk->sort_type = sort ? sort_type : 0; pk->out_type = out_type;
 
     HIP_TRY(hipSetDevice(device));
     DevPtr<void> d_ids, d_sort, d_vals;  // staged copies (TSFA_HOST only)
-    if (space == TSFA_HOST) {
-        HIP_TRY_ALLOC(d_ids, (size_t)n * id_size, "the id column");
-        HIP_TRY(hipMemcpy(d_ids.get(), ids, (size_t)n * id_size, hipMemcpyHostToDevice));
-        if (sort) {
-            HIP_TRY_ALLOC(d_sort, (size_t)n * sort_size, "the sort column");
-            HIP_TRY(hipMemcpy(d_sort.get(), sort, (size_t)n * sort_size, hipMemcpyHostToDevice));
-        }
-        HIP_TRY_ALLOC(d_vals, (size_t)n * val_size, "the value column");
-        HIP_TRY(hipMemcpy(d_vals.get(), values, (size_t)n * val_size, hipMemcpyHostToDevice));
-        ids = d_ids.get(); sort = d_sort.get(); values = d_vals.get();
-    }
-    DevPtr<PkStats> d_st_own;
-    HIP_TRY_ALLOC(d_st_own, sizeof(PkStats), "the packer's counters");
-    PkStats *const d_st = d_st_own.get();
-    pk_stats_init(&st);
-    HIP_TRY(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
-
-    // 1. min / max of both keys, descents
-    k_pack_minmax<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, d_st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
-    const bool in_order = st.descents == 0;
-    if (in_order) pk->flags |= TSFA_PACK_IN_ORDER;
-    // 2. keys, identity permutation, byte histograms.  An ordered frame needs one set of buffers only.
-    DevPtr<pk_u64> d_hi[2], d_lo[2];
-    DevPtr<uint32_t> d_idx[2], d_counts;
-    for (int k = 0; k < (in_order ? 1 : 2); ++k) {
-        HIP_TRY_ALLOC(d_hi[k], (size_t)n * 8, "the id keys (sort scratch: 40 bytes per row in all)");
-        HIP_TRY_ALLOC(d_lo[k], (size_t)n * 8, "the sort keys (sort scratch: 40 bytes per row in all)");
-        HIP_TRY_ALLOC(d_idx[k], (size_t)n * 4, "the row indices (sort scratch: 40 bytes per row in all)");
-    }
-    HIP_TRY_ALLOC(d_counts, (size_t)n_tiles * PK_RADIX * 4, "the per-tile digit counts");
-    pk_u64 *const hi[2] = {d_hi[0].get(), d_hi[1].get()}, *const lo[2] = {d_lo[0].get(), d_lo[1].get()};   // what the launches pass
-    uint32_t *const idx[2] = {d_idx[0].get(), d_idx[1].get()}, *const counts = d_counts.get();
-    k_pack_keys<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, st.kmin[0], sort ? st.kmin[1] : 0ull,
-                                                         pk_sig_bytes(st.kmax[0] - st.kmin[0]),
-                                                         sort ? pk_sig_bytes(st.kmax[1] - st.kmin[1]) : 0, in_order ? 0 : 1, hi[0], lo[0],
-                                                         idx[0], d_st);
-    HIP_TRY(hipGetLastError());
-    if (!in_order) {
-        // 3. the radix passes, least significant digit first; constant digits are skipped
-        int pass_word[16], pass_byte[16];
-        HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
-        const int np = pk_plan_passes(&st, n, sort != nullptr, pass_word, pass_byte);
-        for (int p = 0; p < np; ++p) {
-            const pk_u64 *key = pass_word[p] ? lo[cur] : hi[cur];
-            const int shift = 8 * pass_byte[p];
-            k_pack_hist<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, counts);
-            k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles * PK_RADIX, nullptr);
-            k_pack_scatter<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, counts, hi[cur], lo[cur], idx[cur],
-                                                                     hi[cur ^ 1], lo[cur ^ 1], idx[cur ^ 1]);
-            HIP_TRY(hipGetLastError());
-            cur ^= 1;
-        }
-        pk->n_passes = np;
-    }
+    if ((rc = pk_stage(TSFA_WHO, space, d_ids, &ids, (size_t)n * id_size, "the id column"))) return rc;
+    if ((rc = pk_stage(TSFA_WHO, space, d_sort, &sort, (size_t)n * sort_size, "the sort column"))) return rc;
+    if ((rc = pk_stage(TSFA_WHO, space, d_vals, &values, (size_t)n * val_size, "the value column"))) return rc;
+    // 1. - 3. the rows' indices sorted by (id, sort)
+    PkSorter s(TSFA_WHO);
+    if ((rc = s.run(ids, id_type, sort, sort_type, n))) return rc;
+    PkStats &st = s.st;
+    PkStats *const d_st = s.d_st.get();
+    const int64_t n_tiles = s.n_tiles;
+    const pk_u64 *const hi = s.hi[s.cur].get();
+    const uint32_t *const idx = s.idx[s.cur].get();
+    uint32_t *const counts = s.counts.get();
+    if (s.in_order) pk->flags |= TSFA_PACK_IN_ORDER;
+    pk->n_passes = s.n_passes;
     // 4. group boundaries (counts is reused for the per-tile head counts)
-    k_pack_heads<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi[cur], n, counts);
+    k_pack_heads<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi, n, counts);
     k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles, &d_st->n_groups);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
@@ -310,15 +386,15 @@ extern "C" int tsfa_pack_device(const void *ids, int32_t id_type, const void *so
     DevPtr<void> d_uniq, d_out, d_psort;
     HIP_TRY_ALLOC(d_offsets, (size_t)(pk->n_groups + 1) * 8, "the offsets");
     HIP_TRY_ALLOC(d_uniq, (size_t)pk->n_groups * id_size, "the unique ids");
-    k_pack_groups<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi[cur], idx[cur], n, counts, pk->n_groups, ids, id_size, d_offsets.get(), d_uniq.get());
+    k_pack_groups<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi, idx, n, counts, pk->n_groups, ids, id_size, d_offsets.get(), d_uniq.get());
     HIP_TRY(hipGetLastError());
     // 5. gather
     HIP_TRY_ALLOC(d_out, (size_t)n * pk_itemsize(out_type), "the ragged sample buffer");
-    k_pack_gather<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(values, value_type, idx[cur], n, d_out.get(), d_st);
+    k_pack_gather<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(values, value_type, idx, n, d_out.get(), d_st);
     HIP_TRY(hipGetLastError());
     if (options & TSFA_PACK_KEEP_SORT) {
         HIP_TRY_ALLOC(d_psort, (size_t)n * sort_size, "the packed sort column");
-        k_pack_gather_raw<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(sort, sort_size, idx[cur], n, d_psort.get());
+        k_pack_gather_raw<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(sort, sort_size, idx, n, d_psort.get());
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));  // (synchronises: the staged columns may go)
@@ -347,12 +423,17 @@ extern "C" int tsfa_pack_device_values(const tsfa_pack *pack, const void **value
 extern "C" const int64_t *tsfa_pack_device_offsets(const tsfa_pack *pack) { return pack ? pack->offsets : nullptr; }
 extern "C" const void *tsfa_pack_device_ids(const tsfa_pack *pack) { return pack ? pack->uniq : nullptr; }
 
-static int pk_copy_out(const tsfa_pack *pack, void *dst, const void *src, size_t bytes, const char *who) {
-    if (!pack || !dst) return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": null pointer").c_str());
-    if (!src) return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": the pack does not hold that buffer").c_str());
-    hipError_t e = hipSetDevice(pack->device);
+// One device buffer of a pack or of a window set (the two handle types) to the host.  A pack refuses a buffer it does not
+// hold (no TSFA_PACK_KEEP_SORT); a window set without a window has nothing to copy.
+template <class Handle>
+static int pk_copy_out(const Handle *h, void *dst, const void *src, size_t bytes, const char *who) {
+    constexpr bool is_pack = std::is_same<Handle, tsfa_pack>::value;
+    if (!h || !dst) return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": null pointer").c_str());
+    if (is_pack && !src) return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": the pack does not hold that buffer").c_str());
+    if (!is_pack && !bytes) return TSFA_OK;
+    hipError_t e = hipSetDevice(h->device);
     if (e == hipSuccess) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? (int)TSFA_OK : tsfa_fail_hip("tsfa_pack_device", who, e);
+    return e == hipSuccess ? (int)TSFA_OK : tsfa_fail_hip(who, "hipMemcpy", e);
 }
 
 extern "C" int tsfa_pack_device_copy_ids(const tsfa_pack *pack, void *ids_host) {
@@ -386,115 +467,42 @@ extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void
                                     tsfa_pack_set **out_set) {
     if (!out_set) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: out_set is NULL");
     *out_set = nullptr;
-    if (!ids || n_rows < 1 || (space != TSFA_HOST && space != TSFA_DEVICE) || (options & ~TSFA_PACK_KEEP_SORT))
-        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: bad arguments");
-    if (!pk_is_key_type(id_type, false)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: the id column must be of an integer type");
-    if (sort && !pk_is_key_type(sort_type, true))
-        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: the sort column must be of an integer type, float32 or float64");
-    if (kinds && !pk_is_key_type(kind_type, false))
-        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: the kind column must be of an integer type");
-    if ((options & TSFA_PACK_KEEP_SORT) && !sort)
-        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_create: TSFA_PACK_KEEP_SORT without a sort column");
-    int rc = pk_check_device(device);
+    // (the device check names tsfa_pack_device, as it always has)
+    int rc = pk_check_frame(TSFA_WHO, ids, id_type, sort, sort_type, n_rows, space, options,
+                            kinds && !pk_is_key_type(kind_type, false) ? "the kind column must be of an integer type" : nullptr,
+                            "tsfa_pack_device", device);
     if (rc) return rc;
-    if (n_rows > 0xffffffffll)
-        return tsfa_fail(TSFA_ERR_TOO_LONG, "tsfa_pack_set_create: more than 4 294 967 295 rows (the row indices are 32 bits wide)");
 
-    const int64_t n = n_rows, n_tiles = (n + PK_TILE - 1) / PK_TILE;
+    const int64_t n = n_rows;
     const int id_size = pk_itemsize(id_type), sort_size = sort ? pk_itemsize(sort_type) : 0, kind_size = kinds ? pk_itemsize(kind_type) : 0;
-    PkStats st;
-    PkSetStats ks;
     std::unique_ptr<tsfa_pack_set, void (*)(tsfa_pack_set *)> set(new tsfa_pack_set(), tsfa_pack_set_destroy);
-    int cur = 0;
     set->device = device; set->n_rows = n; set->id_type = id_type; set->sort_type = sort ? sort_type : 0;
     set->kind_type = kinds ? kind_type : 0; set->has_kinds = kinds != nullptr;
 
     HIP_TRY(hipSetDevice(device));
     DevPtr<void> d_ids, d_sort, d_kinds;  // staged copies (TSFA_HOST only)
-    if (space == TSFA_HOST) {
-        HIP_TRY_ALLOC(d_ids, (size_t)n * id_size, "the id column");
-        HIP_TRY(hipMemcpy(d_ids.get(), ids, (size_t)n * id_size, hipMemcpyHostToDevice));
-        if (sort) {
-            HIP_TRY_ALLOC(d_sort, (size_t)n * sort_size, "the sort column");
-            HIP_TRY(hipMemcpy(d_sort.get(), sort, (size_t)n * sort_size, hipMemcpyHostToDevice));
-        }
-        if (kinds) {
-            HIP_TRY_ALLOC(d_kinds, (size_t)n * kind_size, "the kind column");
-            HIP_TRY(hipMemcpy(d_kinds.get(), kinds, (size_t)n * kind_size, hipMemcpyHostToDevice));
-        }
-        ids = d_ids.get(); sort = d_sort.get(); kinds = d_kinds.get();
-    }
-    DevPtr<PkStats> d_st_own;
+    if ((rc = pk_stage(TSFA_WHO, space, d_ids, &ids, (size_t)n * id_size, "the id column"))) return rc;
+    if ((rc = pk_stage(TSFA_WHO, space, d_sort, &sort, (size_t)n * sort_size, "the sort column"))) return rc;
+    if ((rc = pk_stage(TSFA_WHO, space, d_kinds, &kinds, (size_t)n * kind_size, "the kind column"))) return rc;
+    // 1. - 3. the rows' indices sorted by (kind, id, sort).  The kind counters are the entry's: step 4 counts the kinds
+    // in them with or without a kind column.
+    PkSorter s(TSFA_WHO);
+    PkSetStats &ks = s.ks;
     DevPtr<PkSetStats> d_ks_own;
-    HIP_TRY_ALLOC(d_st_own, sizeof(PkStats), "the packer's counters");
     HIP_TRY_ALLOC(d_ks_own, sizeof(PkSetStats), "the packer's kind counters");
-    PkStats *const d_st = d_st_own.get();
     PkSetStats *const d_ks = d_ks_own.get();
-    pk_stats_init(&st);
-    pk_set_stats_init(&ks);
-    HIP_TRY(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_ks, &ks, sizeof(ks), hipMemcpyHostToDevice));
-
-    // 1. min / max of the three keys, descents of (id, sort) and of (kind, id, sort)
-    k_pack_minmax<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, d_st);
-    if (kinds) k_pack_kind_minmax<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(kinds, kind_type, ids, id_type, sort, sort_type, n, d_ks);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
-    const bool inner_in_order = st.descents == 0;                       // (id, sort): only the kind passes are left
-    const bool in_order = kinds ? ks.descents == 0 : inner_in_order;    // (kind, id, sort): nothing is sorted
-    if (in_order) set->flags |= TSFA_PACK_IN_ORDER;
-    // 2. id and sort keys, identity permutation, byte histograms
-    DevPtr<pk_u64> d_hi[2], d_lo[2];
-    DevPtr<uint32_t> d_idx[2], d_counts;
-    for (int k = 0; k < (in_order ? 1 : 2); ++k) {
-        HIP_TRY_ALLOC(d_hi[k], (size_t)n * 8, "the id keys (sort scratch: 40 bytes per row in all)");
-        HIP_TRY_ALLOC(d_lo[k], (size_t)n * 8, "the sort keys (sort scratch: 40 bytes per row in all)");
-        HIP_TRY_ALLOC(d_idx[k], (size_t)n * 4, "the row indices (sort scratch: 40 bytes per row in all)");
-    }
-    HIP_TRY_ALLOC(d_counts, (size_t)n_tiles * PK_RADIX * 4, "the per-tile digit counts");
-    pk_u64 *const hi[2] = {d_hi[0].get(), d_hi[1].get()}, *const lo[2] = {d_lo[0].get(), d_lo[1].get()};   // what the launches pass
-    uint32_t *const idx[2] = {d_idx[0].get(), d_idx[1].get()}, *const counts = d_counts.get();
-    {
-        const int inner_passes = (in_order || inner_in_order) ? 0 : 1;
-        k_pack_keys<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(ids, id_type, sort, sort_type, n, st.kmin[0], sort ? st.kmin[1] : 0ull,
-                                                             pk_sig_bytes(st.kmax[0] - st.kmin[0]),
-                                                             sort ? pk_sig_bytes(st.kmax[1] - st.kmin[1]) : 0, inner_passes, hi[0],
-                                                             lo[0], idx[0], d_st);
-        if (kinds && !in_order)
-            k_pack_kind_hist<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(kinds, kind_type, n, ks.kmin, pk_sig_bytes(ks.kmax - ks.kmin), d_ks);
-        HIP_TRY(hipGetLastError());
-        if (!in_order) {
-            // 3. the radix passes, least significant digit first: sort bytes, id bytes, kind bytes; constant digits are skipped
-            int pass_word[16], pass_byte[16], kind_byte[8];
-            HIP_TRY(hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(&ks, d_ks, sizeof(ks), hipMemcpyDeviceToHost));
-            const int np = inner_passes ? pk_plan_passes(&st, n, sort != nullptr, pass_word, pass_byte) : 0;
-            for (int p = 0; p < np; ++p) {
-                const pk_u64 *key = pass_word[p] ? lo[cur] : hi[cur];
-                const int shift = 8 * pass_byte[p];
-                k_pack_hist<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, counts);
-                k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles * PK_RADIX, nullptr);
-                k_pack_scatter<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, key, shift, n, counts, hi[cur], lo[cur], idx[cur],
-                                                                         hi[cur ^ 1], lo[cur ^ 1], idx[cur ^ 1]);
-                HIP_TRY(hipGetLastError());
-                cur ^= 1;
-            }
-            const int nkp = kinds ? pk_plan_kind_passes(&ks, n, kind_byte) : 0;
-            for (int p = 0; p < nkp; ++p) {
-                const PkKindDigit dg{kinds, kind_type, ks.kmin, idx[cur], 8 * kind_byte[p]};
-                k_pack_hist_kind<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, dg, n, counts);
-                k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles * PK_RADIX, nullptr);
-                k_pack_scatter_kind<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(n_tiles, dg, n, counts, hi[cur], lo[cur], idx[cur],
-                                                                              hi[cur ^ 1], lo[cur ^ 1], idx[cur ^ 1]);
-                HIP_TRY(hipGetLastError());
-                cur ^= 1;
-            }
-            set->n_passes = np + nkp;
-        }
-    }
+    if ((rc = s.run(ids, id_type, sort, sort_type, n, kinds, kind_type, d_ks))) return rc;
+    PkStats &st = s.st;
+    PkStats *const d_st = s.d_st.get();
+    const int64_t n_tiles = s.n_tiles;
+    const pk_u64 *const hi = s.hi[s.cur].get();
+    const uint32_t *const idx = s.idx[s.cur].get();
+    uint32_t *const counts = s.counts.get();
+    if (s.in_order) set->flags |= TSFA_PACK_IN_ORDER;
+    set->n_passes = s.n_passes;
     // 4. group and kind boundaries (counts is reused: [0, n_tiles) head counts, [n_tiles, 2 n_tiles) kind-head counts)
-    k_pack_set_heads<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi[cur], idx[cur], kinds, kind_type, n, counts, counts + n_tiles);
+    k_pack_set_heads<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi, idx, kinds, kind_type, n, counts, counts + n_tiles);
     k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts, (size_t)n_tiles, &d_st->n_groups);
     k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(counts + n_tiles, (size_t)n_tiles, &d_ks->n_kinds);
     HIP_TRY(hipGetLastError());
@@ -512,7 +520,7 @@ extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void
         HIP_TRY_ALLOC(d_krows, (size_t)(nk + 1) * 8, "the kinds' row ranges");
         HIP_TRY_ALLOC(d_kgroups, (size_t)(nk + 1) * 8, "the kinds' group ranges");
         HIP_TRY_ALLOC(d_kvals, (size_t)nk * kind_size, "the kind values");
-        k_pack_set_groups<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi[cur], idx[cur], kinds, kind_type, n, counts, counts + n_tiles, ng, nk,
+        k_pack_set_groups<<<(unsigned)n_tiles, PK_THREADS, 0, 0>>>(hi, idx, kinds, kind_type, n, counts, counts + n_tiles, ng, nk,
                                                                     ids, id_size, d_offsets.get(), d_uniq.get(), d_krows.get(),
                                                                     d_kgroups.get(), d_kvals.get());
         HIP_TRY(hipGetLastError());
@@ -524,7 +532,7 @@ extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void
         }
         if (options & TSFA_PACK_KEEP_SORT) {
             HIP_TRY_ALLOC(d_psort, (size_t)n * sort_size, "the packed sort column");
-            k_pack_gather_raw<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(sort, sort_size, idx[cur], n, d_psort.get());
+            k_pack_gather_raw<<<pk_grid(n), PK_GRID_THREADS, 0, 0>>>(sort, sort_size, idx, n, d_psort.get());
             HIP_TRY(hipGetLastError());
         }
         set->kind_rows.resize((size_t)nk + 1);
@@ -535,7 +543,7 @@ extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void
         if (kind_size) HIP_TRY(hipMemcpy(set->kind_vals.data(), d_kvals.get(), (size_t)nk * kind_size, hipMemcpyDeviceToHost));
     }
     // the set takes over what outlives the call
-    set->perm = pk_share(d_idx[cur].release(), device);
+    set->perm = pk_share(s.idx[s.cur].release(), device);
     set->offsets = pk_share(d_offsets.release(), device);
     set->uniq = pk_share(d_uniq.release(), device);
     if (d_rebased) set->rebased = pk_share(d_rebased.release(), device);
@@ -571,11 +579,7 @@ extern "C" int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int3
     HIP_TRY(hipSetDevice(set->device));
     DevPtr<void> d_vals, d_out_own;
     DevPtr<PkStats> d_st_own;
-    if (space == TSFA_HOST) {
-        HIP_TRY_ALLOC(d_vals, (size_t)n * val_size, "the value column");
-        HIP_TRY(hipMemcpy(d_vals.get(), values, (size_t)n * val_size, hipMemcpyHostToDevice));
-        values = d_vals.get();
-    }
+    if (int rc = pk_stage(TSFA_WHO, space, d_vals, &values, (size_t)n * val_size, "the value column")) return rc;
     HIP_TRY_ALLOC(d_st_own, sizeof(PkStats), "the packer's counters");
     PkStats *const d_st = d_st_own.get();
     HIP_TRY(hipMemset(d_st, 0, sizeof(PkStats)));
@@ -587,25 +591,14 @@ extern "C" int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int3
     HIP_TRY(hipMemcpy(&nan_flag, &d_st->nan_flag, sizeof(nan_flag), hipMemcpyDeviceToHost));  // (synchronises: the staged column may go)
     for (int32_t k = 0; k < set->n_kinds; ++k) {
         const int64_t r0 = set->kind_rows[(size_t)k], g0 = set->kind_groups[(size_t)k];
-        tsfa_pack *pk = new tsfa_pack();
-        pk->device = set->device;
+        tsfa_pack *pk = out_packs[k] = pk_view(set, out_type, nan_flag, out);
         pk->n_rows = set->kind_rows[(size_t)k + 1] - r0;
         pk->n_groups = set->kind_groups[(size_t)k + 1] - g0;
-        pk->flags = set->flags | (nan_flag ? TSFA_PACK_VALUE_NAN : 0);
-        pk->n_passes = set->n_passes;
-        pk->id_type = set->id_type; pk->sort_type = set->sort_type; pk->out_type = out_type;
         pk->values = (char *)d_out + (size_t)r0 * out_size;
-        pk->hold[0] = out;
         // one kind: the set's own offsets; several: the kind's stretch of the rebased buffer (pk_rebase_body's layout)
-        pk->hold[1] = set->rebased ? set->rebased : set->offsets;
         pk->offsets = (int64_t *)pk->hold[1].get() + (set->rebased ? g0 + k : 0);
         pk->uniq = (char *)set->uniq.get() + (size_t)g0 * id_size;
-        pk->hold[2] = set->uniq;
-        if (set->sort) {
-            pk->sort = (char *)set->sort.get() + (size_t)r0 * sort_size;
-            pk->hold[3] = set->sort;
-        }
-        out_packs[k] = pk;
+        if (set->sort) pk->sort = (char *)set->sort.get() + (size_t)r0 * sort_size;
     }
     return TSFA_OK;
 }
@@ -653,24 +646,13 @@ extern "C" int tsfa_pack_set_rows(tsfa_pack_set *set, const void *values, int32_
     std::vector<unsigned int> nan_flags((size_t)n_cols);
     HIP_TRY(hipMemcpy(nan_flags.data(), d_flags.get(), (size_t)n_cols * sizeof(unsigned int), hipMemcpyDeviceToHost));  // (synchronises)
     for (int64_t c = 0; c < n_cols; ++c) {
-        tsfa_pack *pk = new tsfa_pack();
-        pk->device = set->device;
+        tsfa_pack *pk = out_packs[c] = pk_view(set, out_type, nan_flags[(size_t)c], out);  // (no kind column: one kind)
         pk->n_rows = n;
         pk->n_groups = set->n_groups;
-        pk->flags = set->flags | (nan_flags[(size_t)c] ? TSFA_PACK_VALUE_NAN : 0);
-        pk->n_passes = set->n_passes;
-        pk->id_type = set->id_type; pk->sort_type = set->sort_type; pk->out_type = out_type;
         pk->values = (char *)d_out + (size_t)c * (size_t)n * out_size;
-        pk->hold[0] = out;
         pk->offsets = (int64_t *)set->offsets.get();
-        pk->hold[1] = set->offsets;
         pk->uniq = set->uniq.get();
-        pk->hold[2] = set->uniq;
-        if (set->sort) {
-            pk->sort = set->sort.get();
-            pk->hold[3] = set->sort;
-        }
-        out_packs[c] = pk;
+        pk->sort = set->sort.get();
     }
     return TSFA_OK;
 }
@@ -750,9 +732,8 @@ extern "C" int tsfa_roll_windows(const tsfa_pack *pack, int32_t rolling_directio
                                  int64_t steps, tsfa_windows **out_windows) {
     if (!out_windows) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_roll_windows: out_windows is NULL");
     *out_windows = nullptr;
-    int ndev = 0;  // before the handle is looked at: without a device no pack can exist
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_roll_windows: no HIP device visible: tsfresh_amd has no CPU fallback");
+    // before the handle is looked at: without a device no pack can exist (ordinal 0: that there is one; the pack names its own)
+    if (int rc = tsfa_check_device(TSFA_WHO, 0)) return rc;
     if (!pack) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_roll_windows: pack is NULL");
     RlParams p;
     if (const char *why = rl_make_params(rolling_direction, max_timeshift, min_timeshift, steps, &p))
@@ -799,55 +780,35 @@ extern "C" int64_t tsfa_windows_n_windows(const tsfa_windows *windows) { return 
 extern "C" const int64_t *tsfa_windows_starts(const tsfa_windows *windows) { return windows ? windows->starts.get() : nullptr; }
 extern "C" const int64_t *tsfa_windows_ends(const tsfa_windows *windows) { return windows ? windows->ends.get() : nullptr; }
 
-static int rl_copy_out(const tsfa_windows *windows, void *dst, const void *src, size_t bytes, const char *who) {
-    if (!windows || !dst) return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": null pointer").c_str());
-    if (!bytes) return TSFA_OK;
-    hipError_t e = hipSetDevice(windows->device);
-    if (e == hipSuccess) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? (int)TSFA_OK : tsfa_fail_hip(who, "hipMemcpy", e);
-}
-
 extern "C" int tsfa_windows_copy_series(const tsfa_windows *windows, int64_t *series_host) {
-    return rl_copy_out(windows, series_host, windows ? windows->series.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+    return pk_copy_out(windows, series_host, windows ? windows->series.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
                        "tsfa_windows_copy_series");
 }
 
 extern "C" int tsfa_windows_copy_timeshifts(const tsfa_windows *windows, int64_t *timeshifts_host) {
-    return rl_copy_out(windows, timeshifts_host, windows ? windows->shifts.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+    return pk_copy_out(windows, timeshifts_host, windows ? windows->shifts.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
                        "tsfa_windows_copy_timeshifts");
 }
 
 extern "C" int tsfa_windows_copy_starts(const tsfa_windows *windows, int64_t *starts_host) {
-    return rl_copy_out(windows, starts_host, windows ? windows->starts.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+    return pk_copy_out(windows, starts_host, windows ? windows->starts.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
                        "tsfa_windows_copy_starts");
 }
 
 extern "C" int tsfa_windows_copy_ends(const tsfa_windows *windows, int64_t *ends_host) {
-    return rl_copy_out(windows, ends_host, windows ? windows->ends.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
+    return pk_copy_out(windows, ends_host, windows ? windows->ends.get() : nullptr, windows ? (size_t)windows->n_windows * 8 : 0,
                        "tsfa_windows_copy_ends");
 }
 
 // ---------------------------------------------------------------------------------------------
 // The same windows for a batch that is no pack: raw offsets in, caller-owned buffers out (see roll_device.h for the two routes)
 // ---------------------------------------------------------------------------------------------
-namespace {
-
-int rl_check_device(const char *who, int32_t device) {
-    int ndev = 0;  // before the arguments are looked at: without a device no device pointer can exist
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return tsfa_fail(TSFA_ERR_NO_DEVICE, (std::string(who) + ": no HIP device visible: tsfresh_amd has no CPU fallback").c_str());
-    if (device < 0 || device >= ndev) return tsfa_fail(TSFA_ERR_NO_DEVICE, (std::string(who) + ": no such HIP device").c_str());
-    return TSFA_OK;
-}
-
-}  // namespace
-
 #undef TSFA_WHO
 #define TSFA_WHO "tsfa_roll_count"
 extern "C" int tsfa_roll_count(const int64_t *offsets, int64_t n_series, int64_t series_len, int32_t rolling_direction,
                                int64_t max_timeshift, int64_t min_timeshift, int64_t steps, uint32_t *scanned,
                                int64_t *n_windows_host, int32_t device, void *stream) {
-    int rc = rl_check_device(TSFA_WHO, device);
+    int rc = tsfa_check_device(TSFA_WHO, device);  // before the arguments: without a device no device pointer can exist
     if (rc) return rc;
     if (!n_windows_host) return tsfa_fail(TSFA_ERR_INVALID, TSFA_WHO ": n_windows_host is NULL");
     *n_windows_host = 0;
@@ -894,7 +855,7 @@ extern "C" int tsfa_roll_fill(const int64_t *offsets, int64_t n_series, const ui
                               int64_t n_windows, int32_t rolling_direction, int64_t max_timeshift, int64_t min_timeshift,
                               int64_t steps, int64_t *starts, int64_t *ends, int64_t *series, int64_t *timeshifts, int32_t device,
                               void *stream) {
-    int rc = rl_check_device(TSFA_WHO, device);
+    int rc = tsfa_check_device(TSFA_WHO, device);  // before the arguments: without a device no device pointer can exist
     if (rc) return rc;
     RlParams p;
     const char *why = rl_make_params(rolling_direction, max_timeshift, min_timeshift, steps, &p);

@@ -5,8 +5,10 @@
 #include <string>
 
 #include "pack_times.h"
+#include "tsfa_devmem.h"
 
-int tsfa_fail(int code, const char *msg);
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_pack_times"
 
 namespace {
 
@@ -22,25 +24,13 @@ void pt_launch(const PtArgs &a, unsigned grid, hipStream_t st) {
     else k_pack_times<TYPE, false><<<grid, PD_THREADS, 0, st>>>(a);
 }
 
-int pt_fail_hip(const char *what, hipError_t e) {
-    return tsfa_fail(TSFA_ERR_HIP, (std::string("tsfa_pack_times: ") + what + ": " + hipGetErrorString(e)).c_str());
-}
-
-#define PT_HIP(expr)                                       \
-    do {                                                   \
-        hipError_t e_ = (expr);                            \
-        if (e_ != hipSuccess) return pt_fail_hip(#expr, e_); \
-    } while (0)
-
 }  // namespace
 
 extern "C" int tsfa_pack_times(const void *t, int32_t t_type, int64_t ticks_per_second, int64_t n_batch, int64_t n_time,
                                int64_t stride_batch, int64_t stride_time, const int64_t *offsets, double *hours_out,
                                int32_t *flags_out, int32_t device, void *stream) {
-    int ndev = 0;  // before the arguments are looked at: without a device no device pointer can exist
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_pack_times: no HIP device visible: tsfresh_amd has no CPU fallback");
-    if (device < 0 || device >= ndev) return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_pack_times: no such HIP device");
+    // before the arguments are looked at: without a device no device pointer can exist
+    if (int rc = tsfa_check_device(TSFA_WHO, device)) return rc;
     const char *why;
     if (int rc = pt_check(t, t_type, ticks_per_second, n_batch, n_time, stride_batch, stride_time, offsets, hours_out, flags_out, &why))
         return tsfa_fail(rc, (std::string("tsfa_pack_times: ") + why).c_str());
@@ -53,10 +43,10 @@ extern "C" int tsfa_pack_times(const void *t, int32_t t_type, int64_t ticks_per_
     const unsigned grid = (unsigned)(a.n_work < PD_MAX_GRID ? a.n_work : PD_MAX_GRID);
     hipStream_t st = (hipStream_t)stream;   // NULL: the null stream
 
-    PT_HIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     if (t_type == TSFA_I64) pt_launch<TSFA_I64>(a, grid, st);
     else pt_launch<TSFA_F64>(a, grid, st);
-    PT_HIP(hipGetLastError());
-    if (!stream) PT_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    if (!stream) HIP_TRY(hipStreamSynchronize(st));
     return TSFA_OK;
 }

@@ -5,8 +5,10 @@
 #include <string>
 
 #include "pack_valid.h"
+#include "tsfa_devmem.h"
 
-int tsfa_fail(int code, const char *msg);
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_pack_dense_valid"
 
 namespace {
 
@@ -42,16 +44,6 @@ void pv_launch(const PvArgs &a, unsigned grid, hipStream_t st) {
     else pv_launch_typed<TYPE, false>(a, grid, st);
 }
 
-int pv_fail_hip(const char *what, hipError_t e) {
-    return tsfa_fail(TSFA_ERR_HIP, (std::string("tsfa_pack_dense_valid: ") + what + ": " + hipGetErrorString(e)).c_str());
-}
-
-#define PV_HIP(expr)                                       \
-    do {                                                   \
-        hipError_t e_ = (expr);                            \
-        if (e_ != hipSuccess) return pv_fail_hip(#expr, e_); \
-    } while (0)
-
 }  // namespace
 
 extern "C" int tsfa_pack_dense_valid(const void *x, int32_t x_type, int64_t n_batch, int64_t n_channels, int64_t n_time,
@@ -60,10 +52,8 @@ extern "C" int tsfa_pack_dense_valid(const void *x, int32_t x_type, int64_t n_ba
                                      int64_t t_stride_time, void *values_out, int64_t channel_stride_out, int64_t *offsets_out,
                                      int32_t *steps_out, void *stamps_out, void *scratch, int64_t scratch_bytes,
                                      int32_t *flags_out, int32_t device, void *stream) {
-    int ndev = 0;  // before the arguments are looked at: without a device no device pointer can exist
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_pack_dense_valid: no HIP device visible: tsfresh_amd has no CPU fallback");
-    if (device < 0 || device >= ndev) return tsfa_fail(TSFA_ERR_NO_DEVICE, "tsfa_pack_dense_valid: no such HIP device");
+    // before the arguments are looked at: without a device no device pointer can exist
+    if (int rc = tsfa_check_device(TSFA_WHO, device)) return rc;
     const char *why;
     if (int rc = pv_check(x, x_type, n_batch, n_channels, n_time, stride_batch, stride_channel, stride_time, lengths, lengths_type,
                           t, t_type, t_stride_batch, t_stride_time, values_out, channel_stride_out, offsets_out, steps_out,
@@ -81,14 +71,14 @@ extern "C" int tsfa_pack_dense_valid(const void *x, int32_t x_type, int64_t n_ba
     const unsigned grid = (unsigned)(a.n_work < PD_MAX_GRID ? a.n_work : PD_MAX_GRID);
     hipStream_t st = (hipStream_t)stream;   // NULL: the null stream
 
-    PV_HIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     switch (x_type) {
     case TSFA_F64: pv_launch<TSFA_F64>(a, grid, st); break;
     case TSFA_F32: pv_launch<TSFA_F32>(a, grid, st); break;
     case TSFA_F16: pv_launch<TSFA_F16>(a, grid, st); break;
     default: pv_launch<TSFA_BF16>(a, grid, st); break;
     }
-    PV_HIP(hipGetLastError());
-    if (!stream) PV_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    if (!stream) HIP_TRY(hipStreamSynchronize(st));
     return TSFA_OK;
 }

@@ -382,10 +382,7 @@ __global__ void __launch_bounds__(REL_NT) k_rel_ks(const double *__restrict__ X,
 #define REL_NO_CPU_PATH " (there is no CPU path)"   // the note of the entry points that compute on the device
 
 static int rel_check_device(int32_t device, const char *who, const char *note = "") {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev)
-        return tsfa_fail(TSFA_ERR_NO_DEVICE, (std::string(who) + ": no such HIP device" + note).c_str());
-    return TSFA_OK;
+    return tsfa_check_device(who, device, note);
 }
 
 // The n_rows x n_cols input matrix as the kernels read it: the caller's pointer and leading dimension (TSFA_DEVICE), or

@@ -31,26 +31,37 @@ def _synchronize(torch, device):
     torch.cuda.current_stream(device).synchronize()
 
 
+def _pack_outputs(torch, x3, lengths, device):
+    """What `_dense_pack` and `_valid_pack` both make for a (B, C, n) tensor on `device` -> (tsfa_dtype of x3, values, offsets,
+    flag, lengths pointer, lengths type, views).  values: (C, B * n) float64 or float32, offsets: B + 1 int64, flag: one
+    zeroed int32 -- torch allocations made here, before the caller's `_synchronize`.  views(): after the library call, one
+    `_native.DensePack` per channel; they keep the three buffers, x3 and lengths alive."""
+    B, C, n = x3.shape
+    x_type = _X_TYPES[str(x3.dtype)]
+    vtype = _native.TSFA_F64 if x_type == _native.TSFA_F64 else _native.TSFA_F32
+    values = torch.empty((C, B * n), dtype=torch.float64 if vtype == _native.TSFA_F64 else torch.float32, device=x3.device)
+    offsets = torch.empty(B + 1, dtype=torch.int64, device=x3.device)
+    flag = torch.zeros(1, dtype=torch.int32, device=x3.device)
+    lptr, ltype = None, 0
+    if lengths is not None:
+        lptr, ltype = lengths.data_ptr(), (_native.TSFA_I32 if lengths.dtype == torch.int32 else _native.TSFA_I64)
+
+    def views():
+        owner = (values, offsets, flag, x3, lengths)
+        return [_native.DensePack(values.data_ptr() + c * B * n * values.element_size(), vtype, offsets.data_ptr(), B, device,
+                                  owner=owner) for c in range(C)]
+    return x_type, values, offsets, flag, lptr, ltype, views
+
+
 def _dense_pack(torch, x3, lengths, device):
     """(B, C, n) tensor on `device` -> ([one `_native.DensePack` per channel], flag tensor of one int32).  The packed
     samples, the offsets and the flag word are torch allocations the packs keep alive."""
     B, C, n = x3.shape
-    x_type = _X_TYPES[str(x3.dtype)]
-    out_dtype = torch.float64 if x_type == _native.TSFA_F64 else torch.float32
-    values = torch.empty((C, B * n), dtype=out_dtype, device=x3.device)
-    offsets = torch.empty(B + 1, dtype=torch.int64, device=x3.device)
-    flag = torch.zeros(1, dtype=torch.int32, device=x3.device)
+    x_type, values, offsets, flag, lptr, ltype, views = _pack_outputs(torch, x3, lengths, device)
     _synchronize(torch, device)   # the producer of x, and the fill of the flag word, are done before another stream reads
-    lptr, ltype = None, 0
-    if lengths is not None:
-        lptr, ltype = lengths.data_ptr(), (_native.TSFA_I32 if lengths.dtype == torch.int32 else _native.TSFA_I64)
     _native.pack_dense(x3.data_ptr(), x_type, (B, C, n), x3.stride(), values.data_ptr(), B * n, offsets.data_ptr(),
                        flag.data_ptr(), device=device, lengths_ptr=lptr, lengths_type=ltype)
-    owner = (values, offsets, flag, x3, lengths)
-    vtype = _native.TSFA_F64 if x_type == _native.TSFA_F64 else _native.TSFA_F32
-    packs = [_native.DensePack(values.data_ptr() + c * B * n * values.element_size(), vtype, offsets.data_ptr(), B, device,
-                               owner=owner) for c in range(C)]
-    return packs, flag
+    return views(), flag
 
 
 # time_unit -> ticks per second (numpy's datetime64 units of the same names)
@@ -186,20 +197,27 @@ def _kind_jobs(kinds, default_fc_parameters, kind_to_fc_parameters, device, pins
     return jobs, n_cols, columns
 
 
-def _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=False, times=None):
-    """`_dense_pack` of the batch on `device` and its flag word's errors -> (x3 and lengths on the device, packs, steps,
-    hours).  steps (want_steps): the longest series, n without lengths -- with lengths their maximum, which comes back in
-    the same read as the flag word.  times: None or what `_times_argument` returned; hours: None or `_times_pack`'s tensor,
-    whose flag bit travels in the same word."""
-    n = x3.shape[2]
+def _batch_to_device(x3, lengths, times, device):
+    """The head of `_pack_checked` and `_pack_dropped`: x3, lengths and the stamps of `times` (None, or what
+    `_times_argument` returned) on `device` -> (x3, lengths, times), the stamps of logical shape (B, n)."""
     x3 = _to_device(x3, device)
     if lengths is not None:
         lengths = _to_device(lengths, device)
     if times is not None:
         t = _to_device(times[0], device)   # (before the pack: its synchronisation covers the copy)
         if t.ndim == 1:
-            t = t.unsqueeze(0).expand(x3.shape[0], n)   # one clock for the batch: batch stride 0, n stamps on the device
+            t = t.unsqueeze(0).expand(x3.shape[0], x3.shape[2])   # one clock for the batch: batch stride 0, n stamps on the device
         times = (t,) + tuple(times[1:])
+    return x3, lengths, times
+
+
+def _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=False, times=None):
+    """`_dense_pack` of the batch on `device` and its flag word's errors -> (x3 and lengths on the device, packs, steps,
+    hours).  steps (want_steps): the longest series, n without lengths -- with lengths their maximum, which comes back in
+    the same read as the flag word.  times: None or what `_times_argument` returned; hours: None or `_times_pack`'s tensor,
+    whose flag bit travels in the same word."""
+    n = x3.shape[2]
+    x3, lengths, times = _batch_to_device(x3, lengths, times, device)
     packs, flag = _dense_pack(torch, x3, lengths, device)
     hours = _times_pack(torch, times, packs[0], flag, device) if times is not None else None
     steps = n
@@ -236,23 +254,16 @@ def _valid_pack(torch, x3, lengths, times, device):
     sample.  offsets: the int64 tensor of B + 1 offsets the channels share.  The buffers are torch allocations the packs
     keep alive."""
     B, C, n = x3.shape
-    x_type = _X_TYPES[str(x3.dtype)]
-    out_dtype = torch.float64 if x_type == _native.TSFA_F64 else torch.float32
-    values = torch.empty((C, B * n), dtype=out_dtype, device=x3.device)
-    offsets = torch.empty(B + 1, dtype=torch.int64, device=x3.device)
+    x_type, values, offsets, flag, lptr, ltype, views = _pack_outputs(torch, x3, lengths, device)
     steps = torch.empty(B * n, dtype=torch.int32, device=x3.device)   # [0, T) is written, T <= B * n
     scratch_bytes = _native.pack_dense_valid_scratch_bytes(B, n)
     scratch = torch.empty(scratch_bytes // 8, dtype=torch.int64, device=x3.device)
-    flag = torch.zeros(1, dtype=torch.int32, device=x3.device)
     timed, stamps = {}, None
     if times is not None:
         t, t_type, tps = times
         stamps = torch.empty((B, n), dtype=t.dtype, device=x3.device)
         timed = dict(t_ptr=t.data_ptr(), t_type=t_type, t_strides=t.stride(), stamps_ptr=stamps.data_ptr())
     _synchronize(torch, device)   # the producer of x, and the fill of the flag word, are done before another stream reads
-    lptr, ltype = None, 0
-    if lengths is not None:
-        lptr, ltype = lengths.data_ptr(), (_native.TSFA_I32 if lengths.dtype == torch.int32 else _native.TSFA_I64)
     _native.pack_dense_valid(x3.data_ptr(), x_type, (B, C, n), x3.stride(), values.data_ptr(), B * n, offsets.data_ptr(),
                              steps.data_ptr(), scratch.data_ptr(), scratch_bytes, flag.data_ptr(), device=device,
                              lengths_ptr=lptr, lengths_type=ltype, **timed)
@@ -262,11 +273,7 @@ def _valid_pack(torch, x3, lengths, times, device):
         hours = torch.empty(B * n, dtype=torch.float64, device=x3.device)
         _native.pack_times(stamps.data_ptr(), t_type, tps, (B, n), (n, 1), offsets.data_ptr(), hours.data_ptr(), flag.data_ptr(),
                            device=device)
-    owner = (values, offsets, flag, x3, lengths)
-    vtype = _native.TSFA_F64 if x_type == _native.TSFA_F64 else _native.TSFA_F32
-    packs = [_native.DensePack(values.data_ptr() + c * B * n * values.element_size(), vtype, offsets.data_ptr(), B, device,
-                               owner=owner) for c in range(C)]
-    return packs, flag, hours, steps, offsets
+    return views(), flag, hours, steps, offsets
 
 
 def _pack_dropped(torch, x3, lengths, device, want_steps=False, times=None):
@@ -274,14 +281,7 @@ def _pack_dropped(torch, x3, lengths, device, want_steps=False, times=None):
     (want_steps; it comes back in the same read as the flag word), hours, steps).  The flag word is always read: a length
     outside [1, n] and a series without a kept step are errors whatever `check_nan` says."""
     n = x3.shape[2]
-    x3 = _to_device(x3, device)
-    if lengths is not None:
-        lengths = _to_device(lengths, device)
-    if times is not None:
-        t = _to_device(times[0], device)
-        if t.ndim == 1:
-            t = t.unsqueeze(0).expand(x3.shape[0], n)
-        times = (t,) + tuple(times[1:])
+    x3, lengths, times = _batch_to_device(x3, lengths, times, device)
     packs, flag, hours, steps, offsets = _valid_pack(torch, x3, lengths, times, device)
     longest = n
     if want_steps:
