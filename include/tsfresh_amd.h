@@ -648,7 +648,8 @@ int tsfa_impute(double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t s
  * HOST routes are left to the caller: the kernel writes NaN, counts the cell, and the caller overwrites p before
  * tsfa_relevance_fdr -- the exact Mann-Whitney distribution (a class or its complement with <= 8 rows, no ties) and every
  * Kolmogorov-Smirnov tail (with_ks, and two-valued columns under a real target) -- unless the *_ks variants below are asked
- * to serve the exact Kolmogorov-Smirnov tail on the device (TSFA_ROUTE_KS_EXACT). */
+ * to serve the exact Kolmogorov-Smirnov tail on the device (TSFA_ROUTE_KS_EXACT), or tsfa_relevance_tails_classes_mwu the exact
+ * Mann-Whitney tail (TSFA_ROUTE_MWU_EXACT). */
 enum tsfa_route {
     TSFA_ROUTE_NONE = 0,           /* constant column: p = NaN */
     TSFA_ROUTE_MWU_NORMAL = 1,
@@ -656,7 +657,8 @@ enum tsfa_route {
     TSFA_ROUTE_KENDALL = 3,
     TSFA_ROUTE_HOST_MWU_EXACT = 4,
     TSFA_ROUTE_HOST_KS = 5,
-    TSFA_ROUTE_KS_EXACT = 6        /* a Kolmogorov-Smirnov cell whose exact tail the device served (ks_tail, below) */
+    TSFA_ROUTE_KS_EXACT = 6,       /* a Kolmogorov-Smirnov cell whose exact tail the device served (ks_tail, below) */
+    TSFA_ROUTE_MWU_EXACT = 7       /* an exact Mann-Whitney cell that the device served (mwu_tail, below); not a HOST route */
 };
 /* X, y_codes, n_classes as tsfa_relevance_classes; with_ks != 0 additionally runs the sweep of tsfa_relevance_classes_ks and
  * routes every real cell to TSFA_ROUTE_HOST_KS.  Device outputs: p[n_cols * n_classes], route[n_cols * n_classes],
@@ -706,6 +708,35 @@ int tsfa_relevance_tails_real_ks(const double *X, int64_t n_rows, int64_t n_cols
                                  int32_t ks_tail, int32_t device, double *p, unsigned char *route, unsigned char *type,
                                  tsfa_relevance_real_col *cols, int64_t *n_hi_device, double *ks_d_device,
                                  int64_t *n_host_cells);
+/* ---- the exact Mann-Whitney tail on the device (csrc/rel_mwu.h) ----
+ * significance_tests.py mannwhitney_pvalue's exact branch, bit for bit.  With m = min(n1, n2), n = max(n1, n2), top = m * n and
+ * k = clamp(int(u), 0, top + 1), u = max(u1, u2):  p = min(max(2.0 * (S_k / total), 0.0), 1.0), where S_k is the number of
+ * arrangements with a statistic >= k (the coefficients of the Gaussian binomial [n + m choose m]_q, exact integers of three
+ * 64-bit limbs), total = C(n + m, m), and the quotient is the correctly rounded float64 of the rational (ties to even).  The
+ * counts depend on (m, n) alone: one workgroup builds them per distinct table, a lane then serves a cell by a lookup and a long
+ * division.  A table is served when 1 <= m <= 8 and top <= TSFA_MWU_EXACT_MAX_TOP.
+ *
+ * tsfa_mwu_tails: n1[n_tables], n2[n_tables] are HOST arrays (the sample sizes of every table); table[n_cells] (the table of a
+ * cell), u[n_cells] (its statistic), p[n_cells] and route[n_cells] are DEVICE arrays.  A cell is served iff route[cell] is
+ * TSFA_ROUTE_HOST_MWU_EXACT on entry, its table index is valid and that table is served: it gets its p and
+ * TSFA_ROUTE_MWU_EXACT.  Nothing of any other cell is written.  *served (optional, host): how many.  Synchronous, on the null
+ * stream. */
+#define TSFA_MWU_EXACT_MAX_TOP (1 << 21)
+int tsfa_mwu_tails(const int64_t *n1, const int64_t *n2, int32_t n_tables, const int32_t *table, const double *u, int64_t n_cells,
+                   int32_t device, double *p, unsigned char *route, int64_t *served);
+enum tsfa_mwu_tail {
+    TSFA_MWU_TAIL_HOST = 0,  /* every exact Mann-Whitney cell is TSFA_ROUTE_HOST_MWU_EXACT: what tsfa_relevance_tails_classes does */
+    TSFA_MWU_TAIL_DEVICE = 1 /* the cells tsfa_mwu_tails serves get their p and TSFA_ROUTE_MWU_EXACT; the rest stay HOST */
+};
+/* tsfa_relevance_tails_classes_ks with the choice of mwu_tail: with TSFA_MWU_TAIL_DEVICE the exact Mann-Whitney cells are
+ * evaluated from the rank sums the sweep left in HBM, and n_host_cells counts what is left.  rank_sums_device
+ * ([n_cols * n_classes]) is an optional caller-owned DEVICE array that receives the rank sums, so that a caller with a few
+ * cells left fetches those instead of the host copies.  Everything else as tsfa_relevance_tails_classes_ks. */
+int tsfa_relevance_tails_classes_mwu(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                     const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail, int32_t mwu_tail,
+                                     int32_t device, double *p, unsigned char *route, unsigned char *type, tsfa_relevance_col *cols,
+                                     double *rank_sums, int64_t *hi_counts, double *ks_d, double *ks_d_device,
+                                     double *rank_sums_device, int64_t *n_host_cells);
 /* statsmodels' multipletests "fdr_bh" / "fdr_by" per table and relevance.py's combination of the tables.  All pointers are
  * device pointers.  p[n_cols * n_tables] (n_tables <= 256: the classes, or 1), type[n_cols].  Per table the columns whose type
  * is not 0 are tested (m of them); their p-values are sorted (NaN last, never rejected) and everything up to the largest

@@ -30,9 +30,12 @@ TSFA_PACK_KEEP_SORT = 1
 TSFA_HOST, TSFA_DEVICE = 0, 1
 # enum tsfa_route: who evaluates the tail of a p-value cell (tsfa_relevance_tails_*)
 (TSFA_ROUTE_NONE, TSFA_ROUTE_MWU_NORMAL, TSFA_ROUTE_FISHER, TSFA_ROUTE_KENDALL, TSFA_ROUTE_HOST_MWU_EXACT,
- TSFA_ROUTE_HOST_KS, TSFA_ROUTE_KS_EXACT) = range(7)
+ TSFA_ROUTE_HOST_KS, TSFA_ROUTE_KS_EXACT, TSFA_ROUTE_MWU_EXACT) = range(8)
 # enum tsfa_ks_tail: who evaluates the exact Kolmogorov-Smirnov tails (tsfa_relevance_tails_*_ks)
 TSFA_KS_TAIL_HOST, TSFA_KS_TAIL_DEVICE = 0, 1
+# enum tsfa_mwu_tail: who evaluates the exact Mann-Whitney tails (tsfa_relevance_tails_classes_mwu), and the cap on m * n
+TSFA_MWU_TAIL_HOST, TSFA_MWU_TAIL_DEVICE = 0, 1
+TSFA_MWU_EXACT_MAX_TOP = 1 << 21
 
 
 
@@ -146,6 +149,9 @@ PROTOTYPES = {
                                               ptr, P(i64)]),
     "tsfa_relevance_tails_real_ks": (i32, [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i64, f64, f64, i32, i32, ptr, ptr, ptr, ptr,
                                            ptr, ptr, P(i64)]),
+    "tsfa_mwu_tails": (i32, [ptr, ptr, i32, ptr, ptr, i64, i32, ptr, ptr, P(i64)]),
+    "tsfa_relevance_tails_classes_mwu": (i32, [ptr, i64, i64, i64, i32, ptr, i32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr,
+                                               ptr, ptr, ptr, P(i64)]),
     "tsfa_relevance_fdr": (i32, [ptr, ptr, i64, i32, f64, f64, i32, i32, i32, ptr, ptr, ptr, ptr]),
     "tsfa_compact_mask": (i32, [ptr, i64, ptr, P(i64), i32]),
     "tsfa_gather_columns_device": (i32, [ptr, i64, i64, ptr, i64, ptr, i64, i32]),
@@ -1161,14 +1167,39 @@ def ks_tails(n1_ptr, n2_ptr, d_ptr, n_cells, p_ptr, route_ptr, device=0):
     _check(lib, lib.tsfa_ks_tails(n1_ptr, n2_ptr, d_ptr, int(n_cells), int(device), p_ptr, route_ptr))
 
 
+def _mwu_tail_code(mwu_tail):
+    if mwu_tail not in ("host", "device"):
+        raise ValueError("mwu_tail must be 'host' or 'device', not {!r}".format(mwu_tail))
+    return TSFA_MWU_TAIL_DEVICE if mwu_tail == "device" else TSFA_MWU_TAIL_HOST
+
+
+def mwu_tails(n1, n2, table_ptr, u_ptr, n_cells, p_ptr, route_ptr, device=0):
+    """tsfa_mwu_tails: the exact Mann-Whitney tails of n_cells cells (table int32, u float64: device arrays) of the tables whose
+    sample sizes are the host arrays n1, n2, into the device arrays p [n_cells] float64 and route [n_cells] uint8.  Only cells
+    whose route is TSFA_ROUTE_HOST_MWU_EXACT on entry are looked at; a served one gets its p and TSFA_ROUTE_MWU_EXACT.
+    -> the cells served."""
+    lib = load()
+    n1 = np.ascontiguousarray(n1, dtype=np.int64)
+    n2 = np.ascontiguousarray(n2, dtype=np.int64)
+    if n1.ndim != 1 or n1.shape != n2.shape:
+        raise ValueError("n1 and n2: one entry per table")
+    served = ctypes.c_int64(0)
+    _check(lib, lib.tsfa_mwu_tails(n1.ctypes.data, n2.ctypes.data, int(n1.shape[0]), table_ptr, u_ptr, int(n_cells), int(device), p_ptr,
+                                   route_ptr, ctypes.byref(served)))
+    return int(served.value)
+
+
 def relevance_tails_classes(x_ptr, n_rows, n_cols, ld, y_codes, n_classes, p_ptr, route_ptr, type_ptr, device=0, with_ks=False,
-                            want_stats=False, ks_tail="host", ks_d_ptr=None):
+                            want_stats=False, ks_tail="host", ks_d_ptr=None, mwu_tail="host", rank_sums_ptr=None):
     """The class tables of the device matrix at x_ptr, left on the device: p [m, C] float64, route [m, C] uint8, type [m]
     uint8 -> (host-route cells, statistics).  statistics (want_stats): what `relevance_classes` returns, for the caller's
     host routes; None otherwise (nothing but the cell count is copied).  ks_tail="device" (tsfa_relevance_tails_classes_ks)
     serves the exact Kolmogorov-Smirnov tails on the device; ks_d_ptr: an optional device array [m, C] float64 that receives
-    the Kolmogorov-Smirnov distances (with_ks), and the statistics then come without them."""
+    the Kolmogorov-Smirnov distances (with_ks), and the statistics then come without them.  mwu_tail="device"
+    (tsfa_relevance_tails_classes_mwu) serves the exact Mann-Whitney tails on the device; rank_sums_ptr: an optional device
+    array [m, C] float64 that receives the rank sums."""
     ks_code = _ks_tail_code(ks_tail)
+    mwu_code = _mwu_tail_code(mwu_tail)
     lib = load()
     y_codes = np.ascontiguousarray(y_codes, dtype=np.int32)
     if y_codes.shape != (n_rows,):
@@ -1182,7 +1213,10 @@ def relevance_tails_classes(x_ptr, n_rows, n_cols, ld, y_codes, n_classes, p_ptr
         ks_d = np.zeros((n_cols, n_classes), dtype=np.float64) if (with_ks and ks_d_ptr is None) else None
     stats_ptrs = [None if a is None else a.ctypes.data for a in (cols, rank_sums, hi_counts, ks_d)]
     head = (x_ptr, int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_codes.ctypes.data, int(n_classes), int(bool(with_ks)))
-    if ks_code == TSFA_KS_TAIL_HOST and ks_d_ptr is None:
+    if mwu_code == TSFA_MWU_TAIL_DEVICE or rank_sums_ptr is not None:
+        _check(lib, lib.tsfa_relevance_tails_classes_mwu(*head, ks_code, mwu_code, int(device), p_ptr, route_ptr, type_ptr,
+                                                         *stats_ptrs, ks_d_ptr, rank_sums_ptr, ctypes.byref(n_host)))
+    elif ks_code == TSFA_KS_TAIL_HOST and ks_d_ptr is None:
         _check(lib, lib.tsfa_relevance_tails_classes(*head, int(device), p_ptr, route_ptr, type_ptr, *stats_ptrs,
                                                      ctypes.byref(n_host)))
     else:

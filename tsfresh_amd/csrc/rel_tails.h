@@ -13,7 +13,8 @@
 // Every cell carries a route byte (enum below).  The two HOST routes are not served here: the exact Mann-Whitney
 // distribution is a big-integer recurrence and the Kolmogorov-Smirnov tail a lattice walk (tsfa_ks_outer_prob) or
 // scipy's kstwo; the kernel writes NaN there and the caller fills those cells in before the FDR step.  (rel_ks.h serves the
-// lattice walk on the device where the caller asks for it: TSFA_ROUTE_KS_EXACT.)
+// lattice walk on the device where the caller asks for it: TSFA_ROUTE_KS_EXACT; rel_mwu.h the exact Mann-Whitney
+// distribution: TSFA_ROUTE_MWU_EXACT.)
 //
 // Compiled two ways like roll_device.h / pack_dense.h: by hipcc for gfx950 and by g++ -DTSFA_EMUL
 // (tests/emul/emul_rel_tails.cpp).  In the emulation one host thread is a workgroup and the lanes are looped: a per-lane

@@ -15,12 +15,15 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/tsfresh_amd.h"
 #include "rel_tails.h"
 #include "rel_ks.h"
+#include "rel_mwu.h"
 #include "tsfa_devmem.h"
 
 #define REL_NT 1024
@@ -725,11 +728,133 @@ static int ks_tail_check(int32_t ks_tail, const char *who) {
     return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": ks_tail must be TSFA_KS_TAIL_HOST or TSFA_KS_TAIL_DEVICE").c_str());
 }
 
+// ---- the exact Mann-Whitney tail (rel_mwu.h): the TSFA_ROUTE_HOST_MWU_EXACT cells of the tables the device serves ----
+// a distinct (m, n): where its table of prefix sums starts in the block of tables, and where its two buffers start in the
+// scratch block (words; -1: the buffers are LDS)
+struct RmJob {
+    int64_t m, n, off, scratch;
+};
+
+// workgroup = job; the dynamic LDS holds the scan rows and, for a job in LDS form, both buffers
+__global__ void __launch_bounds__(RM_NT) k_mwu_build(const RmJob *__restrict__ jobs, uint64_t *__restrict__ tabs, uint64_t *__restrict__ scratch) {
+    extern __shared__ uint64_t rm_smem[];
+    const RmJob j = jobs[blockIdx.x];
+    const int64_t words = rm_table_words(j.m, j.n);
+    uint64_t *buf0 = (j.scratch < 0) ? rm_smem + RM_SCAN_WORDS : scratch + j.scratch;
+    rm_build(j.m, j.n, buf0, buf0 + words, rm_smem, tabs + j.off);
+}
+
+// thread = cell
+__global__ void __launch_bounds__(RT_THREADS) k_mwu_cells(RmCells s, const RmTable *__restrict__ tables, int32_t n_tables,
+                                                          const uint64_t *__restrict__ tabs, int64_t n_cells, double *p, unsigned char *route,
+                                                          unsigned long long *__restrict__ cnt) {
+    const int64_t cell = (int64_t)blockIdx.x * RT_THREADS + threadIdx.x;
+    if (cell >= n_cells) return;
+    if (rm_cell(s, tables, n_tables, tabs, cell, p, route)) atomicAdd(cnt, 1ull);
+}
+
+#define RM_SCRATCH_WORDS ((int64_t)1 << 27)   // 1 GiB: the jobs in scratch form are built in launches of at most this much (or one job)
+
+// The Mann-Whitney stage on the null stream of the current device: every TSFA_ROUTE_HOST_MWU_EXACT cell of route[n_cells] whose
+// table (n1[t], n2[t]: host) rel_mwu.h serves gets its p and TSFA_ROUTE_MWU_EXACT.  Synchronous; *served: how many.
+static int mwu_tails_run(const int64_t *n1, const int64_t *n2, int32_t n_tables, const RmCells &s, int64_t n_cells, double *p,
+                         unsigned char *route, int64_t *served) {
+    *served = 0;
+    if (n_cells == 0 || n_tables == 0) return TSFA_OK;
+    std::vector<RmTable> tables((size_t)n_tables);
+    std::vector<RmJob> jobs;
+    std::map<std::pair<int64_t, int64_t>, size_t> seen;
+    int64_t tab_words = 0;
+    for (int32_t t = 0; t < n_tables; ++t) {
+        tables[(size_t)t] = {n1[t], n2[t], -1};
+        if (!rm_served(n1[t], n2[t])) continue;
+        const int64_t m = (n1[t] < n2[t]) ? n1[t] : n2[t], n = (n1[t] < n2[t]) ? n2[t] : n1[t];
+        const auto found = seen.find({m, n});
+        if (found == seen.end()) {
+            seen[{m, n}] = jobs.size();
+            jobs.push_back({m, n, tab_words, -1});
+            tab_words += rm_table_words(m, n);
+        }
+        tables[(size_t)t].off = jobs[seen[{m, n}]].off;
+    }
+    if (jobs.empty()) return TSFA_OK;
+    // the launches: consecutive jobs whose scratch fits RM_SCRATCH_WORDS together; the scratch is the largest launch's, and is
+    // only allocated when a job needs it
+    std::vector<size_t> launch_end;
+    int64_t used = 0, scratch_words = 0, lds_elems = 0;
+    for (size_t q = 0; q < jobs.size(); ++q) {
+        const int64_t need = rm_in_lds(jobs[q].m, jobs[q].n) ? 0 : 2 * rm_table_words(jobs[q].m, jobs[q].n);
+        if (need && used && used + need > RM_SCRATCH_WORDS) {
+            launch_end.push_back(q);
+            used = 0;
+        }
+        if (need) {
+            jobs[q].scratch = used;
+            used += need;
+            if (used > scratch_words) scratch_words = used;
+        } else if (jobs[q].m * jobs[q].n + 1 > lds_elems) {
+            lds_elems = jobs[q].m * jobs[q].n + 1;
+        }
+    }
+    launch_end.push_back(jobs.size());
+    const size_t lds = (size_t)(RM_SCAN_WORDS + 2 * RM_LIMBS * lds_elems) * sizeof(uint64_t);
+    unsigned long long cnt = 0ull;
+    DevPtr<uint64_t> dtabs, dscratch;
+    DevPtr<RmTable> dtables;
+    DevPtr<RmJob> djobs;
+    DevPtr<unsigned long long> dcnt;
+    HIP_TRY_MALLOC(dtabs, (size_t)tab_words * sizeof(uint64_t));
+    HIP_TRY_MALLOC(dtables, tables.size() * sizeof(RmTable));
+    HIP_TRY_MALLOC(djobs, jobs.size() * sizeof(RmJob));
+    HIP_TRY_MALLOC(dcnt, sizeof(cnt));
+    if (scratch_words) HIP_TRY_MALLOC(dscratch, (size_t)scratch_words * sizeof(uint64_t));
+    HIP_TRY(hipMemcpy(dtables.get(), tables.data(), tables.size() * sizeof(RmTable), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(djobs.get(), jobs.data(), jobs.size() * sizeof(RmJob), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dcnt.get(), 0, sizeof(cnt)));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_mwu_build, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    size_t q0 = 0;
+    for (const size_t q1 : launch_end) {
+        k_mwu_build<<<dim3((unsigned)(q1 - q0)), RM_NT, lds, 0>>>(djobs.get() + q0, dtabs.get(), dscratch.get());
+        HIP_TRY(hipGetLastError());
+        q0 = q1;
+    }
+    k_mwu_cells<<<dim3((unsigned)((n_cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(s, dtables.get(), n_tables, dtabs.get(), n_cells, p,
+                                                                                             route, dcnt.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&cnt, dcnt.get(), sizeof(cnt), hipMemcpyDeviceToHost));
+    *served = (int64_t)cnt;
+    return TSFA_OK;
+}
+
+extern "C" int tsfa_mwu_tails(const int64_t *n1, const int64_t *n2, int32_t n_tables, const int32_t *table, const double *u, int64_t n_cells,
+                              int32_t device, double *p, unsigned char *route, int64_t *served) {
+    if (served) *served = 0;
+    if (n_cells < 0 || n_tables < 0 || (n_tables > 0 && (!n1 || !n2)) || (n_cells > 0 && (!table || !u || !p || !route)))
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_mwu_tails: null pointer or bad shape");
+    int rc = rel_check_device(device, "tsfa_mwu_tails");
+    if (rc || n_cells == 0) return rc;
+    HIP_TRY(hipSetDevice(device));
+    RmCells s = {};
+    s.table = table;
+    s.u = u;
+    int64_t done = 0;
+    rc = mwu_tails_run(n1, n2, n_tables, s, n_cells, p, route, &done);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (served) *served = done;
+    return TSFA_OK;
+}
+
+static int mwu_tail_check(int32_t mwu_tail, const char *who) {
+    if (mwu_tail == TSFA_MWU_TAIL_HOST || mwu_tail == TSFA_MWU_TAIL_DEVICE) return TSFA_OK;
+    return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": mwu_tail must be TSFA_MWU_TAIL_HOST or TSFA_MWU_TAIL_DEVICE").c_str());
+}
+
 static int relevance_tails_classes_impl(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                        const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail, int32_t device,
-                                        double *p, unsigned char *route, unsigned char *type, tsfa_relevance_col *cols,
+                                        const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail, int32_t mwu_tail,
+                                        int32_t device, double *p, unsigned char *route, unsigned char *type, tsfa_relevance_col *cols,
                                         double *rank_sums, int64_t *hi_counts, double *ks_d, double *ks_d_device,
-                                        int64_t *n_host_cells) {
+                                        double *rank_sums_device, int64_t *n_host_cells) {
     if (n_host_cells) *n_host_cells = 0;
     if (n_cols > 0 && (!p || !route || !type)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: null output pointer");
     if ((ks_d || ks_d_device) && !with_ks) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: ks_d without with_ks");
@@ -767,12 +892,27 @@ static int relevance_tails_classes_impl(const double *X, int64_t n_rows, int64_t
         if (rc) return rc;
         nh -= (unsigned long long)served;
     }
+    if (!with_ks && mwu_tail == TSFA_MWU_TAIL_DEVICE && nh > 0) {
+        std::vector<int64_t> rest((size_t)n_classes);
+        for (int32_t k = 0; k < n_classes; ++k) rest[(size_t)k] = n_rows - class_n[(size_t)k];
+        RmCells s = {};
+        s.rank_sums = d.drs.get();
+        s.class_n = dcn.get();
+        s.n_rows = n_rows;
+        s.n_classes = n_classes;
+        int64_t served = 0;
+        rc = mwu_tails_run(class_n.data(), rest.data(), n_classes, s, cells, p, route, &served);
+        if (rc) return rc;
+        nh -= (unsigned long long)served;
+    }
     if (n_host_cells) *n_host_cells = (int64_t)nh;
     if (cols) HIP_TRY(hipMemcpy(cols, d.dcols.get(), (size_t)n_cols * sizeof(tsfa_relevance_col), hipMemcpyDeviceToHost));
     if (rank_sums) HIP_TRY(hipMemcpy(rank_sums, d.drs.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
     if (hi_counts) HIP_TRY(hipMemcpy(hi_counts, d.dhc.get(), (size_t)n_cols * n_classes * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (ks_d) HIP_TRY(hipMemcpy(ks_d, d.dks.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
     if (ks_d_device) HIP_TRY(hipMemcpy(ks_d_device, d.dks.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToDevice));
+    if (rank_sums_device)
+        HIP_TRY(hipMemcpy(rank_sums_device, d.drs.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToDevice));
     return TSFA_OK;
 }
 
@@ -780,8 +920,8 @@ extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int
                                             const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t device, double *p,
                                             unsigned char *route, unsigned char *type, tsfa_relevance_col *cols, double *rank_sums,
                                             int64_t *hi_counts, double *ks_d, int64_t *n_host_cells) {
-    return relevance_tails_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, with_ks, TSFA_KS_TAIL_HOST, device, p, route,
-                                        type, cols, rank_sums, hi_counts, ks_d, nullptr, n_host_cells);
+    return relevance_tails_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, with_ks, TSFA_KS_TAIL_HOST, TSFA_MWU_TAIL_HOST,
+                                        device, p, route, type, cols, rank_sums, hi_counts, ks_d, nullptr, nullptr, n_host_cells);
 }
 
 extern "C" int tsfa_relevance_tails_classes_ks(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
@@ -791,8 +931,20 @@ extern "C" int tsfa_relevance_tails_classes_ks(const double *X, int64_t n_rows, 
                                                double *ks_d_device, int64_t *n_host_cells) {
     if (n_host_cells) *n_host_cells = 0;
     if (int rc = ks_tail_check(ks_tail, "tsfa_relevance_tails_classes_ks")) return rc;
-    return relevance_tails_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, with_ks, ks_tail, device, p, route, type, cols,
-                                        rank_sums, hi_counts, ks_d, ks_d_device, n_host_cells);
+    return relevance_tails_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, with_ks, ks_tail, TSFA_MWU_TAIL_HOST, device, p,
+                                        route, type, cols, rank_sums, hi_counts, ks_d, ks_d_device, nullptr, n_host_cells);
+}
+
+extern "C" int tsfa_relevance_tails_classes_mwu(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                                const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail,
+                                                int32_t mwu_tail, int32_t device, double *p, unsigned char *route, unsigned char *type,
+                                                tsfa_relevance_col *cols, double *rank_sums, int64_t *hi_counts, double *ks_d,
+                                                double *ks_d_device, double *rank_sums_device, int64_t *n_host_cells) {
+    if (n_host_cells) *n_host_cells = 0;
+    if (int rc = ks_tail_check(ks_tail, "tsfa_relevance_tails_classes_mwu")) return rc;
+    if (int rc = mwu_tail_check(mwu_tail, "tsfa_relevance_tails_classes_mwu")) return rc;
+    return relevance_tails_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, with_ks, ks_tail, mwu_tail, device, p, route, type,
+                                        cols, rank_sums, hi_counts, ks_d, ks_d_device, rank_sums_device, n_host_cells);
 }
 
 static int relevance_tails_real_impl(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,

@@ -19,6 +19,11 @@ array before the FDR step.
 left for the host then are the cells beyond 10 000 rows (scipy's `kstwo`), the rare exact value that rounding pushes outside
 [0, 1] (`ks_2samp_pvalue` falls through to `kstwo` there, and so does this), and the exact Mann-Whitney cells; only the
 triples of those cells are fetched.
+
+`mwu_tail="device"` moves the exact Mann-Whitney tail onto the GPU (`csrc/rel_mwu.h`, route `TSFA_ROUTE_MWU_EXACT`): the
+arrangement counts of a class are built once, in exact integers, and every cell of that class is a lookup and one correctly
+rounded division, equal to `mannwhitney_pvalue` bit for bit.  What is left for the host are classes whose smaller side times
+the larger exceeds `TSFA_MWU_EXACT_MAX_TOP` (8 rows against more than 262 144); only the rank sums of those cells are fetched.
 """
 import warnings
 
@@ -111,10 +116,12 @@ def impute_tensor(X):
 
 
 def _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant, test_for_binary_target_real_feature, fdr_level,
-               hypotheses_independent, check_nan, ks_tail="host"):
+               hypotheses_independent, check_nan, ks_tail="host", mwu_tail="host"):
     from tsfresh_amd.feature_selection.significance_tests import ks_2samp_pvalue, mannwhitney_pvalue, target_tie_statistics
     if ks_tail not in ("host", "device"):
         raise ValueError("ks_tail must be 'host' or 'device', not {!r}".format(ks_tail))
+    if mwu_tail not in ("host", "device"):
+        raise ValueError("mwu_tail must be 'host' or 'device', not {!r}".format(mwu_tail))
     on_device = (ks_tail == "device")
     n, m = X.shape
     y = _target(torch, y, n)
@@ -176,6 +183,19 @@ def _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant,
                 k, dist = (flat % T).cpu().numpy(), ks_dev.view(-1)[flat].cpu().numpy()
                 vals = [ks_2samp_pvalue(class_n[k[q]], n - class_n[k[q]], dist[q]) for q in range(len(k))]
                 p.view(-1)[flat] = torch.as_tensor(vals, dtype=torch.float64, device=dev)
+        elif mwu_tail == "device" and not smir:
+            # the exact Mann-Whitney cells are served where the rank sums are; of the cells left to the host (a class beyond
+            # the cap) only the rank sums are fetched, and an exact cell has no ties
+            small = bool(((class_n <= 8) | (n - class_n <= 8)).any())
+            rs_dev = torch.empty((m, T), dtype=torch.float64, device=dev) if small else None
+            host_cells, _ = _native.relevance_tails_classes(X.data_ptr(), n, m, _ld(X), codes, T, p.data_ptr(), routes.data_ptr(),
+                                                            types.data_ptr(), device=device, mwu_tail="device",
+                                                            rank_sums_ptr=rs_dev.data_ptr() if small else None)
+            if host_cells:
+                flat = torch.nonzero(routes.view(-1) == _native.TSFA_ROUTE_HOST_MWU_EXACT).view(-1)
+                k, rs = (flat % T).cpu().numpy(), rs_dev.view(-1)[flat].cpu().numpy()
+                vals = [mannwhitney_pvalue(rs[q], class_n[k[q]], n - class_n[k[q]], 0) for q in range(len(k))]
+                p.view(-1)[flat] = torch.as_tensor(vals, dtype=torch.float64, device=dev)
         else:
             want_stats = smir or bool(((class_n <= 8) | (n - class_n <= 8)).any())
             host_cells, stats_ = _native.relevance_tails_classes(X.data_ptr(), n, m, _ld(X), codes, T, p.data_ptr(), routes.data_ptr(),
@@ -234,7 +254,7 @@ def _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant,
 
 def calculate_relevance_tensor(X, y, columns=None, ml_task="auto", multiclass=False, n_significant=1,
                                test_for_binary_target_real_feature="mann", fdr_level=0.05, hypotheses_independent=False,
-                               device=None, check_nan=True, ks_tail="host"):
+                               device=None, check_nan=True, ks_tail="host", mwu_tail="host"):
     """`calculate_relevance_table` for a feature matrix held as a tensor; every result stays on the GPU.
 
     :param X: `torch.float64` tensor `[n, m]`.  A CPU tensor or a numpy array is moved to `device` with torch; another dtype, or a
@@ -254,18 +274,23 @@ def calculate_relevance_tensor(X, y, columns=None, ml_task="auto", multiclass=Fa
         (default): `ks_2samp_pvalue`, one cell at a time.  "device": the GPU, for samples of at most 10 000 rows, with equal
         p-values (`routes` then shows `TSFA_ROUTE_KS_EXACT`, and `host_cells` counts what is left to the host).  Anything else
         raises `ValueError`.
+    :param mwu_tail: who evaluates the exact Mann-Whitney tails (classification under "mann": a class or its complement with
+        at most 8 rows, a column without ties).  "host" (default): `mannwhitney_pvalue`, one cell at a time, which rebuilds the
+        arrangement counts for every cell.  "device": the GPU builds the counts once per class, with equal p-values (`routes`
+        then shows `TSFA_ROUTE_MWU_EXACT`, and `host_cells` counts what is left: classes beyond `TSFA_MWU_EXACT_MAX_TOP`).
+        Anything else raises `ValueError`.
     :return: a `RelevanceTensors`.
 
     Synchronous, like `extract_features_tensor`: X is read after everything queued on torch's current stream has finished."""
     import torch
     X, device = _matrix(torch, X, device)
     return _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant, test_for_binary_target_real_feature,
-                      fdr_level, hypotheses_independent, check_nan, ks_tail)
+                      fdr_level, hypotheses_independent, check_nan, ks_tail, mwu_tail)
 
 
 def select_features_tensor(X, y, columns=None, ml_task="auto", multiclass=False, n_significant=1,
                            test_for_binary_target_real_feature="mann", fdr_level=0.05, hypotheses_independent=False, device=None,
-                           check_nan=True, ks_tail="host"):
+                           check_nan=True, ks_tail="host", mwu_tail="host"):
     """`select_features` for a feature matrix held as a tensor: the relevant columns, gathered on the GPU.
 
     Parameters as in `calculate_relevance_tensor`.
@@ -278,7 +303,7 @@ def select_features_tensor(X, y, columns=None, ml_task="auto", multiclass=False,
     import torch
     X, device = _matrix(torch, X, device)
     res = _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant, test_for_binary_target_real_feature,
-                     fdr_level, hypotheses_independent, check_nan, ks_tail)
+                     fdr_level, hypotheses_independent, check_nan, ks_tail, mwu_tail)
     n, m = X.shape
     indices = torch.empty(m, dtype=torch.int32, device=X.device)
     _synchronize(torch, device)
@@ -295,14 +320,15 @@ def select_features_tensor(X, y, columns=None, ml_task="auto", multiclass=False,
 def extract_relevant_features_tensor(x, y, lengths=None, kinds=None, channels_last=False, default_fc_parameters=None,
                                      kind_to_fc_parameters=None, ml_task="auto", multiclass=False, n_significant=1,
                                      test_for_binary_target_real_feature="mann", fdr_level=0.05, hypotheses_independent=False,
-                                     device=None, check_nan=True, ks_tail="host", nan_policy="raise", times=None, time_unit="ns"):
+                                     device=None, check_nan=True, ks_tail="host", mwu_tail="host", nan_policy="raise", times=None,
+                                     time_unit="ns"):
     """`extract_relevant_features` for a batch held as a tensor: `extract_features_tensor`, `impute_tensor` and
     `select_features_tensor` on one matrix that never leaves the GPU.
 
     :param x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device, check_nan: as in
         `extract_features_tensor` (check_nan is about the samples; the imputed matrix holds no NaN).
-    :param y: one target value per series, as in `calculate_relevance_tensor`; the selection options (`ks_tail` among them)
-        likewise.
+    :param y: one target value per series, as in `calculate_relevance_tensor`; the selection options (`ks_tail` and `mwu_tail`
+        among them) likewise.
     :param times, time_unit: as in `extract_features_tensor`: the batch's clock, which adds the `linear_trend_timewise`
         columns to the matrix the selection runs on.
     :param nan_policy: as in `extract_features_tensor`: "drop" extracts from the steps the wide frame keeps after
@@ -313,6 +339,8 @@ def extract_relevant_features_tensor(x, y, lengths=None, kinds=None, channels_la
     from tsfresh_amd.tensor import extract_features_tensor
     if ks_tail not in ("host", "device"):   # before the extraction runs
         raise ValueError("ks_tail must be 'host' or 'device', not {!r}".format(ks_tail))
+    if mwu_tail not in ("host", "device"):
+        raise ValueError("mwu_tail must be 'host' or 'device', not {!r}".format(mwu_tail))
     features, columns = extract_features_tensor(x, lengths=lengths, kinds=kinds, channels_last=channels_last,
                                                 default_fc_parameters=default_fc_parameters,
                                                 kind_to_fc_parameters=kind_to_fc_parameters, device=device, check_nan=check_nan,
@@ -322,5 +350,6 @@ def extract_relevant_features_tensor(x, y, lengths=None, kinds=None, channels_la
                                                 n_significant=n_significant,
                                                 test_for_binary_target_real_feature=test_for_binary_target_real_feature,
                                                 fdr_level=fdr_level, hypotheses_independent=hypotheses_independent,
-                                                device=features.device.index, check_nan=False, ks_tail=ks_tail)
+                                                device=features.device.index, check_nan=False, ks_tail=ks_tail,
+                                                mwu_tail=mwu_tail)
     return selected, names
