@@ -641,15 +641,15 @@ int tsfa_impute(double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t s
  * The chain impute -> relevance table -> selection for a matrix that stays in HBM: the statistics of tsfa_relevance_*
  * are not copied out but turned into p-values where they are, the Benjamini-Hochberg / Benjamini-Yekutieli step-up runs
  * on the p-value array, and the selected columns are gathered into another device matrix.  What comes back to the host is
- * the count of host-route cells, the count of selected columns, and whatever the caller asks for.
+ * the count of host-route cells and the count of selected columns.
  *
  * Every p-value cell has a route: who evaluates its tail (significance_tests.py mannwhitney_pvalue / fisher_exact_pvalue /
- * kendall_pvalue restated in float64; Fisher by one wavefront per cell, the closed forms by one lane per cell).  The two
- * HOST routes are left to the caller: the kernel writes NaN, counts the cell, and the caller overwrites p before
- * tsfa_relevance_fdr -- the exact Mann-Whitney distribution (a class or its complement with <= 8 rows, no ties) and every
- * Kolmogorov-Smirnov tail (with_ks, and two-valued columns under a real target) -- unless the *_ks variants below are asked
- * to serve the exact Kolmogorov-Smirnov tail on the device (TSFA_ROUTE_KS_EXACT), or tsfa_relevance_tails_classes_mwu the exact
- * Mann-Whitney tail (TSFA_ROUTE_MWU_EXACT). */
+ * kendall_pvalue restated in float64; Fisher by one wavefront per cell, the closed forms by one lane per cell).  Two kinds of
+ * cell have no closed form: the exact Mann-Whitney distribution (a class or its complement with <= 8 rows, no ties) and every
+ * Kolmogorov-Smirnov tail (with_ks, and two-valued columns under a real target).  ks_tail and mwu_tail say who serves them.
+ * HOST: the cell gets NaN and its HOST route, is counted, and the caller overwrites p before tsfa_relevance_fdr.  DEVICE: the
+ * cells that tsfa_ks_tails / tsfa_mwu_tails (below) serve are evaluated from the statistics the sweep left in HBM and get
+ * TSFA_ROUTE_KS_EXACT / TSFA_ROUTE_MWU_EXACT; the rest stay HOST cells. */
 enum tsfa_route {
     TSFA_ROUTE_NONE = 0,           /* constant column: p = NaN */
     TSFA_ROUTE_MWU_NORMAL = 1,
@@ -657,25 +657,37 @@ enum tsfa_route {
     TSFA_ROUTE_KENDALL = 3,
     TSFA_ROUTE_HOST_MWU_EXACT = 4,
     TSFA_ROUTE_HOST_KS = 5,
-    TSFA_ROUTE_KS_EXACT = 6,       /* a Kolmogorov-Smirnov cell whose exact tail the device served (ks_tail, below) */
-    TSFA_ROUTE_MWU_EXACT = 7       /* an exact Mann-Whitney cell that the device served (mwu_tail, below); not a HOST route */
+    TSFA_ROUTE_KS_EXACT = 6,       /* a Kolmogorov-Smirnov cell whose exact tail the device served (ks_tail) */
+    TSFA_ROUTE_MWU_EXACT = 7       /* an exact Mann-Whitney cell that the device served (mwu_tail); not a HOST route */
 };
-/* X, y_codes, n_classes as tsfa_relevance_classes; with_ks != 0 additionally runs the sweep of tsfa_relevance_classes_ks and
- * routes every real cell to TSFA_ROUTE_HOST_KS.  Device outputs: p[n_cols * n_classes], route[n_cols * n_classes],
- * type[n_cols] (0 constant, 1 binary, 2 real).  Optional host outputs (NULL: not copied): cols, rank_sums, hi_counts, ks_d
- * (only with with_ks) as tsfa_relevance_classes_ks fills them, and n_host_cells, the number of HOST-route cells.
- * Synchronous, on the null stream. */
+enum tsfa_ks_tail {
+    TSFA_KS_TAIL_HOST = 0,  /* every Kolmogorov-Smirnov cell is TSFA_ROUTE_HOST_KS */
+    TSFA_KS_TAIL_DEVICE = 1 /* the cells tsfa_ks_tails serves get their p and TSFA_ROUTE_KS_EXACT; the rest stay HOST_KS */
+};
+enum tsfa_mwu_tail {
+    TSFA_MWU_TAIL_HOST = 0,  /* every exact Mann-Whitney cell is TSFA_ROUTE_HOST_MWU_EXACT */
+    TSFA_MWU_TAIL_DEVICE = 1 /* the cells tsfa_mwu_tails serves get their p and TSFA_ROUTE_MWU_EXACT; the rest stay HOST */
+};
+/* The class tables.  X, y_codes, n_classes as tsfa_relevance_classes; with_ks != 0 additionally runs the sweep of
+ * tsfa_relevance_classes_ks and makes every real cell a Kolmogorov-Smirnov cell (there is then no Mann-Whitney cell, and
+ * mwu_tail has no effect; without with_ks, ks_tail has none).  Device outputs: p[n_cols * n_classes], route[n_cols * n_classes],
+ * type[n_cols] (0 constant, 1 binary, 2 real).  rank_sums_device and ks_d_device (the latter only with with_ks) are optional
+ * caller-owned DEVICE arrays [n_cols * n_classes] that receive the rank sums / the Kolmogorov-Smirnov distances, so that a
+ * caller with HOST cells left fetches the statistics of those cells alone (the sample sizes of a cell are its class count and
+ * the rest of the rows).  n_host_cells (optional, host): the number of HOST-route cells left.  Nothing else is copied to the
+ * host: tsfa_relevance_classes(_ks) hand the statistics out there.  Synchronous, on the null stream. */
 int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                 const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t device, double *p,
-                                 unsigned char *route, unsigned char *type, tsfa_relevance_col *cols, double *rank_sums,
-                                 int64_t *hi_counts, double *ks_d, int64_t *n_host_cells);
+                                 const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail, int32_t mwu_tail,
+                                 int32_t device, double *p, unsigned char *route, unsigned char *type, double *rank_sums_device,
+                                 double *ks_d_device, int64_t *n_host_cells);
 /* The same for a real target (y_rank, y_perm, y_end as tsfa_relevance_real; ytie, y0, y1: the target's tied pairs,
- * sum t(t-1)(t-2) and sum t(t-1)(2t+5) over its tie groups).  Device outputs p[n_cols], route[n_cols], type[n_cols]; optional
- * host outputs cols[n_cols] and n_host_cells. */
+ * sum t(t-1)(t-2) and sum t(t-1)(2t+5) over its tie groups): its only cells without a closed form are the Kolmogorov-Smirnov
+ * cells of the two-valued columns.  Device outputs p[n_cols], route[n_cols], type[n_cols]; n_hi_device / ks_d_device: optional
+ * caller-owned DEVICE arrays [n_cols] that receive n_hi and ks_d of tsfa_relevance_real_col; n_host_cells as above. */
 int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
                               const int32_t *y_perm, const unsigned char *y_end, int64_t ytie, double y0, double y1,
-                              int32_t device, double *p, unsigned char *route, unsigned char *type,
-                              tsfa_relevance_real_col *cols, int64_t *n_host_cells);
+                              int32_t ks_tail, int32_t device, double *p, unsigned char *route, unsigned char *type,
+                              int64_t *n_hi_device, double *ks_d_device, int64_t *n_host_cells);
 
 /* ---- the exact Kolmogorov-Smirnov tail on the device (csrc/rel_ks.h) ----
  * significance_tests.py ks_2samp_pvalue(n1, n2, d) for max(n1, n2) <= 10 000, bit for bit: g = gcd, lcm = (n1 / g) * n2,
@@ -688,26 +700,6 @@ int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_t n_cols, i
  * cell gets its p and TSFA_ROUTE_KS_EXACT, every other cell NaN and TSFA_ROUTE_HOST_KS.  Synchronous, on the null stream. */
 int tsfa_ks_tails(const int64_t *n1, const int64_t *n2, const double *d, int64_t n_cells, int32_t device, double *p,
                   unsigned char *route);
-enum tsfa_ks_tail {
-    TSFA_KS_TAIL_HOST = 0,  /* every Kolmogorov-Smirnov cell is TSFA_ROUTE_HOST_KS: what tsfa_relevance_tails_* do */
-    TSFA_KS_TAIL_DEVICE = 1 /* the cells tsfa_ks_tails serves get their p and TSFA_ROUTE_KS_EXACT; the rest stay HOST_KS */
-};
-/* tsfa_relevance_tails_classes / tsfa_relevance_tails_real with the choice of ks_tail: with TSFA_KS_TAIL_DEVICE the
- * Kolmogorov-Smirnov cells (with_ks: the real columns of every class table; real target: the two-valued columns) are
- * evaluated from the statistics the sweep left in HBM, and n_host_cells counts what is left.  ks_d_device (class tables:
- * [n_cols * n_classes], only with with_ks) and n_hi_device / ks_d_device (real target: [n_cols]) are optional caller-owned
- * DEVICE arrays that receive the statistics of the Kolmogorov-Smirnov cells, so that a caller with a few cells left fetches
- * those triples instead of the host copies (cols, ks_d).  Everything else as the functions above. */
-int tsfa_relevance_tails_classes_ks(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                    const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail, int32_t device,
-                                    double *p, unsigned char *route, unsigned char *type, tsfa_relevance_col *cols,
-                                    double *rank_sums, int64_t *hi_counts, double *ks_d, double *ks_d_device,
-                                    int64_t *n_host_cells);
-int tsfa_relevance_tails_real_ks(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
-                                 const int32_t *y_perm, const unsigned char *y_end, int64_t ytie, double y0, double y1,
-                                 int32_t ks_tail, int32_t device, double *p, unsigned char *route, unsigned char *type,
-                                 tsfa_relevance_real_col *cols, int64_t *n_hi_device, double *ks_d_device,
-                                 int64_t *n_host_cells);
 /* ---- the exact Mann-Whitney tail on the device (csrc/rel_mwu.h) ----
  * significance_tests.py mannwhitney_pvalue's exact branch, bit for bit.  With m = min(n1, n2), n = max(n1, n2), top = m * n and
  * k = clamp(int(u), 0, top + 1), u = max(u1, u2):  p = min(max(2.0 * (S_k / total), 0.0), 1.0), where S_k is the number of
@@ -724,19 +716,6 @@ int tsfa_relevance_tails_real_ks(const double *X, int64_t n_rows, int64_t n_cols
 #define TSFA_MWU_EXACT_MAX_TOP (1 << 21)
 int tsfa_mwu_tails(const int64_t *n1, const int64_t *n2, int32_t n_tables, const int32_t *table, const double *u, int64_t n_cells,
                    int32_t device, double *p, unsigned char *route, int64_t *served);
-enum tsfa_mwu_tail {
-    TSFA_MWU_TAIL_HOST = 0,  /* every exact Mann-Whitney cell is TSFA_ROUTE_HOST_MWU_EXACT: what tsfa_relevance_tails_classes does */
-    TSFA_MWU_TAIL_DEVICE = 1 /* the cells tsfa_mwu_tails serves get their p and TSFA_ROUTE_MWU_EXACT; the rest stay HOST */
-};
-/* tsfa_relevance_tails_classes_ks with the choice of mwu_tail: with TSFA_MWU_TAIL_DEVICE the exact Mann-Whitney cells are
- * evaluated from the rank sums the sweep left in HBM, and n_host_cells counts what is left.  rank_sums_device
- * ([n_cols * n_classes]) is an optional caller-owned DEVICE array that receives the rank sums, so that a caller with a few
- * cells left fetches those instead of the host copies.  Everything else as tsfa_relevance_tails_classes_ks. */
-int tsfa_relevance_tails_classes_mwu(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                     const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail, int32_t mwu_tail,
-                                     int32_t device, double *p, unsigned char *route, unsigned char *type, tsfa_relevance_col *cols,
-                                     double *rank_sums, int64_t *hi_counts, double *ks_d, double *ks_d_device,
-                                     double *rank_sums_device, int64_t *n_host_cells);
 /* statsmodels' multipletests "fdr_bh" / "fdr_by" per table and relevance.py's combination of the tables.  All pointers are
  * device pointers.  p[n_cols * n_tables] (n_tables <= 256: the classes, or 1), type[n_cols].  Per table the columns whose type
  * is not 0 are tested (m of them); their p-values are sorted (NaN last, never rejected) and everything up to the largest

@@ -73,7 +73,7 @@ def main():
              "Host clock around calls that end synchronised, one warm-up round, %d timed rounds with the legs alternating; seconds, "
              "median (min .. max).  The host leg runs on the first %d columns only (all %d would take minutes a round); the device "
              "leg runs on that subset and on all columns.  `flag` / `serve`: the statistics sweep with the tails kernels on its own "
-             "(`tsfa_relevance_tails_classes*`), all columns, the exact cells only flagged, or served on the device; their difference "
+             "(`tsfa_relevance_tails_classes`), all columns, the exact cells only flagged, or served on the device; their difference "
              "is the Mann-Whitney stage (`k_mwu_build`, `k_mwu_cells`, the allocations and one read-back of a counter).  `table`: "
              "`tsfa_mwu_tails` on one cell, i.e. one table build, one cell and the call's allocations." % (args.runs, mh, m), ""]
 

@@ -518,9 +518,9 @@ def test_gpu_device_space_column_block_inside_a_wider_matrix(gpu):
         M2[:, c0 + 3] = np.nan                          # a column without a finite value
         _upload(lib, dm, M2)
         host_block = np.ascontiguousarray(M2[:, c0:c0 + m])
-        want_stats = _native.impute_matrix(host_block, device=0)
+        want_imputed = _native.impute_matrix(host_block, device=0)
         got_stats = _device_impute(lib, xptr, n, m, ld)
-        for u_, v_ in zip(got_stats, want_stats):
+        for u_, v_ in zip(got_stats, want_imputed):
             assert np.array_equal(u_, v_)
         for c in range(m):
             assert (got_stats[0][c], got_stats[1][c], got_stats[2][c], got_stats[3][c]) == ref.impute_stats(M2[:, c0 + c])

@@ -171,6 +171,67 @@ def test_routes_of_the_real_table():
     assert math.isnan(p[0]) and math.isnan(p[1]) and 0.0 < p[2] < 1.0
 
 
+def _fill_flagged(p, route, n1, stat, n_rows):
+    """What tensor_selection does with the cells the tails kernels flag, on host arrays: `_host_tail_pvalues` on those cells alone,
+    scattered into a copy of p -> (the copy, the mask of the flagged cells)."""
+    from tsfresh_amd.tensor_selection import _host_tail_pvalues
+    flagged = (route == E.HOST_KS) | (route == E.HOST_MWU_EXACT)
+    n1 = np.broadcast_to(n1, route.shape)[flagged]
+    out = p.copy()
+    out[flagged] = _host_tail_pvalues(route[flagged], n1, n_rows - n1, stat[flagged])
+    return out, flagged
+
+
+def test_host_tails_fill_exactly_the_flagged_cells_with_scipys_values():
+    from scipy import stats
+    rng = np.random.default_rng(17)
+    n = 40
+    codes = np.array([0] * 5 + [1] * 35)
+    a, b = rng.standard_normal(n), rng.standard_normal(n) + 0.8 * (codes == 0)
+    X = np.stack([a, b, np.round(a, 0), np.round(b, 0), (a > 0).astype(float), (b > 0.3).astype(float)], axis=1)
+    n_unique, tie, rs, hc, class_n = _class_stats(X, codes, 2)
+    assert tie[:2].tolist() == [0.0, 0.0] and (tie[2:] > 0).all()
+    # "mann": the untied real columns are exact Mann-Whitney cells in both tables (5 rows against 35)
+    p, route, typ, n_host = E.tails_classes(n_unique, tie, rs, hc, class_n)
+    got, flagged = _fill_flagged(p, route, class_n[None, :], rs, n)
+    assert flagged.tolist() == [[True, True]] * 2 + [[False, False]] * 4 and n_host == 4
+    assert np.array_equal(got[~flagged], p[~flagged]) and not np.isnan(got[2:]).any()
+    for j in range(2):
+        for k in range(2):
+            want = stats.mannwhitneyu(X[codes == k, j], X[codes != k, j], alternative="two-sided", method="exact").pvalue
+            assert got[j, k] == pytest.approx(want, **P_TOL), (j, k)
+    # "smir": every real column, tied or not, is a Kolmogorov-Smirnov cell
+    ks_d = np.array([[stats.ks_2samp(X[codes == k, j], X[codes != k, j]).statistic for k in range(2)] for j in range(6)])
+    p, route, typ, n_host = E.tails_classes(n_unique, tie, rs, hc, class_n, with_ks=True)
+    got, flagged = _fill_flagged(p, route, class_n[None, :], ks_d, n)
+    assert flagged.tolist() == [[True, True]] * 4 + [[False, False]] * 2 and n_host == 8
+    assert np.array_equal(got[~flagged], p[~flagged]) and not np.isnan(got[4:]).any()
+    for j in range(4):
+        for k in range(2):
+            want = stats.ks_2samp(X[codes == k, j], X[codes != k, j]).pvalue
+            assert got[j, k] == pytest.approx(want, **P_TOL), (j, k)
+
+
+def test_host_tails_fill_the_binary_columns_of_a_real_target():
+    from scipy import stats
+    rng = np.random.default_rng(19)
+    n = 40
+    y = rng.standard_normal(n)
+    X = np.stack([(y + rng.standard_normal(n) > 0).astype(float), (rng.standard_normal(n) > 0.5).astype(float)], axis=1)
+    cols = np.zeros(3, dtype=E.REAL_COL_DTYPE)
+    cols["n_unique"] = [2, 2, 17]
+    cols["dis"][2] = 300
+    for j in range(2):
+        cols["n_hi"][j] = int(X[:, j].sum())
+        cols["ks_d"][j] = stats.ks_2samp(y[X[:, j] == 1.0], y[X[:, j] == 0.0]).statistic
+    p, route, typ, n_host = E.tails_real(cols, n, 0, 0.0, 0.0)
+    got, flagged = _fill_flagged(p, route, cols["n_hi"], cols["ks_d"], n)
+    assert flagged.tolist() == [True, True, False] and n_host == 2 and got[2] == p[2] and 0.0 < got[2] < 1.0
+    for j in range(2):
+        want = stats.ks_2samp(y[X[:, j] == 1.0], y[X[:, j] == 0.0]).pvalue
+        assert got[j] == pytest.approx(want, **P_TOL), j
+
+
 def _c_m(m, independent):
     return 1.0 if independent else float(np.sum(1.0 / np.arange(1, m + 1)))
 

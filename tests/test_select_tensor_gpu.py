@@ -258,6 +258,47 @@ def test_host_routes_are_filled_in_before_the_fdr_step(gpu):
                 assert res.p_value.cpu().numpy()[j] == pytest.approx(table.loc[f, "p_value"], **P_TOL)
 
 
+@pytest.mark.parametrize("target", ["mann_small_class", "smir", "real"])
+def test_every_combination_of_the_tail_options_gives_the_same_table(gpu, target):
+    """ks_tail x mwu_tail, both on the device included: the options only move cells between the host and the device, so the
+    p-values are equal bit for bit, the selection is the same, and `routes` differs by HOST_KS -> KS_EXACT and
+    HOST_MWU_EXACT -> MWU_EXACT alone."""
+    from tsfresh_amd import _native as N
+    from tsfresh_amd import calculate_relevance_tensor
+    X, y = _case(300, 0 if target == "real" else 3)
+    kw = {}
+    if target == "mann_small_class":
+        y = np.where(np.arange(300) < 5, 0, 1 + (np.arange(300) % 2))   # class 0 has 5 rows
+    elif target == "smir":
+        kw = dict(test_for_binary_target_real_feature="smir")
+    served = {N.TSFA_ROUTE_KS_EXACT: N.TSFA_ROUTE_HOST_KS, N.TSFA_ROUTE_MWU_EXACT: N.TSFA_ROUTE_HOST_MWU_EXACT}
+    results = {}
+    for ks_tail in ("host", "device"):
+        for mwu_tail in ("host", "device"):
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                res = calculate_relevance_tensor(torch.from_numpy(X.copy()).cuda(), y.copy(), columns=NAMES, ks_tail=ks_tail,
+                                                 mwu_tail=mwu_tail, **kw)
+            routes = res.routes.cpu().numpy()
+            host = (routes == N.TSFA_ROUTE_HOST_KS) | (routes == N.TSFA_ROUTE_HOST_MWU_EXACT)
+            assert res.host_cells == int(host.sum())
+            as_flagged = np.vectorize(lambda r: served.get(r, r))(routes)
+            results[ks_tail, mwu_tail] = (res.p_values.cpu().numpy(), res.relevant.cpu().numpy(), as_flagged, res.host_cells)
+    p0, relevant0, flagged0, host0 = results["host", "host"]
+    assert host0 > 0 and not np.isnan(p0[(flagged0 == N.TSFA_ROUTE_HOST_KS) | (flagged0 == N.TSFA_ROUTE_HOST_MWU_EXACT)]).any()
+    for combo, (p, relevant, flagged, host_cells) in results.items():
+        assert p.tobytes() == p0.tobytes(), combo
+        assert relevant.tolist() == relevant0.tolist(), combo
+        assert flagged.tolist() == flagged0.tolist(), combo
+    # the option that matters for the target takes cells off the host; the other one changes nothing
+    moves = "mwu_tail" if target == "mann_small_class" else "ks_tail"
+    for (ks_tail, mwu_tail), (_, _, _, host_cells) in results.items():
+        if dict(ks_tail=ks_tail, mwu_tail=mwu_tail)[moves] == "device":
+            assert host_cells < host0, (ks_tail, mwu_tail)
+        else:
+            assert host_cells == host0, (ks_tail, mwu_tail)
+
+
 def test_impute_tensor(gpu):
     from tsfresh_amd import _native, impute_tensor
     rng = np.random.default_rng(9)

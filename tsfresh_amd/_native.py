@@ -31,9 +31,9 @@ TSFA_HOST, TSFA_DEVICE = 0, 1
 # enum tsfa_route: who evaluates the tail of a p-value cell (tsfa_relevance_tails_*)
 (TSFA_ROUTE_NONE, TSFA_ROUTE_MWU_NORMAL, TSFA_ROUTE_FISHER, TSFA_ROUTE_KENDALL, TSFA_ROUTE_HOST_MWU_EXACT,
  TSFA_ROUTE_HOST_KS, TSFA_ROUTE_KS_EXACT, TSFA_ROUTE_MWU_EXACT) = range(8)
-# enum tsfa_ks_tail: who evaluates the exact Kolmogorov-Smirnov tails (tsfa_relevance_tails_*_ks)
+# enum tsfa_ks_tail: who evaluates the exact Kolmogorov-Smirnov tails (tsfa_relevance_tails_*)
 TSFA_KS_TAIL_HOST, TSFA_KS_TAIL_DEVICE = 0, 1
-# enum tsfa_mwu_tail: who evaluates the exact Mann-Whitney tails (tsfa_relevance_tails_classes_mwu), and the cap on m * n
+# enum tsfa_mwu_tail: who evaluates the exact Mann-Whitney tails (tsfa_relevance_tails_classes), and the cap on m * n
 TSFA_MWU_TAIL_HOST, TSFA_MWU_TAIL_DEVICE = 0, 1
 TSFA_MWU_EXACT_MAX_TOP = 1 << 21
 
@@ -142,16 +142,11 @@ PROTOTYPES = {
     "tsfa_relevance_real": (i32, [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i32, ptr]),
     "tsfa_ks_outer_prob": (f64, [i64, i64, i64, i64]),
     "tsfa_impute": (i32, [ptr, i64, i64, i64, i32, i32, ptr, ptr, ptr, ptr]),
-    "tsfa_relevance_tails_classes": (i32, [ptr, i64, i64, i64, i32, ptr, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, P(i64)]),
-    "tsfa_relevance_tails_real": (i32, [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i64, f64, f64, i32, ptr, ptr, ptr, ptr, P(i64)]),
+    "tsfa_relevance_tails_classes": (i32, [ptr, i64, i64, i64, i32, ptr, i32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, P(i64)]),
+    "tsfa_relevance_tails_real": (i32, [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i64, f64, f64, i32, i32, ptr, ptr, ptr, ptr, ptr,
+                                        P(i64)]),
     "tsfa_ks_tails": (i32, [ptr, ptr, ptr, i64, i32, ptr, ptr]),
-    "tsfa_relevance_tails_classes_ks": (i32, [ptr, i64, i64, i64, i32, ptr, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr,
-                                              ptr, P(i64)]),
-    "tsfa_relevance_tails_real_ks": (i32, [ptr, i64, i64, i64, i32, ptr, ptr, ptr, i64, f64, f64, i32, i32, ptr, ptr, ptr, ptr,
-                                           ptr, ptr, P(i64)]),
     "tsfa_mwu_tails": (i32, [ptr, ptr, i32, ptr, ptr, i64, i32, ptr, ptr, P(i64)]),
-    "tsfa_relevance_tails_classes_mwu": (i32, [ptr, i64, i64, i64, i32, ptr, i32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr,
-                                               ptr, ptr, ptr, P(i64)]),
     "tsfa_relevance_fdr": (i32, [ptr, ptr, i64, i32, f64, f64, i32, i32, i32, ptr, ptr, ptr, ptr]),
     "tsfa_compact_mask": (i32, [ptr, i64, ptr, P(i64), i32]),
     "tsfa_gather_columns_device": (i32, [ptr, i64, i64, ptr, i64, ptr, i64, i32]),
@@ -1154,10 +1149,11 @@ def ks_outer_prob(m, n, g, h):
 # ---- selection on the device (tsfa_relevance_tails_* / tsfa_relevance_fdr / tsfa_compact_mask / tsfa_gather_columns_device):
 # the matrix and every output are device pointers (ints, e.g. torch's `.data_ptr()`) owned by the caller ----
 
-def _ks_tail_code(ks_tail):
-    if ks_tail not in ("host", "device"):
-        raise ValueError("ks_tail must be 'host' or 'device', not {!r}".format(ks_tail))
-    return TSFA_KS_TAIL_DEVICE if ks_tail == "device" else TSFA_KS_TAIL_HOST
+def _tail_code(name, tail):
+    """The value of enum tsfa_ks_tail / tsfa_mwu_tail (both HOST = 0, DEVICE = 1) for the option `name` given as `tail`."""
+    if tail not in ("host", "device"):
+        raise ValueError("{} must be 'host' or 'device', not {!r}".format(name, tail))
+    return 1 if tail == "device" else 0
 
 
 def ks_tails(n1_ptr, n2_ptr, d_ptr, n_cells, p_ptr, route_ptr, device=0):
@@ -1165,12 +1161,6 @@ def ks_tails(n1_ptr, n2_ptr, d_ptr, n_cells, p_ptr, route_ptr, device=0):
     the device arrays p [n_cells] float64 and route [n_cells] uint8 (TSFA_ROUTE_KS_EXACT, or NaN and TSFA_ROUTE_HOST_KS)."""
     lib = load()
     _check(lib, lib.tsfa_ks_tails(n1_ptr, n2_ptr, d_ptr, int(n_cells), int(device), p_ptr, route_ptr))
-
-
-def _mwu_tail_code(mwu_tail):
-    if mwu_tail not in ("host", "device"):
-        raise ValueError("mwu_tail must be 'host' or 'device', not {!r}".format(mwu_tail))
-    return TSFA_MWU_TAIL_DEVICE if mwu_tail == "device" else TSFA_MWU_TAIL_HOST
 
 
 def mwu_tails(n1, n2, table_ptr, u_ptr, n_cells, p_ptr, route_ptr, device=0):
@@ -1190,42 +1180,21 @@ def mwu_tails(n1, n2, table_ptr, u_ptr, n_cells, p_ptr, route_ptr, device=0):
 
 
 def relevance_tails_classes(x_ptr, n_rows, n_cols, ld, y_codes, n_classes, p_ptr, route_ptr, type_ptr, device=0, with_ks=False,
-                            want_stats=False, ks_tail="host", ks_d_ptr=None, mwu_tail="host", rank_sums_ptr=None):
+                            ks_tail="host", ks_d_ptr=None, mwu_tail="host", rank_sums_ptr=None):
     """The class tables of the device matrix at x_ptr, left on the device: p [m, C] float64, route [m, C] uint8, type [m]
-    uint8 -> (host-route cells, statistics).  statistics (want_stats): what `relevance_classes` returns, for the caller's
-    host routes; None otherwise (nothing but the cell count is copied).  ks_tail="device" (tsfa_relevance_tails_classes_ks)
-    serves the exact Kolmogorov-Smirnov tails on the device; ks_d_ptr: an optional device array [m, C] float64 that receives
-    the Kolmogorov-Smirnov distances (with_ks), and the statistics then come without them.  mwu_tail="device"
-    (tsfa_relevance_tails_classes_mwu) serves the exact Mann-Whitney tails on the device; rank_sums_ptr: an optional device
-    array [m, C] float64 that receives the rank sums."""
-    ks_code = _ks_tail_code(ks_tail)
-    mwu_code = _mwu_tail_code(mwu_tail)
+    uint8 -> the host-route cells (nothing else is copied).  ks_tail="device" / mwu_tail="device" serve the exact Kolmogorov-
+    Smirnov / Mann-Whitney tails on the device.  ks_d_ptr (with_ks) / rank_sums_ptr: optional device arrays [m, C] float64 that
+    receive the Kolmogorov-Smirnov distances / the rank sums, for the caller's host routes."""
+    ks_code, mwu_code = _tail_code("ks_tail", ks_tail), _tail_code("mwu_tail", mwu_tail)
     lib = load()
     y_codes = np.ascontiguousarray(y_codes, dtype=np.int32)
     if y_codes.shape != (n_rows,):
         raise ValueError("one class code per row")
     n_host = ctypes.c_int64(0)
-    cols = rank_sums = hi_counts = ks_d = None
-    if want_stats:
-        cols = np.zeros(max(n_cols, 1), dtype=_CLASS_COL_DTYPE)
-        rank_sums = np.zeros((n_cols, n_classes), dtype=np.float64)
-        hi_counts = np.zeros((n_cols, n_classes), dtype=np.int64)
-        ks_d = np.zeros((n_cols, n_classes), dtype=np.float64) if (with_ks and ks_d_ptr is None) else None
-    stats_ptrs = [None if a is None else a.ctypes.data for a in (cols, rank_sums, hi_counts, ks_d)]
-    head = (x_ptr, int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_codes.ctypes.data, int(n_classes), int(bool(with_ks)))
-    if mwu_code == TSFA_MWU_TAIL_DEVICE or rank_sums_ptr is not None:
-        _check(lib, lib.tsfa_relevance_tails_classes_mwu(*head, ks_code, mwu_code, int(device), p_ptr, route_ptr, type_ptr,
-                                                         *stats_ptrs, ks_d_ptr, rank_sums_ptr, ctypes.byref(n_host)))
-    elif ks_code == TSFA_KS_TAIL_HOST and ks_d_ptr is None:
-        _check(lib, lib.tsfa_relevance_tails_classes(*head, int(device), p_ptr, route_ptr, type_ptr, *stats_ptrs,
-                                                     ctypes.byref(n_host)))
-    else:
-        _check(lib, lib.tsfa_relevance_tails_classes_ks(*head, ks_code, int(device), p_ptr, route_ptr, type_ptr, *stats_ptrs,
-                                                        ks_d_ptr, ctypes.byref(n_host)))
-    stats = None
-    if want_stats:
-        stats = (cols["n_unique"][:n_cols].copy(), cols["tie_term"][:n_cols].copy(), rank_sums, hi_counts, ks_d)
-    return int(n_host.value), stats
+    _check(lib, lib.tsfa_relevance_tails_classes(x_ptr, int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_codes.ctypes.data,
+                                                 int(n_classes), int(bool(with_ks)), ks_code, mwu_code, int(device), p_ptr,
+                                                 route_ptr, type_ptr, rank_sums_ptr, ks_d_ptr, ctypes.byref(n_host)))
+    return int(n_host.value)
 
 
 def target_order(y):
@@ -1242,14 +1211,13 @@ def target_order(y):
     return y_rank, y_perm, y_end
 
 
-def relevance_tails_real(x_ptr, n_rows, n_cols, ld, y, tie_statistics, p_ptr, route_ptr, type_ptr, device=0, want_stats=False,
-                         ks_tail="host", n_hi_ptr=None, ks_d_ptr=None):
-    """The table of a real target for the device matrix at x_ptr, left on the device: p [m], route [m], type [m] ->
-    (host-route cells, records).  tie_statistics: callable dense ranks -> (ytie, y0, y1).  records (want_stats): the
-    structured array `relevance_real` returns.  ks_tail="device" (tsfa_relevance_tails_real_ks) serves the exact
+def relevance_tails_real(x_ptr, n_rows, n_cols, ld, y, tie_statistics, p_ptr, route_ptr, type_ptr, device=0, ks_tail="host",
+                         n_hi_ptr=None, ks_d_ptr=None):
+    """The table of a real target for the device matrix at x_ptr, left on the device: p [m], route [m], type [m] -> the
+    host-route cells.  tie_statistics: callable dense ranks -> (ytie, y0, y1).  ks_tail="device" serves the exact
     Kolmogorov-Smirnov tails on the device; n_hi_ptr / ks_d_ptr: optional device arrays [m] (int64 / float64) that receive
-    the two-valued columns' statistics."""
-    ks_code = _ks_tail_code(ks_tail)
+    the two-valued columns' statistics, for the caller's host route."""
+    ks_code = _tail_code("ks_tail", ks_tail)
     lib = load()
     y = np.ascontiguousarray(y, dtype=np.float64)
     if y.shape != (n_rows,):
@@ -1257,16 +1225,10 @@ def relevance_tails_real(x_ptr, n_rows, n_cols, ld, y, tie_statistics, p_ptr, ro
     y_rank, y_perm, y_end = target_order(y)
     ytie, y0, y1 = tie_statistics(y_rank)
     n_host = ctypes.c_int64(0)
-    cols = np.zeros(max(n_cols, 1), dtype=_REAL_COL_DTYPE) if want_stats else None
-    cols_ptr = None if cols is None else cols.ctypes.data
-    head = (x_ptr, int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_rank.ctypes.data, y_perm.ctypes.data, y_end.ctypes.data,
-            int(ytie), float(y0), float(y1))
-    if ks_code == TSFA_KS_TAIL_HOST and n_hi_ptr is None and ks_d_ptr is None:
-        _check(lib, lib.tsfa_relevance_tails_real(*head, int(device), p_ptr, route_ptr, type_ptr, cols_ptr, ctypes.byref(n_host)))
-    else:
-        _check(lib, lib.tsfa_relevance_tails_real_ks(*head, ks_code, int(device), p_ptr, route_ptr, type_ptr, cols_ptr, n_hi_ptr,
-                                                     ks_d_ptr, ctypes.byref(n_host)))
-    return int(n_host.value), (None if cols is None else cols[:n_cols])
+    _check(lib, lib.tsfa_relevance_tails_real(x_ptr, int(n_rows), int(n_cols), int(ld), TSFA_DEVICE, y_rank.ctypes.data,
+                                              y_perm.ctypes.data, y_end.ctypes.data, int(ytie), float(y0), float(y1), ks_code,
+                                              int(device), p_ptr, route_ptr, type_ptr, n_hi_ptr, ks_d_ptr, ctypes.byref(n_host)))
+    return int(n_host.value)
 
 
 def relevance_fdr(p_ptr, type_ptr, n_cols, n_tables, alpha, c_m, n_significant, multiclass, rel_table_ptr, relevant_ptr,

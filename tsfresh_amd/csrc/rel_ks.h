@@ -1,5 +1,5 @@
 // The exact two-sample Kolmogorov-Smirnov tail of the feature selection as device code (tsfa_ks_tails and the ks_tail
-// variants of tsfa_relevance_tails_*, include/tsfresh_amd.h): what rel_tails.h leaves to the caller as TSFA_ROUTE_HOST_KS.
+// argument of tsfa_relevance_tails_*, include/tsfresh_amd.h): what rel_tails.h leaves to the caller as TSFA_ROUTE_HOST_KS.
 //
 // Restates significance_tests.py ks_2samp_pvalue for max(n1, n2) <= 10 000, in float64 and in the operation order of the
 // Python text (-ffp-contract=off):

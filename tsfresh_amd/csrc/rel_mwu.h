@@ -1,5 +1,5 @@
-// The exact Mann-Whitney tail of the feature selection as device code (tsfa_mwu_tails and tsfa_relevance_tails_classes_mwu,
-// include/tsfresh_amd.h): what rel_tails.h leaves to the caller as TSFA_ROUTE_HOST_MWU_EXACT.
+// The exact Mann-Whitney tail of the feature selection as device code (tsfa_mwu_tails and mwu_tail of
+// tsfa_relevance_tails_classes, include/tsfresh_amd.h): what rel_tails.h leaves to the caller as TSFA_ROUTE_HOST_MWU_EXACT.
 //
 // Restates significance_tests.py mannwhitney_pvalue's exact branch, 2 * _mwu_exact_sf(int(u), n1, n2), in exact integers.
 // With m = min(n1, n2) <= 8, n = max(n1, n2), top = m n: c_j, the number of arrangements with statistic j, is the coefficient of

@@ -723,11 +723,6 @@ extern "C" int tsfa_ks_tails(const int64_t *n1, const int64_t *n2, const double 
     return TSFA_OK;
 }
 
-static int ks_tail_check(int32_t ks_tail, const char *who) {
-    if (ks_tail == TSFA_KS_TAIL_HOST || ks_tail == TSFA_KS_TAIL_DEVICE) return TSFA_OK;
-    return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": ks_tail must be TSFA_KS_TAIL_HOST or TSFA_KS_TAIL_DEVICE").c_str());
-}
-
 // ---- the exact Mann-Whitney tail (rel_mwu.h): the TSFA_ROUTE_HOST_MWU_EXACT cells of the tables the device serves ----
 // a distinct (m, n): where its table of prefix sums starts in the block of tables, and where its two buffers start in the
 // scratch block (words; -1: the buffers are LDS)
@@ -845,19 +840,23 @@ extern "C" int tsfa_mwu_tails(const int64_t *n1, const int64_t *n2, int32_t n_ta
     return TSFA_OK;
 }
 
-static int mwu_tail_check(int32_t mwu_tail, const char *who) {
-    if (mwu_tail == TSFA_MWU_TAIL_HOST || mwu_tail == TSFA_MWU_TAIL_DEVICE) return TSFA_OK;
-    return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": mwu_tail must be TSFA_MWU_TAIL_HOST or TSFA_MWU_TAIL_DEVICE").c_str());
+// the two tail options of the tails entries (a real target has no Mann-Whitney cells: its entry passes TSFA_MWU_TAIL_HOST)
+static int tail_check(int32_t ks_tail, int32_t mwu_tail, const char *who) {
+    if (ks_tail != TSFA_KS_TAIL_HOST && ks_tail != TSFA_KS_TAIL_DEVICE)
+        return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": ks_tail must be TSFA_KS_TAIL_HOST or TSFA_KS_TAIL_DEVICE").c_str());
+    if (mwu_tail != TSFA_MWU_TAIL_HOST && mwu_tail != TSFA_MWU_TAIL_DEVICE)
+        return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": mwu_tail must be TSFA_MWU_TAIL_HOST or TSFA_MWU_TAIL_DEVICE").c_str());
+    return TSFA_OK;
 }
 
-static int relevance_tails_classes_impl(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                        const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail, int32_t mwu_tail,
-                                        int32_t device, double *p, unsigned char *route, unsigned char *type, tsfa_relevance_col *cols,
-                                        double *rank_sums, int64_t *hi_counts, double *ks_d, double *ks_d_device,
-                                        double *rank_sums_device, int64_t *n_host_cells) {
+extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                            const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail,
+                                            int32_t mwu_tail, int32_t device, double *p, unsigned char *route, unsigned char *type,
+                                            double *rank_sums_device, double *ks_d_device, int64_t *n_host_cells) {
     if (n_host_cells) *n_host_cells = 0;
+    if (int rc = tail_check(ks_tail, mwu_tail, "tsfa_relevance_tails_classes")) return rc;
     if (n_cols > 0 && (!p || !route || !type)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: null output pointer");
-    if ((ks_d || ks_d_device) && !with_ks) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: ks_d without with_ks");
+    if (ks_d_device && !with_ks) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_classes: ks_d without with_ks");
     RelClassesDev d;
     unsigned long long nh = 0ull;
     std::vector<int64_t> class_n;
@@ -906,52 +905,18 @@ static int relevance_tails_classes_impl(const double *X, int64_t n_rows, int64_t
         nh -= (unsigned long long)served;
     }
     if (n_host_cells) *n_host_cells = (int64_t)nh;
-    if (cols) HIP_TRY(hipMemcpy(cols, d.dcols.get(), (size_t)n_cols * sizeof(tsfa_relevance_col), hipMemcpyDeviceToHost));
-    if (rank_sums) HIP_TRY(hipMemcpy(rank_sums, d.drs.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
-    if (hi_counts) HIP_TRY(hipMemcpy(hi_counts, d.dhc.get(), (size_t)n_cols * n_classes * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (ks_d) HIP_TRY(hipMemcpy(ks_d, d.dks.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToHost));
     if (ks_d_device) HIP_TRY(hipMemcpy(ks_d_device, d.dks.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToDevice));
     if (rank_sums_device)
         HIP_TRY(hipMemcpy(rank_sums_device, d.drs.get(), (size_t)n_cols * n_classes * sizeof(double), hipMemcpyDeviceToDevice));
     return TSFA_OK;
 }
 
-extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                            const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t device, double *p,
-                                            unsigned char *route, unsigned char *type, tsfa_relevance_col *cols, double *rank_sums,
-                                            int64_t *hi_counts, double *ks_d, int64_t *n_host_cells) {
-    return relevance_tails_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, with_ks, TSFA_KS_TAIL_HOST, TSFA_MWU_TAIL_HOST,
-                                        device, p, route, type, cols, rank_sums, hi_counts, ks_d, nullptr, nullptr, n_host_cells);
-}
-
-extern "C" int tsfa_relevance_tails_classes_ks(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                               const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail,
-                                               int32_t device, double *p, unsigned char *route, unsigned char *type,
-                                               tsfa_relevance_col *cols, double *rank_sums, int64_t *hi_counts, double *ks_d,
-                                               double *ks_d_device, int64_t *n_host_cells) {
+extern "C" int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
+                                         const int32_t *y_rank, const int32_t *y_perm, const unsigned char *y_end, int64_t ytie,
+                                         double y0, double y1, int32_t ks_tail, int32_t device, double *p, unsigned char *route,
+                                         unsigned char *type, int64_t *n_hi_device, double *ks_d_device, int64_t *n_host_cells) {
     if (n_host_cells) *n_host_cells = 0;
-    if (int rc = ks_tail_check(ks_tail, "tsfa_relevance_tails_classes_ks")) return rc;
-    return relevance_tails_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, with_ks, ks_tail, TSFA_MWU_TAIL_HOST, device, p,
-                                        route, type, cols, rank_sums, hi_counts, ks_d, ks_d_device, nullptr, n_host_cells);
-}
-
-extern "C" int tsfa_relevance_tails_classes_mwu(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                                const int32_t *y_codes, int32_t n_classes, int32_t with_ks, int32_t ks_tail,
-                                                int32_t mwu_tail, int32_t device, double *p, unsigned char *route, unsigned char *type,
-                                                tsfa_relevance_col *cols, double *rank_sums, int64_t *hi_counts, double *ks_d,
-                                                double *ks_d_device, double *rank_sums_device, int64_t *n_host_cells) {
-    if (n_host_cells) *n_host_cells = 0;
-    if (int rc = ks_tail_check(ks_tail, "tsfa_relevance_tails_classes_mwu")) return rc;
-    if (int rc = mwu_tail_check(mwu_tail, "tsfa_relevance_tails_classes_mwu")) return rc;
-    return relevance_tails_classes_impl(X, n_rows, n_cols, ld, space, y_codes, n_classes, with_ks, ks_tail, mwu_tail, device, p, route, type,
-                                        cols, rank_sums, hi_counts, ks_d, ks_d_device, rank_sums_device, n_host_cells);
-}
-
-static int relevance_tails_real_impl(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space, const int32_t *y_rank,
-                                     const int32_t *y_perm, const unsigned char *y_end, int64_t ytie, double y0, double y1,
-                                     int32_t ks_tail, int32_t device, double *p, unsigned char *route, unsigned char *type,
-                                     tsfa_relevance_real_col *cols, int64_t *n_hi_device, double *ks_d_device, int64_t *n_host_cells) {
-    if (n_host_cells) *n_host_cells = 0;
+    if (int rc = tail_check(ks_tail, TSFA_MWU_TAIL_HOST, "tsfa_relevance_tails_real")) return rc;
     if (n_cols > 0 && (!p || !route || !type)) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_relevance_tails_real: null output pointer");
     RelRealDev d;
     unsigned long long nh = 0ull;
@@ -974,7 +939,6 @@ static int relevance_tails_real_impl(const double *X, int64_t n_rows, int64_t n_
         nh -= (unsigned long long)served;
     }
     if (n_host_cells) *n_host_cells = (int64_t)nh;
-    if (cols) HIP_TRY(hipMemcpy(cols, d.dcols.get(), (size_t)n_cols * sizeof(tsfa_relevance_real_col), hipMemcpyDeviceToHost));
     if (n_hi_device || ks_d_device) {
         k_ks_handout_real<<<dim3((unsigned)((n_cols + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(d.dcols.get(), n_cols, n_hi_device,
                                                                                                        ks_d_device);
@@ -982,25 +946,6 @@ static int relevance_tails_real_impl(const double *X, int64_t n_rows, int64_t n_
         HIP_TRY(hipDeviceSynchronize());
     }
     return TSFA_OK;
-}
-
-extern "C" int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                         const int32_t *y_rank, const int32_t *y_perm, const unsigned char *y_end, int64_t ytie,
-                                         double y0, double y1, int32_t device, double *p, unsigned char *route, unsigned char *type,
-                                         tsfa_relevance_real_col *cols, int64_t *n_host_cells) {
-    return relevance_tails_real_impl(X, n_rows, n_cols, ld, space, y_rank, y_perm, y_end, ytie, y0, y1, TSFA_KS_TAIL_HOST, device, p, route,
-                                     type, cols, nullptr, nullptr, n_host_cells);
-}
-
-extern "C" int tsfa_relevance_tails_real_ks(const double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t space,
-                                            const int32_t *y_rank, const int32_t *y_perm, const unsigned char *y_end, int64_t ytie,
-                                            double y0, double y1, int32_t ks_tail, int32_t device, double *p, unsigned char *route,
-                                            unsigned char *type, tsfa_relevance_real_col *cols, int64_t *n_hi_device,
-                                            double *ks_d_device, int64_t *n_host_cells) {
-    if (n_host_cells) *n_host_cells = 0;
-    if (int rc = ks_tail_check(ks_tail, "tsfa_relevance_tails_real_ks")) return rc;
-    return relevance_tails_real_impl(X, n_rows, n_cols, ld, space, y_rank, y_perm, y_end, ytie, y0, y1, ks_tail, device, p, route, type, cols,
-                                     n_hi_device, ks_d_device, n_host_cells);
 }
 
 // masked sort keys of the p-value matrix (rt_fdr_key): what k_rel_stage / k_rel_sort then order, one key column per table

@@ -8,22 +8,25 @@ Whitney's normal tail, Fisher's exact tail, Kendall's asymptotic tail), the FDR 
 `tsfa_gather_columns_device`).  What crosses PCIe is the target (n values in), one byte per column (the feature types, for the
 constant-features warning and the number of tested hypotheses), the count of selected columns and their indices.
 
-Two tails stay on the host by default and are evaluated by the functions the frame entry points use: the exact Mann-Whitney
-distribution (a class or its complement with at most 8 rows, no ties) and every Kolmogorov-Smirnov tail
-(`test_for_binary_target_real_feature="smir"`, binary features under a real target).  The kernels flag those cells
-(`routes`), the statistics of the run come back only when such cells can occur, and the values are written into the device
-array before the FDR step.
+Two kinds of cell have no closed form: the exact Mann-Whitney distribution (a class or its complement with at most 8 rows, no
+ties) and every Kolmogorov-Smirnov tail (`test_for_binary_target_real_feature="smir"`, binary features under a real target).
+One native call per target kind (`tsfa_relevance_tails_classes`, `tsfa_relevance_tails_real`) takes both options that say who
+serves them, flags the cells it leaves to the host (`routes`) and leaves the one statistic such a cell needs in a device array:
+within one run every host cell is of one kind.  One host step then fetches the statistic and the sample sizes of the flagged
+cells alone, evaluates them with the functions the frame entry points use, and writes the values into the device array before
+the FDR step.
 
-`ks_tail="device"` moves the exact Kolmogorov-Smirnov tail (samples of at most 10 000 rows) onto the GPU as well
-(`csrc/rel_ks.h`, route `TSFA_ROUTE_KS_EXACT`): the same float64 expressions as `ks_2samp_pvalue`, equal bit for bit.  What is
-left for the host then are the cells beyond 10 000 rows (scipy's `kstwo`), the rare exact value that rounding pushes outside
-[0, 1] (`ks_2samp_pvalue` falls through to `kstwo` there, and so does this), and the exact Mann-Whitney cells; only the
-triples of those cells are fetched.
+`ks_tail="host"` / `mwu_tail="host"` (the defaults) leave every such cell to the host.
+
+`ks_tail="device"` moves the exact Kolmogorov-Smirnov tail (samples of at most 10 000 rows) onto the GPU (`csrc/rel_ks.h`,
+route `TSFA_ROUTE_KS_EXACT`): the same float64 expressions as `ks_2samp_pvalue`, equal bit for bit.  What is left for the host
+then are the cells beyond 10 000 rows (scipy's `kstwo`) and the rare exact value that rounding pushes outside [0, 1]
+(`ks_2samp_pvalue` falls through to `kstwo` there, and so does this).
 
 `mwu_tail="device"` moves the exact Mann-Whitney tail onto the GPU (`csrc/rel_mwu.h`, route `TSFA_ROUTE_MWU_EXACT`): the
 arrangement counts of a class are built once, in exact integers, and every cell of that class is a lookup and one correctly
 rounded division, equal to `mannwhitney_pvalue` bit for bit.  What is left for the host are classes whose smaller side times
-the larger exceeds `TSFA_MWU_EXACT_MAX_TOP` (8 rows against more than 262 144); only the rank sums of those cells are fetched.
+the larger exceeds `TSFA_MWU_EXACT_MAX_TOP` (8 rows against more than 262 144).
 """
 import warnings
 
@@ -115,14 +118,37 @@ def impute_tensor(X):
     return X
 
 
+def _check_tails(ks_tail, mwu_tail):
+    for option, tail in (("ks_tail", ks_tail), ("mwu_tail", mwu_tail)):
+        if tail not in ("host", "device"):
+            raise ValueError("{} must be 'host' or 'device', not {!r}".format(option, tail))
+
+
+def _host_tail_pvalues(route, n1, n2, stat):
+    """The p-values of the cells the kernels leave to the host, one entry per cell, numpy in and out: `route`
+    TSFA_ROUTE_HOST_KS with `stat` the Kolmogorov-Smirnov distance, or TSFA_ROUTE_HOST_MWU_EXACT with `stat` the rank sum of the
+    sample of n1 rows; n1, n2: the two sample sizes."""
+    from tsfresh_amd.feature_selection.significance_tests import ks_2samp_pvalue, mannwhitney_pvalue
+    # the tie term 0 is exact, not a shortcut: rt_route_class_cell sends every column with tie_term > 0 to the normal tail
+    return np.array([ks_2samp_pvalue(a, b, s) if r == _native.TSFA_ROUTE_HOST_KS else mannwhitney_pvalue(s, a, b, 0)
+                     for r, a, b, s in zip(route, n1, n2, stat)], dtype=np.float64)
+
+
+def _fill_host_cells(torch, p, routes, stat, n1_of, n_rows):
+    """Evaluates the host-route cells of `routes` and scatters the values into `p`.  stat: the device array of the run's one
+    statistic, a value per cell; n1_of: flat cell indices (a device tensor) -> the size of each cell's first sample (numpy).
+    Only the flagged cells' route, statistic and size are fetched."""
+    r = routes.view(-1)
+    flat = torch.nonzero((r == _native.TSFA_ROUTE_HOST_KS) | (r == _native.TSFA_ROUTE_HOST_MWU_EXACT)).view(-1)
+    n1 = n1_of(flat)
+    vals = _host_tail_pvalues(r[flat].cpu().numpy(), n1, n_rows - n1, stat.view(-1)[flat].cpu().numpy())
+    p.view(-1)[flat] = torch.as_tensor(vals, dtype=torch.float64, device=p.device)
+
+
 def _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant, test_for_binary_target_real_feature, fdr_level,
                hypotheses_independent, check_nan, ks_tail="host", mwu_tail="host"):
-    from tsfresh_amd.feature_selection.significance_tests import ks_2samp_pvalue, mannwhitney_pvalue, target_tie_statistics
-    if ks_tail not in ("host", "device"):
-        raise ValueError("ks_tail must be 'host' or 'device', not {!r}".format(ks_tail))
-    if mwu_tail not in ("host", "device"):
-        raise ValueError("mwu_tail must be 'host' or 'device', not {!r}".format(mwu_tail))
-    on_device = (ks_tail == "device")
+    from tsfresh_amd.feature_selection.significance_tests import target_tie_statistics
+    _check_tails(ks_tail, mwu_tail)
     n, m = X.shape
     y = _target(torch, y, n)
     if columns is not None:
@@ -164,72 +190,32 @@ def _relevance(torch, X, device, y, columns, ml_task, multiclass, n_significant,
     p_min = torch.full((m,), float("nan"), dtype=torch.float64, device=dev)
     _synchronize(torch, device)   # X's producer and the fills above are done before the library's null stream works on them
 
-    host_cells, labels = 0, []
+    # one device array of statistics is all the host step can need: within one run there is one kind of host cell
+    labels = []
     if ml_task == "classification":
         labels = np.unique(y)
         codes = np.searchsorted(labels, y).astype(np.int32)
         class_n = np.bincount(codes, minlength=T)
-        # the host routes can only occur under 'smir' or with a class (or its complement) of at most 8 rows: only then
-        # are the statistics copied out
-        if smir and on_device:
-            # every real cell is a Kolmogorov-Smirnov cell (no exact Mann-Whitney under 'smir'); the distances stay in HBM and
-            # of the cells left to the host only the triples are fetched
-            ks_dev = torch.empty((m, T), dtype=torch.float64, device=dev)
-            host_cells, _ = _native.relevance_tails_classes(X.data_ptr(), n, m, _ld(X), codes, T, p.data_ptr(), routes.data_ptr(),
-                                                            types.data_ptr(), device=device, with_ks=True, want_stats=False,
-                                                            ks_tail="device", ks_d_ptr=ks_dev.data_ptr())
-            if host_cells:
-                flat = torch.nonzero(routes.view(-1) == _native.TSFA_ROUTE_HOST_KS).view(-1)
-                k, dist = (flat % T).cpu().numpy(), ks_dev.view(-1)[flat].cpu().numpy()
-                vals = [ks_2samp_pvalue(class_n[k[q]], n - class_n[k[q]], dist[q]) for q in range(len(k))]
-                p.view(-1)[flat] = torch.as_tensor(vals, dtype=torch.float64, device=dev)
-        elif mwu_tail == "device" and not smir:
-            # the exact Mann-Whitney cells are served where the rank sums are; of the cells left to the host (a class beyond
-            # the cap) only the rank sums are fetched, and an exact cell has no ties
-            small = bool(((class_n <= 8) | (n - class_n <= 8)).any())
-            rs_dev = torch.empty((m, T), dtype=torch.float64, device=dev) if small else None
-            host_cells, _ = _native.relevance_tails_classes(X.data_ptr(), n, m, _ld(X), codes, T, p.data_ptr(), routes.data_ptr(),
-                                                            types.data_ptr(), device=device, mwu_tail="device",
-                                                            rank_sums_ptr=rs_dev.data_ptr() if small else None)
-            if host_cells:
-                flat = torch.nonzero(routes.view(-1) == _native.TSFA_ROUTE_HOST_MWU_EXACT).view(-1)
-                k, rs = (flat % T).cpu().numpy(), rs_dev.view(-1)[flat].cpu().numpy()
-                vals = [mannwhitney_pvalue(rs[q], class_n[k[q]], n - class_n[k[q]], 0) for q in range(len(k))]
-                p.view(-1)[flat] = torch.as_tensor(vals, dtype=torch.float64, device=dev)
-        else:
-            want_stats = smir or bool(((class_n <= 8) | (n - class_n <= 8)).any())
-            host_cells, stats_ = _native.relevance_tails_classes(X.data_ptr(), n, m, _ld(X), codes, T, p.data_ptr(), routes.data_ptr(),
-                                                                 types.data_ptr(), device=device, with_ks=smir, want_stats=want_stats)
-            if host_cells:
-                _, tie_term, rank_sums, _, ks_d = stats_
-                r = routes.cpu().numpy()
-                cells = np.argwhere((r == _native.TSFA_ROUTE_HOST_MWU_EXACT) | (r == _native.TSFA_ROUTE_HOST_KS))
-                vals = [ks_2samp_pvalue(class_n[k], n - class_n[k], ks_d[j, k]) if r[j, k] == _native.TSFA_ROUTE_HOST_KS
-                        else mannwhitney_pvalue(rank_sums[j, k], class_n[k], n - class_n[k], tie_term[j]) for j, k in cells]
-                p.view(-1)[torch.as_tensor(cells[:, 0] * T + cells[:, 1], device=dev)] = torch.as_tensor(vals, dtype=torch.float64,
-                                                                                                       device=dev)
+        # under 'smir' every real cell is a Kolmogorov-Smirnov cell; under 'mann' an exact Mann-Whitney cell needs a class (or
+        # its complement) of at most 8 rows
+        ks_dev = torch.empty((m, T), dtype=torch.float64, device=dev) if smir else None
+        small = not smir and bool(((class_n <= 8) | (n - class_n <= 8)).any())
+        rs_dev = torch.empty((m, T), dtype=torch.float64, device=dev) if small else None
+        host_cells = _native.relevance_tails_classes(X.data_ptr(), n, m, _ld(X), codes, T, p.data_ptr(), routes.data_ptr(),
+                                                     types.data_ptr(), device=device, with_ks=smir, ks_tail=ks_tail,
+                                                     ks_d_ptr=ks_dev.data_ptr() if smir else None, mwu_tail=mwu_tail,
+                                                     rank_sums_ptr=rs_dev.data_ptr() if small else None)
+        stat, n1_of = (ks_dev if smir else rs_dev), (lambda flat: class_n[(flat % T).cpu().numpy()])
         labels = labels.tolist()
     else:
-        yv = y.astype(np.float64)
-        if on_device:
-            n_hi_dev = torch.empty(m, dtype=torch.int64, device=dev)
-            ks_dev = torch.empty(m, dtype=torch.float64, device=dev)
-            host_cells, _ = _native.relevance_tails_real(X.data_ptr(), n, m, _ld(X), yv, target_tie_statistics, p.data_ptr(),
-                                                         routes.data_ptr(), types.data_ptr(), device=device, want_stats=False,
-                                                         ks_tail="device", n_hi_ptr=n_hi_dev.data_ptr(), ks_d_ptr=ks_dev.data_ptr())
-            if host_cells:   # only the triples of the cells that are left
-                flat = torch.nonzero(routes.view(-1) == _native.TSFA_ROUTE_HOST_KS).view(-1)
-                n_hi, dist = n_hi_dev[flat].cpu().numpy(), ks_dev[flat].cpu().numpy()
-                vals = [ks_2samp_pvalue(n_hi[q], n - n_hi[q], dist[q]) for q in range(len(n_hi))]
-                p.view(-1)[flat] = torch.as_tensor(vals, dtype=torch.float64, device=dev)
-        else:
-            host_cells, rec = _native.relevance_tails_real(X.data_ptr(), n, m, _ld(X), yv, target_tie_statistics, p.data_ptr(),
-                                                           routes.data_ptr(), types.data_ptr(), device=device, want_stats=True)
-            if host_cells:
-                r = routes.cpu().numpy()[:, 0]
-                cells = np.nonzero(r == _native.TSFA_ROUTE_HOST_KS)[0]
-                vals = [ks_2samp_pvalue(rec["n_hi"][j], n - rec["n_hi"][j], rec["ks_d"][j]) for j in cells]
-                p.view(-1)[torch.as_tensor(cells, device=dev)] = torch.as_tensor(vals, dtype=torch.float64, device=dev)
+        n_hi_dev = torch.empty(m, dtype=torch.int64, device=dev)
+        ks_dev = torch.empty(m, dtype=torch.float64, device=dev)
+        host_cells = _native.relevance_tails_real(X.data_ptr(), n, m, _ld(X), y.astype(np.float64), target_tie_statistics,
+                                                  p.data_ptr(), routes.data_ptr(), types.data_ptr(), device=device, ks_tail=ks_tail,
+                                                  n_hi_ptr=n_hi_dev.data_ptr(), ks_d_ptr=ks_dev.data_ptr())
+        stat, n1_of = ks_dev, (lambda flat: n_hi_dev[flat].cpu().numpy())
+    if host_cells:
+        _fill_host_cells(torch, p, routes, stat, n1_of, n)
 
     types_host = types.cpu().numpy()   # one byte per column: the constant columns' names and the number of hypotheses
     constant = np.nonzero(types_host == 0)[0]
@@ -337,10 +323,7 @@ def extract_relevant_features_tensor(x, y, lengths=None, kinds=None, channels_la
     :return: `(features, columns)`: the relevant columns `[B, k]` on the device, in ascending column index of the extracted
         matrix, and their names."""
     from tsfresh_amd.tensor import extract_features_tensor
-    if ks_tail not in ("host", "device"):   # before the extraction runs
-        raise ValueError("ks_tail must be 'host' or 'device', not {!r}".format(ks_tail))
-    if mwu_tail not in ("host", "device"):
-        raise ValueError("mwu_tail must be 'host' or 'device', not {!r}".format(mwu_tail))
+    _check_tails(ks_tail, mwu_tail)   # before the extraction runs
     features, columns = extract_features_tensor(x, lengths=lengths, kinds=kinds, channels_last=channels_last,
                                                 default_fc_parameters=default_fc_parameters,
                                                 kind_to_fc_parameters=kind_to_fc_parameters, device=device, check_nan=check_nan,
