@@ -483,6 +483,34 @@ int tsfa_pack_dense_valid(const void *x, int32_t x_type, int64_t n_batch, int64_
                           void *stamps_out, void *scratch, int64_t scratch_bytes, int32_t *flags_out, int32_t device,
                           void *stream);
 
+/* Per-kind valid-step packer: tsfa_pack_dense_valid for a multi-rate batch -- what the LONG frame of the same batch holds
+ * after `dropna()`, where every (id, kind) group has its own length.  Step t of (b, c) is dropped when x[b, c, t] is NaN
+ * and, with stamps, when the stamp t[b, t] is NaT or a NaN second (the stamp belongs to the step, so such a step goes for
+ * every kind); +-inf stays; steps at or beyond lengths[b] are never read; the kept steps keep their order.  The arguments
+ * are those of tsfa_pack_dense_valid, except
+ *   offsets_out         [n_channels, n_batch + 1] int64: every kind has its own exclusive scan of its kept counts, starting
+ *                       at 0, into its own stretch values_out + c * channel_stride_out.  Kind c (that stretch, the offsets
+ *                       offsets_out + c * (n_batch + 1)) goes to tsfa_extract* as a channel of tsfa_pack_dense does.
+ *   steps_out           int32 [n_channels, n_batch * n_time]: steps_out[c * n_batch * n_time + offsets[c][b] + k] = the
+ *                       original step index of the k-th kept step of (b, c)
+ *   stamps_out          NULL without t; else [n_channels, n_batch, n_time] elements of t's type, right-padded per (c, b).
+ *                       tsfa_pack_times on (stamps_out + c * n_batch * n_time, the offsets of kind c), once per kind, gives
+ *                       the hours since the first KEPT stamp of each (b, c).
+ *   scratch             scratch_bytes >= 200 * n_channels * n_batch * ceil(n_time / 1024) bytes, aligned to 8
+ *   flags_out           TSFA_DENSE_BAD_LENGTH as in tsfa_pack_dense; TSFA_DENSE_EMPTY_SERIES some (b, c) has no kept step
+ *                       (its offsets are equal: the long frame has no such group; which ones is the caller's to find in
+ *                       offsets_out).  TSFA_PACK_VALUE_NAN is never raised.
+ * Three launches over work items of 1024 steps of one (kind, series) row, kind-major: count, one scan workgroup per kind,
+ * compaction, in tsfa_pack_dense_valid's rounds of 64 steps per ballot; a lane reads one channel only.  The time stride is
+ * a compile-time 1 when it is 1.  No atomic on a position: the result is deterministic.
+ * Errors: those of tsfa_pack_dense_valid; TSFA_ERR_INVALID also for more than 65 536 kinds. */
+int tsfa_pack_dense_valid_kinds(const void *x, int32_t x_type, int64_t n_batch, int64_t n_channels, int64_t n_time,
+                                int64_t stride_batch, int64_t stride_channel, int64_t stride_time, const void *lengths,
+                                int32_t lengths_type, const void *t, int32_t t_type, int64_t t_stride_batch,
+                                int64_t t_stride_time, void *values_out, int64_t channel_stride_out, int64_t *offsets_out,
+                                int32_t *steps_out, void *stamps_out, void *scratch, int64_t scratch_bytes,
+                                int32_t *flags_out, int32_t device, void *stream);
+
 /* Window builder: the rolled (forecasting) layout of one pack, built on the device from the pack's offsets.  Replaces, for a
  * frame packed by tsfa_pack_device / tsfa_pack_set_*, the host's enumeration of n_series x n_shifts window candidates
  * (tsfresh/utilities/dataframe_functions.py:340-358, _roll_out_time_series, for all shifts at once) and the upload of the

@@ -118,6 +118,8 @@ PROTOTYPES = {
     "tsfa_pack_times": (i32, [ptr, i32, i64, i64, i64, i64, i64, ptr, ptr, ptr, i32, ptr]),
     "tsfa_pack_dense_valid": (i32, [ptr, i32, i64, i64, i64, i64, i64, i64, ptr, i32, ptr, i32, i64, i64, ptr, i64, ptr, ptr, ptr,
                                     ptr, i64, ptr, i32, ptr]),
+    "tsfa_pack_dense_valid_kinds": (i32, [ptr, i32, i64, i64, i64, i64, i64, i64, ptr, i32, ptr, i32, i64, i64, ptr, i64, ptr, ptr,
+                                          ptr, ptr, i64, ptr, i32, ptr]),
     "tsfa_roll_windows": (i32, [ptr, i32, i64, i64, i64, P(ptr)]),
     "tsfa_windows_n_windows": (i64, [ptr]),
     "tsfa_windows_starts": (ptr, [ptr]),
@@ -564,6 +566,24 @@ def pack_dense_valid(x_ptr, x_type, shape, strides, values_ptr, channel_stride_o
     lib = load()
     (n_batch, n_channels, n_time), (sb, sc, st), (tsb, tst) = shape, strides, t_strides
     _check(lib, lib.tsfa_pack_dense_valid(
+        x_ptr, int(x_type), int(n_batch), int(n_channels), int(n_time), int(sb), int(sc), int(st), lengths_ptr or None,
+        int(lengths_type), t_ptr or None, int(t_type), int(tsb), int(tst), values_ptr, int(channel_stride_out), offsets_ptr,
+        steps_ptr, stamps_ptr or None, scratch_ptr, int(scratch_bytes), flags_ptr, int(device), stream or None))
+
+
+def pack_dense_valid_kinds(x_ptr, x_type, shape, strides, values_ptr, channel_stride_out, offsets_ptr, steps_ptr, scratch_ptr,
+                           scratch_bytes, flags_ptr, device=0, lengths_ptr=None, lengths_type=0, t_ptr=None, t_type=0,
+                           t_strides=(0, 0), stamps_ptr=None, stream=None):
+    """tsfa_pack_dense_valid_kinds on raw device pointers (ints): `pack_dense_valid` with the steps dropped per kind -- step t
+    of (series b, channel c) goes when x[b, c, t] is NaN or its stamp is NaT / NaN, what the long frame loses to dropna().
+    The arguments are `pack_dense_valid`'s, with every per-batch output once per channel: offsets_ptr receives
+    n_channels * (n_batch + 1) int64 (each channel's own offsets, starting at 0), steps_ptr n_channels * n_batch * n_time
+    int32, stamps_ptr n_channels * n_batch * n_time stamps (for one `pack_times` call per channel), and scratch_ptr is
+    `pack_dense_valid_scratch_bytes(n_batch * n_channels, n_time)` of device memory.  flags_ptr: one int32 the call ORs
+    TSFA_DENSE_BAD_LENGTH and TSFA_DENSE_EMPTY_SERIES (some (b, c) kept no step) into."""
+    lib = load()
+    (n_batch, n_channels, n_time), (sb, sc, st), (tsb, tst) = shape, strides, t_strides
+    _check(lib, lib.tsfa_pack_dense_valid_kinds(
         x_ptr, int(x_type), int(n_batch), int(n_channels), int(n_time), int(sb), int(sc), int(st), lengths_ptr or None,
         int(lengths_type), t_ptr or None, int(t_type), int(tsb), int(tst), values_ptr, int(channel_stride_out), offsets_ptr,
         steps_ptr, stamps_ptr or None, scratch_ptr, int(scratch_bytes), flags_ptr, int(device), stream or None))

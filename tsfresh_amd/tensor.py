@@ -236,13 +236,14 @@ def _pack_checked(torch, x3, lengths, kinds, device, check_nan, want_steps=False
     return x3, lengths, packs, int(steps), hours
 
 
-_NAN_POLICIES = ("raise", "drop")
+_NAN_POLICIES = ("raise", "drop", "drop_per_kind")
 
 
 def _check_nan_policy(nan_policy):
+    """The policy's name, checked -> "raise", "drop" or "drop_per_kind"."""
     if nan_policy not in _NAN_POLICIES:
-        raise ValueError("nan_policy must be one of 'raise', 'drop': got {!r}".format(nan_policy))
-    return nan_policy == "drop"
+        raise ValueError("nan_policy must be one of 'raise', 'drop', 'drop_per_kind': got {!r}".format(nan_policy))
+    return nan_policy
 
 
 def _valid_pack(torch, x3, lengths, times, device):
@@ -298,6 +299,88 @@ def _pack_dropped(torch, x3, lengths, device, want_steps=False, times=None):
     return x3, packs, int(longest), hours, steps
 
 
+def _valid_pack_kinds(torch, x3, lengths, times, device):
+    """(B, C, n) tensor on `device` without the steps the LONG frame loses to `dropna()` (`tsfa_pack_dense_valid_kinds`: step
+    t of (b, c) goes when x[b, c, t] is NaN, or its stamp NaT / NaN) -> (values, tsfa_dtype of values, offsets, flag,
+    hours).  values: (C, B * n), kind c's kept samples at the front of row c; offsets: (C, B + 1) int64, every kind's own;
+    flag: one int32; hours: None, or (C, B * n) float64 laid out like values -- `tsfa_pack_times` once per kind on that
+    kind's kept stamps and offsets (hours since the first kept stamp of each (b, c))."""
+    B, C, n = x3.shape
+    x_type, values, _, flag, lptr, ltype, _ = _pack_outputs(torch, x3, lengths, device)
+    vtype = _native.TSFA_F64 if x_type == _native.TSFA_F64 else _native.TSFA_F32
+    offsets = torch.empty((C, B + 1), dtype=torch.int64, device=x3.device)
+    steps = torch.empty((C, B * n), dtype=torch.int32, device=x3.device)
+    scratch_bytes = _native.pack_dense_valid_scratch_bytes(B * C, n)
+    scratch = torch.empty(scratch_bytes // 8, dtype=torch.int64, device=x3.device)
+    timed, stamps = {}, None
+    if times is not None:
+        t, t_type, tps = times
+        stamps = torch.empty((C, B, n), dtype=t.dtype, device=x3.device)
+        timed = dict(t_ptr=t.data_ptr(), t_type=t_type, t_strides=t.stride(), stamps_ptr=stamps.data_ptr())
+    _synchronize(torch, device)   # the producer of x, and the fill of the flag word, are done before another stream reads
+    _native.pack_dense_valid_kinds(x3.data_ptr(), x_type, (B, C, n), x3.stride(), values.data_ptr(), B * n, offsets.data_ptr(),
+                                   steps.data_ptr(), scratch.data_ptr(), scratch_bytes, flag.data_ptr(), device=device,
+                                   lengths_ptr=lptr, lengths_type=ltype, **timed)
+    hours = None
+    if times is not None:
+        hours = torch.empty((C, B * n), dtype=torch.float64, device=x3.device)
+        for c in range(C):   # a kind's kept stamps are a right-padded (B, n) batch with its offsets
+            _native.pack_times(stamps[c].data_ptr(), t_type, tps, (B, n), (n, 1), offsets[c].data_ptr(), hours[c].data_ptr(),
+                               flag.data_ptr(), device=device)
+    return values, vtype, offsets, flag, hours
+
+
+def _pack_dropped_kinds(torch, x3, lengths, device, times=None):
+    """`_valid_pack_kinds` of the batch on `device` and its flag word's errors -> (x3 on the device, values, tsfa_dtype of
+    values, offsets, hours, present).  present: None when every (b, c) kept a step; else a (C, B) bool tensor, False where
+    kind c lacks series b.  The flag word is read once; the kept counts are looked at only when it names an empty group."""
+    B, C, n = x3.shape
+    x3, lengths, times = _batch_to_device(x3, lengths, times, device)
+    values, vtype, offsets, flag, hours = _valid_pack_kinds(torch, x3, lengths, times, device)
+    flags = int(flag.item())
+    if flags & _native.TSFA_DENSE_BAD_LENGTH:
+        raise ValueError("lengths must lie in [1, {}] (the samples per series of x)".format(n))
+    present = None
+    if flags & _native.TSFA_DENSE_EMPTY_SERIES:
+        present = offsets[:, 1:] > offsets[:, :-1]
+        gone = torch.nonzero(~present.any(dim=0))
+        if gone.shape[0]:
+            raise ValueError("series {} has no step left after nan_policy='drop_per_kind': every sample of every kind is NaN{}".format(
+                int(gone[0].item()), "" if times is None else " or has a NaT / NaN stamp"))
+    return x3, values, vtype, offsets, hours, present
+
+
+def _extract_kinds(torch, jobs, features, values, vtype, offsets, hours, present, device):
+    """The extraction of a per-kind pack into `features` (B rows).  A kind that has every series extracts straight into its
+    column block.  A kind that lacks some takes tensor_long.py's scheme: its offsets without the empty groups (the value
+    buffer does not change: an empty group holds no sample), a transient block, and a row scatter into NaN cells."""
+    C, T = values.shape
+    B = features.shape[0]
+    whole = [True] * C if present is None else present.all(dim=1).tolist()
+    owner = (values, offsets, hours)
+    matrix = _native.BorrowedMatrix(features.data_ptr(), B, features.shape[1], device, owner=features)
+    for c, kind, fplan, nplan, col0 in jobs:
+        values_ptr = values.data_ptr() + c * T * values.element_size()
+        timed = {} if hours is None else {"times_ptr": hours[c].data_ptr()}
+        if whole[c]:
+            pack = _native.DensePack(values_ptr, vtype, offsets[c].data_ptr(), B, device, owner=owner)
+            nplan.extract_into(None, None, matrix, col0=col0, pack=pack, **timed)
+            pack.close()
+            continue
+        width = len(fplan.names)
+        rows = torch.nonzero(present[c]).reshape(-1)
+        kept = torch.cat([offsets[c, :-1][present[c]], offsets[c, -1:]])
+        block = torch.empty((int(rows.shape[0]), width), dtype=torch.float64, device=features.device)
+        features[:, col0:col0 + width] = float("nan")
+        _synchronize(torch, device)
+        pack = _native.DensePack(values_ptr, vtype, kept.data_ptr(), block.shape[0], device, owner=owner + (kept,))
+        nplan.extract_into(None, None, _native.BorrowedMatrix(block.data_ptr(), block.shape[0], width, device, owner=block),
+                           col0=0, pack=pack, **timed)
+        pack.close()
+        features[rows, col0:col0 + width] = block   # the device row scatter
+    _synchronize(torch, device)
+
+
 def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, default_fc_parameters=None,
                             kind_to_fc_parameters=None, device=None, check_nan=True, show_warnings=False, nan_policy="raise",
                             times=None, time_unit="ns"):
@@ -324,8 +407,16 @@ def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, de
         +-inf is a value and stays.  Steps at or beyond `lengths[b]` are never read.  `check_nan` is irrelevant: nothing that
         is NaN reaches the kernels, and the one flag word is always read -- a series with no kept step has no row in that
         frame and raises `ValueError` with its batch index.  Anything else raises `ValueError`.  Not offered: a
-        user-supplied validity mask, per-kind lengths (a kind dropping steps on its own), the frame entries (use
-        `frame.dropna()`), an enqueue-only mode.
+        user-supplied validity mask, the frame entries (use `frame.dropna()`), an enqueue-only mode.
+        "drop_per_kind": every kind drops its own steps -- the result is what `extract_features` returns for the LONG frame of
+        the batch (one row per `(id=b, sort=step, kind=c, value)`, the stamps its `DatetimeIndex`) after `dropna()`: step t
+        of `(b, c)` is dropped when `x[b, c, t]` is NaN, and for every kind when its stamp is NaT / NaN
+        (`tsfa_pack_dense_valid_kinds`; every kind has its own offsets, the hours count from the first kept stamp of each
+        `(b, c)`).  The case is a multi-rate recording pivoted onto one grid, NaN where a sensor has no sample: "drop" keeps
+        the steps every sensor has, this value keeps each sensor's own.  A `(b, c)` without a kept step is an id the kind
+        lacks: its cells are NaN and the row stays.  A series without a kept step in ANY kind raises `ValueError` with its
+        batch index.  `check_nan` is irrelevant.  Not offered: a user-supplied validity mask, the frame entries, an
+        enqueue-only mode.
     :param times: optional time stamps of the samples, for an irregularly sampled batch: a `torch.Tensor` or numpy array of
         shape `(n,)` (one clock for the batch) or `(B, n)` (one per series), any strides (expanded and stepped views are not
         copied first); the kinds share the clock, as the value columns of a frame share its index.  dtype int64 (ticks,
@@ -355,7 +446,7 @@ def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, de
 
     from tsfresh_amd.feature_extraction import extraction
 
-    drop = _check_nan_policy(nan_policy)
+    policy = _check_nan_policy(nan_policy)
     x3, lengths, kinds, default_fc_parameters, device = _batch_arguments(
         torch, x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device)
     B = x3.shape[0]
@@ -370,7 +461,13 @@ def extract_features_tensor(x, lengths=None, kinds=None, channels_last=False, de
                                            "build a DataFrame and call extract_features on it", timed=times is not None)
         x3 = _to_device(x3, device)
         features = torch.empty((B, n_cols), dtype=torch.float64, device=x3.device)
-        if drop:
+        if policy == "drop_per_kind":
+            x3, values, vtype, offsets, hours, present = _pack_dropped_kinds(torch, x3, lengths, device, times=times)
+            if n_cols:
+                _extract_kinds(torch, jobs, features, values, vtype, offsets, hours, present, device)
+            extraction._trim_cache(extraction._thread_cache())
+            return features, columns
+        if policy == "drop":
             x3, packs, _, hours, _ = _pack_dropped(torch, x3, lengths, device, times=times)
         else:
             x3, lengths, packs, _, hours = _pack_checked(torch, x3, lengths, kinds, device, check_nan, times=times)
@@ -428,7 +525,9 @@ def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=Fa
         index): they come from the ragged route (count, scan, fill on the compacted offsets; the longest kept length comes
         back with the flag word), and `positions` holds ORIGINAL step indices -- of the window's last kept step for a
         positive direction, of its first for a negative one -- gathered on the device from the packer's step array.  The
-        same things are not offered (a validity mask, per-kind lengths, the frame entries, an enqueue-only mode).
+        same things are not offered (a validity mask, the frame entries, an enqueue-only mode).  "drop_per_kind" raises
+        `ValueError` here: every kind would keep its own steps and so roll its own window set, and there is no single
+        `[n_windows, columns]` matrix for them.
     :return: `(features, columns, series, positions)`, all tensors on the device:
         `features` `torch.float64` `[n_windows, number of columns]`; `columns` the names ``"{kind}__{feature}"`` in exactly the
         order `extract_rolled_features` gives for the equivalent wide frame; `series` `torch.int64` `[n_windows]`, the batch
@@ -463,7 +562,10 @@ def extract_rolled_features_tensor(x, lengths=None, kinds=None, channels_last=Fa
     from tsfresh_amd.utilities.dataframe_functions import check_roll_arguments
 
     check_roll_arguments(rolling_direction, max_timeshift, min_timeshift)
-    drop = _check_nan_policy(nan_policy)
+    drop = _check_nan_policy(nan_policy) != "raise"
+    if nan_policy == "drop_per_kind":
+        raise ValueError("nan_policy='drop_per_kind' is not offered for rolled features: every kind would keep its own steps and "
+                         "roll its own windows, so there is no single [n_windows, columns] matrix; use 'drop' or roll each kind")
     x3, lengths, kinds, default_fc_parameters, device = _batch_arguments(
         torch, x, lengths, kinds, channels_last, default_fc_parameters, kind_to_fc_parameters, device)
     n = x3.shape[2]

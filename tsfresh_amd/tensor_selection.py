@@ -318,8 +318,9 @@ def extract_relevant_features_tensor(x, y, lengths=None, kinds=None, channels_la
     :param times, time_unit: as in `extract_features_tensor`: the batch's clock, which adds the `linear_trend_timewise`
         columns to the matrix the selection runs on.
     :param nan_policy: as in `extract_features_tensor`: "drop" extracts from the steps the wide frame keeps after
-        `dropna()`; `y` stays one value per series.  Not offered here either: a validity mask, per-kind lengths, the frame
-        entries, an enqueue-only mode.
+        `dropna()`, "drop_per_kind" from each kind's own kept steps (what the long frame keeps; a kind that lacks a
+        series leaves NaN cells, which the impute step fills); `y` stays one value per series.  Not offered here either: a
+        validity mask, the frame entries, an enqueue-only mode.
     :return: `(features, columns)`: the relevant columns `[B, k]` on the device, in ascending column index of the extracted
         matrix, and their names."""
     from tsfresh_amd.tensor import extract_features_tensor
