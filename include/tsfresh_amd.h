@@ -677,7 +677,8 @@ int tsfa_impute(double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t s
  * Kolmogorov-Smirnov tail (with_ks, and two-valued columns under a real target).  ks_tail and mwu_tail say who serves them.
  * HOST: the cell gets NaN and its HOST route, is counted, and the caller overwrites p before tsfa_relevance_fdr.  DEVICE: the
  * cells that tsfa_ks_tails / tsfa_mwu_tails (below) serve are evaluated from the statistics the sweep left in HBM and get
- * TSFA_ROUTE_KS_EXACT / TSFA_ROUTE_MWU_EXACT; the rest stay HOST cells. */
+ * TSFA_ROUTE_KS_EXACT / TSFA_ROUTE_MWU_EXACT; the rest stay HOST cells.  DEVICE_LARGE (ks_tail only): what DEVICE serves, and
+ * then the cells of more than 10 000 rows that tsfa_ks_large_tails serves, which get TSFA_ROUTE_KS_KOLMOGN. */
 enum tsfa_route {
     TSFA_ROUTE_NONE = 0,           /* constant column: p = NaN */
     TSFA_ROUTE_MWU_NORMAL = 1,
@@ -686,11 +687,13 @@ enum tsfa_route {
     TSFA_ROUTE_HOST_MWU_EXACT = 4,
     TSFA_ROUTE_HOST_KS = 5,
     TSFA_ROUTE_KS_EXACT = 6,       /* a Kolmogorov-Smirnov cell whose exact tail the device served (ks_tail) */
-    TSFA_ROUTE_MWU_EXACT = 7       /* an exact Mann-Whitney cell that the device served (mwu_tail); not a HOST route */
+    TSFA_ROUTE_MWU_EXACT = 7,      /* an exact Mann-Whitney cell that the device served (mwu_tail); not a HOST route */
+    TSFA_ROUTE_KS_KOLMOGN = 8      /* a Kolmogorov-Smirnov cell beyond 10 000 rows whose kstwo tail the device served; not a HOST route */
 };
 enum tsfa_ks_tail {
     TSFA_KS_TAIL_HOST = 0,  /* every Kolmogorov-Smirnov cell is TSFA_ROUTE_HOST_KS */
-    TSFA_KS_TAIL_DEVICE = 1 /* the cells tsfa_ks_tails serves get their p and TSFA_ROUTE_KS_EXACT; the rest stay HOST_KS */
+    TSFA_KS_TAIL_DEVICE = 1, /* the cells tsfa_ks_tails serves get their p and TSFA_ROUTE_KS_EXACT; the rest stay HOST_KS */
+    TSFA_KS_TAIL_DEVICE_LARGE = 2 /* DEVICE, then the cells tsfa_ks_large_tails serves get their p and TSFA_ROUTE_KS_KOLMOGN */
 };
 enum tsfa_mwu_tail {
     TSFA_MWU_TAIL_HOST = 0,  /* every exact Mann-Whitney cell is TSFA_ROUTE_HOST_MWU_EXACT */
@@ -728,6 +731,19 @@ int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_t n_cols, i
  * cell gets its p and TSFA_ROUTE_KS_EXACT, every other cell NaN and TSFA_ROUTE_HOST_KS.  Synchronous, on the null stream. */
 int tsfa_ks_tails(const int64_t *n1, const int64_t *n2, const double *d, int64_t n_cells, int32_t device, double *p,
                   unsigned char *route);
+/* ---- the Kolmogorov-Smirnov tail beyond 10 000 rows on the device (csrc/rel_ks_large.h) ----
+ * What ks_2samp_pvalue(n1, n2, d) does for max(n1, n2) > 10 000: scipy.stats.kstwo.sf(d, n), n = rint(big * small / (big + small))
+ * in float64, the two-sided one-sample distribution of Simard and L'Ecuyer (2011), restated in float64 (1e-6 relative to the
+ * host's value, not bit for bit).  A cell is served iff max(n1, n2) > 10 000, min(n1, n2) >= 1, d is a number,
+ * 141 <= n <= 1 000 000, and kstwo.sf would not take Durbin's matrix for it, i.e. not (n d^2 < 2.2 and n <= 100 000 and
+ * n d^1.5 <= 1.4).  The closed branches (0, 1, Ruben-Gambino, Pelz-Good) take a lane per cell; the one-sided sum of Birnbaum
+ * and Tingey, floor(n (1 - d)) + 1 terms, a wavefront per cell.
+ *
+ * tsfa_ks_large_tails: arguments as tsfa_ks_tails.  A served cell gets its p and TSFA_ROUTE_KS_KOLMOGN, every other cell --
+ * every cell with max(n1, n2) <= 10 000 among them -- NaN and TSFA_ROUTE_HOST_KS.  n_cells < 2^31.  Synchronous, on the null
+ * stream. */
+int tsfa_ks_large_tails(const int64_t *n1, const int64_t *n2, const double *d, int64_t n_cells, int32_t device, double *p,
+                        unsigned char *route);
 /* ---- the exact Mann-Whitney tail on the device (csrc/rel_mwu.h) ----
  * significance_tests.py mannwhitney_pvalue's exact branch, bit for bit.  With m = min(n1, n2), n = max(n1, n2), top = m * n and
  * k = clamp(int(u), 0, top + 1), u = max(u1, u2):  p = min(max(2.0 * (S_k / total), 0.0), 1.0), where S_k is the number of

@@ -1249,6 +1249,22 @@ TSFA_DEV double tsfa_lgamma(double x) {
     for (int i = 1; i < 9; ++i) a += c[i] / (x + (double)i);
     return 0.5 * log(2.0 * M_PI) + (x + 0.5) * log(t) - t + log(a);
 }
+// the same series for a caller that knows x >= 0.5 (rel_ks_large.h: x >= 1): without the reflection branch there is no
+// recursion, so this one is inlined where tsfa_lgamma is a call with a stack frame.  Same bits as tsfa_lgamma there.
+TSFA_DEV double tsfa_lgamma_pos(double x) {
+    x -= 1.0;
+    const double t = x + 7.5;
+    double a = 0.99999999999980993;
+    a += 676.5203681218851 / (x + 1.0);
+    a += -1259.1392167224028 / (x + 2.0);
+    a += 771.32342877765313 / (x + 3.0);
+    a += -176.61502916214059 / (x + 4.0);
+    a += 12.507343278686905 / (x + 5.0);
+    a += -0.13857109526572012 / (x + 6.0);
+    a += 9.9843695780195716e-6 / (x + 7.0);
+    a += 1.5056327351493116e-7 / (x + 8.0);
+    return 0.5 * log(2.0 * M_PI) + (x + 0.5) * log(t) - t + log(a);
+}
 
 // continued fraction for the regularized incomplete beta (modified Lentz)
 TSFA_DEV double tsfa_betacf(double a, double b, double x) {

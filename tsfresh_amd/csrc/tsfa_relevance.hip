@@ -23,6 +23,7 @@
 #include "../../include/tsfresh_amd.h"
 #include "rel_tails.h"
 #include "rel_ks.h"
+#include "rel_ks_large.h"
 #include "rel_mwu.h"
 #include "tsfa_devmem.h"
 
@@ -723,6 +724,81 @@ extern "C" int tsfa_ks_tails(const int64_t *n1, const int64_t *n2, const double 
     return TSFA_OK;
 }
 
+// ---- the Kolmogorov-Smirnov tail beyond 10 000 rows (rel_ks_large.h): the TSFA_ROUTE_HOST_KS cells kstwo.sf would serve ----
+// branches and closed forms: thread = cell.  The cells of the one-sided sum are appended to list[]: a wavefront counts its
+// cells by a ballot and takes its places with ONE atomic on cnt[0], whose low word counts the list and whose high word the
+// cells a closed branch served.  (Every lane of a wavefront reaches the ballot: no early return.)
+__global__ void __launch_bounds__(RT_THREADS) k_ksl_route(RkCells s, int64_t n_cells, double *__restrict__ p, unsigned char *__restrict__ route,
+                                                          unsigned long long *__restrict__ cnt, int32_t *__restrict__ list) {
+    const int64_t cell = (int64_t)blockIdx.x * RT_THREADS + threadIdx.x;
+    const int lane = (int)(threadIdx.x & 63);
+    const int r = (cell < n_cells) ? ksl_route_cell(s, cell, p, route) : KSL_LEAVE;
+    const unsigned long long sums = __ballot(r == KSL_SMIRNOV), closed = __ballot(r != KSL_SMIRNOV && r != KSL_LEAVE);
+    if ((sums | closed) == 0ull) return;   // wave-uniform
+    const int leader = __ffsll((long long)(sums | closed)) - 1;
+    unsigned long long base = 0ull;
+    if (lane == leader) base = atomicAdd(cnt, (unsigned long long)__popcll(sums) + ((unsigned long long)__popcll(closed) << 32));
+    base = __shfl(base, leader, 64) & 0xffffffffull;
+    if (r == KSL_SMIRNOV) list[base + (unsigned long long)__popcll(sums & ((1ull << lane) - 1ull))] = (int32_t)cell;
+}
+
+// the one-sided sum: wavefront = cell of the list, in a grid-stride loop (the list holds cells of 141 terms next to cells of
+// a million: a wavefront that draws short cells simply draws more of them).  The wavefronts of a workgroup never meet: no
+// barrier, no LDS.
+__global__ void __launch_bounds__(RT_THREADS) k_ksl_smirnov(RkCells s, const int32_t *__restrict__ list, int64_t n_list, double *__restrict__ p,
+                                                            unsigned char *__restrict__ route) {
+    const int64_t wave = (int64_t)blockIdx.x * (RT_THREADS / 64) + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * (RT_THREADS / 64);
+    for (int64_t i = wave; i < n_list; i += n_waves) ksl_smirnov_cell(s, (int64_t)list[i], p, route);
+}
+
+#define KSL_MAX_WORKGROUPS 16384   // of 4 wavefronts; beyond, the grid-stride loop
+
+// The stage on the null stream of the current device: every TSFA_ROUTE_HOST_KS cell of route[n_cells] that rel_ks_large.h
+// serves gets its p and TSFA_ROUTE_KS_KOLMOGN.  Synchronous; *served: how many.  One block of device memory: the counter word
+// and a work list of n_cells int32 (a table of 2^31 cells or more is left to the caller).
+static int ks_large_run(const RkCells &s, int64_t n_cells, double *p, unsigned char *route, int64_t *served) {
+    *served = 0;
+    if (n_cells == 0 || n_cells > (int64_t)INT32_MAX) return TSFA_OK;
+    unsigned long long cnt = 0ull;
+    DevPtr<unsigned long long> dblock;
+    HIP_TRY_MALLOC(dblock, sizeof(cnt) + (size_t)n_cells * sizeof(int32_t));
+    int32_t *list = (int32_t *)(dblock.get() + 1);
+    HIP_TRY(hipMemset(dblock.get(), 0, sizeof(cnt)));
+    k_ksl_route<<<dim3((unsigned)((n_cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(s, n_cells, p, route, dblock.get(), list);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&cnt, dblock.get(), sizeof(cnt), hipMemcpyDeviceToHost));
+    const int64_t n_list = (int64_t)(cnt & 0xffffffffull), n_closed = (int64_t)(cnt >> 32);
+    if (n_list > 0) {
+        int64_t nwg = (n_list + RT_THREADS / 64 - 1) / (RT_THREADS / 64);
+        if (nwg > KSL_MAX_WORKGROUPS) nwg = KSL_MAX_WORKGROUPS;
+        k_ksl_smirnov<<<dim3((unsigned)nwg), RT_THREADS, 0, 0>>>(s, list, n_list, p, route);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());   // the block is freed on return
+    }
+    *served = n_list + n_closed;
+    return TSFA_OK;
+}
+
+extern "C" int tsfa_ks_large_tails(const int64_t *n1, const int64_t *n2, const double *d, int64_t n_cells, int32_t device, double *p,
+                                   unsigned char *route) {
+    if (n_cells < 0 || n_cells > (int64_t)INT32_MAX || (n_cells > 0 && (!n1 || !n2 || !d || !p || !route)))
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_ks_large_tails: null pointer or bad shape");
+    int rc = rel_check_device(device, "tsfa_ks_large_tails");
+    if (rc || n_cells == 0) return rc;
+    HIP_TRY(hipSetDevice(device));
+    k_ks_init<<<dim3((unsigned)((n_cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(n_cells, p, route);
+    HIP_TRY(hipGetLastError());
+    RkCells s = {};
+    s.n1 = n1;
+    s.n2 = n2;
+    s.d = d;
+    int64_t served = 0;
+    rc = ks_large_run(s, n_cells, p, route, &served);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return TSFA_OK;
+}
+
 // ---- the exact Mann-Whitney tail (rel_mwu.h): the TSFA_ROUTE_HOST_MWU_EXACT cells of the tables the device serves ----
 // a distinct (m, n): where its table of prefix sums starts in the block of tables, and where its two buffers start in the
 // scratch block (words; -1: the buffers are LDS)
@@ -842,8 +918,9 @@ extern "C" int tsfa_mwu_tails(const int64_t *n1, const int64_t *n2, int32_t n_ta
 
 // the two tail options of the tails entries (a real target has no Mann-Whitney cells: its entry passes TSFA_MWU_TAIL_HOST)
 static int tail_check(int32_t ks_tail, int32_t mwu_tail, const char *who) {
-    if (ks_tail != TSFA_KS_TAIL_HOST && ks_tail != TSFA_KS_TAIL_DEVICE)
-        return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": ks_tail must be TSFA_KS_TAIL_HOST or TSFA_KS_TAIL_DEVICE").c_str());
+    if (ks_tail != TSFA_KS_TAIL_HOST && ks_tail != TSFA_KS_TAIL_DEVICE && ks_tail != TSFA_KS_TAIL_DEVICE_LARGE)
+        return tsfa_fail(TSFA_ERR_INVALID,
+                         (std::string(who) + ": ks_tail must be TSFA_KS_TAIL_HOST, TSFA_KS_TAIL_DEVICE or TSFA_KS_TAIL_DEVICE_LARGE").c_str());
     if (mwu_tail != TSFA_MWU_TAIL_HOST && mwu_tail != TSFA_MWU_TAIL_DEVICE)
         return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": mwu_tail must be TSFA_MWU_TAIL_HOST or TSFA_MWU_TAIL_DEVICE").c_str());
     return TSFA_OK;
@@ -880,7 +957,7 @@ extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpy(&nh, dnh.get(), sizeof(nh), hipMemcpyDeviceToHost));
-    if (with_ks && ks_tail == TSFA_KS_TAIL_DEVICE && nh > 0) {
+    if (with_ks && ks_tail != TSFA_KS_TAIL_HOST && nh > 0) {
         RkCells s = {};
         s.d = d.dks.get();
         s.class_n = dcn.get();
@@ -890,6 +967,11 @@ extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int
         rc = ks_tails_run(s, cells, p, route, &served);
         if (rc) return rc;
         nh -= (unsigned long long)served;
+        if (ks_tail == TSFA_KS_TAIL_DEVICE_LARGE && nh > 0) {   // what is still flagged: the cells beyond RK_MAX_ROWS
+            rc = ks_large_run(s, cells, p, route, &served);
+            if (rc) return rc;
+            nh -= (unsigned long long)served;
+        }
     }
     if (!with_ks && mwu_tail == TSFA_MWU_TAIL_DEVICE && nh > 0) {
         std::vector<int64_t> rest((size_t)n_classes);
@@ -929,7 +1011,7 @@ extern "C" int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_
                                                                                               route, type, dnh.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(&nh, dnh.get(), sizeof(nh), hipMemcpyDeviceToHost));
-    if (ks_tail == TSFA_KS_TAIL_DEVICE && nh > 0) {
+    if (ks_tail != TSFA_KS_TAIL_HOST && nh > 0) {
         RkCells s = {};
         s.rcols = d.dcols.get();
         s.n_rows = n_rows;
@@ -937,6 +1019,11 @@ extern "C" int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_
         rc = ks_tails_run(s, n_cols, p, route, &served);
         if (rc) return rc;
         nh -= (unsigned long long)served;
+        if (ks_tail == TSFA_KS_TAIL_DEVICE_LARGE && nh > 0) {
+            rc = ks_large_run(s, n_cols, p, route, &served);
+            if (rc) return rc;
+            nh -= (unsigned long long)served;
+        }
     }
     if (n_host_cells) *n_host_cells = (int64_t)nh;
     if (n_hi_device || ks_d_device) {

@@ -23,6 +23,12 @@ route `TSFA_ROUTE_KS_EXACT`): the same float64 expressions as `ks_2samp_pvalue`,
 then are the cells beyond 10 000 rows (scipy's `kstwo`) and the rare exact value that rounding pushes outside [0, 1]
 (`ks_2samp_pvalue` falls through to `kstwo` there, and so does this).
 
+`ks_tail="device_large"` serves what `"device"` serves and then the cells beyond 10 000 rows (`csrc/rel_ks_large.h`, route
+`TSFA_ROUTE_KS_KOLMOGN`): `kstwo.sf(d, n)` with n = round(n1 n2 / (n1 + n2)), restated in float64 -- within 1e-6 relative of
+the host's value, not bit for bit.  A cell is served for 141 <= n <= 1 000 000 unless `kstwo` would take Durbin's matrix for it
+(n d^2 < 2.2, n <= 100 000 and n d^1.5 <= 1.4: all such cells have p >= 0.9).  What is left for the host are those cells, rare
+classes with n <= 140 and samples beyond n = 1 000 000.
+
 `mwu_tail="device"` moves the exact Mann-Whitney tail onto the GPU (`csrc/rel_mwu.h`, route `TSFA_ROUTE_MWU_EXACT`): the
 arrangement counts of a class are built once, in exact integers, and every cell of that class is a lookup and one correctly
 rounded division, equal to `mannwhitney_pvalue` bit for bit.  What is left for the host are classes whose smaller side times
@@ -42,7 +48,9 @@ class RelevanceTensors:
 
     types [m] int8 (0 constant, 1 binary, 2 real); p_values [m, T] float64; relevant_per_table [m, T] bool; relevant [m] bool;
     n_significant [m] int32 (tables that reject the column); p_value [m] float64 (the smallest over the tables, NaN for a
-    constant column); routes [m, T] uint8 (`_native.TSFA_ROUTE_*`: who evaluated the cell); labels: the ascending distinct
+    constant column); routes [m, T] uint8 (`_native.TSFA_ROUTE_*`: who evaluated the cell; `TSFA_ROUTE_KS_EXACT` /
+    `TSFA_ROUTE_KS_KOLMOGN` / `TSFA_ROUTE_MWU_EXACT` where `ks_tail` / `mwu_tail` moved a cell onto the GPU); labels: the
+    ascending distinct
     values of y behind the tables (empty for regression); host_cells: how many cells the host evaluated; columns: the names
     given, or None."""
 
@@ -119,9 +127,8 @@ def impute_tensor(X):
 
 
 def _check_tails(ks_tail, mwu_tail):
-    for option, tail in (("ks_tail", ks_tail), ("mwu_tail", mwu_tail)):
-        if tail not in ("host", "device"):
-            raise ValueError("{} must be 'host' or 'device', not {!r}".format(option, tail))
+    _native._tail_code("ks_tail", ks_tail)   # "host", "device" or "device_large"
+    _native._tail_code("mwu_tail", mwu_tail)   # "host" or "device"
 
 
 def _host_tail_pvalues(route, n1, n2, stat):
@@ -258,8 +265,10 @@ def calculate_relevance_tensor(X, y, columns=None, ml_task="auto", multiclass=Fa
         column; False skips the check and its read-back of one word.
     :param ks_tail: who evaluates the exact Kolmogorov-Smirnov tails ("smir"; binary features under a real target).  "host"
         (default): `ks_2samp_pvalue`, one cell at a time.  "device": the GPU, for samples of at most 10 000 rows, with equal
-        p-values (`routes` then shows `TSFA_ROUTE_KS_EXACT`, and `host_cells` counts what is left to the host).  Anything else
-        raises `ValueError`.
+        p-values (`routes` then shows `TSFA_ROUTE_KS_EXACT`, and `host_cells` counts what is left to the host).
+        "device_large": as "device", and the GPU also evaluates scipy's `kstwo.sf` for the cells beyond 10 000 rows with
+        141 <= round(n1 n2 / (n1 + n2)) <= 1 000 000 that are not Durbin-matrix cells, within 1e-6 relative of the host's
+        p-values (`routes` shows `TSFA_ROUTE_KS_KOLMOGN` there).  Anything else raises `ValueError`.
     :param mwu_tail: who evaluates the exact Mann-Whitney tails (classification under "mann": a class or its complement with
         at most 8 rows, a column without ties).  "host" (default): `mannwhitney_pvalue`, one cell at a time, which rebuilds the
         arrangement counts for every cell.  "device": the GPU builds the counts once per class, with equal p-values (`routes`
