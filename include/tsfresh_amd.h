@@ -678,7 +678,8 @@ int tsfa_impute(double *X, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t s
  * HOST: the cell gets NaN and its HOST route, is counted, and the caller overwrites p before tsfa_relevance_fdr.  DEVICE: the
  * cells that tsfa_ks_tails / tsfa_mwu_tails (below) serve are evaluated from the statistics the sweep left in HBM and get
  * TSFA_ROUTE_KS_EXACT / TSFA_ROUTE_MWU_EXACT; the rest stay HOST cells.  DEVICE_LARGE (ks_tail only): what DEVICE serves, and
- * then the cells of more than 10 000 rows that tsfa_ks_large_tails serves, which get TSFA_ROUTE_KS_KOLMOGN. */
+ * then the cells of more than 10 000 rows that tsfa_ks_large_tails serves, which get TSFA_ROUTE_KS_KOLMOGN.  DEVICE_MATRIX
+ * (ks_tail only): what DEVICE_LARGE serves, and then the cells tsfa_ks_matrix_tails serves, which get TSFA_ROUTE_KS_MATRIX. */
 enum tsfa_route {
     TSFA_ROUTE_NONE = 0,           /* constant column: p = NaN */
     TSFA_ROUTE_MWU_NORMAL = 1,
@@ -688,12 +689,14 @@ enum tsfa_route {
     TSFA_ROUTE_HOST_KS = 5,
     TSFA_ROUTE_KS_EXACT = 6,       /* a Kolmogorov-Smirnov cell whose exact tail the device served (ks_tail) */
     TSFA_ROUTE_MWU_EXACT = 7,      /* an exact Mann-Whitney cell that the device served (mwu_tail); not a HOST route */
-    TSFA_ROUTE_KS_KOLMOGN = 8      /* a Kolmogorov-Smirnov cell beyond 10 000 rows whose kstwo tail the device served; not a HOST route */
+    TSFA_ROUTE_KS_KOLMOGN = 8,     /* a Kolmogorov-Smirnov cell beyond 10 000 rows whose kstwo tail the device served; not a HOST route */
+    TSFA_ROUTE_KS_MATRIX = 9       /* such a cell where kstwo takes Durbin's matrix or n <= 140, served by the device; not a HOST route */
 };
 enum tsfa_ks_tail {
     TSFA_KS_TAIL_HOST = 0,  /* every Kolmogorov-Smirnov cell is TSFA_ROUTE_HOST_KS */
     TSFA_KS_TAIL_DEVICE = 1, /* the cells tsfa_ks_tails serves get their p and TSFA_ROUTE_KS_EXACT; the rest stay HOST_KS */
-    TSFA_KS_TAIL_DEVICE_LARGE = 2 /* DEVICE, then the cells tsfa_ks_large_tails serves get their p and TSFA_ROUTE_KS_KOLMOGN */
+    TSFA_KS_TAIL_DEVICE_LARGE = 2, /* DEVICE, then the cells tsfa_ks_large_tails serves get their p and TSFA_ROUTE_KS_KOLMOGN */
+    TSFA_KS_TAIL_DEVICE_MATRIX = 3 /* DEVICE_LARGE, then the cells tsfa_ks_matrix_tails serves get their p and TSFA_ROUTE_KS_MATRIX */
 };
 enum tsfa_mwu_tail {
     TSFA_MWU_TAIL_HOST = 0,  /* every exact Mann-Whitney cell is TSFA_ROUTE_HOST_MWU_EXACT */
@@ -744,6 +747,19 @@ int tsfa_ks_tails(const int64_t *n1, const int64_t *n2, const double *d, int64_t
  * stream. */
 int tsfa_ks_large_tails(const int64_t *n1, const int64_t *n2, const double *d, int64_t n_cells, int32_t device, double *p,
                         unsigned char *route);
+/* ---- the Kolmogorov-Smirnov tail of rare classes on the device (csrc/rel_ks_matrix.h) ----
+ * What kstwo.sf(d, n) does where tsfa_ks_large_tails leaves a cell: for n <= 140 every branch of scipy's _kolmogn (the closed
+ * ones, the one-sided sum, Durbin's matrix for n d^2 <= 0.754693, Pomeranz's recursion up to n d^2 <= 4), and for
+ * 141 <= n <= 100 000 the cells of Durbin's matrix (n d^2 < 2.2 and n d^1.5 <= 1.4), restated in float64 (1e-6 relative to the
+ * host's value).  A cell is served iff max(n1, n2) > 10 000, min(n1, n2) >= 1, d is a number and n is as just said.  A lane
+ * per cell for the closed branches, a wavefront per cell for the sum, the matrices of at most 21 rows and the recursion, a
+ * workgroup per cell for the matrices of up to 117 rows (squared in LDS by v_mfma_f64_16x16x4_f64).
+ *
+ * tsfa_ks_matrix_tails: arguments as tsfa_ks_tails.  A served cell gets its p and TSFA_ROUTE_KS_MATRIX, every other cell --
+ * every cell tsfa_ks_tails or tsfa_ks_large_tails serves among them -- NaN and TSFA_ROUTE_HOST_KS.  n_cells < 2^31.
+ * Synchronous, on the null stream. */
+int tsfa_ks_matrix_tails(const int64_t *n1, const int64_t *n2, const double *d, int64_t n_cells, int32_t device, double *p,
+                         unsigned char *route);
 /* ---- the exact Mann-Whitney tail on the device (csrc/rel_mwu.h) ----
  * significance_tests.py mannwhitney_pvalue's exact branch, bit for bit.  With m = min(n1, n2), n = max(n1, n2), top = m * n and
  * k = clamp(int(u), 0, top + 1), u = max(u1, u2):  p = min(max(2.0 * (S_k / total), 0.0), 1.0), where S_k is the number of

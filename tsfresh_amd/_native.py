@@ -30,9 +30,9 @@ TSFA_PACK_KEEP_SORT = 1
 TSFA_HOST, TSFA_DEVICE = 0, 1
 # enum tsfa_route: who evaluates the tail of a p-value cell (tsfa_relevance_tails_*)
 (TSFA_ROUTE_NONE, TSFA_ROUTE_MWU_NORMAL, TSFA_ROUTE_FISHER, TSFA_ROUTE_KENDALL, TSFA_ROUTE_HOST_MWU_EXACT,
- TSFA_ROUTE_HOST_KS, TSFA_ROUTE_KS_EXACT, TSFA_ROUTE_MWU_EXACT, TSFA_ROUTE_KS_KOLMOGN) = range(9)
+ TSFA_ROUTE_HOST_KS, TSFA_ROUTE_KS_EXACT, TSFA_ROUTE_MWU_EXACT, TSFA_ROUTE_KS_KOLMOGN, TSFA_ROUTE_KS_MATRIX) = range(10)
 # enum tsfa_ks_tail: who evaluates the exact Kolmogorov-Smirnov tails (tsfa_relevance_tails_*)
-TSFA_KS_TAIL_HOST, TSFA_KS_TAIL_DEVICE, TSFA_KS_TAIL_DEVICE_LARGE = 0, 1, 2
+TSFA_KS_TAIL_HOST, TSFA_KS_TAIL_DEVICE, TSFA_KS_TAIL_DEVICE_LARGE, TSFA_KS_TAIL_DEVICE_MATRIX = 0, 1, 2, 3
 # enum tsfa_mwu_tail: who evaluates the exact Mann-Whitney tails (tsfa_relevance_tails_classes), and the cap on m * n
 TSFA_MWU_TAIL_HOST, TSFA_MWU_TAIL_DEVICE = 0, 1
 TSFA_MWU_EXACT_MAX_TOP = 1 << 21
@@ -149,6 +149,7 @@ PROTOTYPES = {
                                         P(i64)]),
     "tsfa_ks_tails": (i32, [ptr, ptr, ptr, i64, i32, ptr, ptr]),
     "tsfa_ks_large_tails": (i32, [ptr, ptr, ptr, i64, i32, ptr, ptr]),
+    "tsfa_ks_matrix_tails": (i32, [ptr, ptr, ptr, i64, i32, ptr, ptr]),
     "tsfa_mwu_tails": (i32, [ptr, ptr, i32, ptr, ptr, i64, i32, ptr, ptr, P(i64)]),
     "tsfa_relevance_fdr": (i32, [ptr, ptr, i64, i32, f64, f64, i32, i32, i32, ptr, ptr, ptr, ptr]),
     "tsfa_compact_mask": (i32, [ptr, i64, ptr, P(i64), i32]),
@@ -1171,11 +1172,12 @@ def ks_outer_prob(m, n, g, h):
 # the matrix and every output are device pointers (ints, e.g. torch's `.data_ptr()`) owned by the caller ----
 
 def _tail_code(name, tail):
-    """The value of enum tsfa_ks_tail / tsfa_mwu_tail (both HOST = 0, DEVICE = 1; ks_tail also DEVICE_LARGE = 2) for the option
-    `name` given as `tail`."""
+    """The value of enum tsfa_ks_tail / tsfa_mwu_tail (both HOST = 0, DEVICE = 1; ks_tail also DEVICE_LARGE = 2 and
+    DEVICE_MATRIX = 3) for the option `name` given as `tail`."""
     codes = {"host": 0, "device": 1}
     if name == "ks_tail":
         codes["device_large"] = TSFA_KS_TAIL_DEVICE_LARGE
+        codes["device_matrix"] = TSFA_KS_TAIL_DEVICE_MATRIX
     if tail not in codes:
         raise ValueError("{} must be {}, not {!r}".format(name, " or ".join(repr(k) for k in codes), tail))
     return codes[tail]
@@ -1193,6 +1195,14 @@ def ks_large_tails(n1_ptr, n2_ptr, d_ptr, n_cells, p_ptr, route_ptr, device=0):
     `ks_tails`; a served cell gets its p and TSFA_ROUTE_KS_KOLMOGN, every other cell NaN and TSFA_ROUTE_HOST_KS."""
     lib = load()
     _check(lib, lib.tsfa_ks_large_tails(n1_ptr, n2_ptr, d_ptr, int(n_cells), int(device), p_ptr, route_ptr))
+
+
+def ks_matrix_tails(n1_ptr, n2_ptr, d_ptr, n_cells, p_ptr, route_ptr, device=0):
+    """tsfa_ks_matrix_tails: the Kolmogorov-Smirnov tails beyond 10 000 rows that `ks_large_tails` leaves (kstwo.sf for n <= 140,
+    and Durbin's matrix up to n = 100 000) of n_cells triples, arguments as `ks_tails`; a served cell gets its p and
+    TSFA_ROUTE_KS_MATRIX, every other cell NaN and TSFA_ROUTE_HOST_KS."""
+    lib = load()
+    _check(lib, lib.tsfa_ks_matrix_tails(n1_ptr, n2_ptr, d_ptr, int(n_cells), int(device), p_ptr, route_ptr))
 
 
 def mwu_tails(n1, n2, table_ptr, u_ptr, n_cells, p_ptr, route_ptr, device=0):
@@ -1216,7 +1226,7 @@ def relevance_tails_classes(x_ptr, n_rows, n_cols, ld, y_codes, n_classes, p_ptr
     """The class tables of the device matrix at x_ptr, left on the device: p [m, C] float64, route [m, C] uint8, type [m]
     uint8 -> the host-route cells (nothing else is copied).  ks_tail="device" / mwu_tail="device" serve the exact Kolmogorov-
     Smirnov / Mann-Whitney tails on the device, ks_tail="device_large" also the Kolmogorov-Smirnov cells beyond 10 000 rows
-    that `ks_large_tails` serves.  ks_d_ptr (with_ks) / rank_sums_ptr: optional device arrays [m, C] float64 that
+    that `ks_large_tails` serves, ks_tail="device_matrix" then those `ks_matrix_tails` serves.  ks_d_ptr (with_ks) / rank_sums_ptr: optional device arrays [m, C] float64 that
     receive the Kolmogorov-Smirnov distances / the rank sums, for the caller's host routes."""
     ks_code, mwu_code = _tail_code("ks_tail", ks_tail), _tail_code("mwu_tail", mwu_tail)
     lib = load()
@@ -1248,7 +1258,7 @@ def relevance_tails_real(x_ptr, n_rows, n_cols, ld, y, tie_statistics, p_ptr, ro
                          n_hi_ptr=None, ks_d_ptr=None):
     """The table of a real target for the device matrix at x_ptr, left on the device: p [m], route [m], type [m] -> the
     host-route cells.  tie_statistics: callable dense ranks -> (ytie, y0, y1).  ks_tail="device" serves the exact
-    Kolmogorov-Smirnov tails on the device, "device_large" also the cells beyond 10 000 rows; n_hi_ptr / ks_d_ptr: optional device arrays [m] (int64 / float64) that receive
+    Kolmogorov-Smirnov tails on the device, "device_large" also the cells beyond 10 000 rows, "device_matrix" then those `ks_matrix_tails` serves; n_hi_ptr / ks_d_ptr: optional device arrays [m] (int64 / float64) that receive
     the two-valued columns' statistics, for the caller's host route."""
     ks_code = _tail_code("ks_tail", ks_tail)
     lib = load()

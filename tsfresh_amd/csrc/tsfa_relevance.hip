@@ -24,6 +24,7 @@
 #include "rel_tails.h"
 #include "rel_ks.h"
 #include "rel_ks_large.h"
+#include "rel_ks_matrix.h"
 #include "rel_mwu.h"
 #include "tsfa_devmem.h"
 
@@ -799,6 +800,127 @@ extern "C" int tsfa_ks_large_tails(const int64_t *n1, const int64_t *n2, const d
     return TSFA_OK;
 }
 
+// ---- the Kolmogorov-Smirnov tail of rare classes (rel_ks_matrix.h): the TSFA_ROUTE_HOST_KS cells the stage above leaves ----
+// branches and closed forms: thread = cell.  The other cells are appended to the work list of their branch, lists[b * n_cells ..]:
+// a wavefront counts its cells of a list by a ballot and takes their places with ONE atomic on cnt[b].  cnt[KSM_LISTS]: the
+// cells a closed branch served; cnt[KSM_LISTS + 1]: the largest k of a KSM_DURBIN_LARGE cell, which sizes that kernel's LDS.
+// (Every lane of a wavefront reaches the ballots: no early return.)
+__global__ void __launch_bounds__(RT_THREADS) k_ksm_route(RkCells s, int64_t n_cells, double *__restrict__ p, unsigned char *__restrict__ route,
+                                                          unsigned long long *__restrict__ cnt, int32_t *__restrict__ lists) {
+    const int64_t cell = (int64_t)blockIdx.x * RT_THREADS + threadIdx.x;
+    const int lane = (int)(threadIdx.x & 63);
+    int k = 0;
+    const int r = (cell < n_cells) ? ksm_route_cell(s, cell, p, route, &k) : KSM_LEAVE;
+    for (int b = 0; b < KSM_LISTS; ++b) {
+        const unsigned long long mine = __ballot(r == KSM_SMIRNOV + b);
+        if (mine == 0ull) continue;   // wave-uniform
+        const int leader = __ffsll((long long)mine) - 1;
+        unsigned long long base = 0ull;
+        if (lane == leader) base = atomicAdd(cnt + b, (unsigned long long)__popcll(mine));
+        base = __shfl(base, leader, 64);
+        if (r == KSM_SMIRNOV + b) lists[(int64_t)b * n_cells + (int64_t)base + __popcll(mine & ((1ull << lane) - 1ull))] = (int32_t)cell;
+    }
+    const unsigned long long closed = __ballot(r != KSM_LEAVE && r < KSM_SMIRNOV);
+    if (closed != 0ull && lane == __ffsll((long long)closed) - 1) atomicAdd(cnt + KSM_LISTS, (unsigned long long)__popcll(closed));
+    if (r == KSM_DURBIN_LARGE) atomicMax(cnt + KSM_LISTS + 1, (unsigned long long)k);
+}
+
+// the one-sided sum: wavefront = cell of the list, in a grid-stride loop, as k_ksl_smirnov
+__global__ void __launch_bounds__(RT_THREADS) k_ksm_smirnov(RkCells s, const int32_t *__restrict__ list, int64_t n_list, double *__restrict__ p,
+                                                            unsigned char *__restrict__ route) {
+    const int64_t wave = (int64_t)blockIdx.x * (RT_THREADS / 64) + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * (RT_THREADS / 64);
+    for (int64_t i = wave; i < n_list; i += n_waves) ksm_list_cell(s, (int64_t)list[i], KSM_SMIRNOV, nullptr, p, route);
+}
+
+// Durbin's matrix up to 21 rows and Pomeranz's recursion: workgroup = ONE wavefront = cell of the list, in a grid-stride loop;
+// the workgroup's barrier is that wavefront's own
+__global__ void __launch_bounds__(64) k_ksm_durbin_small(RkCells s, const int32_t *__restrict__ list, int64_t n_list, double *__restrict__ p,
+                                                         unsigned char *__restrict__ route) {
+    __shared__ double lds[KSM_SMALL_LDS];
+    for (int64_t i = blockIdx.x; i < n_list; i += gridDim.x) ksm_list_cell(s, (int64_t)list[i], KSM_DURBIN_SMALL, lds, p, route);
+}
+__global__ void __launch_bounds__(64) k_ksm_pomeranz(RkCells s, const int32_t *__restrict__ list, int64_t n_list, double *__restrict__ p,
+                                                     unsigned char *__restrict__ route) {
+    __shared__ double lds[3 * KSM_PZ];
+    for (int64_t i = blockIdx.x; i < n_list; i += gridDim.x) ksm_list_cell(s, (int64_t)list[i], KSM_POMERANZ, lds, p, route);
+}
+
+// Durbin's matrix up to 127 rows: workgroup = cell of the list, in a grid-stride loop; dynamic LDS: ksm_large_lds(the list's
+// largest k) doubles
+__global__ void __launch_bounds__(KSM_LG_NT) k_ksm_durbin_large(RkCells s, const int32_t *__restrict__ list, int64_t n_list, double *__restrict__ p,
+                                                                unsigned char *__restrict__ route) {
+    extern __shared__ double ksm_smem[];
+    for (int64_t i = blockIdx.x; i < n_list; i += gridDim.x) ksm_list_cell(s, (int64_t)list[i], KSM_DURBIN_LARGE, ksm_smem, p, route);
+}
+
+#define KSM_MAX_WORKGROUPS 65536   // of one wavefront; beyond, the grid-stride loop
+#define KSM_LG_MAX_WORKGROUPS 1024
+
+// The stage on the null stream of the current device: every TSFA_ROUTE_HOST_KS cell of route[n_cells] that rel_ks_matrix.h
+// serves gets its p and TSFA_ROUTE_KS_MATRIX.  Synchronous; *served: how many.  One block of device memory: the counters and
+// KSM_LISTS work lists of n_cells int32 (a table of 2^31 cells or more is left to the caller).
+static int ks_matrix_run(const RkCells &s, int64_t n_cells, double *p, unsigned char *route, int64_t *served) {
+    *served = 0;
+    if (n_cells == 0 || n_cells > (int64_t)INT32_MAX) return TSFA_OK;
+    unsigned long long cnt[KSM_LISTS + 2];
+    DevPtr<unsigned long long> dblock;
+    HIP_TRY_MALLOC(dblock, sizeof(cnt) + (size_t)KSM_LISTS * (size_t)n_cells * sizeof(int32_t));
+    int32_t *lists = (int32_t *)(dblock.get() + KSM_LISTS + 2);
+    HIP_TRY(hipMemset(dblock.get(), 0, sizeof(cnt)));
+    k_ksm_route<<<dim3((unsigned)((n_cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(s, n_cells, p, route, dblock.get(), lists);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(cnt, dblock.get(), sizeof(cnt), hipMemcpyDeviceToHost));
+    const int64_t n_sum = (int64_t)cnt[KSM_LIST_OF(KSM_SMIRNOV)], n_small = (int64_t)cnt[KSM_LIST_OF(KSM_DURBIN_SMALL)],
+                  n_pz = (int64_t)cnt[KSM_LIST_OF(KSM_POMERANZ)], n_large = (int64_t)cnt[KSM_LIST_OF(KSM_DURBIN_LARGE)];
+    if (n_sum > 0) {
+        int64_t nwg = (n_sum + RT_THREADS / 64 - 1) / (RT_THREADS / 64);
+        if (nwg > KSL_MAX_WORKGROUPS) nwg = KSL_MAX_WORKGROUPS;
+        k_ksm_smirnov<<<dim3((unsigned)nwg), RT_THREADS, 0, 0>>>(s, lists + KSM_LIST_OF(KSM_SMIRNOV) * n_cells, n_sum, p, route);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_small > 0) {
+        const int64_t nwg = (n_small < KSM_MAX_WORKGROUPS) ? n_small : KSM_MAX_WORKGROUPS;
+        k_ksm_durbin_small<<<dim3((unsigned)nwg), 64, 0, 0>>>(s, lists + KSM_LIST_OF(KSM_DURBIN_SMALL) * n_cells, n_small, p, route);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_pz > 0) {
+        const int64_t nwg = (n_pz < KSM_MAX_WORKGROUPS) ? n_pz : KSM_MAX_WORKGROUPS;
+        k_ksm_pomeranz<<<dim3((unsigned)nwg), 64, 0, 0>>>(s, lists + KSM_LIST_OF(KSM_POMERANZ) * n_cells, n_pz, p, route);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_large > 0) {
+        const int k_max = (int)cnt[KSM_LISTS + 1];   // <= KSM_LG_MAX_K: ksm_branch leaves the cell otherwise
+        const size_t lds = ksm_large_lds(k_max) * sizeof(double);
+        const int64_t nwg = (n_large < KSM_LG_MAX_WORKGROUPS) ? n_large : KSM_LG_MAX_WORKGROUPS;
+        HIP_TRY(hipFuncSetAttribute((const void *)k_ksm_durbin_large, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k_ksm_durbin_large<<<dim3((unsigned)nwg), KSM_LG_NT, lds, 0>>>(s, lists + KSM_LIST_OF(KSM_DURBIN_LARGE) * n_cells, n_large, p, route);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipDeviceSynchronize());   // the block is freed on return
+    *served = n_sum + n_small + n_pz + n_large + (int64_t)cnt[KSM_LISTS];
+    return TSFA_OK;
+}
+
+extern "C" int tsfa_ks_matrix_tails(const int64_t *n1, const int64_t *n2, const double *d, int64_t n_cells, int32_t device, double *p,
+                                    unsigned char *route) {
+    if (n_cells < 0 || n_cells > (int64_t)INT32_MAX || (n_cells > 0 && (!n1 || !n2 || !d || !p || !route)))
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_ks_matrix_tails: null pointer or bad shape");
+    int rc = rel_check_device(device, "tsfa_ks_matrix_tails");
+    if (rc || n_cells == 0) return rc;
+    HIP_TRY(hipSetDevice(device));
+    k_ks_init<<<dim3((unsigned)((n_cells + RT_THREADS - 1) / RT_THREADS)), RT_THREADS, 0, 0>>>(n_cells, p, route);
+    HIP_TRY(hipGetLastError());
+    RkCells s = {};
+    s.n1 = n1;
+    s.n2 = n2;
+    s.d = d;
+    int64_t served = 0;
+    rc = ks_matrix_run(s, n_cells, p, route, &served);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return TSFA_OK;
+}
+
 // ---- the exact Mann-Whitney tail (rel_mwu.h): the TSFA_ROUTE_HOST_MWU_EXACT cells of the tables the device serves ----
 // a distinct (m, n): where its table of prefix sums starts in the block of tables, and where its two buffers start in the
 // scratch block (words; -1: the buffers are LDS)
@@ -918,9 +1040,10 @@ extern "C" int tsfa_mwu_tails(const int64_t *n1, const int64_t *n2, int32_t n_ta
 
 // the two tail options of the tails entries (a real target has no Mann-Whitney cells: its entry passes TSFA_MWU_TAIL_HOST)
 static int tail_check(int32_t ks_tail, int32_t mwu_tail, const char *who) {
-    if (ks_tail != TSFA_KS_TAIL_HOST && ks_tail != TSFA_KS_TAIL_DEVICE && ks_tail != TSFA_KS_TAIL_DEVICE_LARGE)
-        return tsfa_fail(TSFA_ERR_INVALID,
-                         (std::string(who) + ": ks_tail must be TSFA_KS_TAIL_HOST, TSFA_KS_TAIL_DEVICE or TSFA_KS_TAIL_DEVICE_LARGE").c_str());
+    if (ks_tail != TSFA_KS_TAIL_HOST && ks_tail != TSFA_KS_TAIL_DEVICE && ks_tail != TSFA_KS_TAIL_DEVICE_LARGE &&
+        ks_tail != TSFA_KS_TAIL_DEVICE_MATRIX)
+        return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": ks_tail must be TSFA_KS_TAIL_HOST, TSFA_KS_TAIL_DEVICE, "
+                                                               "TSFA_KS_TAIL_DEVICE_LARGE or TSFA_KS_TAIL_DEVICE_MATRIX").c_str());
     if (mwu_tail != TSFA_MWU_TAIL_HOST && mwu_tail != TSFA_MWU_TAIL_DEVICE)
         return tsfa_fail(TSFA_ERR_INVALID, (std::string(who) + ": mwu_tail must be TSFA_MWU_TAIL_HOST or TSFA_MWU_TAIL_DEVICE").c_str());
     return TSFA_OK;
@@ -967,8 +1090,13 @@ extern "C" int tsfa_relevance_tails_classes(const double *X, int64_t n_rows, int
         rc = ks_tails_run(s, cells, p, route, &served);
         if (rc) return rc;
         nh -= (unsigned long long)served;
-        if (ks_tail == TSFA_KS_TAIL_DEVICE_LARGE && nh > 0) {   // what is still flagged: the cells beyond RK_MAX_ROWS
+        if (ks_tail >= TSFA_KS_TAIL_DEVICE_LARGE && nh > 0) {   // what is still flagged: the cells beyond RK_MAX_ROWS
             rc = ks_large_run(s, cells, p, route, &served);
+            if (rc) return rc;
+            nh -= (unsigned long long)served;
+        }
+        if (ks_tail == TSFA_KS_TAIL_DEVICE_MATRIX && nh > 0) {   // and of those, Durbin's matrix and n <= 140
+            rc = ks_matrix_run(s, cells, p, route, &served);
             if (rc) return rc;
             nh -= (unsigned long long)served;
         }
@@ -1019,8 +1147,13 @@ extern "C" int tsfa_relevance_tails_real(const double *X, int64_t n_rows, int64_
         rc = ks_tails_run(s, n_cols, p, route, &served);
         if (rc) return rc;
         nh -= (unsigned long long)served;
-        if (ks_tail == TSFA_KS_TAIL_DEVICE_LARGE && nh > 0) {
+        if (ks_tail >= TSFA_KS_TAIL_DEVICE_LARGE && nh > 0) {
             rc = ks_large_run(s, n_cols, p, route, &served);
+            if (rc) return rc;
+            nh -= (unsigned long long)served;
+        }
+        if (ks_tail == TSFA_KS_TAIL_DEVICE_MATRIX && nh > 0) {
+            rc = ks_matrix_run(s, n_cols, p, route, &served);
             if (rc) return rc;
             nh -= (unsigned long long)served;
         }

@@ -29,6 +29,11 @@ the host's value, not bit for bit.  A cell is served for 141 <= n <= 1 000 000 u
 (n d^2 < 2.2, n <= 100 000 and n d^1.5 <= 1.4: all such cells have p >= 0.9).  What is left for the host are those cells, rare
 classes with n <= 140 and samples beyond n = 1 000 000.
 
+`ks_tail="device_matrix"` serves what `"device_large"` serves and then, of the cells still left, every cell with n <= 140 and the
+Durbin-matrix cells up to n = 100 000 (`csrc/rel_ks_matrix.h`, route `TSFA_ROUTE_KS_MATRIX`): scipy's `_kolmogn` with Durbin's
+matrix and Pomeranz's recursion restated in float64, within 1e-6 relative of the host's value.  What is left for the host are
+samples beyond n = 1 000 000.
+
 `mwu_tail="device"` moves the exact Mann-Whitney tail onto the GPU (`csrc/rel_mwu.h`, route `TSFA_ROUTE_MWU_EXACT`): the
 arrangement counts of a class are built once, in exact integers, and every cell of that class is a lookup and one correctly
 rounded division, equal to `mannwhitney_pvalue` bit for bit.  What is left for the host are classes whose smaller side times
@@ -127,7 +132,7 @@ def impute_tensor(X):
 
 
 def _check_tails(ks_tail, mwu_tail):
-    _native._tail_code("ks_tail", ks_tail)   # "host", "device" or "device_large"
+    _native._tail_code("ks_tail", ks_tail)   # "host", "device", "device_large" or "device_matrix"
     _native._tail_code("mwu_tail", mwu_tail)   # "host" or "device"
 
 
@@ -268,7 +273,9 @@ def calculate_relevance_tensor(X, y, columns=None, ml_task="auto", multiclass=Fa
         p-values (`routes` then shows `TSFA_ROUTE_KS_EXACT`, and `host_cells` counts what is left to the host).
         "device_large": as "device", and the GPU also evaluates scipy's `kstwo.sf` for the cells beyond 10 000 rows with
         141 <= round(n1 n2 / (n1 + n2)) <= 1 000 000 that are not Durbin-matrix cells, within 1e-6 relative of the host's
-        p-values (`routes` shows `TSFA_ROUTE_KS_KOLMOGN` there).  Anything else raises `ValueError`.
+        p-values (`routes` shows `TSFA_ROUTE_KS_KOLMOGN` there).  "device_matrix": as "device_large", and the GPU also evaluates
+        the cells of rare classes (round(n1 n2 / (n1 + n2)) <= 140) and the Durbin-matrix cells up to 100 000, to the same bar
+        (`TSFA_ROUTE_KS_MATRIX`).  Anything else raises `ValueError`.
     :param mwu_tail: who evaluates the exact Mann-Whitney tails (classification under "mann": a class or its complement with
         at most 8 rows, a column without ties).  "host" (default): `mannwhitney_pvalue`, one cell at a time, which rebuilds the
         arrangement counts for every cell.  "device": the GPU builds the counts once per class, with equal p-values (`routes`
