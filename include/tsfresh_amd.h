@@ -373,7 +373,45 @@ int tsfa_pack_set_rows(tsfa_pack_set *set, const void *values, int32_t value_typ
  * TSFA_ERR_INVALID: a null pointer, another type, a ticks_per_second outside the four values, a negative stride. */
 int tsfa_pack_set_hours(const tsfa_pack_set *set, const void *t, int32_t t_type, int64_t ticks_per_second, int64_t stride,
                         double *hours_out, int32_t *flags_out);
+/* Compose: after tsfa_pack_rows_valid (below) compacted the key columns and a set was created on the compacted columns, the
+ * set's permutation indexes compacted rows.  This call rewrites it once, perm[p] = src[perm[p]], so that tsfa_pack_set_rows,
+ * tsfa_pack_set_values and tsfa_pack_set_hours afterwards read the ORIGINAL, uncompacted value matrix / value column / stamp
+ * column of n_source_rows rows: values and stamps are read once, where they lie, and never copied.  Those three calls size
+ * their outputs by the set's (kept) rows and index their input only through the permutation; their stride checks and the
+ * staging of a TSFA_HOST value column use n_source_rows from here on.
+ *   src             the set's n_rows 32-bit input-row indices (a device pointer), each below n_source_rows; free to go after
+ *   n_source_rows   rows of the uncompacted frame, in [the set's n_rows, 2^32 - 1]
+ * One kernel, one lane per sorted position.  Synchronous.  TSFA_ERR_INVALID: a null pointer, n_source_rows out of range, a
+ * set that has been remapped before. */
+int tsfa_pack_set_remap(tsfa_pack_set *set, const uint32_t *src, int64_t n_source_rows);
 void tsfa_pack_set_destroy(tsfa_pack_set *set);
+
+/* Valid-row packer: the key columns of a frame held as columns in device memory WITHOUT the rows `dropna()` drops, for a pack
+ * set that is then created on them.  A row is dropped when one of its n_cols values is NaN (TSFA_F32 / TSFA_F64 values; any
+ * other element type is not read), when its sort key is NaN (TSFA_F32 / TSFA_F64 keys) or when its stamp is NaT (INT64_MIN
+ * ticks) or a NaN second.  +-inf stays.  Kept rows keep their relative order.
+ *   ids, sort, kinds        contiguous device columns as tsfa_pack_set_create takes them (sort and kinds may be NULL)
+ *   values, value_type, n_cols, stride_row, stride_col   the value matrix as tsfa_pack_set_rows takes it (a long frame's value
+ *                           column: n_cols 1), or NULL: no values are tested
+ *   t, t_type, t_stride     the stamps as tsfa_pack_set_hours takes them, or NULL
+ *   ids_out, sort_out, kinds_out   device buffers of n_rows elements of the columns' own types (the kept count is not known
+ *                           before the call); the first *n_kept are written
+ *   src_out                 n_rows uint32: src_out[slot] = input row of compacted row `slot` (for tsfa_pack_set_remap)
+ *   n_kept                  kept rows.  When it is 0 or n_rows NOTHING has been written to the four outputs: with n_rows the
+ *                           caller goes on with its own columns.
+ * Three launches over blocks of TSFA_ROWS_VALID_BLOCK rows: mark (one 64-bit validity word per 64 rows from a wavefront
+ * ballot and the block's kept count; a row-major matrix -- stride_col == 1, up to 2^20 columns -- is read as flat coalesced
+ * tiles with lane = element and per-row flags in LDS, anything else with lane = row), the scan of the block counts (the
+ * sort's own scan kernel), compact (slot = block base + prefix population count; no atomic on positions, no sort).  When
+ * nothing can be NaN (no float values, no float sort keys, no stamps) nothing is launched and *n_kept = n_rows.
+ * Scratch, freed before the call returns: 8 bytes per 64 rows + 4 bytes per 1024 rows.  Synchronous.
+ * TSFA_ERR_INVALID: a null pointer, a key column of another type, the argument errors of tsfa_pack_set_rows for the matrix
+ * and of tsfa_pack_set_hours for the stamps; TSFA_ERR_TOO_LONG: more than 2^32 - 1 rows. */
+#define TSFA_ROWS_VALID_BLOCK 1024
+int tsfa_pack_rows_valid(const void *ids, int32_t id_type, const void *sort, int32_t sort_type, const void *kinds,
+                         int32_t kind_type, const void *values, int32_t value_type, int64_t n_cols, int64_t stride_row,
+                         int64_t stride_col, const void *t, int32_t t_type, int64_t t_stride, int64_t n_rows, int32_t device,
+                         void *ids_out, void *sort_out, void *kinds_out, uint32_t *src_out, int64_t *n_kept);
 
 /* Dense packer: the ragged layout for a batch that already IS an array in device memory -- (n_batch, n_channels, n_time) with
  * any non-negative element strides: [B, C, n], the channels-last [B, n, C] of a multivariate recording, [B, n] (one channel,

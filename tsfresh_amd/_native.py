@@ -28,6 +28,7 @@ TSFA_DENSE_BAD_TIME = 16   # tsfa_pack_times
 TSFA_DENSE_EMPTY_SERIES = 32   # tsfa_pack_dense_valid
 TSFA_PACK_KEEP_SORT = 1
 TSFA_HOST, TSFA_DEVICE = 0, 1
+TSFA_ROWS_VALID_BLOCK = 1024   # rows of one workgroup block of tsfa_pack_rows_valid
 # enum tsfa_route: who evaluates the tail of a p-value cell (tsfa_relevance_tails_*)
 (TSFA_ROUTE_NONE, TSFA_ROUTE_MWU_NORMAL, TSFA_ROUTE_FISHER, TSFA_ROUTE_KENDALL, TSFA_ROUTE_HOST_MWU_EXACT,
  TSFA_ROUTE_HOST_KS, TSFA_ROUTE_KS_EXACT, TSFA_ROUTE_MWU_EXACT, TSFA_ROUTE_KS_KOLMOGN, TSFA_ROUTE_KS_MATRIX) = range(10)
@@ -113,7 +114,10 @@ PROTOTYPES = {
     "tsfa_pack_set_values": (i32, [ptr, ptr, i32, i32, P(ptr)]),
     "tsfa_pack_set_rows": (i32, [ptr, ptr, i32, i64, i64, i64, P(ptr)]),
     "tsfa_pack_set_hours": (i32, [ptr, ptr, i32, i64, i64, ptr, ptr]),
+    "tsfa_pack_set_remap": (i32, [ptr, ptr, i64]),
     "tsfa_pack_set_destroy": (None, [ptr]),
+    "tsfa_pack_rows_valid": (i32, [ptr, i32, ptr, i32, ptr, i32, ptr, i32, i64, i64, i64, ptr, i32, i64, i64, i32, ptr, ptr, ptr, ptr,
+                                   P(i64)]),
     "tsfa_pack_dense": (i32, [ptr, i32, i64, i64, i64, i64, i64, i64, ptr, i32, ptr, i64, ptr, ptr, i32, ptr]),
     "tsfa_pack_times": (i32, [ptr, i32, i64, i64, i64, i64, i64, ptr, ptr, ptr, i32, ptr]),
     "tsfa_pack_dense_valid": (i32, [ptr, i32, i64, i64, i64, i64, i64, i64, ptr, i32, ptr, i32, i64, i64, ptr, i64, ptr, ptr, ptr,
@@ -521,6 +525,30 @@ class DevicePackSet(_Owner):
             raise ValueError("the pack set is closed")
         _check(self._lib, self._lib.tsfa_pack_set_hours(self._h, t_ptr, int(t_type), int(ticks_per_second), int(stride),
                                                         hours_ptr, flags_ptr))
+
+    def remap(self, src_ptr, n_source_rows):
+        """tsfa_pack_set_remap: the set was made on key columns compacted by `pack_rows_valid`; src_ptr: the n_rows uint32
+        input-row indices it wrote (a device pointer).  Afterwards `rows` / `values` / `hours` take the UNCOMPACTED value
+        matrix / value column / stamps of n_source_rows rows."""
+        if not self._h:
+            raise ValueError("the pack set is closed")
+        _check(self._lib, self._lib.tsfa_pack_set_remap(self._h, src_ptr, int(n_source_rows)))
+
+
+def pack_rows_valid(ids, sort, kinds, values, stamps, n_rows, ids_out_ptr, sort_out_ptr, kinds_out_ptr, src_out_ptr, device=0):
+    """tsfa_pack_rows_valid on raw device pointers (ints): the key columns without the rows that hold a NaN value, a NaN
+    sort key or a NaT / NaN stamp -> the kept rows.  ids / sort / kinds: (pointer, tsfa_dtype code) of contiguous columns, or
+    None; values: (pointer, tsfa_dtype code, n_cols, stride_row, stride_col) or None; stamps: (pointer, tsfa_dtype code,
+    stride) or None.  The outputs hold n_rows elements each; when the result is 0 or n_rows they are left unwritten."""
+    lib = load()
+    (ids_p, ids_t), (sort_p, sort_t), (kind_p, kind_t) = [c or (None, 0) for c in (ids, sort, kinds)]
+    val_p, val_t, n_cols, sr, sc = values or (None, 0, 0, 0, 0)
+    t_p, t_t, t_stride = stamps or (None, 0, 0)
+    n_kept = ctypes.c_int64()
+    _check(lib, lib.tsfa_pack_rows_valid(ids_p, int(ids_t), sort_p, int(sort_t), kind_p, int(kind_t), val_p, int(val_t), int(n_cols),
+                                         int(sr), int(sc), t_p, int(t_t), int(t_stride), int(n_rows), int(device), ids_out_ptr,
+                                         sort_out_ptr, kinds_out_ptr, src_out_ptr, ctypes.byref(n_kept)))
+    return int(n_kept.value)
 
 
 def pack_dense(x_ptr, x_type, shape, strides, values_ptr, channel_stride_out, offsets_ptr, flags_ptr, device=0,

@@ -6,6 +6,8 @@
 // sorter's twin on looped kernel bodies.  Staging, argument checks, view filling and copy-out are one helper each.
 // The window builder (tsfa_roll_windows, roll_device.h) lives here as well: it reads a pack's buffers and reuses k_pack_scan.
 // So does the row packer (tsfa_pack_set_rows, tsfa_pack_set_hours; pack_rows.h): it reads a set's permutation and offsets.
+// And the valid-row packer (tsfa_pack_rows_valid, tsfa_pack_set_remap; pack_rows_valid.h): it compacts the key columns a set
+// is then made on, reuses k_pack_scan, and rewrites a set's permutation.
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -15,6 +17,7 @@
 
 #include "pack_device.h"
 #include "pack_rows.h"
+#include "pack_rows_valid.h"
 #include "roll_device.h"
 #include "tsfa_devmem.h"
 
@@ -38,6 +41,7 @@ struct tsfa_pack {
 struct tsfa_pack_set {
     int32_t device = 0;
     int64_t n_rows = 0, n_groups = 0;
+    int64_t n_src = 0;  // rows of the arrays perm indexes: n_rows, or after tsfa_pack_set_remap the uncompacted frame's
     int32_t n_kinds = 0, flags = 0, n_passes = 0;
     int32_t id_type = 0, sort_type = 0, kind_type = 0;
     bool has_kinds = false;
@@ -192,6 +196,25 @@ __global__ void __launch_bounds__(PK_THREADS) k_pack_set_hours(PhArgs a) {
     __shared__ int64_t head;
     const PkBlk b{(int)threadIdx.x, PK_THREADS};
     ph_hours_body<TYPE>(b, (int64_t)blockIdx.x, (int64_t)gridDim.x, a, starts, &head);
+}
+
+// ---- the valid-row packer's kernels (pack_rows_valid.h) ----
+template <int VT, bool FLAT>
+__global__ void __launch_bounds__(PK_THREADS) k_pack_rows_valid_mark(PrvArgs a) {
+    __shared__ uint32_t bad[FLAT ? PRV_BLOCK : 1];
+    __shared__ unsigned int ws[PRV_WAVES];
+    const PkBlk b{(int)threadIdx.x, PK_THREADS};
+    prv_mark_body<VT, FLAT>(b, (int64_t)blockIdx.x, (int64_t)gridDim.x, a, bad, ws);
+}
+
+__global__ void __launch_bounds__(PK_THREADS) k_pack_rows_valid_compact(PrvArgs a) {
+    const PkBlk b{(int)threadIdx.x, PK_THREADS};
+    prv_compact_body(b, (int64_t)blockIdx.x, (int64_t)gridDim.x, a);
+}
+
+__global__ void __launch_bounds__(PK_GRID_THREADS) k_pack_set_remap(uint32_t *perm, const uint32_t *src, int64_t n) {
+    const PkBlk b{(int)threadIdx.x, (int)blockDim.x};
+    prv_remap_body(b, (int64_t)blockIdx.x * blockDim.x, (int64_t)gridDim.x * blockDim.x, perm, src, n);
 }
 
 // a device buffer as several holders keep it: freed on its device when the last of them goes
@@ -476,7 +499,7 @@ extern "C" int tsfa_pack_set_create(const void *ids, int32_t id_type, const void
     const int64_t n = n_rows;
     const int id_size = pk_itemsize(id_type), sort_size = sort ? pk_itemsize(sort_type) : 0, kind_size = kinds ? pk_itemsize(kind_type) : 0;
     std::unique_ptr<tsfa_pack_set, void (*)(tsfa_pack_set *)> set(new tsfa_pack_set(), tsfa_pack_set_destroy);
-    set->device = device; set->n_rows = n; set->id_type = id_type; set->sort_type = sort ? sort_type : 0;
+    set->device = device; set->n_rows = n; set->n_src = n; set->id_type = id_type; set->sort_type = sort ? sort_type : 0;
     set->kind_type = kinds ? kind_type : 0; set->has_kinds = kinds != nullptr;
 
     HIP_TRY(hipSetDevice(device));
@@ -579,7 +602,8 @@ extern "C" int tsfa_pack_set_values(tsfa_pack_set *set, const void *values, int3
     HIP_TRY(hipSetDevice(set->device));
     DevPtr<void> d_vals, d_out_own;
     DevPtr<PkStats> d_st_own;
-    if (int rc = pk_stage(TSFA_WHO, space, d_vals, &values, (size_t)n * val_size, "the value column")) return rc;
+    // (the column is row-aligned with the frame perm indexes: n_src rows, of which the n sorted positions are gathered)
+    if (int rc = pk_stage(TSFA_WHO, space, d_vals, &values, (size_t)set->n_src * val_size, "the value column")) return rc;
     HIP_TRY_ALLOC(d_st_own, sizeof(PkStats), "the packer's counters");
     PkStats *const d_st = d_st_own.get();
     HIP_TRY(hipMemset(d_st, 0, sizeof(PkStats)));
@@ -610,7 +634,7 @@ extern "C" int tsfa_pack_set_rows(tsfa_pack_set *set, const void *values, int32_
     if (!set) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_rows: set is NULL");
     if (set->has_kinds) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_rows: the set was made with a kind column (a value matrix is a wide frame)");
     const char *why;
-    if (int rc = pr_check(values, value_type, set->n_rows, n_cols, stride_row, stride_col, out_packs, &why))
+    if (int rc = pr_check(values, value_type, set->n_src, n_cols, stride_row, stride_col, out_packs, &why))
         return tsfa_fail(rc, (std::string("tsfa_pack_set_rows: ") + why).c_str());
     const int64_t n = set->n_rows;
     const int out_type = pk_out_type(value_type), out_size = pk_itemsize(out_type);
@@ -663,7 +687,7 @@ extern "C" int tsfa_pack_set_hours(const tsfa_pack_set *set, const void *t, int3
                                    double *hours_out, int32_t *flags_out) {
     if (!set) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_hours: set is NULL");
     const char *why;
-    if (int rc = ph_check(t, t_type, ticks_per_second, set->n_rows, stride, hours_out, flags_out, &why))
+    if (int rc = ph_check(t, t_type, ticks_per_second, set->n_src, stride, hours_out, flags_out, &why))
         return tsfa_fail(rc, (std::string("tsfa_pack_set_hours: ") + why).c_str());
     PhArgs a;
     a.t = t; a.stride = stride; a.tps = t_type == TSFA_I64 ? (double)ticks_per_second : 1.0;
@@ -679,7 +703,75 @@ extern "C" int tsfa_pack_set_hours(const tsfa_pack_set *set, const void *t, int3
     return TSFA_OK;
 }
 
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_pack_set_remap"
+extern "C" int tsfa_pack_set_remap(tsfa_pack_set *set, const uint32_t *src, int64_t n_source_rows) {
+    if (!set || !src) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_remap: null pointer");
+    if (n_source_rows < set->n_rows || n_source_rows > 0xffffffffll)
+        return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_remap: n_source_rows must lie in [the set's rows, 4 294 967 295]");
+    if (set->n_src != set->n_rows) return tsfa_fail(TSFA_ERR_INVALID, "tsfa_pack_set_remap: the set has been remapped");
+    HIP_TRY(hipSetDevice(set->device));
+    k_pack_set_remap<<<pk_grid(set->n_rows), PK_GRID_THREADS, 0, 0>>>((uint32_t *)set->perm.get(), src, set->n_rows);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(0));  // (src may go)
+    set->n_src = n_source_rows;
+    return TSFA_OK;
+}
+
 extern "C" void tsfa_pack_set_destroy(tsfa_pack_set *set) { delete set; }
+
+// ---------------------------------------------------------------------------------------------
+// Valid-row packer: the key columns of a frame without the rows dropna() drops (pack_rows_valid.h)
+// ---------------------------------------------------------------------------------------------
+#undef TSFA_WHO
+#define TSFA_WHO "tsfa_pack_rows_valid"
+extern "C" int tsfa_pack_rows_valid(const void *ids, int32_t id_type, const void *sort, int32_t sort_type, const void *kinds,
+                                    int32_t kind_type, const void *values, int32_t value_type, int64_t n_cols, int64_t stride_row,
+                                    int64_t stride_col, const void *t, int32_t t_type, int64_t t_stride, int64_t n_rows,
+                                    int32_t device, void *ids_out, void *sort_out, void *kinds_out, uint32_t *src_out,
+                                    int64_t *n_kept) {
+    const char *why;
+    if (int rc = prv_check(ids, id_type, sort, sort_type, kinds, kind_type, values, value_type, n_cols, stride_row, stride_col, t,
+                           t_type, t_stride, n_rows, ids_out, sort_out, kinds_out, src_out, n_kept, &why))
+        return tsfa_fail(rc, (std::string("tsfa_pack_rows_valid: ") + why).c_str());
+    if (int rc = tsfa_check_device(TSFA_WHO, device)) return rc;
+    *n_kept = n_rows;
+    const bool test_values = values && prv_is_float(value_type), test_sort = sort && prv_is_float(sort_type);
+    if (!test_values && !test_sort && !t) return TSFA_OK;  // nothing can be NaN: nothing is launched
+
+    PrvArgs a;
+    a.ids = ids; a.sort = sort; a.kinds = kinds;
+    a.id_size = pk_itemsize(id_type); a.sort_size = sort ? pk_itemsize(sort_type) : 0; a.kind_size = kinds ? pk_itemsize(kind_type) : 0;
+    a.sort_type = sort ? sort_type : -1;
+    a.values = test_values ? values : nullptr; a.n_cols = test_values ? n_cols : 0; a.sr = stride_row; a.sc = stride_col;
+    a.t = t; a.t_type = t_type; a.t_stride = t_stride;
+    a.n_rows = n_rows; a.n_blocks = (n_rows + PRV_BLOCK - 1) / PRV_BLOCK;
+    a.ids_out = ids_out; a.sort_out = sort_out; a.kinds_out = kinds_out; a.src = src_out;
+
+    HIP_TRY(hipSetDevice(device));
+    DevPtr<pk_u64> d_words;
+    DevPtr<uint32_t> d_counts;  // n_blocks counts and their total
+    HIP_TRY_ALLOC(d_words, (size_t)a.n_blocks * PRV_WORDS * 8, "the validity words (8 bytes per 64 rows)");
+    HIP_TRY_ALLOC(d_counts, (size_t)(a.n_blocks + 1) * 4, "the blocks' kept counts");
+    a.words = d_words.get(); a.counts = d_counts.get();
+    const unsigned grid = (unsigned)(a.n_blocks < PRV_MAX_GRID ? a.n_blocks : PRV_MAX_GRID);
+    const bool flat = test_values && prv_flat(n_cols, stride_col);
+    if (!test_values) k_pack_rows_valid_mark<PRV_NO_VALUES, false><<<grid, PK_THREADS, 0, 0>>>(a);
+    else if (value_type == TSFA_F32 && flat) k_pack_rows_valid_mark<TSFA_F32, true><<<grid, PK_THREADS, 0, 0>>>(a);
+    else if (value_type == TSFA_F32) k_pack_rows_valid_mark<TSFA_F32, false><<<grid, PK_THREADS, 0, 0>>>(a);
+    else if (flat) k_pack_rows_valid_mark<TSFA_F64, true><<<grid, PK_THREADS, 0, 0>>>(a);
+    else k_pack_rows_valid_mark<TSFA_F64, false><<<grid, PK_THREADS, 0, 0>>>(a);
+    k_pack_scan<<<1, PK_SCAN_THREADS, 0, 0>>>(a.counts, (size_t)a.n_blocks, a.counts + a.n_blocks);
+    HIP_TRY(hipGetLastError());
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpy(&total, a.counts + a.n_blocks, sizeof(total), hipMemcpyDeviceToHost));  // (synchronises)
+    *n_kept = (int64_t)total;
+    if (total == 0 || (int64_t)total == n_rows) return TSFA_OK;  // nothing to compact: the outputs stay unwritten
+    k_pack_rows_valid_compact<<<grid, PK_THREADS, 0, 0>>>(a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(0));  // (the scratch may go)
+    return TSFA_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Window builder: the rolled layout of one pack (roll_device.h), built from the pack's offsets on the device

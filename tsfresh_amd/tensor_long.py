@@ -10,11 +10,18 @@ stamps become hours since each series' first stamp in the same order (`tsfa_pack
 kernels `extract_features` runs, through the same FCParameters handling, plan cache and composite plans.  The feature matrix
 and the ids of its rows stay on the device.
 
-Scratch of the pack while the call runs: 40 bytes per row (two buffers of 16-byte composite key + 4-byte row index), as for
-`extract_features(pack="device")`; the set keeps 4 bytes per row (the permutation) until the call returns.
+`nan_policy="drop"` drops the rows `dropna()` would drop in the packer itself: `tsfa_pack_rows_valid` marks the rows (one
+64-bit word per 64 rows from a wavefront ballot), compacts the KEY columns only and hands out the kept rows' input indices;
+the set is made on the compacted keys and its permutation composed with those indices (`tsfa_pack_set_remap`), so the value
+matrix and the stamps are still read once, where they lie, and never copied.
 
-Not offered: `nan_policy="drop"` (drop the rows with torch first), a rolled twin, an enqueue-only mode, string or float ids
-(factorize them first: the codes are integer ids).
+Scratch of the pack while the call runs: 40 bytes per row (two buffers of 16-byte composite key + 4-byte row index), as for
+`extract_features(pack="device")`; the set keeps 4 bytes per row (the permutation) until the call returns.  With
+`nan_policy="drop"`, when a column can hold NaN: 8 bytes per 64 rows (the words) and, sized for all N rows because the kept
+count is known only after the mark, 4 bytes per row (the indices) plus one copy of the id, sort and kind columns; the sort's
+40 bytes are then per KEPT row.
+
+Not offered: a rolled twin, an enqueue-only mode, string or float ids (factorize them first: the codes are integer ids).
 """
 import numpy as np
 
@@ -184,7 +191,7 @@ def _union_rows(torch, id_sets, dtype):
 
 def extract_features_long_tensor(ids, values, sort=None, kinds=None, kind_names=None, times=None, time_unit="ns",
                                  default_fc_parameters=None, kind_to_fc_parameters=None, device=None, check_nan=True,
-                                 show_warnings=False):
+                                 show_warnings=False, nan_policy="raise"):
     """Extract features from a frame held as column tensors, rows in any order; the feature matrix stays on the GPU.
 
     :param ids: `[N]` tensor or numpy array of an integer dtype: the id of every row.  bool, float and string ids raise
@@ -207,6 +214,14 @@ def extract_features_long_tensor(ids, values, sort=None, kinds=None, kind_names=
     :param check_nan: True (default): after the pack, from one read-back, a NaN value raises the reference's
         `ValueError("Column must not contain NaN values: <kind>")`, a NaN in a float `sort` the same error naming `sort`,
         a NaT / NaN stamp `ValueError("times must not contain NaT / NaN")`.  False skips the checks and the read-back.
+        Without effect under `nan_policy="drop"`: nothing that is NaN reaches the pack, and there is no read-back.
+    :param nan_policy: "raise" (default): see `check_nan`.  "drop": the equivalent frame after `dropna()` -- a row is dropped
+        on the device when any of its C values is NaN (the long form: its one value, so the drop is per kind already; there
+        is no "drop_per_kind" here), when its float `sort` key is NaN, or when its stamp is NaT / NaN.  +-inf stays; integer
+        and bool columns hold no NaN; kept rows keep their relative order.  An id without a kept row in any kind has no row
+        in `ids_out`; one that a kind lacks has NaN cells there; hours count from each series' first kept stamp; no row
+        left raises `ValueError`.  When nothing can be NaN (integer or bool values, an integer or absent `sort`, no
+        `times`) nothing extra is launched.  Any other value raises `ValueError`.
     :return: `(features, columns, ids_out)`: `features` `torch.float64` `[U, number of columns]` on the device; `columns`
         the names ``"{kind}__{feature}"`` in exactly the order `extract_features` gives for the equivalent frame (the wide
         form's kinds in `kind_names` order, the long form's in the sorted order of their NAMES); `ids_out` `[U]` on the
@@ -218,11 +233,15 @@ def extract_features_long_tensor(ids, values, sort=None, kinds=None, kind_names=
     when the call returns.
 
     Memory: the sort's scratch is 40 bytes per row while the call runs (more than 2^32 - 1 rows raise `ValueError`); the
-    packed samples are one more copy of `values` in its output type.
+    packed samples are one more copy of `values` in its output type.  `nan_policy="drop"` adds, while the call runs, 8 bytes
+    per 64 rows, 4 bytes per row and one copy of the id, sort and kind columns (sized for N rows); the sort's 40 bytes are
+    then per kept row.
 
-    Not offered: `nan_policy="drop"`, a rolled twin, an enqueue-only mode, string or float ids.  Not mirrored, as in
+    Not offered: a rolled twin, an enqueue-only mode, string or float ids.  Not mirrored, as in
     `extract_features_tensor`: the reference's exceptions that depend on the samples.
     """
+    if nan_policy not in ("raise", "drop"):
+        raise ValueError('nan_policy must be "raise" or "drop", not {!r}'.format(nan_policy))
     import torch
 
     from tsfresh_amd.feature_extraction import extraction
@@ -252,9 +271,32 @@ def extract_features_long_tensor(ids, values, sort=None, kinds=None, kind_names=
         else:
             kinds = _to_device(kinds, device).contiguous()
             values = values.contiguous()
+        # "drop" with a column that can hold NaN: room for the compacted key columns and the kept rows' input indices
+        drop = nan_policy == "drop" and (values.is_floating_point() or timed or (sort is not None and sort.is_floating_point()))
+        kept = [None if col is None else torch.empty_like(col) for col in (ids, sort, kinds)] if drop else None
+        src = torch.empty(N, dtype=torch.int32, device=ids.device) if drop else None
         _synchronize(torch, device)   # the producers of the columns, the copies and the fill of the flag word are done
 
-        pack_set = _pack_set(ids, sort, kinds, device)
+        n_kept = N
+        if drop:
+            n_kept = _native.pack_rows_valid(
+                _key_column(ids)[:2], None if sort is None else _key_column(sort)[:2], None if kinds is None else _key_column(kinds)[:2],
+                (v2.data_ptr(), _VALUE_TYPES[str(v2.dtype)][0], v2.shape[1], v2.stride(0), v2.stride(1)) if wide else
+                (values.data_ptr(), _VALUE_TYPES[str(values.dtype)][0], 1, 1, 1),
+                (stamps.data_ptr(), times[1], stamps.stride(0)) if timed else None, N, kept[0].data_ptr(),
+                None if sort is None else kept[1].data_ptr(), None if kinds is None else kept[2].data_ptr(), src.data_ptr(),
+                device=device)
+            if n_kept == 0:
+                raise ValueError("no row is left after dropping the rows with a NaN value, a NaN sort key or a NaT / NaN stamp")
+        if n_kept < N:   # the set on the compacted keys, its permutation composed with the kept rows' input indices
+            pack_set = _pack_set(*[None if col is None else col[:n_kept] for col in kept], device)
+            try:
+                pack_set.remap(src.data_ptr(), N)
+            except BaseException:
+                pack_set.close()
+                raise
+        else:
+            pack_set = _pack_set(ids, sort, kinds, device)
         packs = []
         try:
             if wide:
@@ -268,7 +310,7 @@ def extract_features_long_tensor(ids, values, sort=None, kinds=None, kind_names=
                     raise ValueError("kind code {} has no name in kind_names".format(missing[0]))
             if timed:
                 pack_set.hours(stamps.data_ptr(), times[1], times[2], stamps.stride(0), hours.data_ptr(), flag.data_ptr())
-            if check_nan:
+            if check_nan and nan_policy == "raise":
                 _raise_for_nan(torch, packs, kind_of, values, kinds, pack_set, sort, flag)
 
             # the frame's column order: a wide frame's kinds as given, a long frame's in the sorted order of their names
