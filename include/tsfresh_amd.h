@@ -187,7 +187,10 @@ int32_t tsfa_plan_last_timings(const tsfa_plan *plan, const char **names, float 
  *                 SPECTRAL: 1 chirp-z scratch attached
  *                 SORT: bit 0 a k_perm launch is queued for the group, bit 1 one wavefront per series with a sorted copy,
  *                       bit 2 one wavefront per series with the entropy kernel's 16-bit order in its place
- *                 AR: 1 the second pass works in HBM scratch    others: 0
+ *                 AR: 1 the second pass works in HBM scratch
+ *                 MPROFILE: 1 the tiled route (three launches per window, the working arrays in HBM scratch of its own;
+ *                       threads = 256, long_build = 0, lds_bytes still the one-workgroup carve the route is decided by)
+ *                 others: 0
  * Returns the number of records; at most `cap` are written to `out` (cap = 0 or out = NULL only counts).
  */
 typedef struct tsfa_launch_info {
@@ -219,6 +222,11 @@ int32_t tsfa_plan_last_launches(const tsfa_plan *plan, tsfa_launch_info *out, in
  *   "sort_waves"     1|2   k_sort up to 2048 samples: one wavefront per series (1), or the two-wavefront form it replaced (2)
  *   "seq_rows"       -1|0|1 lempel_ziv_complexity's symbol rows in LDS (0), in HBM (1), or in HBM where that puts more series on a CU (-1, default)
  *   "cwt_links"      0|1   number_cwt_peaks with n <= 5: ridge lines linked column by column (1), or by the general linker of the wider plans (0)
+ *   "mp_tiles"       -1|0|1 matrix_profile: the sweep of a series cut into tiles and spread over the chip (1, wherever a series has an
+ *                          admissible pair), one workgroup per series (0), or the tiles for a launch group whose longest series
+ *                          lies beyond the LDS layout or takes more than half of a CU's LDS (-1, default); any other value:
+ *                          TSFA_ERR_INVALID.  "force_long" 1 keeps
+ *                          meaning the one-workgroup HBM-scratch build unless "mp_tiles" is 1
  *   "host_chunks"    n     row chunks of the TSFA_HOST pipeline (0: by batch size)
  *   "side_lane"      mask  two lanes: bit f = family f (enum tsfa_family) runs on a low-priority side stream beside the others,
  *                          behind the main lane's ENTROPY family; 0 = one lane.  Default: SEQ | TREND.  BASIC, SORT and ENTROPY

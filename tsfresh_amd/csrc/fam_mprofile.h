@@ -30,6 +30,10 @@
 // and the sort are fixed: a series gives the same bits whatever the batch, the length class, the workgroup size, and
 // whether the working set lies in LDS or in the long-series build's HBM slot.
 //
+// TILES (tsfa_mprofile_tiles.hip, plan option mp_tiles): because of that independence the sweep of one series can be cut at the
+// restart rows and spread over many workgroups without changing a bit.  That route calls the per-window functions of the
+// prologue (mp_window_mean, mp_window_inv, mp_window_diffs), mp_cov_direct's sum, and mp_epilogue / mp_feature below.
+//
 // The same body compiles single-threaded under g++ (tests/emul/emul_mprofile.cpp).
 #ifndef TSFA_FAM_MPROFILE_H
 #define TSFA_FAM_MPROFILE_H
@@ -38,6 +42,10 @@
 
 #define TSFA_MP_RESTART 256   // rows between two direct recomputations of a diagonal's covariance
 #define TSFA_MP_MIN_W 4       // smallest window served (tsfa_validate_spec)
+// the tiled route (tsfa_mprofile_tiles.hip): a tile is TSFA_MP_RESTART rows by TSFA_MP_TILE_D neighbouring diagonals --
+// four wavefronts, every lane TSFA_MP_LANE_D neighbouring diagonals in registers
+#define TSFA_MP_LANE_D 4
+#define TSFA_MP_TILE_D (256 * TSFA_MP_LANE_D)
 enum { TSFA_MP_MIN = 0, TSFA_MP_MAX = 1, TSFA_MP_MEAN = 2, TSFA_MP_MEDIAN = 3, TSFA_MP_P25 = 4, TSFA_MP_P75 = 5 };
 
 typedef unsigned long long mp_key_t;
@@ -86,34 +94,50 @@ TSFA_DEV double mp_cov_direct(const XV &x, int i, int j, int w, double mi, doubl
     return c;
 }
 
+// mean and inverse norm of window i: the direct sums every route takes, in this order (the inverse norm of a flat window: NaN)
+template <class XV>
+TSFA_DEV double mp_window_mean(const XV &x, int i, int w, bool *is_flat) {
+    const double x0 = x[i];
+    double s = 0.0;
+    bool flat = true;
+    for (int k = 0; k < w; ++k) {
+        const double v = x[i + k];
+        s += v;
+        flat = flat && (v == x0);
+    }
+    *is_flat = flat;
+    return s / (double)w;
+}
+template <class XV>
+TSFA_DEV double mp_window_inv(const XV &x, int i, int w, double m, bool flat) {
+    double q = 0.0;
+    for (int k = 0; k < w; ++k) {
+        const double d = x[i + k] - m;
+        q += d * d;
+    }
+    return (flat || !(q > 0.0) || !(q < TSFA_INF)) ? TSFA_NAN : 1.0 / sqrt(q);
+}
+// the difference arrays of the diagonal recurrence at window i (mi, mi1: the means of windows i and i + 1); the last window
+// has no successor: its differences are never used in a result
+template <class XV>
+TSFA_DEV void mp_window_diffs(const XV &x, int i, int w, int L, double mi, double mi1, double *df, double *dg) {
+    const bool in = i + 1 < L;
+    *df = in ? (x[i + w] - x[i]) / 2.0 : 0.0;
+    *dg = in ? (x[i + w] - mi1) + (x[i] - mi) : 0.0;
+}
+
 template <class XV>
 TSFA_DEV void mp_prologue(const Blk &b, const XV &x, int n, int w, const MpWork &W) {
     const int L = n - w + 1;
     for (int i = b.tid; i < L; i += b.nt) {
-        const double x0 = x[i];
-        double s = 0.0;
-        bool flat = true;
-        for (int k = 0; k < w; ++k) {
-            const double v = x[i + k];
-            s += v;
-            flat = flat && (v == x0);
-        }
-        const double m = s / (double)w;
-        double q = 0.0;
-        for (int k = 0; k < w; ++k) {
-            const double d = x[i + k] - m;
-            q += d * d;
-        }
+        bool flat;
+        const double m = mp_window_mean(x, i, w, &flat);
         W.mu[i] = m;
-        W.inv[i] = (flat || !(q > 0.0) || !(q < TSFA_INF)) ? TSFA_NAN : 1.0 / sqrt(q);
+        W.inv[i] = mp_window_inv(x, i, w, m, flat);
         W.key[i] = 0ull;
     }
     blk_sync();
-    for (int i = b.tid; i < L; i += b.nt) {
-        const bool in = i + 1 < L;   // (the last window has no successor: its differences are never used in a result)
-        W.df[i] = in ? (x[i + w] - x[i]) / 2.0 : 0.0;
-        W.dg[i] = in ? (x[i + w] - W.mu[i + 1]) + (x[i] - W.mu[i]) : 0.0;
-    }
+    for (int i = b.tid; i < L; i += b.nt) mp_window_diffs(x, i, w, L, W.mu[i], (i + 1 < L) ? W.mu[i + 1] : 0.0, &W.df[i], &W.dg[i]);
     blk_sync();
 }
 
@@ -176,13 +200,52 @@ TSFA_DEV double mp_percentile(const double *a, int m, double q) {
     return (t >= 0.5) ? hi_v - diff * (1.0 - t) : lo_v + diff * t;
 }
 
+// The epilogue of one (series, window) on the working set the sweep left -- in LDS, or in HBM under a build whose blk_sync
+// orders global memory: keys -> distances, sorted in df | dg's storage (non-finite ones as +inf behind the others; 2 maxn
+// doubles >= the power of two above L); mu is dead and holds them by window (non-finite: 0) for the fixed-order sum.
+// Returns the number of finite distances; *mean: their mean (untouched where there is none).
+TSFA_DEV int mp_epilogue(const Blk &b, int L, int w, const MpWork &W, double *mean) {
+    double *srt = W.df;
+    const double w2 = 2.0 * (double)w;
+    const int np2 = next_pow2(L);
+    double cnt = 0.0;
+    for (int i = b.tid; i < np2; i += b.nt) {
+        const mp_key_t k = (i < L) ? mp_key_load(&W.key[i]) : 0ull;
+        const double p = k ? sqrt(w2 * (1.0 - mp_dec(k))) : TSFA_INF;
+        const bool fin = p < TSFA_INF;   // (false for NaN too)
+        srt[i] = fin ? p : TSFA_INF;
+        if (i < L) W.mu[i] = fin ? p : 0.0;
+        cnt += fin ? 1.0 : 0.0;
+    }
+    const int m = (int)blk_sum(b, cnt);
+    blk_sync();
+    const double *pm = W.mu;
+    const double total = np_sum(b, L, [=](int i) { return pm[i]; });
+    blk_bitonic_sort(b, srt, np2);
+    if (m > 0) *mean = total / (double)m;
+    return m;
+}
+
+// one column from the m sorted finite distances and their mean
+TSFA_DEV double mp_feature(int feature, const double *srt, int m, double mean) {
+    if (m <= 0) return TSFA_NAN;
+    switch (feature) {
+    case TSFA_MP_MIN: return srt[0];
+    case TSFA_MP_MAX: return srt[m - 1];
+    case TSFA_MP_MEAN: return mean;
+    case TSFA_MP_MEDIAN: return (m & 1) ? srt[m / 2] : (srt[m / 2 - 1] + srt[m / 2]) / 2.0;
+    case TSFA_MP_P25: return mp_percentile(srt, m, 0.25);
+    case TSFA_MP_P75: return mp_percentile(srt, m, 0.75);
+    default: return TSFA_NAN;
+    }
+}
+
 // every matrix_profile column of a plan for one series.  specs: sorted by window (p0); p1: TSFA_MP_*.
 template <class XV>
 TSFA_DEV void fam_mprofile_series(const Blk &b, const XV &x, int n, const TsfaSpec *specs, int nspecs, double *out_row,
                                   const MpWork &W) {
     int cur_w = -1, m = 0;
     double mean = TSFA_NAN;
-    double *srt = W.df;   // df | dg: 2 maxn doubles >= the power of two above L
     for (int s = 0; s < nspecs; ++s) {
         const TsfaSpec sp = specs[s];
         const int w = (int)sp.p[0];
@@ -195,39 +258,10 @@ TSFA_DEV void fam_mprofile_series(const Blk &b, const XV &x, int n, const TsfaSp
             if (w >= TSFA_MP_MIN_W && L > mp_excl(w) + 1) {
                 mp_prologue(b, x, n, w, W);
                 mp_sweep(b, x, n, w, W);
-                // distances: sorted in df | dg's storage (non-finite ones as +inf behind the others); mu is dead and holds
-                // them by window (non-finite: 0) for the fixed-order sum
-                const double w2 = 2.0 * (double)w;
-                const int np2 = next_pow2(L);
-                double cnt = 0.0;
-                for (int i = b.tid; i < np2; i += b.nt) {
-                    const mp_key_t k = (i < L) ? mp_key_load(&W.key[i]) : 0ull;
-                    const double p = k ? sqrt(w2 * (1.0 - mp_dec(k))) : TSFA_INF;
-                    const bool fin = p < TSFA_INF;   // (false for NaN too)
-                    srt[i] = fin ? p : TSFA_INF;
-                    if (i < L) W.mu[i] = fin ? p : 0.0;
-                    cnt += fin ? 1.0 : 0.0;
-                }
-                m = (int)blk_sum(b, cnt);
-                blk_sync();
-                const double *pm = W.mu;
-                const double total = np_sum(b, L, [=](int i) { return pm[i]; });
-                blk_bitonic_sort(b, srt, np2);
-                if (m > 0) mean = total / (double)m;
+                m = mp_epilogue(b, L, w, W, &mean);
             }
         }
-        double v = TSFA_NAN;
-        if (m > 0) {
-            switch ((int)sp.p[1]) {
-            case TSFA_MP_MIN: v = srt[0]; break;
-            case TSFA_MP_MAX: v = srt[m - 1]; break;
-            case TSFA_MP_MEAN: v = mean; break;
-            case TSFA_MP_MEDIAN: v = (m & 1) ? srt[m / 2] : (srt[m / 2 - 1] + srt[m / 2]) / 2.0; break;
-            case TSFA_MP_P25: v = mp_percentile(srt, m, 0.25); break;
-            case TSFA_MP_P75: v = mp_percentile(srt, m, 0.75); break;
-            default: break;
-            }
-        }
+        const double v = mp_feature((int)sp.p[1], W.df, m, mean);
         if (b.tid == 0) out_row[sp.col] = v;
     }
 }

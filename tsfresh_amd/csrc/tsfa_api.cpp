@@ -73,6 +73,7 @@ struct PlanOptions {
     bool row_form = true;         // BASIC / TREND: series of <= 256 samples four to a wavefront (k_basic_rows / k_trend_rows)
     int seq_rows = -1;            // lempel_ziv symbol rows: 0 in LDS, 1 in HBM, -1: in HBM where that puts more series on a CU
     unsigned side_lane = TSFA_SIDE_DEFAULT;   // two lanes (tsfa_plan::side): bit f = family f on the side lane; 0: one lane
+    int mp_tiles = -1;            // matrix_profile: 1 = the tiled route (tsfa_mprofile_tiles.hip), 0 = one workgroup per series, -1 = tiles where the carve leaves one workgroup per CU or leaves LDS
     int cwt_links = 1;            // number_cwt_peaks, widths <= 5: 1 = ridge lines linked column by column; 0 = the general linker it replaced there
     int fail_after = -1;          // test hook: run_batch returns an error after this family's launches (its exits after the fork)
 };
@@ -101,8 +102,9 @@ struct tsfa_plan {
     DevPtr<int> d_cols, d_coeff;
     DevPtr<double> d_dectab, d_twc, d_tws, d_consts;
     DevPtr<long long> d_stats;
-    // (long_scratch: the HBM slots of every long-series family, k_mprofile's among them)
-    DevBuf values, offsets, out, gscratch, times, deg_list, sel, long_scratch, pf_buf, perm_buf, stats_buf, dd_scratch, gen_scratch, seq_rows;
+    // (long_scratch: the HBM slots of every long-series family, k_mprofile's among them; mp_scratch: the working arrays of
+    //  matrix_profile's tiled route, 40 bytes per sample and series of a launch group)
+    DevBuf values, offsets, out, gscratch, times, deg_list, sel, long_scratch, pf_buf, perm_buf, stats_buf, dd_scratch, gen_scratch, seq_rows, mp_scratch;
     // k_general (fam_general.h): the columns of the calculators whose parameters lie beyond the tuned kernels' tables
     std::vector<TsfaSpec> gen_specs;
     DevPtr<TsfaSpec> d_gen_specs;
@@ -327,6 +329,7 @@ int tsfa_plan_set_option(tsfa_plan *plan, const char *name, double value) {
     else if (n == "seq_rows") o.seq_rows = (value < 0.0) ? -1 : (on ? 1 : 0);
     else if (n == "entropy_route") { if (value != 0.0 && value != 1.0 && value != 2.0) return fail(TSFA_ERR_INVALID, "entropy_route: 0, 1 or 2"); o.entropy_route = (int)value; }
     else if (n == "sort_waves") { if (value != 1.0 && value != 2.0) return fail(TSFA_ERR_INVALID, "sort_waves: 1 or 2"); o.sort_waves = (int)value; }
+    else if (n == "mp_tiles") { if (value != -1.0 && value != 0.0 && value != 1.0) return fail(TSFA_ERR_INVALID, "mp_tiles: -1 (auto), 0 or 1"); o.mp_tiles = (int)value; }
     else if (n == "cwt_links") { if (value != 0.0 && value != 1.0) return fail(TSFA_ERR_INVALID, "cwt_links: 0 or 1"); o.cwt_links = (int)value; }
     else if (n == "bluestein_min") o.bluestein_min = value > 0.0 ? (int)std::min(value, 32767.0) : 0;
     else if (n == "gscratch_slots") o.gscratch_slots = value > 0.0 ? (int)std::min(value, 2147483647.0) : 0;
@@ -844,7 +847,18 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
             // A series whose working set does not fit a CU's LDS runs from the long-series build of the same kernels
             // (tsfa_kernels_long.hip): the working set in a slot of HBM scratch per resident workgroup, a persistent
             // grid walking the group's series.  Slower per sample, but every length up to 65 535 extracts.
-            const bool use_long = lds > TSFA_LDS_LIMIT || plan->opt.force_long || (f == TSFA_FAM_ENTROPY && a.ent_cnt == 4);
+            // matrix_profile: the tiled route (tsfa_mprofile_tiles.hip) spreads the sweep of a series over the chip, its working
+            // arrays in scratch of its own.  Auto: where the one-workgroup kernel would leave LDS, and where its carve leaves one
+            // workgroup per CU (measured: 4.0x at 1 000 x 3600; at three series per CU, 10 000 x 1024, the tiles gain 1.17x for
+            // 400 MB of scratch and auto stays on k_mprofile: profiles/mprofile_tiles_timing.md)
+            const bool mp_tiles = f == TSFA_FAM_MPROFILE && (plan->opt.mp_tiles == 1 || (plan->opt.mp_tiles < 0 && lds > TSFA_LDS_LIMIT / 2 && !plan->opt.force_long));
+            size_t mp_bytes = 0;
+            if (mp_tiles) {
+                mp_bytes = tsfa_mprofile_tiles_scratch(a.n_series, maxn, (size_t)4 << 30);   // (the cap of the long-series scratch below)
+                if (plan->mp_scratch.ensure(mp_bytes)) return fail(TSFA_ERR_HIP, "hipMalloc failed for the matrix_profile tile scratch");
+                a.nt = 256;
+            }
+            const bool use_long = !mp_tiles && (lds > TSFA_LDS_LIMIT || plan->opt.force_long || (f == TSFA_FAM_ENTROPY && a.ent_cnt == 4));
             if (TSFA_LAB_ONLY(f == TSFA_FAM_SPECTRAL && plan->opt.trace))
                 fprintf(stderr, "[tsfa] spectral group %d: n_series %lld maxn %d max_np2 %lld lds %zu long %d chirp-z %d slots %lld nt %d\n", g,
                         (long long)a.n_series, maxn, max_np2, lds, (int)use_long, (int)(a.gscratch != nullptr), (long long)a.gscratch_slots, a.nt);
@@ -940,7 +954,8 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                              : (f == TSFA_FAM_SEQ) ? (seq_group | (seq_grows << 8))
                              : (f == TSFA_FAM_SPECTRAL) ? (a.gscratch != nullptr ? 1 : 0)
                              : (f == TSFA_FAM_SORT) ? ((a.hint_d != 0 ? 1 : 0) | (a.sort_mode << 1))   // bit 1: one wavefront, bit 2: ... with the 16-bit order
-                             : (f == TSFA_FAM_AR) ? (a.dd_scratch != nullptr ? 1 : 0) : 0;
+                             : (f == TSFA_FAM_AR) ? (a.dd_scratch != nullptr ? 1 : 0)
+                             : (f == TSFA_FAM_MPROFILE) ? (mp_tiles ? 1 : 0) : 0;
                 plan->launches.push_back(li);
             }
             int rc = 0;
@@ -959,6 +974,8 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                 // a plan that only asks the sort family for median / quantile columns (MinimalFCParameters): selection
                 // in registers, one wavefront per series, no sorted copy (tsfa_kernels.hip: k_order_stats)
                 rc = tsfa_launch_order_stats(a);
+            } else if (mp_tiles) {
+                rc = tsfa_launch_mprofile_tiles(a, plan->fam_specs[f].data(), (unsigned char *)plan->mp_scratch.p, mp_bytes);
             } else if (f == TSFA_FAM_SEQ) {
                 for (int s0 = 0; rc == 0 && s0 < a.nspecs; s0 += seq_group) {
                     lz_build_group(plan->fam_specs[f].data() + s0, std::min(seq_group, a.nspecs - s0), maxn, &a.seq, seq_grows);

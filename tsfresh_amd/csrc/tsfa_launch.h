@@ -99,7 +99,13 @@ size_t tsfa_entropy_lds_bytes(int maxn, int with_cnt);
 size_t tsfa_seq_lds_bytes(const TsfaSeqGroup &g);
 size_t tsfa_sort_lds_bytes(const TsfaLaunch &a, int xs_bytes);   // k_sort's layout for this launch: SortLds::carve with the kernel's own arguments
 int tsfa_launch_family(const TsfaLaunch &a);         // (TSFA_FAM_MPROFILE: k_mprofile reads specs / nspecs / maxn only; its aux is the sample size)
-int tsfa_launch_rows(const TsfaLaunch &a);          // BASIC / TREND: the series of at most TSFA_ROW_MAXN samples, four per wavefront (k_basic_rows / k_trend_rows)
+// TSFA_FAM_MPROFILE, the tiled route (tsfa_mprofile_tiles.hip): per distinct window a prologue, the tile sweep and the epilogue
+// on a.stream, the working arrays of the group's series in `scratch` (40 bytes per sample of a.maxn and series, behind the
+// tile table; a group that does not fit goes out in chunks of series).  h_specs: a.specs on the host, sorted by window.
+// tsfa_mprofile_tiles_scratch: the bytes to hand it for a group, at most `cap` unless one series alone needs more.
+size_t tsfa_mprofile_tiles_scratch(int64_t n_series, int maxn, size_t cap);
+int tsfa_launch_mprofile_tiles(const TsfaLaunch &a, const TsfaSpec *h_specs, unsigned char *scratch, size_t bytes);
+int tsfa_launch_rows(const TsfaLaunch &a);         // BASIC / TREND: the series of at most TSFA_ROW_MAXN samples, four per wavefront (k_basic_rows / k_trend_rows)
 int tsfa_launch_family_long(const TsfaLaunch &a);   // working set in a.long_scratch instead of LDS (any length <= 65535)
 // k_general (fam_general.h): a.specs / a.nspecs = the plan's GENERAL columns, every series of the batch in one launch
 size_t tsfa_general_slot_doubles(int maxn, const TsfaGenPlan &g);
