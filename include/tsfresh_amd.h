@@ -227,6 +227,12 @@ int32_t tsfa_plan_last_launches(const tsfa_plan *plan, tsfa_launch_info *out, in
  *                          lies beyond the LDS layout or takes more than half of a CU's LDS (-1, default); any other value:
  *                          TSFA_ERR_INVALID.  "force_long" 1 keeps
  *                          meaning the one-workgroup HBM-scratch build unless "mp_tiles" is 1
+ *   "ent_tiles"      -1|0|1 sample_entropy / approximate_entropy with m = 2: the ordered-pair sweep of a series cut into tiles and
+ *                          spread over the chip (1, wherever every entropy column has m = 2 and the longest series 3 samples), never
+ *                          (0), or the tiles for a launch group that would run the one-workgroup pair sweep of the HBM-scratch
+ *                          build (-1, default: a group whose series lie beyond the bit-matrix sweeps and LDS; under "force_long" 1
+ *                          only a group of fewer series than the device has CUs); any other value: TSFA_ERR_INVALID.
+ *                          "entropy_route" 1 | 2 keep their meaning unless "ent_tiles" is 1.  Launch record: variant 5, long_build 1
  *   "host_chunks"    n     row chunks of the TSFA_HOST pipeline (0: by batch size)
  *   "side_lane"      mask  two lanes: bit f = family f (enum tsfa_family) runs on a low-priority side stream beside the others,
  *                          behind the main lane's ENTROPY family; 0 = one lane.  Default: SEQ | TREND.  BASIC, SORT and ENTROPY

@@ -4,7 +4,8 @@
     python profiles/kernel_resources.py k_pack tsfa_pack_device.hip
     python profiles/kernel_resources.py mprofile                          (k_mprofile: 36 VGPRs, no scratch, dynamic LDS)
     python profiles/kernel_resources.py mprofile tsfa_kernels_long.hip    (kl_mprofile, the HBM-scratch build: 56 VGPRs, no scratch)
-    python profiles/kernel_resources.py k_mpt tsfa_mprofile_tiles.hip     (the tiled route: k_mpt_sweep 80 VGPRs, no scratch, 49 152 B LDS)"""
+    python profiles/kernel_resources.py k_mpt tsfa_mprofile_tiles.hip     (the tiled route: k_mpt_sweep 80 VGPRs, no scratch, 49 152 B LDS)
+    python profiles/kernel_resources.py k_ent tsfa_entropy_tiles.hip      (the tiled entropies: k_ent_sweep, 49 248 B LDS, no scratch)"""
 import os
 import re
 import subprocess

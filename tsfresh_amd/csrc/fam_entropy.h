@@ -476,6 +476,21 @@ TSFA_DEV void entropy_sweep_staged(const Blk &b, const double *xs, int n, const 
     }
 }
 
+// The tail of the ordered-pair sweep, shared with the tiled route (tsfa_entropy_tiles.hip): one row's counts of one
+// threshold join the thread's totals.  Both routes call it for the rows qi = pass * nt + tid in ascending passes and reduce
+// with blk_sum, so their totals are the same bits.
+TSFA_DEV void ent_acc_row(bool row_m, bool row_m1, int c2, int c3, double dm, double dm1, double &slm, double &slm1,
+                          double &scm, double &scm1) {
+    if (row_m) {
+        scm += (double)c2;
+        slm += log((double)c2 / dm);
+    }
+    if (row_m1) {
+        scm1 += (double)c3;
+        slm1 += log((double)c3 / dm1);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Ordered-pair sweep (no LDS counters): thread = row i, the loop runs over the columns j of the row block's r_max
 // window, x[j..j+2] is a wave-uniform broadcast read, per-row counters live in registers.
@@ -533,16 +548,7 @@ TSFA_DEV void entropy_sweep_m2(const Blk &b, const XT *xs, int n, const double *
             }
         }
 #pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            if (row_m) {
-                scm[k] += (double)c2[k];
-                slm[k] += log((double)c2[k] / dm);
-            }
-            if (row_m1) {
-                scm1[k] += (double)c3[k];
-                slm1[k] += log((double)c3[k] / dm1);
-            }
-        }
+        for (int k = 0; k < NK; ++k) ent_acc_row(row_m, row_m1, c2[k], c3[k], dm, dm1, slm[k], slm1[k], scm[k], scm1[k]);
     }
 #pragma unroll
     for (int k = 0; k < NK; ++k)
@@ -668,6 +674,12 @@ TSFA_DEV double sampen_from_acc(const EntAcc &a, int n, int m) {
     const double B = a.sum_cnt_m - (double)(n - m + 1);
     const double A = a.sum_cnt_m1 - (double)(n - m);
     return -log(A / B);
+}
+
+// the value of an m = 2 column from its four totals (both routes)
+TSFA_DEV double ent_m2_value(int calc, const EntAcc &a, int n) {
+    if (calc == TSFA_C_APPROXIMATE_ENTROPY) return (n <= 3) ? 0.0 : apen_from_acc(a, n, 2);  // N <= m + 1
+    return (n < 3) ? TSFA_NAN : sampen_from_acc(a, n, 2);  // no length-3 template: A = 0, B = 0 -> -log(0/0)
 }
 
 // Evaluate the ENTROPY specs of one series.
@@ -811,14 +823,7 @@ TSFA_DEV void fam_entropy_series(const Blk &b0, XT *xs, int n, const TsfaSpec *s
                 a.sum_cnt_m = racc[4 * k + 2];
                 a.sum_cnt_m1 = racc[4 * k + 3];
                 ++k;
-                double v;
-                if (sp.calc == TSFA_C_APPROXIMATE_ENTROPY) {
-                    if (n <= 3) v = 0.0;  // N <= m + 1
-                    else v = apen_from_acc(a, n, 2);
-                } else {
-                    if (n < 3) v = TSFA_NAN;  // no length-3 template: A = 0, B = 0 -> -log(0/0)
-                    else v = sampen_from_acc(a, n, 2);
-                }
+                const double v = ent_m2_value(sp.calc, a, n);
                 if (b.tid == 0) out_row[sp.col] = v;
             }
         }

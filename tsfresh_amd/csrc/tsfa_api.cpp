@@ -74,6 +74,7 @@ struct PlanOptions {
     int seq_rows = -1;            // lempel_ziv symbol rows: 0 in LDS, 1 in HBM, -1: in HBM where that puts more series on a CU
     unsigned side_lane = TSFA_SIDE_DEFAULT;   // two lanes (tsfa_plan::side): bit f = family f on the side lane; 0: one lane
     int mp_tiles = -1;            // matrix_profile: 1 = the tiled route (tsfa_mprofile_tiles.hip), 0 = one workgroup per series, -1 = tiles where the carve leaves one workgroup per CU or leaves LDS
+    int ent_tiles = -1;           // m = 2 entropies: 1 = the tiled route (tsfa_entropy_tiles.hip), 0 = never, -1 = tiles where the pair sweep of the long-series build would run (series beyond LDS; under force_long: fewer series than CUs)
     int cwt_links = 1;            // number_cwt_peaks, widths <= 5: 1 = ridge lines linked column by column; 0 = the general linker it replaced there
     int fail_after = -1;          // test hook: run_batch returns an error after this family's launches (its exits after the fork)
 };
@@ -103,8 +104,10 @@ struct tsfa_plan {
     DevPtr<double> d_dectab, d_twc, d_tws, d_consts;
     DevPtr<long long> d_stats;
     // (long_scratch: the HBM slots of every long-series family, k_mprofile's among them; mp_scratch: the working arrays of
-    //  matrix_profile's tiled route, 40 bytes per sample and series of a launch group)
-    DevBuf values, offsets, out, gscratch, times, deg_list, sel, long_scratch, pf_buf, perm_buf, stats_buf, dd_scratch, gen_scratch, seq_rows, mp_scratch;
+    //  matrix_profile's tiled route, 40 bytes per sample and series of a launch group; ent_scratch: those of the entropies'
+    //  tiled route, about 92 bytes per sample and series)
+    DevBuf values, offsets, out, gscratch, times, deg_list, sel, long_scratch, pf_buf, perm_buf, stats_buf, dd_scratch, gen_scratch, seq_rows, mp_scratch, ent_scratch;
+    int n_cus = 0;                              // the device's compute units (read at the first ENTROPY launch that asks)
     // k_general (fam_general.h): the columns of the calculators whose parameters lie beyond the tuned kernels' tables
     std::vector<TsfaSpec> gen_specs;
     DevPtr<TsfaSpec> d_gen_specs;
@@ -330,6 +333,7 @@ int tsfa_plan_set_option(tsfa_plan *plan, const char *name, double value) {
     else if (n == "entropy_route") { if (value != 0.0 && value != 1.0 && value != 2.0) return fail(TSFA_ERR_INVALID, "entropy_route: 0, 1 or 2"); o.entropy_route = (int)value; }
     else if (n == "sort_waves") { if (value != 1.0 && value != 2.0) return fail(TSFA_ERR_INVALID, "sort_waves: 1 or 2"); o.sort_waves = (int)value; }
     else if (n == "mp_tiles") { if (value != -1.0 && value != 0.0 && value != 1.0) return fail(TSFA_ERR_INVALID, "mp_tiles: -1 (auto), 0 or 1"); o.mp_tiles = (int)value; }
+    else if (n == "ent_tiles") { if (value != -1.0 && value != 0.0 && value != 1.0) return fail(TSFA_ERR_INVALID, "ent_tiles: -1 (auto), 0 or 1"); o.ent_tiles = (int)value; }
     else if (n == "cwt_links") { if (value != 0.0 && value != 1.0) return fail(TSFA_ERR_INVALID, "cwt_links: 0 or 1"); o.cwt_links = (int)value; }
     else if (n == "bluestein_min") o.bluestein_min = value > 0.0 ? (int)std::min(value, 32767.0) : 0;
     else if (n == "gscratch_slots") o.gscratch_slots = value > 0.0 ? (int)std::min(value, 2147483647.0) : 0;
@@ -858,7 +862,32 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                 if (plan->mp_scratch.ensure(mp_bytes)) return fail(TSFA_ERR_HIP, "hipMalloc failed for the matrix_profile tile scratch");
                 a.nt = 256;
             }
-            const bool use_long = !mp_tiles && (lds > TSFA_LDS_LIMIT || plan->opt.force_long || (f == TSFA_FAM_ENTROPY && a.ent_cnt == 4));
+            // The m = 2 entropies: the tiled route (tsfa_entropy_tiles.hip) spreads the ordered-pair sweep of a series over the chip.
+            // Auto: where the group would run that sweep from the long-series build, one workgroup per series.  A group whose
+            // series left LDS by their length takes the tiles whatever its size (measured at 20 000 samples and more: 93x for one
+            // series, 4.7x for 256, 3.9x for 2 000 -- profiles/entropy_tiles_timing.md); series that are only forced onto the
+            // long-series build (force_long, not measured) take them while the group holds fewer series than the device has CUs.
+            bool ent_tiles = false;
+            size_t ent_bytes = 0;
+            if (f == TSFA_FAM_ENTROPY && plan->opt.ent_tiles != 0 && maxn >= 3) {
+                bool all_m2 = true;
+                for (const auto &s : plan->fam_specs[f])
+                    if (s.calc == TSFA_C_APPROXIMATE_ENTROPY && (int)s.p[0] != 2) all_m2 = false;
+                bool take = plan->opt.ent_tiles == 1;
+                if (!take && all_m2 && plan->opt.entropy_route == 0 && a.ent_cnt != 4 && (lds > TSFA_LDS_LIMIT || plan->opt.force_long)) {
+                    if (plan->n_cus == 0) HIP_TRY(hipDeviceGetAttribute(&plan->n_cus, hipDeviceAttributeMultiprocessorCount, plan->device));
+                    take = lds > TSFA_LDS_LIMIT || a.n_series < plan->n_cus;
+                }
+                ent_tiles = all_m2 && take;
+            }
+            if (ent_tiles) {
+                ent_bytes = tsfa_entropy_tiles_scratch(a.n_series, maxn, (size_t)1 << 30);   // (1 GB holds 560 series of 20 000 samples: such a chunk fills the chip)
+                if (plan->ent_scratch.ensure(ent_bytes)) return fail(TSFA_ERR_HIP, "hipMalloc failed for the entropy tile scratch");
+                a.nt = 256;
+                a.ent_cnt = 0;   // (no bit-matrix sweep ran: no sample order is handed to k_sort)
+                a.ent_fast = 0;
+            }
+            const bool use_long = !mp_tiles && !ent_tiles && (lds > TSFA_LDS_LIMIT || plan->opt.force_long || (f == TSFA_FAM_ENTROPY && a.ent_cnt == 4));
             if (TSFA_LAB_ONLY(f == TSFA_FAM_SPECTRAL && plan->opt.trace))
                 fprintf(stderr, "[tsfa] spectral group %d: n_series %lld maxn %d max_np2 %lld lds %zu long %d chirp-z %d slots %lld nt %d\n", g,
                         (long long)a.n_series, maxn, max_np2, lds, (int)use_long, (int)(a.gscratch != nullptr), (long long)a.gscratch_slots, a.nt);
@@ -948,8 +977,8 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                 li.threads = a.nt;
                 li.n_series = a.n_series;
                 li.lds_bytes = (int64_t)lds;
-                li.long_build = use_long ? 1 : 0;
-                li.variant = (f == TSFA_FAM_ENTROPY) ? a.ent_cnt
+                li.long_build = (use_long || ent_tiles) ? 1 : 0;   // (the tiled entropies: every array in HBM)
+                li.variant = (f == TSFA_FAM_ENTROPY) ? (ent_tiles ? 5 : a.ent_cnt)
                              : (f == TSFA_FAM_CWT) ? a.cwt_rowv
                              : (f == TSFA_FAM_SEQ) ? (seq_group | (seq_grows << 8))
                              : (f == TSFA_FAM_SPECTRAL) ? (a.gscratch != nullptr ? 1 : 0)
@@ -976,6 +1005,8 @@ static int run_batch(tsfa_plan *plan, const void *d_values, int dtype, const dou
                 rc = tsfa_launch_order_stats(a);
             } else if (mp_tiles) {
                 rc = tsfa_launch_mprofile_tiles(a, plan->fam_specs[f].data(), (unsigned char *)plan->mp_scratch.p, mp_bytes);
+            } else if (ent_tiles) {
+                rc = tsfa_launch_entropy_tiles(a, (unsigned char *)plan->ent_scratch.p, ent_bytes);
             } else if (f == TSFA_FAM_SEQ) {
                 for (int s0 = 0; rc == 0 && s0 < a.nspecs; s0 += seq_group) {
                     lz_build_group(plan->fam_specs[f].data() + s0, std::min(seq_group, a.nspecs - s0), maxn, &a.seq, seq_grows);

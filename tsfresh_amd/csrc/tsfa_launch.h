@@ -105,7 +105,14 @@ int tsfa_launch_family(const TsfaLaunch &a);         // (TSFA_FAM_MPROFILE: k_mp
 // tsfa_mprofile_tiles_scratch: the bytes to hand it for a group, at most `cap` unless one series alone needs more.
 size_t tsfa_mprofile_tiles_scratch(int64_t n_series, int maxn, size_t cap);
 int tsfa_launch_mprofile_tiles(const TsfaLaunch &a, const TsfaSpec *h_specs, unsigned char *scratch, size_t bytes);
-int tsfa_launch_rows(const TsfaLaunch &a);         // BASIC / TREND: the series of at most TSFA_ROW_MAXN samples, four per wavefront (k_basic_rows / k_trend_rows)
+// TSFA_FAM_ENTROPY, the tiled route (tsfa_entropy_tiles.hip; every spec has m = 2): a prologue per series, then per batch of
+// TSFA_ENT_MAXK tolerances the windows, the tile table, the tile sweep and the epilogue on a.stream.  `scratch`: behind the
+// tables, per series of the group the order, the sorted triples and the counters (about 92 bytes per sample of a.maxn; a
+// group that does not fit goes out in chunks of series).  a.stats_in as for k_entropy.
+// tsfa_entropy_tiles_scratch: the bytes to hand it for a group, at most `cap` unless one series alone needs more.
+size_t tsfa_entropy_tiles_scratch(int64_t n_series, int maxn, size_t cap);
+int tsfa_launch_entropy_tiles(const TsfaLaunch &a, unsigned char *scratch, size_t bytes);
+int tsfa_launch_rows(const TsfaLaunch &a);        // BASIC / TREND: the series of at most TSFA_ROW_MAXN samples, four per wavefront (k_basic_rows / k_trend_rows)
 int tsfa_launch_family_long(const TsfaLaunch &a);   // working set in a.long_scratch instead of LDS (any length <= 65535)
 // k_general (fam_general.h): a.specs / a.nspecs = the plan's GENERAL columns, every series of the batch in one launch
 size_t tsfa_general_slot_doubles(int maxn, const TsfaGenPlan &g);

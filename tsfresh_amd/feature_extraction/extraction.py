@@ -76,9 +76,9 @@ def _warn_long_entropy(fc_parameters, pk, show_warnings=False):
     if longest > ENTROPY_FAST_MAX_LEN:
         _LONG_ENTROPY_WARNED = True
         warnings.warn("kind {!r}: series of up to {} samples with sample_entropy / approximate_entropy in the settings: these "
-                      "calculators are O(n^2) and beyond {} samples leave the bit-matrix sweeps for a float64 pair sweep (several "
-                      "milliseconds per series at 32 768 samples on a full MI355X, four times that per doubling: nearly all of the "
-                      "extraction).  EfficientFCParameters() leaves them out, as the reference recommends for long series.".format(pk.kind, longest, ENTROPY_FAST_MAX_LEN),
+                      "calculators are O(n^2) and beyond {} samples leave the bit-matrix sweeps for a float64 pair sweep, cut into "
+                      "tiles over the whole MI355X (about a millisecond per series at 32 768 samples, four times that per doubling: "
+                      "nearly all of the extraction).  EfficientFCParameters() leaves them out, as the reference recommends for long series.".format(pk.kind, longest, ENTROPY_FAST_MAX_LEN),
                       UserWarning, stacklevel=3)
 
 
